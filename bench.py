@@ -15,6 +15,15 @@ A "step" is one forward pass of a benchmark network over one synthetic batch alr
       Only that net (its images/s becomes `value`).
   python bench.py --mode convstack [--net ...]
       Only the convolution layers, each through ConvBooster::Forward with bias + ReLU fused and its input re-drawn (not chained).
+  python bench.py ... --dump-outputs DIR
+      After the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32): the output blob a caller
+      of Net::Extract receives for every net the run timed (<name> = the net, or its key in the line's nets, e.g. resnet50_global512),
+      rank 0's shard at N > 1; in convstack mode the last layer's output (convstack_<net>).  Inputs and weights are seeded, so the same
+      arguments give the same inputs from run to run.  At most 64 MB of data in all: a larger array is cut to a fixed, seeded sample of its
+      images (of its elements where not even one image fits).
+
+--steps K sets the number of timed steps of every net the run times (the steady-state cross-check region, --no-steady to drop it, is
+separate); `ms_per_step` in the line is one timed step of the headline net.
 
 Rank 0 prints ONE JSON line of at most 8 KiB (benchkit/report.py enforces it): the contract keys, `config` (with `other_nets`: images/s and
 the roofline fraction of each hot kernel of the other metric nets, and `resnet50_scaling`: weak and strong efficiency with their
@@ -76,9 +85,34 @@ def parse():
                     help="route convolutions with the reference's SelectAlgo rule instead of the MI355X cost model (fhip_conv_select_algo_tuned)")
     ap.add_argument("--sub-batches", type=int, default=0, help="replicas of the net on streams of their own, each taking a share of the batch "
                     "(fhip_net_set_sub_batches); 0 = per-net default: 2 for mobilenet_v1 (HBM-bound depthwise under MFMA-bound 1x1 layers), else 1")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the output of the last timed step of every "
+                    "timed net to DIR/<name>.npy (float32, <= 64 MB in all; see the module docstring)")
     ap.add_argument("--fusion", type=int, default=3, help="net mode: 0 none, 1 the reference's TryFuse patterns, 2 + BN/Scale folded into conv weights, "
                     "conv+pool, conv+add, depthwise+pointwise, 3 + chained Winograd layers (feather_net.h, fhip_net_set_fusion)")
     return ap.parse_args()
+
+
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: one float32 .npy per timed net, DUMP_LIMIT bytes of data in all.  An array over its share keeps a fixed, seeded sample of
+    its images (first axis), in order; where not even one image fits, a fixed, seeded sample of its elements (flattened, in order).  Two builds
+    given the same arguments therefore write the same sample."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT // max(len(outputs), 1)
+    for name, arr in outputs.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        if arr.nbytes > share:
+            per_image = arr[:1].nbytes
+            rng = np.random.default_rng(0)
+            if arr.ndim > 1 and per_image <= share:
+                arr = arr[np.sort(rng.choice(arr.shape[0], size=share // per_image, replace=False))]
+            else:
+                flat = arr.reshape(-1)
+                arr = flat[np.sort(rng.choice(flat.size, size=share // flat.itemsize, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def solo(fn, extras, name):
@@ -138,13 +172,15 @@ def main():
     explicit = a.net is not None
     head_net = a.net or "vgg16"
     steady = 0 if a.no_steady else STEADY_STEPS
-    quick = (max(a.steps // 5, 5), max(a.warmup // 2, 1))  # steps / warm-up of the 512-image one-GPU points (30 ms per step)
+    outputs = {} if (a.dump_outputs and rank == 0) else None  # --dump-outputs: rank 0's output of the last timed step, per net
 
     if a.mode == "convstack":
         from benchkit.convstack import setup_convstack
         a.net = head_net
-        step, finalize, batch = setup_convstack(a, env)
+        step, finalize, batch, last_output = setup_convstack(a, env)
         dt = timing.timed_region(step, a.steps, a.warmup, env)
+        if outputs is not None:
+            outputs["convstack_" + head_net] = last_output()
         head = finalize(dt / a.steps * 1e3)
         total = a.global_batch if a.global_batch else world * batch
         head.update({"net": head_net, "images_per_s": round(total * a.steps / dt, 2), "ms_per_step": round(dt / a.steps * 1e3, 4),
@@ -152,26 +188,32 @@ def main():
         model, extras = None, {}
     else:
         # ---- headline: BASELINE.json configs[1] (VGG-16, 32 images per GPU) unless --net says otherwise; weak scaling at N > 1
-        head, model = timing.measure_net(head_net, a, env, a.steps, a.warmup, a.global_batch, a.batch, steady=steady, passes=ATTRIBUTION_PASSES)
+        head, model = timing.measure_net(head_net, a, env, a.steps, a.warmup, a.global_batch, a.batch, steady=steady, passes=ATTRIBUTION_PASSES,
+                                         outputs=outputs)
         extras = {}
         if not explicit and not a.headline_only:
             # ---- the other nets BASELINE.json's metric names, same process, same timing procedure
             if world == 1:
-                for name in ("resnet50", "mobilenet_v1"):  # not the contract's headline: never fewer than 100 timed steps
-                    extras[name], _ = timing.measure_net(name, a, env, max(a.steps, 100), a.warmup, steady=steady, passes=ATTRIBUTION_PASSES)
+                for name in ("resnet50", "mobilenet_v1"):
+                    extras[name], _ = timing.measure_net(name, a, env, a.steps, a.warmup, steady=steady, passes=ATTRIBUTION_PASSES, outputs=outputs)
                 # the one-GPU point of configs[4]'s strong-scaling curve (ResNet-50, 512 images in total)
-                extras["resnet50_global512"], _ = timing.measure_net("resnet50", a, env, *quick, global_batch=512, detail=False)
+                extras["resnet50_global512"], _ = timing.measure_net("resnet50", a, env, a.steps, a.warmup, global_batch=512, detail=False,
+                                                                     outputs=outputs, output_name="resnet50_global512")
             else:
                 # configs[4]: ResNet-50, 512 images in total sharded over the ranks (strong), plus its weak point (64 per GPU)
-                extras["resnet50_global512"], r50_model = timing.measure_net("resnet50", a, env, a.steps, a.warmup, global_batch=512, passes=ATTRIBUTION_PASSES)
-                extras["resnet50"], _ = timing.measure_net("resnet50", a, env, a.steps, a.warmup, detail=False)
+                extras["resnet50_global512"], r50_model = timing.measure_net("resnet50", a, env, a.steps, a.warmup, global_batch=512, passes=ATTRIBUTION_PASSES,
+                                                                             outputs=outputs, output_name="resnet50_global512")
+                extras["resnet50"], _ = timing.measure_net("resnet50", a, env, a.steps, a.warmup, detail=False, outputs=outputs)
                 # the ONE-GPU points of both curves, in the same run: rank 0 alone (its env says world = 1 and it already holds the model, so
                 # there is no collective inside); the other ranks wait at the barrier below
                 if rank == 0:
                     one = dict(env, world=1)
-                    solo(lambda: timing.measure_net("resnet50", a, one, *quick, global_batch=512, detail=False, model=r50_model), extras, "resnet50_global512_one_gpu")
-                    solo(lambda: timing.measure_net("resnet50", a, one, a.steps, a.warmup, detail=False, model=r50_model), extras, "resnet50_one_gpu")
-                    solo(lambda: timing.measure_net(head_net, a, one, a.steps, a.warmup, detail=False, model=model), extras, head_net + "_one_gpu")
+                    solo(lambda: timing.measure_net("resnet50", a, one, a.steps, a.warmup, global_batch=512, detail=False, model=r50_model, outputs=outputs,
+                                                    output_name="resnet50_global512_one_gpu"), extras, "resnet50_global512_one_gpu")
+                    solo(lambda: timing.measure_net("resnet50", a, one, a.steps, a.warmup, detail=False, model=r50_model, outputs=outputs,
+                                                    output_name="resnet50_one_gpu"), extras, "resnet50_one_gpu")
+                    solo(lambda: timing.measure_net(head_net, a, one, a.steps, a.warmup, detail=False, model=model, outputs=outputs,
+                                                    output_name=head_net + "_one_gpu"), extras, head_net + "_one_gpu")
                 dist.barrier()
     shard_ok = None
     if world > 1:
@@ -209,6 +251,8 @@ def main():
             with open(a.manifest_out, "w") as f:
                 json.dump(dict(tree, fusion=a.fusion, argv=sys.argv[1:],
                                nets={k: {q: v[q] for q in ("per_gpu_batch", "sub_batches", "global_batch") if q in v} for k, v in detail["nets"].items()}), f, indent=1)
+        if outputs is not None:
+            dump_outputs(outputs, a.dump_outputs)
         if a.layers_out:
             os.makedirs(os.path.dirname(os.path.abspath(a.layers_out)), exist_ok=True)
             with open(a.layers_out, "w") as f:

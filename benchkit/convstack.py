@@ -10,7 +10,7 @@ from .timing import per_gpu_batch
 
 
 def setup_convstack(a, env):
-    """Conv-stack mode (the hot path in isolation).  -> (step, finalize, batch)"""
+    """Conv-stack mode (the hot path in isolation).  -> (step, finalize, batch, last_output)"""
     import torch
 
     from feathercnn_amd import ConvLayer, booster, nets
@@ -65,6 +65,13 @@ def setup_convstack(a, env):
         except Exception as e:  # capture is an optimisation, never a requirement
             print(f"bench: hipGraph capture unavailable ({e!r}); timing eager launches", file=sys.stderr)
             step, graph_used = eager_step, False
+
+    def last_output():
+        """What the caller of the last layer's ConvBooster::Forward holds after a step: that layer's output, [N][K][Ho][Wo] at the start of `out`."""
+        prm = built[-1][1]
+        shape = (batch, prm.output_channels, prm.output_h, prm.output_w)
+        torch.cuda.synchronize()
+        return out[:batch * prm.output_channels * prm.output_h * prm.output_w].reshape(shape).cpu().numpy()
 
     def finalize(ms_per_step):
         res = {"metric": "images/sec fp32 forward (conv stack) @224x224", "launch": "hipGraph replay per step" if graph_used else "eager launches",
@@ -129,4 +136,4 @@ def setup_convstack(a, env):
             res["weight_broadcast"] = {"ms": round(t_bcast * 1e3, 3), "bytes": bcast_bytes, "collective": "1 flat RCCL broadcast from rank 0"}
         return res
 
-    return step, finalize, batch
+    return step, finalize, batch, last_output

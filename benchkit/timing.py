@@ -48,10 +48,11 @@ def timed_region(step, steps, warmup, env):
     return dt
 
 
-def measure_net(net_name, a, env, steps, warmup, global_batch=0, batch=0, detail=True, steady=0, model=None, passes=5):
+def measure_net(net_name, a, env, steps, warmup, global_batch=0, batch=0, detail=True, steady=0, model=None, passes=5, outputs=None, output_name=None):
     """One benchmark network through the feather::Net runtime: build (rank 0) + one RCCL broadcast of the .bin, timed region,
     per-kernel attribution.  -> result dict (rank 0 carries the detail).  `model` given: no broadcast (the caller already holds the
-    model -- the one-rank reference point that rank 0 times by itself inside an N > 1 run, env["world"] == 1 there)."""
+    model -- the one-rank reference point that rank 0 times by itself inside an N > 1 run, env["world"] == 1 there).  `outputs` given:
+    the output blob of the last timed step (what Net::Extract hands a caller) is stored there under `output_name` (default: the net)."""
     import numpy as np
     import torch
 
@@ -86,6 +87,8 @@ def measure_net(net_name, a, env, steps, warmup, global_batch=0, batch=0, detail
         raise SystemExit(f"bench: {net_name}: the net's output is not a probability vector")
     sustained_mfma()  # the device's pure-MFMA ceiling (reported next to every MFMA roofline) is measured BEFORE the timed region, once per process
     dt = timed_region(net.Forward, steps, warmup, env)
+    if outputs is not None:
+        outputs[output_name or net_name] = net.Extract(out_name)
     total_images = global_batch if global_batch else world * nb
     res = {"net": net_name, "images_per_s": round(total_images * steps / dt, 2), "ms_per_step": round(dt / steps * 1e3, 4), "steps": steps,
            "warmup": warmup, "per_gpu_batch": nb, "global_batch": total_images, "scaling": "strong" if global_batch else "weak",

@@ -80,9 +80,17 @@ def test_bench_gpus_flag_starts_the_ranks_itself(cuda, tmp_path):
 
 @pytest.mark.gpu
 def test_bench_eight_ranks_rehearsal_on_one_gpu(cuda, tmp_path):
-    """the REAL 8-rank shape before an 8-GPU node sees it -- launcher, port choice, eight per-rank arenas, config 5 split 64 per
-    rank, the 17-image ragged shard check, the line size -- rehearsed on one GPU (every rank on cuda:0, collectives over gloo)."""
-    env = dict(os.environ, FHIP_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    """the REAL 8-rank shape -- launcher, port choice, eight per-rank arenas, config 5 split 64 per rank, the 17-image ragged
+    shard check, the line size -- one rank per GPU over RCCL.  (The name is kept from its first form, which put all eight ranks on one GPU:
+    eight rank processes plus the test and the launcher hold one device at once, more than a shared test machine admits.)  On one GPU,
+    test_bench_three_ranks_rehearsal_on_one_gpu rehearses an N > 2 run within that bound; tests/test_bench_report_cpu.py checks the N = 8
+    line and tests/test_distributed_cpu.py the 8-way shard arithmetic."""
+    import torch
+    have = torch.cuda.device_count()
+    if have < 8:
+        pytest.skip(f"needs 8 GPUs, found {have}")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.pop("FHIP_BENCH_SHARE_GPU", None)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline"]
@@ -98,6 +106,28 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu(cuda, tmp_path):
     assert s8["n_gpus"] == 8 and s8["strong_eff"] > 0 and s8["weak_eff"] > 0
     d = json.load(open(detail))
     assert d["nets"]["resnet50_global512"]["global_batch"] == 512 and d["nets"]["resnet50"]["global_batch"] == 512
+
+
+@pytest.mark.gpu
+def test_bench_three_ranks_rehearsal_on_one_gpu(cuda, tmp_path):
+    """An N > 2 run rehearsed on one GPU (FHIP_BENCH_SHARE_GPU=1, every rank on cuda:0, collectives over gloo) with a process count a shared
+    machine admits (the test, the torch.distributed.run agent and three ranks): three per-rank arenas, config 5's 512 images split RAGGED
+    over the ranks (171 / 171 / 170), the 7-image ragged shard check, both scaling efficiencies, and the line."""
+    env = dict(os.environ, FHIP_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1", "--master-port",
+           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline"]
+    out, detail = _run(cmd, env, tmp_path)
+    r = _line(out)
+    assert r["n_gpus"] == 3 and r["steps"] == 2 and r["scaling"] == "weak" and r["value"] > 0 and r["config"]["global_batch"] == 96
+    sc = r["shard_check"]
+    assert sc["ok"] and sc["global_batch"] == 7 and sc["shares"] == [3, 2, 2] and sc["max_norm_err"] <= 1e-5, sc
+    other = r["config"]["other_nets"]
+    assert other["resnet50_g512"]["per_gpu_batch"] == 171 and other["resnet50_g512"]["img_s"] > 0   # rank 0's share of config 5
+    assert other["resnet50_b64"]["per_gpu_batch"] == 64 and other["resnet50_g512_one_gpu"]["per_gpu_batch"] == 512
+    s3 = other["resnet50_scaling"]
+    assert s3["n_gpus"] == 3 and s3["strong_eff"] > 0 and s3["weak_eff"] > 0
+    d = json.load(open(detail))
+    assert d["nets"]["resnet50_global512"]["global_batch"] == 512 and d["nets"]["resnet50"]["global_batch"] == 192
 
 
 @pytest.mark.gpu
@@ -125,3 +155,39 @@ def test_bench_single_rank_line_is_compact_and_complete(cuda, tmp_path):
     assert ro["bound"] == "mfma" and len(ro["frac_passes"]) == 7 and ro["frac_min"] <= ro["frac"] <= ro["frac_max"] and abs(ro["frac"] - ro["achieved"] / ro["peak"]) < 2e-3
     d = json.load(open(detail))
     assert len(d["tables"]["vgg16"]) >= 15 and d["rooflines"]["vgg16"][0]["note"]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_what_the_timed_net_computed(cuda, tmp_path):
+    """--dump-outputs: the .npy bench.py writes is the output blob of its last timed step -- the same numbers a caller gets from a Net of the
+    same model, settings and seeded input (MobileNet-V1 runs as two sub-batch replicas: the dump is the whole batch)."""
+    import numpy as np
+    import torch
+
+    from feathercnn_amd import model_zoo
+    from feathercnn_amd.net import Net
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FHIP_BENCH_SHARE_GPU"):
+        env.pop(k, None)
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--net", "mobilenet_v1", "--batch", "4",
+           "--no-steady", "--no-cpu-baseline", "--dump-outputs", str(dump)]
+    out, _ = _run(cmd, env, tmp_path)
+    r = _line(out, only_line=True)
+    assert r["steps"] == 2 and r["config"]["per_gpu_batch"] == 4
+    assert os.listdir(dump) == ["mobilenet_v1.npy"]
+    got = np.load(dump / "mobilenet_v1.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 1000, 1, 1)
+    p, b, i, o = model_zoo.MODELS["mobilenet_v1"]()
+    gen = torch.Generator(device=cuda)
+    gen.manual_seed(4321)  # benchkit.timing.measure_net's input of rank 0
+    x = torch.rand((4, 3, 224, 224), device=cuda, generator=gen) * 2 - 1
+    net = Net(fusion=3, graph=True, tuned=True, concurrency=True, sub_batches=2)  # what bench.py builds by default
+    net.LoadParam(p)
+    net.LoadWeights(b)
+    net.FeedInput(i, x)
+    net.Forward()
+    want = net.Extract(o)
+    net.close()
+    assert np.abs(got - want).max() <= 1e-5 * np.abs(want).max()
+    np.testing.assert_allclose(got.reshape(4, -1).sum(axis=1), 1.0, atol=1e-3)
