@@ -749,7 +749,10 @@ int depthwise_init(const fhip_conv_param& p, float* packed, const float* kernel,
     const size_t n = (size_t)p.group * p.kernel_h * p.kernel_w;
     FHIP_CHECK_HIP(hipMemcpyAsync(packed, kernel, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     size_t off = 0;
-    if (depthwise_packed_floats(p, &off) > off)
+    const size_t total = depthwise_packed_floats(p, &off);
+    // the words between the dense filters and the 16-byte-aligned 12-float copies: every word of the reported size is defined
+    if (off > n) FHIP_CHECK_HIP(hipMemsetAsync(packed + n, 0, (off - n) * sizeof(float), s));
+    if (total > off)
     {
         hipLaunchKernelGGL(depthwise_pack12_kernel, dim3(ceil_div(p.group * 12, 256)), dim3(256), 0, s, packed + off, kernel, p.group);
         FHIP_CHECK_HIP(hipGetLastError());
