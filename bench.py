@@ -7,30 +7,40 @@ A "step" is one forward pass of a benchmark network over one synthetic batch alr
       The headline `value` is BASELINE.json configs[1]: VGG-16, 32 images per GPU, fp32, 224x224, the whole network through the
       feather::Net runtime (every convolution through the ConvBooster hot path plus the layers between them), timed exactly as the
       contract says: W untimed steps, then K steps between barrier + synchronize, max over ranks; weak scaling at N > 1.
-      The SAME process then times the other nets BASELINE.json's metric names with the same procedure:  N = 1: ResNet-50 b64
+      A plain run does only that: set up, warm up, time the K steps, write --dump-outputs if given, print the line.  With
+      --dump-outputs it also builds the other nets --full times (below) and steps each once, untimed, for its array, so that both
+      write the same files.
+  python bench.py --full [--gpus N] [--steps K] [--warmup W]
+      The same headline first (the pure-MFMA calibration runs once before its timed region), then everything else the benchmark
+      measures or checks.  After the K steps the headline net runs the steady-state cross-check region (--no-steady drops it) and its
+      per-kernel attribution passes (roofline rows, per-layer table), and the SAME process then times the other nets BASELINE.json's
+      metric names with the same procedure:  N = 1: ResNet-50 b64
       (configs[2]), MobileNet-V1 b256 (configs[3]) and ResNet-50 with 512 images (the one-GPU point of configs[4]);  N > 1: configs[4]
       itself -- ResNet-50, 512 images in total sharded over the ranks (strong scaling) -- its weak point (64 per GPU), and the one-GPU
-      points of both curves (rank 0 alone), so that weak AND strong efficiency come out of ONE run.
+      points of both curves (rank 0 alone), so that weak AND strong efficiency come out of ONE run.  Then the N > 1 shard check and, at
+      N = 1, the CPU baseline (--no-cpu-baseline drops it).
   python bench.py --net resnet50|mobilenet_v1|vgg16|squeezenet_v1.1 [--batch B | --global-batch G] [--fusion 0|1|2|3]
       Only that net (its images/s becomes `value`).
   python bench.py --mode convstack [--net ...]
-      Only the convolution layers, each through ConvBooster::Forward with bias + ReLU fused and its input re-drawn (not chained).
+      Only the convolution layers, each through ConvBooster::Forward with bias + ReLU fused and its input re-drawn (not chained); with
+      --full also their per-layer stage timing and roofline rows.
   python bench.py ... --dump-outputs DIR
       After the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32): the output blob a caller
-      of Net::Extract receives for every net the run timed (<name> = the net, or its key in the line's nets, e.g. resnet50_global512),
+      of Net::Extract receives for every net a --full run times (<name> = the net, or its key in the line's nets, e.g. resnet50_global512),
       rank 0's shard at N > 1; in convstack mode the last layer's output (convstack_<net>).  Inputs and weights are seeded, so the same
       arguments give the same inputs from run to run.  At most 64 MB of data in all: a larger array is cut to a fixed, seeded sample of its
       images (of its elements where not even one image fits).
 
---steps K sets the number of timed steps of every net the run times (the steady-state cross-check region, --no-steady to drop it, is
-separate); `ms_per_step` in the line is one timed step of the headline net.
+--steps K sets the number of timed steps of every net the run times (the steady-state cross-check region of --full is separate);
+`ms_per_step` in the line is one timed step of the headline net.
 
-Rank 0 prints ONE JSON line of at most 8 KiB (benchkit/report.py enforces it): the contract keys, `config` (with `other_nets`: images/s and
-the roofline fraction of each hot kernel of the other metric nets, and `resnet50_scaling`: weak and strong efficiency with their
-definitions), `roofline` (the dominant kernel of the headline net -- the Winograd tile GEMM on fp32 MFMA for VGG-16 -- with `frac` = the
-median of >= 5 eager attribution passes next to frac_min / frac_max / frac_passes, `traffic` from the committed PMC digest, `also` = the
-other hot kernels) and `cpu_baseline` (the REAL reference runtime, oracle/_ref, on this host's cores).  Everything long -- every roofline
-row with its notes, per-layer tables, the CPU sweep -- goes to the side file named by `detail` (--detail-out, default bench_detail.json).
+Rank 0 prints ONE JSON line of at most 8 KiB (benchkit/report.py enforces it): the contract keys and `config`; with --full also
+`config.other_nets` (images/s and the roofline fraction of each hot kernel of the other metric nets, and `resnet50_scaling`: weak and
+strong efficiency with their definitions), `roofline` (the dominant kernel of the headline net -- the Winograd tile GEMM on fp32 MFMA for
+VGG-16 -- with `frac` = the median of >= 5 eager attribution passes next to frac_min / frac_max / frac_passes, `traffic` from the committed
+PMC digest, `also` = the other hot kernels) and `cpu_baseline` (the REAL reference runtime, oracle/_ref, on this host's cores).  Everything
+long -- every roofline row with its notes, per-layer tables, the CPU sweep -- goes to the side file named by `detail` (--detail-out,
+default bench_detail.json).
 
 Multi-GPU: the batch dimension is sharded; the model is generated on rank 0 and its .bin broadcast once over RCCL/xGMI, every rank runs its
 own Init; there is no steady-state collective.  `python bench.py --gpus N` without a launcher starts its N ranks itself; under a launcher
@@ -41,6 +51,7 @@ The work is in benchkit/ (timing, attribution, roofs, cpu, convstack, launcher, 
 from __future__ import annotations
 
 import argparse
+import functools
 import json
 import os
 import sys
@@ -65,16 +76,19 @@ def parse():
                     "else 1).  Started WITHOUT a launcher and N > 1, bench.py starts the N ranks itself (launch_ranks)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--net", default=None, choices=list(DEFAULT_BATCH), help="time ONLY this net (default: VGG-16 as the headline value, then ResNet-50 and MobileNet-V1 in the same process)")
-    ap.add_argument("--headline-only", action="store_true", help="skip the additional nets of the default run")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the benchmark measures or checks: steady-state "
+                    "region, attribution passes and roofline rows, the other nets, the N > 1 shard check, the CPU baseline (see the module docstring)")
+    ap.add_argument("--net", default=None, choices=list(DEFAULT_BATCH), help="time ONLY this net (default: VGG-16 as the headline value; with --full "
+                    "then ResNet-50 and MobileNet-V1 in the same process)")
+    ap.add_argument("--headline-only", action="store_true", help="skip the additional nets (of --full, and their --dump-outputs arrays)")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the BASELINE.json config)")
     ap.add_argument("--global-batch", type=int, default=0, help="fix the TOTAL batch instead (strong scaling, SURVEY.md 8d config 5: "
                     "--net resnet50 --global-batch 512 --gpus 8); rank r takes shard_range(global, r, N) images")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-steady", action="store_true", help="skip the 200-step steady-state cross-check region (profiling runs: every extra step is traced)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-steady", action="store_true", help="--full: skip the 200-step steady-state cross-check region (profiling runs: every extra step is traced)")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of one hipGraph replay per step")
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes for the CPU baseline (default: one per host core, bounded by free memory)")
-    ap.add_argument("--layers-out", default="", help="write the per-layer table (JSON) here")
+    ap.add_argument("--layers-out", default="", help="--full: write the per-layer table (JSON) here")
     ap.add_argument("--detail-out", default="", help="side file for everything that is not in the stdout line (default: bench_detail.json in the "
                     "working directory; the line names it under `detail`)")
     ap.add_argument("--manifest-out", default="", help="write what ran (tree head, source fingerprint, per-net batch / replicas, fusion level) here: "
@@ -89,7 +103,10 @@ def parse():
                     "timed net to DIR/<name>.npy (float32, <= 64 MB in all; see the module docstring)")
     ap.add_argument("--fusion", type=int, default=3, help="net mode: 0 none, 1 the reference's TryFuse patterns, 2 + BN/Scale folded into conv weights, "
                     "conv+pool, conv+add, depthwise+pointwise, 3 + chained Winograd layers (feather_net.h, fhip_net_set_fusion)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.layers_out and not a.full:
+        ap.error("--layers-out needs --full (the per-layer table comes from the attribution passes)")
+    return a
 
 
 DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
@@ -171,7 +188,8 @@ def main():
         affinity = pin_rank_to_gpu_numa_node(local, local_world, ids)
     explicit = a.net is not None
     head_net = a.net or "vgg16"
-    steady = 0 if a.no_steady else STEADY_STEPS
+    steady = STEADY_STEPS if a.full and not a.no_steady else 0
+    passes = ATTRIBUTION_PASSES if a.full else 0  # 0: no attribution passes, no MFMA calibration
     outputs = {} if (a.dump_outputs and rank == 0) else None  # --dump-outputs: rank 0's output of the last timed step, per net
 
     if a.mode == "convstack":
@@ -181,50 +199,54 @@ def main():
         dt = timing.timed_region(step, a.steps, a.warmup, env)
         if outputs is not None:
             outputs["convstack_" + head_net] = last_output()
-        head = finalize(dt / a.steps * 1e3)
+        head = finalize(dt / a.steps * 1e3, attribute=a.full)
         total = a.global_batch if a.global_batch else world * batch
         head.update({"net": head_net, "images_per_s": round(total * a.steps / dt, 2), "ms_per_step": round(dt / a.steps * 1e3, 4),
                      "per_gpu_batch": batch, "global_batch": total, "scaling": "strong" if a.global_batch else "weak"})
         model, extras = None, {}
     else:
         # ---- headline: BASELINE.json configs[1] (VGG-16, 32 images per GPU) unless --net says otherwise; weak scaling at N > 1
-        head, model = timing.measure_net(head_net, a, env, a.steps, a.warmup, a.global_batch, a.batch, steady=steady, passes=ATTRIBUTION_PASSES,
+        head, model = timing.measure_net(head_net, a, env, a.steps, a.warmup, a.global_batch, a.batch, steady=steady, passes=passes,
                                          outputs=outputs)
         extras = {}
-        if not explicit and not a.headline_only:
-            # ---- the other nets BASELINE.json's metric names, same process, same timing procedure
+        if (a.full or a.dump_outputs) and not explicit and not a.headline_only:
+            # ---- the other nets BASELINE.json's metric names, same process, same timing procedure.  A plain run with --dump-outputs runs
+            # them for their arrays alone (output_only: built and stepped once, nothing timed, nothing reported), so that it writes the same
+            # files as --full
+            measure = functools.partial(timing.measure_net, output_only=not a.full)
+            record = extras if a.full else {}
             if world == 1:
                 for name in ("resnet50", "mobilenet_v1"):
-                    extras[name], _ = timing.measure_net(name, a, env, a.steps, a.warmup, steady=steady, passes=ATTRIBUTION_PASSES, outputs=outputs)
+                    record[name], _ = measure(name, a, env, a.steps, a.warmup, steady=steady, passes=ATTRIBUTION_PASSES, outputs=outputs)
                 # the one-GPU point of configs[4]'s strong-scaling curve (ResNet-50, 512 images in total)
-                extras["resnet50_global512"], _ = timing.measure_net("resnet50", a, env, a.steps, a.warmup, global_batch=512, detail=False,
-                                                                     outputs=outputs, output_name="resnet50_global512")
+                record["resnet50_global512"], _ = measure("resnet50", a, env, a.steps, a.warmup, global_batch=512, detail=False,
+                                                          outputs=outputs, output_name="resnet50_global512")
             else:
                 # configs[4]: ResNet-50, 512 images in total sharded over the ranks (strong), plus its weak point (64 per GPU)
-                extras["resnet50_global512"], r50_model = timing.measure_net("resnet50", a, env, a.steps, a.warmup, global_batch=512, passes=ATTRIBUTION_PASSES,
-                                                                             outputs=outputs, output_name="resnet50_global512")
-                extras["resnet50"], _ = timing.measure_net("resnet50", a, env, a.steps, a.warmup, detail=False, outputs=outputs)
+                record["resnet50_global512"], r50_model = measure("resnet50", a, env, a.steps, a.warmup, global_batch=512, passes=ATTRIBUTION_PASSES,
+                                                                  outputs=outputs, output_name="resnet50_global512")
+                record["resnet50"], _ = measure("resnet50", a, env, a.steps, a.warmup, detail=False, outputs=outputs)
                 # the ONE-GPU points of both curves, in the same run: rank 0 alone (its env says world = 1 and it already holds the model, so
                 # there is no collective inside); the other ranks wait at the barrier below
                 if rank == 0:
                     one = dict(env, world=1)
-                    solo(lambda: timing.measure_net("resnet50", a, one, a.steps, a.warmup, global_batch=512, detail=False, model=r50_model, outputs=outputs,
-                                                    output_name="resnet50_global512_one_gpu"), extras, "resnet50_global512_one_gpu")
-                    solo(lambda: timing.measure_net("resnet50", a, one, a.steps, a.warmup, detail=False, model=r50_model, outputs=outputs,
-                                                    output_name="resnet50_one_gpu"), extras, "resnet50_one_gpu")
-                    solo(lambda: timing.measure_net(head_net, a, one, a.steps, a.warmup, detail=False, model=model, outputs=outputs,
-                                                    output_name=head_net + "_one_gpu"), extras, head_net + "_one_gpu")
+                    solo(lambda: measure("resnet50", a, one, a.steps, a.warmup, global_batch=512, detail=False, model=r50_model, outputs=outputs,
+                                         output_name="resnet50_global512_one_gpu"), record, "resnet50_global512_one_gpu")
+                    solo(lambda: measure("resnet50", a, one, a.steps, a.warmup, detail=False, model=r50_model, outputs=outputs,
+                                         output_name="resnet50_one_gpu"), record, "resnet50_one_gpu")
+                    solo(lambda: measure(head_net, a, one, a.steps, a.warmup, detail=False, model=model, outputs=outputs,
+                                         output_name=head_net + "_one_gpu"), record, head_net + "_one_gpu")
                 dist.barrier()
     shard_ok = None
     if world > 1:
-        if a.mode == "net":
+        if a.mode == "net" and a.full:
             # errors of a rank's own run are caught inside and agreed on with an all_reduce before the gather (no mismatched collectives)
             shard_ok = timing.shard_check(head_net, model, a, env)
         dist.barrier()
 
     if rank == 0:
         cpu = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             from benchkit import cpu as cpu_leg
             try:
                 cpu = cpu_leg.cpu_baseline(head_net, a.cpu_procs) if a.mode == "convstack" else cpu_leg.net_cpu_baseline(head_net, model, a.cpu_procs)
@@ -234,11 +256,13 @@ def main():
         tree = provenance.tree_head()
         args = {"mode": a.mode, "steps": a.steps, "warmup": a.warmup, "no_graph": a.no_graph, "reference_selection": a.reference_selection,
                 "no_overlap": a.no_overlap, "fusion": a.fusion}
-        calib = dict(sustained_mfma(), note="fhip_calibrate_mfma_f32: a kernel of nothing but v_mfma_f32_32x32x2_f32 chains at 3 waves per SIMD on every "
-                     "CU; its TFLOP/s and the shader clock it ran at (nominal peak 157.3 TFLOP/s assumes 2.4 GHz)")
+        calib = None
+        if a.full:
+            calib = dict(sustained_mfma(), note="fhip_calibrate_mfma_f32: a kernel of nothing but v_mfma_f32_32x32x2_f32 chains at 3 waves per SIMD on "
+                         "every CU; its TFLOP/s and the shader clock it ran at (nominal peak 157.3 TFLOP/s assumes 2.4 GHz)")
         detail_path = a.detail_out or "bench_detail.json"
         line, detail = report.compose(head, extras, args=args, world=world, cpu=cpu, shard_ok=shard_ok, affinity=affinity, tree=tree,
-                                      calibration=calib, detail_path=detail_path, traffic_note=TRAFFIC_NOTE)
+                                      calibration=calib, detail_path=detail_path, traffic_note=TRAFFIC_NOTE if a.full else "")
         text = report.fit_line(line)  # <= 8 KiB, or optional keys are shed; never more
         try:
             os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)

@@ -19,4 +19,4 @@ DEFAULT_BATCH = {"vgg16": 32, "resnet50": 64, "mobilenet_v1": 256, "squeezenet_v
 # sub-batch replicas of the net per GPU (fhip_net_set_sub_batches), measured with tools/dual_stream_bench.py: MobileNet-V1 b256 gains 8 %
 # with two (its HBM-bound depthwise kernels run under the other share's MFMA-bound 1x1 kernels), VGG-16 and ResNet-50 gain nothing
 SUB_BATCHES = {"mobilenet_v1": 2}
-STEADY_STEPS = 200  # length of the cross-check region timed after the contract's K steps ("steady_state" in the detail file)
+STEADY_STEPS = 200  # length of the cross-check region bench.py --full times after the contract's K steps ("steady_state" in the detail file)

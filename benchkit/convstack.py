@@ -73,10 +73,15 @@ def setup_convstack(a, env):
         torch.cuda.synchronize()
         return out[:batch * prm.output_channels * prm.output_h * prm.output_w].reshape(shape).cpu().numpy()
 
-    def finalize(ms_per_step):
+    def finalize(ms_per_step, attribute=True):
+        """-> the result dict; on rank 0 with `attribute` (bench.py --full) also the per-layer stage timing and the roofline rows."""
         res = {"metric": "images/sec fp32 forward (conv stack) @224x224", "launch": "hipGraph replay per step" if graph_used else "eager launches",
                "workload": f"{a.net} conv layers ({len(layers)}), batch {batch} per GPU, 224x224x3, bias+ReLU fused, fp32"}
         if rank != 0:
+            return res
+        if world > 1:
+            res["weight_broadcast"] = {"ms": round(t_bcast * 1e3, 3), "bytes": bcast_bytes, "collective": "1 flat RCCL broadcast from rank 0"}
+        if not attribute:
             return res
         table = []
         reps = max(3, min(a.steps, 10))
@@ -132,8 +137,6 @@ def setup_convstack(a, env):
         res["conv_gflops_per_s_direct"] = round(flops_direct_total * world / (ms_per_step * 1e6), 1)
         res["conv_direct_frac_of_mfma_peak"] = round(flops_direct_total / (ms_per_step * 1e6) / 1e3 / PEAK_MFMA_F32_TFLOPS, 4)
         res["table"] = table
-        if world > 1:
-            res["weight_broadcast"] = {"ms": round(t_bcast * 1e3, 3), "bytes": bcast_bytes, "collective": "1 flat RCCL broadcast from rank 0"}
         return res
 
     return step, finalize, batch, last_output

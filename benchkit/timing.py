@@ -48,11 +48,15 @@ def timed_region(step, steps, warmup, env):
     return dt
 
 
-def measure_net(net_name, a, env, steps, warmup, global_batch=0, batch=0, detail=True, steady=0, model=None, passes=5, outputs=None, output_name=None):
+def measure_net(net_name, a, env, steps, warmup, global_batch=0, batch=0, detail=True, steady=0, model=None, passes=5, outputs=None, output_name=None,
+                output_only=False):
     """One benchmark network through the feather::Net runtime: build (rank 0) + one RCCL broadcast of the .bin, timed region,
     per-kernel attribution.  -> result dict (rank 0 carries the detail).  `model` given: no broadcast (the caller already holds the
     model -- the one-rank reference point that rank 0 times by itself inside an N > 1 run, env["world"] == 1 there).  `outputs` given:
-    the output blob of the last timed step (what Net::Extract hands a caller) is stored there under `output_name` (default: the net)."""
+    the output blob of the last timed step (what Net::Extract hands a caller) is stored there under `output_name` (default: the net).
+    passes=0 (a plain bench run, no --full): neither the MFMA calibration nor the attribution passes run; `detail` then keeps only the
+    workload, device memory and weight broadcast.  output_only: no timed region either -- the net is built and runs ONE step (a replay of
+    the step the timed region repeats on the same input) for `outputs` alone -> (None, model)."""
     import numpy as np
     import torch
 
@@ -85,7 +89,17 @@ def measure_net(net_name, a, env, steps, warmup, global_batch=0, batch=0, detail
     prob = net.Extract(out_name)
     if not np.isfinite(prob).all() or abs(float(prob[0].sum()) - 1.0) > 1e-3:
         raise SystemExit(f"bench: {net_name}: the net's output is not a probability vector")
-    sustained_mfma()  # the device's pure-MFMA ceiling (reported next to every MFMA roofline) is measured BEFORE the timed region, once per process
+    if output_only:
+        net.Forward()
+        torch.cuda.synchronize()
+        if outputs is not None:
+            outputs[output_name or net_name] = net.Extract(out_name)
+        net.close()
+        del net, x
+        torch.cuda.empty_cache()
+        return None, model
+    if passes:
+        sustained_mfma()  # the device's pure-MFMA ceiling (reported next to every MFMA roofline) is measured BEFORE the timed region, once per process
     dt = timed_region(net.Forward, steps, warmup, env)
     if outputs is not None:
         outputs[output_name or net_name] = net.Extract(out_name)
@@ -100,22 +114,25 @@ def measure_net(net_name, a, env, steps, warmup, global_batch=0, batch=0, detail
         dt2 = timed_region(net.Forward, n2, 0, env)
         res["steady_state"] = {"steps": n2, "images_per_s": round(total_images * n2 / dt2, 2), "ms_per_step": round(dt2 / n2 * 1e3, 4)}
     if rank == 0 and detail:
-        if replicas > 1:
-            # kernels of concurrent replicas share the chip, so their individual durations are not a roofline measurement: the
-            # per-kernel attribution runs the same batch through a single-stream net (same kernels, same shapes but the batch)
-            net.close()
-            net = make_net(1)
-            net.FeedInput(in_name, x)
-            net.Forward()
-            torch.cuda.synchronize()
-        att = attribute(net, max(5, passes))
-        attach_traffic(net_name, att["rooflines"], batch=nb, sub_batches=replicas, fusion=a.fusion)
+        att = None
+        if passes:
+            if replicas > 1:
+                # kernels of concurrent replicas share the chip, so their individual durations are not a roofline measurement: the
+                # per-kernel attribution runs the same batch through a single-stream net (same kernels, same shapes but the batch)
+                net.close()
+                net = make_net(1)
+                net.FeedInput(in_name, x)
+                net.Forward()
+                torch.cuda.synchronize()
+            att = attribute(net, max(5, passes))
+            attach_traffic(net_name, att["rooflines"], batch=nb, sub_batches=replicas, fusion=a.fusion)
         n_model_layers = len(netcheck_layers(p))
         res["workload"] = (f"{net_name} whole net ({n_model_layers} layers in the model file, {len(net.layers())} after fusion level {a.fusion}), "
                            f"batch {nb} per GPU" + (f" as {replicas} concurrent sub-batch replicas of the net (fhip_net_set_sub_batches)" if replicas > 1 else "")
                            + ", 224x224x3, fp32, synthetic ncnn .param/.bin")
-        res["conv_tflops_direct"] = round(att.pop("conv_direct_flops_per_step") * world / (dt / steps) / 1e12, 2)
-        res.update(att)
+        if att is not None:
+            res["conv_tflops_direct"] = round(att.pop("conv_direct_flops_per_step") * world / (dt / steps) / 1e12, 2)
+            res.update(att)
         res["device_memory"] = net.memory()
         if world > 1:
             res["weight_broadcast"] = {"ms": round(t_bcast * 1e3, 3), "bytes": bcast_bytes, "collective": "1 flat RCCL broadcast of the .bin from rank 0"}

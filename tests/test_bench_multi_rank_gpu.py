@@ -38,7 +38,7 @@ def test_bench_two_ranks_share_one_gpu(cuda, tmp_path):
     from feathercnn_amd import model_zoo
     env = dict(os.environ, FHIP_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline"]
+           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline", "--full"]
     out, detail = _run(cmd, env, tmp_path)
     r = _line(out)
     d = json.load(open(detail))
@@ -64,7 +64,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself(cuda, tmp_path):
     env = dict(os.environ, FHIP_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline", "--full"]
     out, detail = _run(cmd, env, tmp_path)
     r = _line(out, only_line=True)  # the launcher's stdout is rank 0's JSON line and nothing else
     assert r["n_gpus"] == 2 and r["scaling"] == "weak" and r["value"] > 0
@@ -93,7 +93,7 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu(cuda, tmp_path):
     env.pop("FHIP_BENCH_SHARE_GPU", None)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline", "--full"]
     out, detail = _run(cmd, env, tmp_path)
     r = _line(out, only_line=True)
     assert r["n_gpus"] == 8 and r["scaling"] == "weak" and r["value"] > 0 and r["config"]["global_batch"] == 256
@@ -115,7 +115,7 @@ def test_bench_three_ranks_rehearsal_on_one_gpu(cuda, tmp_path):
     over the ranks (171 / 171 / 170), the 7-image ragged shard check, both scaling efficiencies, and the line."""
     env = dict(os.environ, FHIP_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1", "--master-port",
-           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline"]
+           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--no-steady", "--no-cpu-baseline", "--full"]
     out, detail = _run(cmd, env, tmp_path)
     r = _line(out)
     assert r["n_gpus"] == 3 and r["steps"] == 2 and r["scaling"] == "weak" and r["value"] > 0 and r["config"]["global_batch"] == 96
@@ -141,12 +141,12 @@ def test_bench_gpus_flag_must_agree_with_the_launcher(cuda):
 
 @pytest.mark.gpu
 def test_bench_single_rank_line_is_compact_and_complete(cuda, tmp_path):
-    """The N = 1 form of the driver's command (shortened: headline net only, no CPU leg): ONE stdout line of at most 8 KiB that json.loads, with the contract keys,
+    """The N = 1 form of the driver's command with --full (shortened: headline net only, no CPU leg): ONE stdout line of at most 8 KiB that json.loads, with the contract keys,
     `roofline` carrying the spread of its 7 attribution passes, and everything long in the detail side file the line names."""
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FHIP_BENCH_SHARE_GPU"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--headline-only", "--no-steady", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--headline-only", "--no-steady", "--no-cpu-baseline", "--full"]
     out, detail = _run(cmd, env, tmp_path)
     r = _line(out, only_line=True)
     assert r["n_gpus"] == 1 and r["steps"] == 3 and r["warmup"] == 1 and r["value"] > 0 and r["dtype"] == "f32" and r["vs_baseline"] is None
@@ -155,6 +155,25 @@ def test_bench_single_rank_line_is_compact_and_complete(cuda, tmp_path):
     assert ro["bound"] == "mfma" and len(ro["frac_passes"]) == 7 and ro["frac_min"] <= ro["frac"] <= ro["frac_max"] and abs(ro["frac"] - ro["achieved"] / ro["peak"]) < 2e-3
     d = json.load(open(detail))
     assert len(d["tables"]["vgg16"]) >= 15 and d["rooflines"]["vgg16"][0]["note"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_only(cuda, tmp_path):
+    """The driver's plain command (no --full): the headline net alone is timed -- its contract keys and `config` in ONE line, and none of what
+    --full adds (other nets, roofline, CPU baseline, calibration).  --dump-outputs still writes the array of every net --full times."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FHIP_BENCH_SHARE_GPU"):
+        env.pop(k, None)
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)]
+    out, detail = _run(cmd, env, tmp_path)
+    r = _line(out, only_line=True)
+    assert r["n_gpus"] == 1 and r["steps"] == 3 and r["warmup"] == 1 and r["value"] > 0 and r["ms_per_step"] > 0 and r["dtype"] == "f32"
+    assert r["metric"] == "images/sec fp32 forward @224x224" and r["unit"] == "images/s" and r["higher_is_better"] is True
+    assert r["config"]["net"] == "vgg16" and r["config"]["per_gpu_batch"] == 32 and r["config"]["workload"] and r["config"]["other_nets"] == {}
+    assert not {"roofline", "cpu_baseline", "mfma_calibration", "shard_check"} & set(r)
+    assert list(json.load(open(detail))["nets"]) == ["vgg16"]
+    assert sorted(os.listdir(dump)) == ["mobilenet_v1.npy", "resnet50.npy", "resnet50_global512.npy", "vgg16.npy"]
 
 
 @pytest.mark.gpu

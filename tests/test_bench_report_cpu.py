@@ -155,6 +155,36 @@ def test_convstack_line():
     assert "conv stack" in r["metric"] and r["cpu_baseline"] == {"value": None, "error": "boom"}
 
 
+def test_line_of_a_plain_run():
+    """A plain run (no --full) times the headline net alone, with no attribution passes, calibration or CPU leg: the line carries the contract
+    keys and `config` and nothing that was not measured."""
+    head = {"net": "vgg16", "images_per_s": 9921.83, "ms_per_step": 3.2252, "steps": 100, "warmup": 5, "per_gpu_batch": 32, "global_batch": 32,
+            "scaling": "weak", "sub_batches": 1, "workload": "vgg16 whole net (38 layers in the model file, 22 after fusion level 3), batch 32 per GPU",
+            "device_memory": {"arena": 1 << 30}}
+    line, detail = report.compose(head, {}, args=ARGS, world=1, tree=TREE, detail_path="bench_detail.json")
+    r = json.loads(report.fit_line(line))
+    for k in report.CONTRACT_KEYS:
+        assert k in r, k
+    assert r["value"] == 9921.83 and r["ms_per_step"] == 3.2252 and r["unit"] == "images/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert r["config"]["workload"] and r["config"]["other_nets"] == {} and "shed" not in r
+    assert not {"roofline", "cpu_baseline", "mfma_calibration", "shard_check"} & set(r)
+    assert detail["nets"]["vgg16"]["images_per_s"] == 9921.83 and detail["tables"] == {"vgg16": []}
+
+
+def test_plain_run_is_the_default_and_layers_out_needs_full(monkeypatch):
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--layers-out", "t.json"])
+    assert bench.parse().full is True
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--layers-out", "t.json"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_only_the_cpu_baseline_leg_touches_the_oracle():
     """bench.py may use oracle/ in its cpu_baseline leg only: of benchkit's modules exactly cpu.py imports it, bench.py itself does not."""
     import os

@@ -20,7 +20,7 @@ for round in $(seq 1 ${ROUNDS:-2}); do
   for bp in $BPS; do
     cp $R/tools/_build/bp_$bp/libfeather_hip.so $R/feathercnn_amd/libfeather_hip.so
     for net in ${NETS:-vgg16 resnet50}; do
-      timeout 300 python $R/bench.py --net $net --steps 30 --warmup 5 --no-cpu-baseline --no-steady > $O/${net}_bp${bp}_r$round.json 2> $O/${net}_bp${bp}_r$round.err || echo "FAILED $net bp $bp"
+      timeout 300 python $R/bench.py --net $net --steps 30 --warmup 5 --full --no-cpu-baseline --no-steady > $O/${net}_bp${bp}_r$round.json 2> $O/${net}_bp${bp}_r$round.err || echo "FAILED $net bp $bp"
     done
   done
 done

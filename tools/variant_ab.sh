@@ -22,7 +22,7 @@ for round in $(seq 1 ${ROUNDS:-3}); do
     name=${v%%=*}
     cp $R/tools/_build/var_$name/libfeather_hip.so $R/feathercnn_amd/libfeather_hip.so
     for net in ${NETS:-vgg16}; do
-      timeout 300 python $R/bench.py --net $net --steps 30 --warmup 5 --no-cpu-baseline --no-steady > $O/${net}_${name}_r$round.json 2> $O/${net}_${name}_r$round.err || echo "FAILED $net $name"
+      timeout 300 python $R/bench.py --net $net --steps 30 --warmup 5 --full --no-cpu-baseline --no-steady > $O/${net}_${name}_r$round.json 2> $O/${net}_${name}_r$round.err || echo "FAILED $net $name"
     done
   done
 done
