@@ -35,6 +35,10 @@ struct StageTimer
     int slot;
 };
 
+// Channels of a pixel type (feather_net.h FHIP_PIXEL_*): *cin in the source bytes, *cout in the fp32 output.  0, or FHIP_E_BADARG for a
+// type that is not one of ncnn's 13 (layers.hip).
+int pixel_channels(int type, int* cin, int* cout);
+
 // Compute units of the current device (cached per device; 256 on MI355X).
 int device_compute_units();
 // LDS bytes per CU of the current device (cached per device; 160 KiB on MI355X): the residency estimates of the persistent grids use it

@@ -66,24 +66,143 @@ __global__ __launch_bounds__(256) void add_kernel(float* __restrict__ y, const f
     }
 }
 
+// ---- sources of affine_kernel --------------------------------------------------------------------------------
+// PlaneSrc: the layers' source, the dense fp32 tensor x itself, with mul / add as device vectors (BatchNorm, Scale, fhip_affine).
+struct PlaneSrc
+{
+    __device__ __forceinline__ float4 load4(const float* __restrict__ x, size_t i, size_t) const { return reinterpret_cast<const float4*>(x)[i]; }
+    __device__ __forceinline__ float load1(const float* __restrict__ x, size_t i) const { return x[i]; }
+    __device__ __forceinline__ float mul(const float* __restrict__ m, int c) const { return m[c]; }
+    __device__ __forceinline__ float add(const float* __restrict__ a, int c) const { return a ? a[c] : 0.f; }
+    static __device__ __forceinline__ float map(float v, float m, float a) { return v * m + a; }
+};
+
+// PixelSrc: a batch of uint8 images [N][h][w][cin] (any byte offset) seen as the [N][cout][th][tw] fp32 tensor that ncnn's
+// Mat::from_pixels_resize + substract_mean_normalize make of each (reference src/ncnn/mat_pixel.cpp:1369-1410): a bilinear resize in
+// the source format when the size changes (mat_pixel_resize.cpp, 11-bit fixed-point coefficients), then the channel conversion of the
+// pixel type on the resized bytes.  Coefficients are computed per output element from the by-value scales (nothing to upload, so the
+// call is stream-capturable); mean / norm travel by value too.  x, mul and add of the kernel are unused (NULL).
+struct PixelSrc
+{
+    const unsigned char* px;
+    int w, h, cin, cout, tw, th;
+    int resize;     // 0: target size == source size, the bytes are read as they are
+    int gray;       // 1: every output channel is (s0*wt0 + s1*wt1 + s2*wt2) >> 8; 0: output channel c is source channel sel[c]
+    int sel[4], wt[3];
+    double scale_x, scale_y; // (double)w / tw, (double)h / th as the reference computes them (host side, IEEE division)
+    float m[4], a[4];        // output channel c: v * m[c] + a[c], two roundings (see map)
+
+    // ncnn's coefficient of output index d along an axis of `src` source pixels (resize_bilinear_c1, mat_pixel_resize.cpp:46-71):
+    // float / double steps exactly as written there, so no contraction into FMAs
+    static __device__ __forceinline__ void coef(int d, int src, double scale, int& s, int& k0, int& k1)
+    {
+#pragma clang fp contract(off)
+        float f = (float)((d + 0.5) * scale - 0.5);
+        s = (int)floorf(f);
+        f -= (float)s;
+        if (s < 0)
+        {
+            s = 0;
+            f = 0.f;
+        }
+        if (s >= src - 1)
+        {
+            s = src - 2;
+            f = 1.f;
+        }
+        const float c0 = (1.f - f) * 2048.f, c1 = f * 2048.f;
+        k0 = min(max((int)(c0 + (c0 >= 0.f ? 0.5f : -0.5f)), -32768), 32767); // SATURATE_CAST_SHORT
+        k1 = min(max((int)(c1 + (c1 >= 0.f ? 0.5f : -0.5f)), -32768), 32767);
+    }
+    // source channel k of output pixel (oy, ox) of image n after the resize: the horizontal pass ((S0*a0 + S1*a1) >> 4, kept as a short
+    // row value) on rows sy and sy + 1, then the vertical pass of the reference's scalar loop (mat_pixel_resize.cpp:272)
+    __device__ __forceinline__ int sample(const unsigned char* img, int k, int sy, int b0, int b1, int sx, int a0, int a1) const
+    {
+        const unsigned char* r0 = img + ((size_t)sy * w + sx) * cin + k;
+        const unsigned char* r1 = r0 + (size_t)w * cin;
+        const short row0 = (short)((r0[0] * a0 + r0[cin] * a1) >> 4);
+        const short row1 = (short)((r1[0] * a0 + r1[cin] * a1) >> 4);
+        return (unsigned char)(((short)((b0 * row0) >> 16) + (short)((b1 * row1) >> 16) + 2) >> 2);
+    }
+    // the pixel type's conversion of one (resized) pixel into output channel c (mat_pixel.cpp from_* functions)
+    template <class Get>
+    __device__ __forceinline__ float convert(int c, const Get& get) const
+    {
+        if (gray) return (float)((get(0) * wt[0] + get(1) * wt[1] + get(2) * wt[2]) >> 8);
+        return (float)get(sel[c]);
+    }
+    // output values [e, e + COLS) of one output row (the caller keeps them inside a row); the row's coefficients are computed once
+    template <int COLS>
+    __device__ __forceinline__ void values(size_t e, float* out) const
+    {
+        const int ox = (int)(e % tw);
+        const size_t t = e / tw;
+        const int oy = (int)(t % th);
+        const size_t nc = t / th;
+        const int c = (int)(nc % cout);
+        const unsigned char* img = px + (nc / cout) * ((size_t)h * w * cin);
+        if (!resize)
+        {
+#pragma unroll
+            for (int j = 0; j < COLS; ++j)
+            {
+                const unsigned char* p = img + ((size_t)oy * w + ox + j) * cin;
+                out[j] = convert(c, [&](int k) { return (int)p[k]; });
+            }
+            return;
+        }
+        int sy, b0, b1;
+        coef(oy, h, scale_y, sy, b0, b1);
+#pragma unroll
+        for (int j = 0; j < COLS; ++j)
+        {
+            int sx, a0, a1;
+            coef(ox + j, w, scale_x, sx, a0, a1);
+            out[j] = convert(c, [&](int k) { return sample(img, k, sy, b0, b1, sx, a0, a1); });
+        }
+    }
+    __device__ __forceinline__ float4 load4(const float*, size_t, size_t e) const
+    {
+        float v[4];
+        values<4>(e, v);
+        return make_float4(v[0], v[1], v[2], v[3]);
+    }
+    __device__ __forceinline__ float load1(const float*, size_t i) const
+    {
+        float v;
+        values<1>(i, &v);
+        return v;
+    }
+    __device__ __forceinline__ float mul(const float*, int c) const { return m[c]; }
+    __device__ __forceinline__ float add(const float*, int c) const { return a[c]; }
+    // x * m + a rounded twice (never an FMA), as upstream ncnn's substract_mean_normalize computes it in plain C; m = 1 / a = -0.f stand in
+    // for a missing norm / mean, so each one-sided form is the reference's exact x - mean or x * norm
+    static __device__ __forceinline__ float map(float v, float m, float a)
+    {
+#pragma clang fp contract(off)
+        return v * m + a;
+    }
+};
+
 // y[n][c][:] = x[n][c][:] * mul[c] + add[c]  (+ ReLU); one float4 (VEC: HW % 4 == 0, so it stays inside a plane) or one
-// float per lane, no loop
-template <bool RELU, bool VEC>
+// float per lane, no loop.  Src supplies x and the per-channel mul / add: PlaneSrc (the default) reads the tensor x and the device
+// vectors, PixelSrc computes x from uint8 images (fhip_pixels_to_float).
+template <bool RELU, bool VEC, class Src = PlaneSrc>
 __global__ __launch_bounds__(256) void affine_kernel(float* __restrict__ y, const float* __restrict__ x, const float* __restrict__ mul,
-                                                    const float* __restrict__ add, int C, int HW, size_t total)
+                                                    const float* __restrict__ add, int C, int HW, size_t total, const Src src = Src())
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const size_t e = VEC ? i * 4 : i;
     const int c = (int)((e / HW) % C);
-    const float m = mul[c], a = add ? add[c] : 0.f;
+    const float m = src.mul(mul, c), a = src.add(add, c);
     if (VEC)
     {
-        float4 v = reinterpret_cast<const float4*>(x)[i];
-        v.x = v.x * m + a;
-        v.y = v.y * m + a;
-        v.z = v.z * m + a;
-        v.w = v.w * m + a;
+        float4 v = src.load4(x, i, e);
+        v.x = Src::map(v.x, m, a);
+        v.y = Src::map(v.y, m, a);
+        v.z = Src::map(v.z, m, a);
+        v.w = Src::map(v.w, m, a);
         if (RELU)
         {
             v.x = fmaxf(v.x, 0.f);
@@ -95,7 +214,7 @@ __global__ __launch_bounds__(256) void affine_kernel(float* __restrict__ y, cons
     }
     else
     {
-        const float v = x[i] * m + a;
+        const float v = Src::map(src.load1(x, i), m, a);
         y[i] = RELU ? fmaxf(v, 0.f) : v;
     }
 }
@@ -280,6 +399,18 @@ __global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ y, con
     for (int i = threadIdx.x; i < cols; i += 256) yp[i] = yp[i] / sum;
 }
 
+int pixel_channels(int type, int* cin, int* cout)
+{
+    const int from = type & 0xffff, to = (unsigned)type >> 16;
+    const int ch[9] = {0, 3, 3, 0, 1, 0, 0, 0, 4}; // channels of RGB = 1, BGR = 2, GRAY = 4, RGBA = 8
+    if (from < 1 || from > 8 || !ch[from] || to > 8 || (to && !ch[to])) return FHIP_E_BADARG;
+    // the conversions ncnn's Mat::from_pixels knows (mat_pixel.cpp:1329-1367): none into RGBA, none from a format into itself
+    if (to == FHIP_PIXEL_RGBA || to == from) return FHIP_E_BADARG;
+    *cin = ch[from];
+    *cout = to ? ch[to] : ch[from];
+    return 0;
+}
+
 // threads needed: one per float4 plus one per leftover float
 static unsigned ew_grid(size_t n4, size_t n) { return (unsigned)((n4 + (n - n4 * 4) + 255) / 256); }
 
@@ -333,6 +464,57 @@ int fhip_affine(float* y, const float* x, const float* mul, const float* add, in
         hipLaunchKernelGGL((affine_kernel<false, true>), grid, dim3(256), 0, s, y, x, mul, add, channels, hw, total);
     else
         hipLaunchKernelGGL((affine_kernel<false, false>), grid, dim3(256), 0, s, y, x, mul, add, channels, hw, total);
+    FHIP_CHECK_HIP(hipGetLastError());
+    return FHIP_OK;
+}
+
+int fhip_pixels_to_float(float* output, const unsigned char* pixels, int batch, int type, int w, int h, int target_w, int target_h,
+                         const float* mean, const float* norm, void* stream)
+{
+    int cin, cout;
+    if (pixel_channels(type, &cin, &cout)) return fail(FHIP_E_BADARG, "unknown pixel type");
+    if (!output || !pixels || batch < 1 || w < 1 || h < 1 || target_w < 1 || target_h < 1) return fail(FHIP_E_BADARG, "bad argument");
+    if ((uintptr_t)output & 3) return fail(FHIP_E_BADARG, "output not 4-byte aligned");
+    const bool resize = w != target_w || h != target_h;
+    // the reference's resize reads column / row -1 for a 1-pixel source axis (sx = srcw - 2); refused here
+    if (resize && (w < 2 || h < 2)) return fail(FHIP_E_BADARG, "a source 1 pixel wide or high cannot be resized");
+    PixelSrc src = {};
+    src.px = pixels;
+    src.w = w;
+    src.h = h;
+    src.cin = cin;
+    src.cout = cout;
+    src.tw = target_w;
+    src.th = target_h;
+    src.resize = resize;
+    src.scale_x = (double)w / target_w;
+    src.scale_y = (double)h / target_h;
+    const int to = (type >> 16) ? (type >> 16) : type; // the output format
+    const bool swap = (to == FHIP_PIXEL_BGR && (type & 0xffff) != FHIP_PIXEL_BGR) || (to == FHIP_PIXEL_RGB && (type & 0xffff) == FHIP_PIXEL_BGR);
+    src.gray = cout == 1 && cin > 1;
+    const bool bgr_src = (type & 0xffff) == FHIP_PIXEL_BGR; // BGR2GRAY weighs channel 0 as blue
+    src.wt[0] = bgr_src ? 29 : 77;
+    src.wt[1] = 150;
+    src.wt[2] = bgr_src ? 77 : 29;
+    for (int c = 0; c < 4; ++c)
+        src.sel[c] = cin == 1 ? 0 : (swap && c < 3 ? 2 - c : c); // GRAY2RGB / GRAY2BGR replicate the one channel
+    for (int c = 0; c < cout; ++c)
+    {
+        const bool has_norm = norm != nullptr, has_mean = mean != nullptr;
+        src.m[c] = has_norm ? norm[c] : 1.f;
+        src.a[c] = has_mean ? (has_norm ? -(mean[c] * norm[c]) : -mean[c]) : -0.f;
+    }
+    const int hw = target_w * target_h;
+    const size_t count = (size_t)batch * cout * hw;
+    const bool vec = (target_w % 4) == 0 && ((uintptr_t)output & 15) == 0;
+    const size_t total = vec ? count / 4 : count;
+    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large");
+    const dim3 grid((unsigned)((total + 255) / 256));
+    hipStream_t s = (hipStream_t)stream;
+    if (vec)
+        hipLaunchKernelGGL((affine_kernel<false, true, PixelSrc>), grid, dim3(256), 0, s, output, nullptr, nullptr, nullptr, cout, hw, total, src);
+    else
+        hipLaunchKernelGGL((affine_kernel<false, false, PixelSrc>), grid, dim3(256), 0, s, output, nullptr, nullptr, nullptr, cout, hw, total, src);
     FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }

@@ -1616,8 +1616,11 @@ struct fhip_net
     std::vector<hipEvent_t> joins;
     std::vector<int> share;                    // images per replica at the last FeedInput (index 0 = impl)
     std::map<std::string, DeviceVec> gathered; // Extract: blobs put back together (device pointer API)
+    unsigned char* staging = nullptr;          // FeedPixels from host memory: the uint8 images, uploaded once
+    size_t staging_bytes = 0;
     ~fhip_net()
     {
+        if (staging) (void)hipFree(staging);
         more.clear();
         for (hipStream_t st : more_streams) (void)hipStreamDestroy(st);
         if (fork) (void)hipEventDestroy(fork);
@@ -1827,6 +1830,67 @@ int fhip_net_feed_input(fhip_net* n, const char* blob_name, int num, int c, int 
     }
     FHIP_CHECK_HIP(hipMemcpyAsync(b->data, data, b->count() * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, n->impl.stream));
     return FHIP_OK;
+}
+
+int fhip_net_feed_pixels(fhip_net* n, const char* blob_name, int num, const unsigned char* pixels, int type, int w, int h, int target_w,
+                         int target_h, const float* mean, const float* norm, int on_device)
+{
+    NET_GUARD(n);
+    int cin, cout;
+    if (pixel_channels(type, &cin, &cout)) return fail(FHIP_E_BADARG, "unknown pixel type");
+    if (!blob_name || !pixels || num < 1 || w < 1 || h < 1 || target_w < 1 || target_h < 1) return fail(FHIP_E_BADARG, "bad argument");
+    if ((w != target_w || h != target_h) && (w < 2 || h < 2)) return fail(FHIP_E_BADARG, "a source 1 pixel wide or high cannot be resized");
+    if (!n->impl.find(blob_name)) return failf(NET_E_IO, "Invalid input blob %s, not found in map.", blob_name);
+    const size_t image = (size_t)h * w * cin;
+    if (!on_device)
+    {
+        // one uint8 upload of the whole batch on the net's stream; the replicas then read their shares from the staging buffer
+        const size_t bytes = image * num;
+        if (bytes > n->staging_bytes)
+        {
+            // the old buffer may still be read by conversions queued earlier (every replica's is joined into the net's stream)
+            FHIP_CHECK_HIP(hipStreamSynchronize(n->impl.stream));
+            if (n->staging) FHIP_CHECK_HIP(hipFree(n->staging));
+            n->staging = nullptr;
+            n->staging_bytes = 0;
+            FHIP_CHECK_HIP(hipMalloc((void**)&n->staging, bytes));
+            n->staging_bytes = bytes;
+        }
+        FHIP_CHECK_HIP(hipMemcpyAsync(n->staging, pixels, bytes, hipMemcpyHostToDevice, n->impl.stream));
+        pixels = n->staging;
+    }
+    if (!n->more.empty())
+    {
+        // the shares of fhip_net_feed_input: contiguous, each converted by its replica on its own stream after the fork, joined back
+        deal(num, (int)n->more.size() + 1, n->share);
+        FHIP_CHECK_HIP(hipEventRecord(n->fork, n->impl.stream));
+        size_t first = n->share[0];
+        for (size_t r = 0; r < n->more.size(); ++r)
+        {
+            const int cnt = n->share[r + 1];
+            if (cnt > 0)
+            {
+                FHIP_CHECK_HIP(hipStreamWaitEvent(n->more[r]->impl.stream, n->fork, 0));
+                const int rc = fhip_net_feed_pixels(n->more[r].get(), blob_name, cnt, pixels + first * image, type, w, h, target_w, target_h,
+                                                    mean, norm, 1);
+                if (rc) return rc;
+                FHIP_CHECK_HIP(hipEventRecord(n->joins[r], n->more[r]->impl.stream));
+                FHIP_CHECK_HIP(hipStreamWaitEvent(n->impl.stream, n->joins[r], 0));
+            }
+            first += cnt;
+        }
+        num = n->share[0];
+    }
+    Blob* b = n->impl.find(blob_name);
+    if (b->n != num || b->c != cout || b->h != target_h || b->w != target_w)
+    {
+        const float* old = b->data;
+        const int rc = b->reshape(num, cout, target_h, target_w);
+        if (rc) return rc;
+        n->impl.shapes_dirty = true;
+        if (old != b->data) n->impl.drop_graph();
+    }
+    return fhip_pixels_to_float(b->data, pixels, num, type, w, h, target_w, target_h, mean, norm, n->impl.stream);
 }
 
 int fhip_net_forward(fhip_net* n)

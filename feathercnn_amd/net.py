@@ -82,6 +82,25 @@ class Net:
         del keep
         return 0
 
+    def FeedPixels(self, input_name: str, pixels, ptype: int, target=None, mean=None, norm=None) -> int:
+        """ncnn's Mat::from_pixels_resize (+ substract_mean_normalize) straight into the input blob, on the device
+        (fhip_net_feed_pixels): `pixels` is uint8 [N][H][W][C] (or [H][W][C]), a numpy array (uploaded once as uint8) or a CUDA
+        tensor; ptype a PIXEL_* code; target = (w, h), default the source size; mean / norm: one value per output channel, or None."""
+        from .pixels import _images, _per_channel, pixel_channels
+        import torch
+        n, h, w, ptr, dev, keep = _images(pixels, ptype)
+        tw, th = (w, h) if target is None else (int(target[0]), int(target[1]))
+        _, cout = pixel_channels(ptype)
+        m, mp = _per_channel(mean, cout, "mean")
+        s, sp = _per_channel(norm, cout, "norm")
+        if dev:
+            torch.cuda.current_stream().synchronize()  # the net's stream may differ from the producer's
+        _check(self._lib.fhip_net_feed_pixels(self._h, input_name.encode(), n, ptr, int(ptype), w, h, tw, th, mp, sp, dev),
+               "fhip_net_feed_pixels")
+        self.synchronize()  # the host array / device tensor may be freed or overwritten by the caller
+        del keep, m, s
+        return 0
+
     def Forward(self) -> int:
         _check(self._lib.fhip_net_forward(self._h), "fhip_net_forward")
         return 0

@@ -1,0 +1,90 @@
+"""uint8 images to the fp32 input tensor on the device: ncnn's ``Mat::from_pixels_resize`` (+ ``substract_mean_normalize``) for a
+batch, over ``fhip_pixels_to_float`` (include/feather_hip/feather_net.h).  ``PIXEL_*`` are ncnn's codes (reference src/ncnn/mat.h:125-146)."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .booster import FeatherHipError, _check, _stream
+
+PIXEL_CONVERT_SHIFT = 16
+PIXEL_RGB = 1
+PIXEL_BGR = 1 << 1
+PIXEL_GRAY = 1 << 2
+PIXEL_RGBA = 1 << 3
+PIXEL_RGB2BGR = PIXEL_RGB | (PIXEL_BGR << PIXEL_CONVERT_SHIFT)
+PIXEL_RGB2GRAY = PIXEL_RGB | (PIXEL_GRAY << PIXEL_CONVERT_SHIFT)
+PIXEL_BGR2RGB = PIXEL_BGR | (PIXEL_RGB << PIXEL_CONVERT_SHIFT)
+PIXEL_BGR2GRAY = PIXEL_BGR | (PIXEL_GRAY << PIXEL_CONVERT_SHIFT)
+PIXEL_GRAY2RGB = PIXEL_GRAY | (PIXEL_RGB << PIXEL_CONVERT_SHIFT)
+PIXEL_GRAY2BGR = PIXEL_GRAY | (PIXEL_BGR << PIXEL_CONVERT_SHIFT)
+PIXEL_RGBA2RGB = PIXEL_RGBA | (PIXEL_RGB << PIXEL_CONVERT_SHIFT)
+PIXEL_RGBA2BGR = PIXEL_RGBA | (PIXEL_BGR << PIXEL_CONVERT_SHIFT)
+PIXEL_RGBA2GRAY = PIXEL_RGBA | (PIXEL_GRAY << PIXEL_CONVERT_SHIFT)
+
+_CHANNELS = {PIXEL_RGB: 3, PIXEL_BGR: 3, PIXEL_GRAY: 1, PIXEL_RGBA: 4}
+_TYPES = (PIXEL_RGB, PIXEL_BGR, PIXEL_GRAY, PIXEL_RGBA, PIXEL_RGB2BGR, PIXEL_RGB2GRAY, PIXEL_BGR2RGB, PIXEL_BGR2GRAY, PIXEL_GRAY2RGB,
+          PIXEL_GRAY2BGR, PIXEL_RGBA2RGB, PIXEL_RGBA2BGR, PIXEL_RGBA2GRAY)
+
+
+def pixel_channels(ptype: int):
+    """(source channels, output channels) of a pixel type."""
+    if ptype not in _TYPES:
+        raise FeatherHipError(f"unknown pixel type {ptype:#x}")
+    return _CHANNELS[ptype & 0xFFFF], _CHANNELS[(ptype >> 16) or (ptype & 0xFFFF)]
+
+
+def _per_channel(v, cout, what):
+    """A host float32 array of cout values (kept alive by the caller) and its pointer, or (None, None)."""
+    if v is None:
+        return None, None
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1))
+    if a.size != cout:
+        raise FeatherHipError(f"{what} needs {cout} values (one per output channel), got {a.size}")
+    return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _images(pixels, ptype):
+    """(n, h, w, pointer, on_device, keep-alive) of a uint8 [N][H][W][C] / [H][W][C] numpy array or CUDA tensor."""
+    import torch
+    cin, _ = pixel_channels(ptype)
+    if isinstance(pixels, torch.Tensor):
+        if not pixels.is_cuda or pixels.dtype != torch.uint8:
+            raise FeatherHipError("pixels: a uint8 CUDA tensor or a uint8 numpy array")
+        t = pixels.contiguous()
+        shape, ptr, dev = tuple(t.shape), t.data_ptr(), 1
+    else:
+        t = np.ascontiguousarray(pixels)
+        if t.dtype != np.uint8:
+            raise FeatherHipError("pixels: a uint8 CUDA tensor or a uint8 numpy array")
+        shape, ptr, dev = t.shape, t.ctypes.data, 0
+    if len(shape) == 3:
+        shape = (1,) + tuple(shape)
+    if len(shape) != 4 or shape[3] != cin:
+        raise FeatherHipError(f"pixels: [N][H][W][{cin}] or [H][W][{cin}] for pixel type {ptype:#x}, got {tuple(shape)}")
+    n, h, w, _ = (int(v) for v in shape)
+    return n, h, w, ctypes.c_void_p(ptr), dev, t
+
+
+def pixels_to_float(pixels, ptype: int, target=None, mean=None, norm=None, out=None):
+    """ncnn's from_pixels_resize (+ substract_mean_normalize) of a batch on the current stream: uint8 CUDA tensor [N][H][W][C] (or
+    [H][W][C]) -> fp32 CUDA tensor [N][cout][target_h][target_w].  target = (w, h), default the source size; mean / norm: cout values
+    or None.  `out` may be given (a contiguous fp32 CUDA tensor of that shape)."""
+    import torch
+    if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda):
+        raise FeatherHipError("pixels_to_float wants a uint8 CUDA tensor (Net.FeedPixels takes host arrays too)")
+    n, h, w, ptr, _, keep = _images(pixels, ptype)
+    tw, th = (w, h) if target is None else (int(target[0]), int(target[1]))
+    _, cout = pixel_channels(ptype)
+    m, mp = _per_channel(mean, cout, "mean")
+    s, sp = _per_channel(norm, cout, "norm")
+    if out is None:
+        out = torch.empty((n, cout, th, tw), dtype=torch.float32, device=keep.device)
+    elif tuple(out.shape) != (n, cout, th, tw) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise FeatherHipError(f"out must be a contiguous fp32 tensor of shape {(n, cout, th, tw)}")
+    _check(_lib.load_library().fhip_pixels_to_float(ctypes.c_void_p(out.data_ptr()), ptr, n, int(ptype), w, h, tw, th, mp, sp, _stream()),
+           "fhip_pixels_to_float")
+    del m, s  # read by value at the call
+    return out

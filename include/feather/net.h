@@ -11,7 +11,8 @@
 //
 // Differences, all forced by the GPU batch path:
 //   * blobs live in HBM: Extract(name, float**, ...) returns a DEVICE pointer (use ExtractHost for a host copy);
-//   * besides the reference's FeedInput(name, ncnn::Mat&) (N = 1, net.cpp:235-246) there are pointer forms with an explicit batch;
+//   * besides the reference's FeedInput(name, ncnn::Mat&) (N = 1, net.cpp:235-246) there are pointer forms with an explicit batch,
+//     and FeedPixels: ncnn's from_pixels_resize of a batch of uint8 images, done on the device;
 //   * Extract(name, ncnn::Mat&) copies channel by channel like the reference (net.cpp:281-296) -- but every channel, where the
 //     reference copies channel 0 into all of them (its source pointer never advances); a batch > 1 comes back as n*c channels;
 //   * public data members of the reference class are not mirrored: `blob_map` (std::map<std::string, Blob<float>*>, net.h:54)
@@ -74,6 +75,25 @@ class Net
     int FeedInputDevice(const char* input_name, int n, int c, int h, int w, const float* device_data)
     {
         return fhip_net_feed_input(net_, input_name, n, c, h, w, device_data, 1);
+    }
+
+    // uint8 images straight into the input blob, on the device (fhip_net_feed_pixels): ncnn's Mat::from_pixels_resize (+
+    // substract_mean_normalize when mean / norm are given, cout values each) of `n` images [n][h][w][cin], host memory (one uint8 upload)
+    // or, with FeedPixelsDevice, device memory.  The blob becomes [n][cout][target_h][target_w].  `type` is an ncnn::Mat::PIXEL_* code.
+    int FeedPixels(const char* input_name, const unsigned char* pixels, int type, int w, int h, int target_w, int target_h,
+                   const float* mean = NULL, const float* norm = NULL)
+    {
+        return fhip_net_feed_pixels(net_, input_name, 1, pixels, type, w, h, target_w, target_h, mean, norm, 0);
+    }
+    int FeedPixels(const char* input_name, int n, const unsigned char* pixels, int type, int w, int h, int target_w, int target_h,
+                   const float* mean = NULL, const float* norm = NULL)
+    {
+        return fhip_net_feed_pixels(net_, input_name, n, pixels, type, w, h, target_w, target_h, mean, norm, 0);
+    }
+    int FeedPixelsDevice(const char* input_name, int n, const unsigned char* device_pixels, int type, int w, int h, int target_w, int target_h,
+                         const float* mean = NULL, const float* norm = NULL)
+    {
+        return fhip_net_feed_pixels(net_, input_name, n, device_pixels, type, w, h, target_w, target_h, mean, norm, 1);
     }
 
     int Forward() { return fhip_net_forward(net_); } // net.cpp:297-334

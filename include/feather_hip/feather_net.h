@@ -29,6 +29,41 @@ FHIP_API int fhip_add(float* y, const float* a, const float* b, size_t count, in
 FHIP_API int fhip_affine(float* y, const float* x, const float* mul, const float* add, int batch, int channels, int hw,
                          int relu, void* stream);
 
+/* ---- uint8 images to the input tensor --------------------------------------------------------------- */
+
+/* Pixel types: ncnn's Mat::PIXEL_* codes with the same values (reference src/ncnn/mat.h:125-146).  A plain format is read as it is
+ * (RGB and BGR in source order, no swap); FROM | (TO << 16) converts.  Gray is (r*77 + g*150 + b*29) >> 8 in integer arithmetic. */
+enum
+{
+    FHIP_PIXEL_CONVERT_SHIFT = 16,
+    FHIP_PIXEL_RGB = 1,
+    FHIP_PIXEL_BGR = (1 << 1),
+    FHIP_PIXEL_GRAY = (1 << 2),
+    FHIP_PIXEL_RGBA = (1 << 3),
+    FHIP_PIXEL_RGB2BGR = FHIP_PIXEL_RGB | (FHIP_PIXEL_BGR << FHIP_PIXEL_CONVERT_SHIFT),
+    FHIP_PIXEL_RGB2GRAY = FHIP_PIXEL_RGB | (FHIP_PIXEL_GRAY << FHIP_PIXEL_CONVERT_SHIFT),
+    FHIP_PIXEL_BGR2RGB = FHIP_PIXEL_BGR | (FHIP_PIXEL_RGB << FHIP_PIXEL_CONVERT_SHIFT),
+    FHIP_PIXEL_BGR2GRAY = FHIP_PIXEL_BGR | (FHIP_PIXEL_GRAY << FHIP_PIXEL_CONVERT_SHIFT),
+    FHIP_PIXEL_GRAY2RGB = FHIP_PIXEL_GRAY | (FHIP_PIXEL_RGB << FHIP_PIXEL_CONVERT_SHIFT),
+    FHIP_PIXEL_GRAY2BGR = FHIP_PIXEL_GRAY | (FHIP_PIXEL_BGR << FHIP_PIXEL_CONVERT_SHIFT),
+    FHIP_PIXEL_RGBA2RGB = FHIP_PIXEL_RGBA | (FHIP_PIXEL_RGB << FHIP_PIXEL_CONVERT_SHIFT),
+    FHIP_PIXEL_RGBA2BGR = FHIP_PIXEL_RGBA | (FHIP_PIXEL_BGR << FHIP_PIXEL_CONVERT_SHIFT),
+    FHIP_PIXEL_RGBA2GRAY = FHIP_PIXEL_RGBA | (FHIP_PIXEL_GRAY << FHIP_PIXEL_CONVERT_SHIFT)
+};
+
+/* ncnn's Mat::from_pixels_resize (reference src/ncnn/mat_pixel.cpp:1369-1410) + substract_mean_normalize for a batch, on the device.
+ *   pixels: DEVICE, `batch` images of h rows x w pixels of the type's source channels, dense ([N][h][w][cin] bytes, any byte offset);
+ *   output: DEVICE, [N][cout][target_h][target_w] fp32 (cout = 3, 1 or 4 as from_pixels gives them), 4-byte aligned.
+ * When the size changes, each image is resized first, in its source format, with ncnn's fixed-point bilinear resize
+ * (mat_pixel_resize.cpp resize_bilinear_c1 / c3 / c4), and the conversion runs on the resized bytes; the output is bit-identical to the
+ * reference's.  One deliberate difference: a source 1 pixel wide or high that must be resized is refused (FHIP_E_BADARG) -- the reference
+ * reads column / row -1 there.
+ *   mean / norm: HOST arrays of cout floats, or NULL (upstream ncnn's substract_mean_normalize, compiled out of the reference build):
+ *     mean only: x - mean; norm only: x * norm; both: x * norm + (-(mean * norm)), rounded after the product and after the sum (no FMA).
+ * Asynchronous on `stream` and stream-capturable: no allocation, no copy, everything the kernel needs is passed by value.  One launch. */
+FHIP_API int fhip_pixels_to_float(float* output, const unsigned char* pixels, int batch, int type, int w, int h, int target_w, int target_h,
+                                  const float* mean, const float* norm, void* stream);
+
 /* Convolution (+bias, +ReLU as the param says) followed by a 2x2 / stride-2 / unpadded MAX pooling, fused: the pooled
  * tensor [N][K][OH/2][OW/2] is written straight from the Winograd output transform and the full-resolution activation
  * never reaches HBM (VGG: every pooling layer follows a 3x3 convolution).  Same arguments as fhip_conv_forward.  Only the
@@ -194,6 +229,13 @@ FHIP_API int fhip_net_load_weights_device(fhip_net* net, const void* device_data
  * whether it is a device pointer (copied device-to-device on the net's stream) or a host pointer. */
 FHIP_API int fhip_net_feed_input(fhip_net* net, const char* blob_name, int n, int c, int h, int w, const float* data,
                                  int on_device);
+/* Net::FeedInput of `n` uint8 images: fhip_pixels_to_float (same type, sizes, mean, norm) straight into the input blob, which becomes
+ * [n][cout][target_h][target_w] (reshaped, and the graph dropped, only when that shape changes).  Enqueued on the net's stream; with
+ * sub-batch replicas each replica's share of the images is converted into its own blob, forked and joined like fhip_net_feed_input.
+ * `on_device` = 0: `pixels` is host memory, uploaded once as uint8 into a staging buffer the net owns (no fp32 on the host); 1: device
+ * memory, ordered on the net's stream.  FHIP_E_BADARG for a bad type or size, the error codes of fhip_net_feed_input otherwise. */
+FHIP_API int fhip_net_feed_pixels(fhip_net* net, const char* blob_name, int n, const unsigned char* pixels, int type, int w, int h,
+                                  int target_w, int target_h, const float* mean, const float* norm, int on_device);
 /* Net::Forward, net.cpp:297-334: Reshape when the input shape changed, Init once, then every layer in file
  * order on the net's stream.  Asynchronous: returns after enqueueing. */
 FHIP_API int fhip_net_forward(fhip_net* net);

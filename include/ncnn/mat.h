@@ -9,11 +9,21 @@
 //
 // Same include guard as the reference header: a program that already includes the real ncnn mat.h keeps using that one (the
 // Net overloads only need data / w / h / c / cstep / elemsize / create() / channel()).
-// Host-side fp32 container only: no allocators, no packing, no pixel conversion, no SIMD -- none of that is on the hot path,
-// which runs on device blobs.
+// Host-side fp32 container only: no allocators, no packing, no SIMD -- none of that is on the hot path, which runs on device blobs.
+// The pixel entry points (from_pixels, from_pixels_resize, substract_mean_normalize) are plain host code for one image, so that
+//
+//     ncnn::Mat in = ncnn::Mat::from_pixels_resize(bgr, ncnn::Mat::PIXEL_BGR2RGB, w, h, 224, 224);
+//     net.FeedInput("data", in);
+//
+// compiles and runs unchanged; their output is bit-identical to the reference's (mat_pixel.cpp, mat_pixel_resize.cpp).  The fast path
+// for a batch is feather::Net::FeedPixels (include/feather/net.h), which does the same on the device.  One deliberate difference: a
+// source 1 pixel wide or high that must be resized gives an empty Mat (the reference reads index -1 there).  substract_mean_normalize
+// rounds x * norm and the sum separately ("both" form), like the device; build without FMA contraction (-ffp-contract=off, or no
+// -mfma) for bit-equality with it.
 #ifndef NCNN_MAT_H
 #define NCNN_MAT_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
@@ -121,6 +131,97 @@ class Mat
     float& operator[](int i) { return ((float*)data)[i]; }
     const float& operator[](int i) const { return ((const float*)data)[i]; }
 
+    // ---- pixels (reference mat.h:123-157; ncnn's codes and values) ----
+    enum
+    {
+        PIXEL_CONVERT_SHIFT = 16,
+        PIXEL_FORMAT_MASK = 0x0000ffff,
+        PIXEL_CONVERT_MASK = 0xffff0000,
+
+        PIXEL_RGB = 1,
+        PIXEL_BGR = (1 << 1),
+        PIXEL_GRAY = (1 << 2),
+        PIXEL_RGBA = (1 << 3),
+
+        PIXEL_RGB2BGR = PIXEL_RGB | (PIXEL_BGR << PIXEL_CONVERT_SHIFT),
+        PIXEL_RGB2GRAY = PIXEL_RGB | (PIXEL_GRAY << PIXEL_CONVERT_SHIFT),
+        PIXEL_BGR2RGB = PIXEL_BGR | (PIXEL_RGB << PIXEL_CONVERT_SHIFT),
+        PIXEL_BGR2GRAY = PIXEL_BGR | (PIXEL_GRAY << PIXEL_CONVERT_SHIFT),
+        PIXEL_GRAY2RGB = PIXEL_GRAY | (PIXEL_RGB << PIXEL_CONVERT_SHIFT),
+        PIXEL_GRAY2BGR = PIXEL_GRAY | (PIXEL_BGR << PIXEL_CONVERT_SHIFT),
+        PIXEL_RGBA2RGB = PIXEL_RGBA | (PIXEL_RGB << PIXEL_CONVERT_SHIFT),
+        PIXEL_RGBA2BGR = PIXEL_RGBA | (PIXEL_BGR << PIXEL_CONVERT_SHIFT),
+        PIXEL_RGBA2GRAY = PIXEL_RGBA | (PIXEL_GRAY << PIXEL_CONVERT_SHIFT)
+    };
+    // a (w, h, cout) fp32 Mat of the pixels, converted as `type` says; an empty Mat for an unknown type.  The allocator is ignored.
+    static Mat from_pixels(const unsigned char* pixels, int type, int w_, int h_, void* allocator = 0)
+    {
+        (void)allocator;
+        int cin, cout;
+        Mat m;
+        if (!pixels || w_ < 1 || h_ < 1 || !pixel_channels(type, cin, cout)) return m;
+        m.create(w_, h_, cout, 4u);
+        if (m.empty()) return m;
+        const int from = type & PIXEL_FORMAT_MASK, to = (type >> PIXEL_CONVERT_SHIFT) ? (type >> PIXEL_CONVERT_SHIFT) : from;
+        const bool swap = (to == PIXEL_BGR) != (from == PIXEL_BGR); // RGB <-> BGR, RGBA -> BGR
+        const bool bgr = from == PIXEL_BGR;
+        const size_t size = (size_t)w_ * h_;
+        for (int q = 0; q < cout; ++q)
+        {
+            float* out = (float*)m.data + m.cstep * q;
+            const int k = cin == 1 ? 0 : (swap && q < 3 ? 2 - q : q);
+            for (size_t i = 0; i < size; ++i)
+            {
+                const unsigned char* p = pixels + i * cin;
+                if (cout == 1 && cin > 1) // (r*77 + g*150 + b*29) >> 8
+                    out[i] = (float)(((bgr ? p[2] : p[0]) * 77 + p[1] * 150 + (bgr ? p[0] : p[2]) * 29) >> 8);
+                else
+                    out[i] = (float)p[k];
+            }
+        }
+        return m;
+    }
+    // from_pixels after ncnn's fixed-point bilinear resize in the source format (mat_pixel.cpp:1369-1410), when the size changes
+    static Mat from_pixels_resize(const unsigned char* pixels, int type, int w_, int h_, int target_width, int target_height, void* allocator = 0)
+    {
+        if (w_ == target_width && h_ == target_height) return from_pixels(pixels, type, w_, h_, allocator);
+        int cin, cout;
+        if (!pixels || w_ < 2 || h_ < 2 || target_width < 1 || target_height < 1 || !pixel_channels(type, cin, cout)) return Mat();
+        unsigned char* dst = new unsigned char[(size_t)target_width * target_height * cin];
+        resize_bilinear(pixels, w_, h_, cin, dst, target_width, target_height);
+        Mat m = from_pixels(dst, type, target_width, target_height, allocator);
+        delete[] dst;
+        return m;
+    }
+    // upstream ncnn (mat.cpp): per channel, mean only: x - mean; norm only: x * norm; both: x * norm + (-(mean * norm)).  NULL skips.
+    void substract_mean_normalize(const float* mean_vals, const float* norm_vals)
+    {
+        const size_t size = (size_t)w * h;
+        for (int q = 0; q < c; ++q)
+        {
+            float* p = (float*)data + cstep * q;
+            if (mean_vals && norm_vals)
+            {
+                const float s = norm_vals[q], mb = -(mean_vals[q] * norm_vals[q]);
+                for (size_t i = 0; i < size; ++i)
+                {
+                    const float t = p[i] * s;
+                    p[i] = t + mb;
+                }
+            }
+            else if (mean_vals)
+            {
+                const float mv = mean_vals[q];
+                for (size_t i = 0; i < size; ++i) p[i] = p[i] - mv;
+            }
+            else if (norm_vals)
+            {
+                const float s = norm_vals[q];
+                for (size_t i = 0; i < size; ++i) p[i] = p[i] * s;
+            }
+        }
+    }
+
     void* data;
     int* refcount;
     size_t elemsize;
@@ -129,6 +230,73 @@ class Mat
     size_t cstep;
 
   private:
+    static bool pixel_channels(int type, int& cin, int& cout)
+    {
+        static const int ch[9] = {0, 3, 3, 0, 1, 0, 0, 0, 4};
+        const int from = type & PIXEL_FORMAT_MASK, to = (int)((unsigned)type >> PIXEL_CONVERT_SHIFT);
+        if (from < 1 || from > 8 || !ch[from] || to > 8 || (to && !ch[to]) || to == PIXEL_RGBA || to == from) return false;
+        cin = ch[from];
+        cout = to ? ch[to] : ch[from];
+        return true;
+    }
+    // 11-bit fixed-point coefficient of output index d along an axis of `src` pixels (resize_bilinear_c1 / c3 / c4)
+    static void resize_coef(int d, int src, double scale, int& s, short& k0, short& k1)
+    {
+        float f = (float)((d + 0.5) * scale - 0.5);
+        s = (int)floorf(f);
+        f -= (float)s;
+        if (s < 0)
+        {
+            s = 0;
+            f = 0.f;
+        }
+        if (s >= src - 1)
+        {
+            s = src - 2;
+            f = 1.f;
+        }
+        const float c0 = (1.f - f) * 2048.f, c1 = f * 2048.f;
+        k0 = sat_short(c0);
+        k1 = sat_short(c1);
+    }
+    static short sat_short(float x)
+    {
+        int v = (int)(x + (x >= 0.f ? 0.5f : -0.5f));
+        return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v));
+    }
+    // horizontal pass per source row ((S0*a0 + S1*a1) >> 4 as a short), then the vertical one; every channel alike
+    static void resize_bilinear(const unsigned char* src, int sw, int sh, int cn, unsigned char* dst, int dw, int dh)
+    {
+        const double scale_x = (double)sw / dw, scale_y = (double)sh / dh;
+        int* xofs = new int[dw];
+        short* alpha = new short[dw * 2];
+        short* rows = new short[(size_t)dw * cn * 2];
+        for (int dx = 0; dx < dw; ++dx) resize_coef(dx, sw, scale_x, xofs[dx], alpha[dx * 2], alpha[dx * 2 + 1]);
+        for (int dy = 0; dy < dh; ++dy)
+        {
+            int sy;
+            short b0, b1;
+            resize_coef(dy, sh, scale_y, sy, b0, b1);
+            for (int r = 0; r < 2; ++r)
+            {
+                const unsigned char* S = src + (size_t)(sy + r) * sw * cn;
+                short* row = rows + (size_t)r * dw * cn;
+                for (int dx = 0; dx < dw; ++dx)
+                    for (int k = 0; k < cn; ++k)
+                    {
+                        const unsigned char* p = S + (size_t)xofs[dx] * cn + k;
+                        row[dx * cn + k] = (short)((p[0] * alpha[dx * 2] + p[cn] * alpha[dx * 2 + 1]) >> 4);
+                    }
+            }
+            const short* r0 = rows;
+            const short* r1 = rows + (size_t)dw * cn;
+            unsigned char* D = dst + (size_t)dy * dw * cn;
+            for (int i = 0; i < dw * cn; ++i) D[i] = (unsigned char)(((short)((b0 * r0[i]) >> 16) + (short)((b1 * r1[i]) >> 16) + 2) >> 2);
+        }
+        delete[] rows;
+        delete[] alpha;
+        delete[] xofs;
+    }
     static size_t align_size(size_t sz, size_t n) { return (sz + n - 1) & ~(n - 1); }
     void alloc(int dims_, int w_, int h_, int c_, size_t elemsize_, size_t cstep_)
     {
