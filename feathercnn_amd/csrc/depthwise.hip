@@ -622,7 +622,7 @@ static inline void dw_flat_launch(const DwParams& q, int grid, hipStream_t s)
         const size_t lds = dw_flat_lds_bytes(H_, cp, q.SH);                                                                                     \
         if (q.SH == 1)                                                                                                                          \
             hipLaunchKernelGGL((depthwise3x3_flat_kernel<H_, 1, dw_flat_unr(H_, 1)>), dim3(std::min(grid, chunks)), dim3(256), lds, s, q, cp, chunks); \
-        else                                                                                                                                    \
+        else if constexpr ((H_ & 1) == 0) /* odd planes at stride 2 go to the chunk kernel (depthwise_forward): no flat form of them */          \
             hipLaunchKernelGGL((depthwise3x3_flat_kernel<H_, 2, dw_flat_unr(H_, 2)>), dim3(std::min(grid, chunks)), dim3(256), lds, s, q, cp, chunks); \
         break;                                                                                                                                  \
     }
@@ -824,10 +824,8 @@ int depthwise_forward(const fhip_conv_param& p, int batch, float* out, const flo
         const size_t lds = (size_t)(tile_floats + cp * 12) * sizeof(float);
         const long long chunks = (planes + cp - 1) / cp;
         if (chunks > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*C too large");
-        if (q.SH == 1)
-            hipLaunchKernelGGL(depthwise3x3_chunk_kernel<1>, dim3((unsigned)chunks), dim3(256), lds, s, q, cp, tile_floats);
-        else
-            hipLaunchKernelGGL(depthwise3x3_chunk_kernel<2>, dim3((unsigned)chunks), dim3(256), lds, s, q, cp, tile_floats);
+        // (small_plane implies stride 2: stride-1 planes never reach this kernel, so only its stride-2 form is instantiated)
+        hipLaunchKernelGGL(depthwise3x3_chunk_kernel<2>, dim3((unsigned)chunks), dim3(256), lds, s, q, cp, tile_floats);
     }
     else if (k3)
     {

@@ -1192,12 +1192,19 @@ static void wino_tile_gemm_launch(WinoGemmPolicy::Params& g, int columns, hipStr
     {
         g.m_tiles = g.Kp / WinoShapeSmallM::BM;
         g.n_tiles = ceil_div(columns, WinoShapeSmallM::BN); // Pp is a multiple of every BN: no pure-padding tiles
+#if FHIP_V_NT_ONCE && FHIP_V_NT_BYTES == 0
+        // every V is streamed once (v_nt always holds): the cached-V form of the small-M kernel is not instantiated
+        (void)v_nt;
+        hipLaunchKernelGGL((gemm_mfma_kernel<WinoShapeSmallM, WinoGemmPolicyT<NT | 1>>), dim3(g.batches * g.m_tiles * g.n_tiles),
+                           dim3(WinoShapeSmallM::THREADS), 0, s, g);
+#else
         if (v_nt)
             hipLaunchKernelGGL((gemm_mfma_kernel<WinoShapeSmallM, WinoGemmPolicyT<NT | 1>>), dim3(g.batches * g.m_tiles * g.n_tiles),
                                dim3(WinoShapeSmallM::THREADS), 0, s, g);
         else
             hipLaunchKernelGGL((gemm_mfma_kernel<WinoShapeSmallM, WinoGemmPolicyT<NT>>), dim3(g.batches * g.m_tiles * g.n_tiles),
                                dim3(WinoShapeSmallM::THREADS), 0, s, g);
+#endif
         return;
     }
     g.m_tiles = g.Kp / WinoShapeBig::BM;
@@ -1211,11 +1218,21 @@ static void wino_tile_gemm_launch(WinoGemmPolicy::Params& g, int columns, hipStr
     else if (g.k_tiles >= 8) // C = 64 (4 k-tiles, HBM bound): the register-staged loop is 6 % faster (83.9 vs 78.7 TF)
     {
         const int tiles = g.batches * g.m_tiles * g.n_tiles;
-        wino_gemm_row_split(tiles, device_compute_units(), kWinoRowSplitMaxRounds, g.tail_first, g.tail_parts);
-        if (g.tail_parts > 1)
-            hipLaunchKernelGGL((wino_gemm_glds_kernel<2, 16, 6, NT, true>), dim3(wino_gemm_row_split_grid(tiles, g.tail_first, g.tail_parts)), dim3(256), 0, s, g);
-        else
-            hipLaunchKernelGGL((wino_gemm_glds_kernel<2, 16, 6, NT>), dim3(tiles), dim3(256), 0, s, g);
+        g.tail_first = tiles;
+        g.tail_parts = 1;
+        // the row split takes launches of at most kWinoRowSplitMaxRounds (8) tiles per CU: 2048 tiles of 128 x 64 on 256 CUs, so K * Pp <=
+        // 524288 -- below the 614400 of a big M (FHIP_M_NT_BYTES).  Only the FHIP_M_NT_SMALL form has a row-split instantiation.
+        if constexpr (NT == FHIP_M_NT_SMALL)
+        {
+            wino_gemm_row_split(tiles, device_compute_units(), kWinoRowSplitMaxRounds, g.tail_first, g.tail_parts);
+            if (g.tail_parts > 1)
+            {
+                hipLaunchKernelGGL((wino_gemm_glds_kernel<2, 16, 6, NT, true>), dim3(wino_gemm_row_split_grid(tiles, g.tail_first, g.tail_parts)), dim3(256),
+                                   0, s, g);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((wino_gemm_glds_kernel<2, 16, 6, NT>), dim3(tiles), dim3(256), 0, s, g);
     }
     else if (v_nt && g.m_tiles == 1) // only while one row tile covers all of K: with more, every V element is read by m_tiles blocks and must stay cached
         hipLaunchKernelGGL((gemm_mfma_kernel<WinoShapeBig, WinoGemmPolicyT<NT | 1>>), dim3(g.batches * g.m_tiles * g.n_tiles),
@@ -1438,10 +1455,13 @@ int winograd_output_to_next_input(const fhip_conv_param& p, const fhip_conv_para
     }
     else
     {
-        if (has_bias && relu) FHIP_CHAIN(true, true, false);
-        else if (has_bias) FHIP_CHAIN(true, false, false);
-        else if (relu) FHIP_CHAIN(false, true, false);
-        else FHIP_CHAIN(false, false, false);
+        // without pooling the producer's plane IS the consumer's (T == T2 <= 455 by winograd_can_chain): never more than 512 tiles, so
+        // the looping phase 1 (MULTI) exists only behind the pooling
+        if (multi) return fail(FHIP_E_UNSUPPORTED, "chained transform: an unpooled plane of more than 512 tiles");
+        if (has_bias && relu) hipLaunchKernelGGL((wino_chain_kernel<true, true, false, false>), dim3(grid), dim3(threads), lds, s, vn, m, bias, g, (int)units);
+        else if (has_bias) hipLaunchKernelGGL((wino_chain_kernel<true, false, false, false>), dim3(grid), dim3(threads), lds, s, vn, m, bias, g, (int)units);
+        else if (relu) hipLaunchKernelGGL((wino_chain_kernel<false, true, false, false>), dim3(grid), dim3(threads), lds, s, vn, m, bias, g, (int)units);
+        else hipLaunchKernelGGL((wino_chain_kernel<false, false, false, false>), dim3(grid), dim3(threads), lds, s, vn, m, bias, g, (int)units);
     }
 #undef FHIP_CHAIN
     FHIP_CHECK_HIP(hipGetLastError());
