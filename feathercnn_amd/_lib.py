@@ -79,6 +79,7 @@ SIGNATURES = {
     "fhip_conv_can_fuse_maxpool2": (_I, [_P, _I]),
     "fhip_conv_forward_maxpool2": (_I, [_P, _I, _I, _V, _V, _V, _V, _V, _V]),
     "fhip_pixels_to_float": (_I, [_V, _V, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_yuv420sp_to_float": (_I, [_V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
     "fhip_pooling_output_dim": (_I, [_Q, _PI, _PI]),
     "fhip_pooling": (_I, [_Q, _I, _V, _V, _V]),
     "fhip_softmax": (_I, [_V, _V, _I, _I, _V]),
@@ -98,6 +99,7 @@ SIGNATURES = {
     "fhip_net_load_weights_device": (_I, [_V, _V, _SZ]),
     "fhip_net_feed_input": (_I, [_V, ctypes.c_char_p, _I, _I, _I, _I, _V, _I]),
     "fhip_net_feed_pixels": (_I, [_V, ctypes.c_char_p, _I, _V, _I, _I, _I, _I, _I, _V, _V, _I]),
+    "fhip_net_feed_yuv420sp": (_I, [_V, ctypes.c_char_p, _I, _V, _I, _I, _I, _I, _I, _I, _V, _V, _I]),
     "fhip_net_forward": (_I, [_V]),
     "fhip_net_extract": (_I, [_V, ctypes.c_char_p, ctypes.POINTER(_V), _PI, _PI, _PI, _PI]),
     "fhip_net_extract_host": (_I, [_V, ctypes.c_char_p, _V, _SZ]),

@@ -38,6 +38,9 @@ struct StageTimer
 // Channels of a pixel type (feather_net.h FHIP_PIXEL_*): *cin in the source bytes, *cout in the fp32 output.  0, or FHIP_E_BADARG for a
 // type that is not one of ncnn's 13 (layers.hip).
 int pixel_channels(int type, int* cin, int* cout);
+// The refusals of fhip_yuv420sp_to_float / fhip_net_feed_yuv420sp other than pointers and batch (layers.hip): 0 and *cout, or
+// FHIP_E_BADARG with the last error set.
+int yuv420sp_check(int type, int w, int h, int target_w, int target_h, int resize_first, int* cout);
 
 // Compute units of the current device (cached per device; 256 on MI355X).
 int device_compute_units();

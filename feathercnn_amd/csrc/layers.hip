@@ -82,15 +82,22 @@ struct PlaneSrc
 // the source format when the size changes (mat_pixel_resize.cpp, 11-bit fixed-point coefficients), then the channel conversion of the
 // pixel type on the resized bytes.  Coefficients are computed per output element from the by-value scales (nothing to upload, so the
 // call is stream-capturable); mean / norm travel by value too.  x, mul and add of the kernel are unused (NULL).
+// With yuv != 0 the images are NV21 frames (w*h Y bytes, then w/2 x h/2 interleaved V,U pairs) and the pixel type's source is the RGB
+// that the reference's yuv420sp2rgb makes of them (fhip_yuv420sp_to_float):
+//   yuv = 1: resize_bilinear_yuv420sp first (Y plane as c1, VU plane as c2 at half size), then yuv420sp2rgb at the target size;
+//   yuv = 2: yuv420sp2rgb at the source size, then from_pixels_resize's resize in RGB (c3).
 struct PixelSrc
 {
     const unsigned char* px;
+    size_t image;   // bytes per image (h*w*cin, or h*w*3/2 for an NV21 frame)
     int w, h, cin, cout, tw, th;
     int resize;     // 0: target size == source size, the bytes are read as they are
     int gray;       // 1: every output channel is (s0*wt0 + s1*wt1 + s2*wt2) >> 8; 0: output channel c is source channel sel[c]
+    int yuv;        // 0: raw pixels, 1 / 2: NV21, resized before / after the conversion to RGB (above)
     int sel[4], wt[3];
-    double scale_x, scale_y; // (double)w / tw, (double)h / th as the reference computes them (host side, IEEE division)
-    float m[4], a[4];        // output channel c: v * m[c] + a[c], two roundings (see map)
+    double scale_x, scale_y;       // (double)w / tw, (double)h / th as the reference computes them (host side, IEEE division)
+    double uv_scale_x, uv_scale_y; // yuv = 1: (double)(w/2) / (tw/2), (double)(h/2) / (th/2), the VU plane's resize_bilinear_c2
+    float m[4], a[4];              // output channel c: v * m[c] + a[c], two roundings (see map)
 
     // ncnn's coefficient of output index d along an axis of `src` source pixels (resize_bilinear_c1, mat_pixel_resize.cpp:46-71):
     // float / double steps exactly as written there, so no contraction into FMAs
@@ -114,15 +121,31 @@ struct PixelSrc
         k0 = min(max((int)(c0 + (c0 >= 0.f ? 0.5f : -0.5f)), -32768), 32767); // SATURATE_CAST_SHORT
         k1 = min(max((int)(c1 + (c1 >= 0.f ? 0.5f : -0.5f)), -32768), 32767);
     }
-    // source channel k of output pixel (oy, ox) of image n after the resize: the horizontal pass ((S0*a0 + S1*a1) >> 4, kept as a short
-    // row value) on rows sy and sy + 1, then the vertical pass of the reference's scalar loop (mat_pixel_resize.cpp:272)
-    __device__ __forceinline__ int sample(const unsigned char* img, int k, int sy, int b0, int b1, int sx, int a0, int a1) const
+    // one channel of the resized source at an output pixel: the horizontal pass ((S0*a0 + S1*a1) >> 4, kept as a short row value) on
+    // rows sy and sy + 1, then the vertical pass of the reference's scalar loop (mat_pixel_resize.cpp:272).  at(dy, dx) is that channel's
+    // byte at source pixel (sy + dy, sx + dx), dy and dx 0 or 1: raw image bytes, a plane of an NV21 frame, or RGB computed from one
+    template <class At>
+    static __device__ __forceinline__ int sample(const At& at, int b0, int b1, int a0, int a1)
     {
-        const unsigned char* r0 = img + ((size_t)sy * w + sx) * cin + k;
-        const unsigned char* r1 = r0 + (size_t)w * cin;
-        const short row0 = (short)((r0[0] * a0 + r0[cin] * a1) >> 4);
-        const short row1 = (short)((r1[0] * a0 + r1[cin] * a1) >> 4);
+        const short row0 = (short)((at(0, 0) * a0 + at(0, 1) * a1) >> 4);
+        const short row1 = (short)((at(1, 0) * a0 + at(1, 1) * a1) >> 4);
         return (unsigned char)(((short)((b0 * row0) >> 16) + (short)((b1 * row1) >> 16) + 2) >> 2);
+    }
+    // at() of a plane of `step`-byte pixels, rows of `pitch` bytes, starting at the sample's top-left byte p
+    struct PlaneAt
+    {
+        const unsigned char* p;
+        size_t pitch;
+        int step;
+        __device__ __forceinline__ int operator()(int dy, int dx) const { return p[dy * pitch + dx * step]; }
+    };
+    // channel k (0 R, 1 G, 2 B) of the reference's yuv420sp2rgb (C path, mat_pixel.cpp:1266-1320) for luma y and the block's V, U
+    static __device__ __forceinline__ int yuv_rgb(int k, int y, int v, int u)
+    {
+        v -= 128;
+        u -= 128;
+        const int d = k == 0 ? 90 * v : (k == 1 ? -46 * v + -22 * u : 113 * u);
+        return min(max(((y << 6) + d) >> 6, 0), 255);
     }
     // the pixel type's conversion of one (resized) pixel into output channel c (mat_pixel.cpp from_* functions)
     template <class Get>
@@ -140,7 +163,12 @@ struct PixelSrc
         const int oy = (int)(t % th);
         const size_t nc = t / th;
         const int c = (int)(nc % cout);
-        const unsigned char* img = px + (nc / cout) * ((size_t)h * w * cin);
+        const unsigned char* img = px + (nc / cout) * image;
+        if (__builtin_expect(yuv != 0, 0)) // keeps the raw-pixel path (fhip_pixels_to_float) the straight-line one
+        {
+            yuv_values<COLS>(img, c, oy, ox, out);
+            return;
+        }
         if (!resize)
         {
 #pragma unroll
@@ -158,7 +186,62 @@ struct PixelSrc
         {
             int sx, a0, a1;
             coef(ox + j, w, scale_x, sx, a0, a1);
-            out[j] = convert(c, [&](int k) { return sample(img, k, sy, b0, b1, sx, a0, a1); });
+            const unsigned char* p = img + ((size_t)sy * w + sx) * cin;
+            out[j] = convert(c, [&](int k) { return sample(PlaneAt{p + k, (size_t)w * cin, cin}, b0, b1, a0, a1); });
+        }
+    }
+    // values() of an NV21 frame; Y at img, the VU plane (w/2 pairs per row) at img + w*h
+    template <int COLS>
+    __device__ __forceinline__ void yuv_values(const unsigned char* img, int c, int oy, int ox, float* out) const
+    {
+        const unsigned char* Y = img;
+        const unsigned char* VU = img + (size_t)w * h;
+        // the frame's RGB at source pixel (y, x), channel k: what yuv420sp2rgb writes there
+        const auto rgb = [&](int y, int x, int k) {
+            const unsigned char* vu = VU + (size_t)(y >> 1) * w + (x & ~1);
+            return yuv_rgb(k, Y[(size_t)y * w + x], vu[0], vu[1]);
+        };
+        if (!resize)
+        {
+#pragma unroll
+            for (int j = 0; j < COLS; ++j) out[j] = convert(c, [&](int k) { return rgb(oy, ox + j, k); });
+            return;
+        }
+        int sy, b0, b1;
+        coef(oy, h, scale_y, sy, b0, b1);
+        if (yuv == 2)
+        {
+            // yuv420sp2rgb, then resize_bilinear_c3 of the RGB bytes
+#pragma unroll
+            for (int j = 0; j < COLS; ++j)
+            {
+                int sx, a0, a1;
+                coef(ox + j, w, scale_x, sx, a0, a1);
+                out[j] = convert(c, [&](int k) { return sample([&](int dy, int dx) { return rgb(sy + dy, sx + dx, k); }, b0, b1, a0, a1); });
+            }
+            return;
+        }
+        // resize_bilinear_yuv420sp: Y resized as c1 at (w, h) -> (tw, th); VU resized as c2 at (w/2, h/2) -> (tw/2, th/2); then
+        // yuv420sp2rgb of the resized frame, whose output pixel (oy, ox) takes the VU pair (oy/2, ox/2)
+        int uy, c0, c1;
+        coef(oy >> 1, h >> 1, uv_scale_y, uy, c0, c1);
+        int v = 0, u = 0;
+#pragma unroll
+        for (int j = 0; j < COLS; ++j)
+        {
+            // VEC (COLS = 4) keeps ox a multiple of 4, so columns 2i and 2i + 1 share one VU pair
+            if (COLS == 1 || (j & 1) == 0)
+            {
+                int ux, d0, d1;
+                coef((ox + j) >> 1, w >> 1, uv_scale_x, ux, d0, d1);
+                const unsigned char* p = VU + (size_t)uy * w + ux * 2;
+                v = sample(PlaneAt{p, (size_t)w, 2}, c0, c1, d0, d1);
+                u = sample(PlaneAt{p + 1, (size_t)w, 2}, c0, c1, d0, d1);
+            }
+            int sx, a0, a1;
+            coef(ox + j, w, scale_x, sx, a0, a1);
+            const int yy = sample(PlaneAt{Y + (size_t)sy * w + sx, (size_t)w, 1}, b0, b1, a0, a1);
+            out[j] = convert(c, [&](int k) { return yuv_rgb(k, yy, v, u); });
         }
     }
     __device__ __forceinline__ float4 load4(const float*, size_t, size_t e) const
@@ -411,6 +494,72 @@ int pixel_channels(int type, int* cin, int* cout)
     return 0;
 }
 
+int yuv420sp_check(int type, int w, int h, int target_w, int target_h, int resize_first, int* cout)
+{
+    // yuv420sp2rgb gives RGB bytes; from_pixels takes them as RGB, RGB2BGR or RGB2GRAY
+    if (type != FHIP_PIXEL_RGB && type != (FHIP_PIXEL_RGB | (FHIP_PIXEL_BGR << 16)) && type != (FHIP_PIXEL_RGB | (FHIP_PIXEL_GRAY << 16)))
+        return fail(FHIP_E_BADARG, "an NV21 frame converts as PIXEL_RGB, PIXEL_RGB2BGR or PIXEL_RGB2GRAY");
+    if (w < 1 || h < 1 || target_w < 1 || target_h < 1) return fail(FHIP_E_BADARG, "bad argument");
+    if ((w | h) & 1) return fail(FHIP_E_BADARG, "an NV21 frame has an even width and height");
+    // resize_bilinear_yuv420sp halves the target size for the VU plane and resizes it as c2, which reads index -1 for a 1-pair axis
+    if (resize_first && ((target_w | target_h) & 1)) return fail(FHIP_E_BADARG, "resize_first needs an even target width and height");
+    if (resize_first && (w < 4 || h < 4)) return fail(FHIP_E_BADARG, "resize_first needs a frame of at least 4x4 pixels");
+    *cout = (type >> 16) == FHIP_PIXEL_GRAY ? 1 : 3;
+    return 0;
+}
+
+// the conversion part of a PixelSrc (everything but the source layout: image, yuv, uv scales)
+static PixelSrc pixel_src(const unsigned char* px, int type, int cin, int cout, int w, int h, int target_w, int target_h, const float* mean,
+                          const float* norm)
+{
+    PixelSrc src = {};
+    src.px = px;
+    src.w = w;
+    src.h = h;
+    src.cin = cin;
+    src.cout = cout;
+    src.tw = target_w;
+    src.th = target_h;
+    src.resize = w != target_w || h != target_h;
+    src.scale_x = (double)w / target_w;
+    src.scale_y = (double)h / target_h;
+    const int to = (type >> 16) ? (type >> 16) : type; // the output format
+    const bool swap = (to == FHIP_PIXEL_BGR && (type & 0xffff) != FHIP_PIXEL_BGR) || (to == FHIP_PIXEL_RGB && (type & 0xffff) == FHIP_PIXEL_BGR);
+    src.gray = cout == 1 && cin > 1;
+    const bool bgr_src = (type & 0xffff) == FHIP_PIXEL_BGR; // BGR2GRAY weighs channel 0 as blue
+    src.wt[0] = bgr_src ? 29 : 77;
+    src.wt[1] = 150;
+    src.wt[2] = bgr_src ? 77 : 29;
+    for (int c = 0; c < 4; ++c)
+        src.sel[c] = cin == 1 ? 0 : (swap && c < 3 ? 2 - c : c); // GRAY2RGB / GRAY2BGR replicate the one channel
+    for (int c = 0; c < cout; ++c)
+    {
+        const bool has_norm = norm != nullptr, has_mean = mean != nullptr;
+        src.m[c] = has_norm ? norm[c] : 1.f;
+        src.a[c] = has_mean ? (has_norm ? -(mean[c] * norm[c]) : -mean[c]) : -0.f;
+    }
+    return src;
+}
+
+// one affine_kernel<false, *, PixelSrc> launch over [batch][cout][th][tw]: float4 lanes when a row is a multiple of 4 and the output
+// 16-byte aligned, one float per lane otherwise
+static int launch_pixels(float* output, const PixelSrc& src, int batch, void* stream)
+{
+    const int hw = src.tw * src.th;
+    const size_t count = (size_t)batch * src.cout * hw;
+    const bool vec = (src.tw % 4) == 0 && ((uintptr_t)output & 15) == 0;
+    const size_t total = vec ? count / 4 : count;
+    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large");
+    const dim3 grid((unsigned)((total + 255) / 256));
+    hipStream_t s = (hipStream_t)stream;
+    if (vec)
+        hipLaunchKernelGGL((affine_kernel<false, true, PixelSrc>), grid, dim3(256), 0, s, output, nullptr, nullptr, nullptr, src.cout, hw, total, src);
+    else
+        hipLaunchKernelGGL((affine_kernel<false, false, PixelSrc>), grid, dim3(256), 0, s, output, nullptr, nullptr, nullptr, src.cout, hw, total, src);
+    FHIP_CHECK_HIP(hipGetLastError());
+    return FHIP_OK;
+}
+
 // threads needed: one per float4 plus one per leftover float
 static unsigned ew_grid(size_t n4, size_t n) { return (unsigned)((n4 + (n - n4 * 4) + 255) / 256); }
 
@@ -478,45 +627,24 @@ int fhip_pixels_to_float(float* output, const unsigned char* pixels, int batch, 
     const bool resize = w != target_w || h != target_h;
     // the reference's resize reads column / row -1 for a 1-pixel source axis (sx = srcw - 2); refused here
     if (resize && (w < 2 || h < 2)) return fail(FHIP_E_BADARG, "a source 1 pixel wide or high cannot be resized");
-    PixelSrc src = {};
-    src.px = pixels;
-    src.w = w;
-    src.h = h;
-    src.cin = cin;
-    src.cout = cout;
-    src.tw = target_w;
-    src.th = target_h;
-    src.resize = resize;
-    src.scale_x = (double)w / target_w;
-    src.scale_y = (double)h / target_h;
-    const int to = (type >> 16) ? (type >> 16) : type; // the output format
-    const bool swap = (to == FHIP_PIXEL_BGR && (type & 0xffff) != FHIP_PIXEL_BGR) || (to == FHIP_PIXEL_RGB && (type & 0xffff) == FHIP_PIXEL_BGR);
-    src.gray = cout == 1 && cin > 1;
-    const bool bgr_src = (type & 0xffff) == FHIP_PIXEL_BGR; // BGR2GRAY weighs channel 0 as blue
-    src.wt[0] = bgr_src ? 29 : 77;
-    src.wt[1] = 150;
-    src.wt[2] = bgr_src ? 77 : 29;
-    for (int c = 0; c < 4; ++c)
-        src.sel[c] = cin == 1 ? 0 : (swap && c < 3 ? 2 - c : c); // GRAY2RGB / GRAY2BGR replicate the one channel
-    for (int c = 0; c < cout; ++c)
-    {
-        const bool has_norm = norm != nullptr, has_mean = mean != nullptr;
-        src.m[c] = has_norm ? norm[c] : 1.f;
-        src.a[c] = has_mean ? (has_norm ? -(mean[c] * norm[c]) : -mean[c]) : -0.f;
-    }
-    const int hw = target_w * target_h;
-    const size_t count = (size_t)batch * cout * hw;
-    const bool vec = (target_w % 4) == 0 && ((uintptr_t)output & 15) == 0;
-    const size_t total = vec ? count / 4 : count;
-    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large");
-    const dim3 grid((unsigned)((total + 255) / 256));
-    hipStream_t s = (hipStream_t)stream;
-    if (vec)
-        hipLaunchKernelGGL((affine_kernel<false, true, PixelSrc>), grid, dim3(256), 0, s, output, nullptr, nullptr, nullptr, cout, hw, total, src);
-    else
-        hipLaunchKernelGGL((affine_kernel<false, false, PixelSrc>), grid, dim3(256), 0, s, output, nullptr, nullptr, nullptr, cout, hw, total, src);
-    FHIP_CHECK_HIP(hipGetLastError());
-    return FHIP_OK;
+    PixelSrc src = pixel_src(pixels, type, cin, cout, w, h, target_w, target_h, mean, norm);
+    src.image = (size_t)h * w * cin;
+    return launch_pixels(output, src, batch, stream);
+}
+
+int fhip_yuv420sp_to_float(float* output, const unsigned char* yuv, int batch, int type, int w, int h, int target_w, int target_h,
+                           int resize_first, const float* mean, const float* norm, void* stream)
+{
+    int cout;
+    if (yuv420sp_check(type, w, h, target_w, target_h, resize_first, &cout)) return FHIP_E_BADARG;
+    if (!output || !yuv || batch < 1) return fail(FHIP_E_BADARG, "bad argument");
+    if ((uintptr_t)output & 3) return fail(FHIP_E_BADARG, "output not 4-byte aligned");
+    PixelSrc src = pixel_src(yuv, type, 3, cout, w, h, target_w, target_h, mean, norm);
+    src.image = (size_t)h * w * 3 / 2;
+    src.yuv = resize_first ? 1 : 2;
+    src.uv_scale_x = (double)(w / 2) / (target_w / 2);
+    src.uv_scale_y = (double)(h / 2) / (target_h / 2);
+    return launch_pixels(output, src, batch, stream);
 }
 
 int fhip_pooling_output_dim(const fhip_pool_param* p, int* out_h, int* out_w)

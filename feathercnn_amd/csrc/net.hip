@@ -1635,6 +1635,65 @@ static void deal(int num, int parts, std::vector<int>& share)
     for (int r = 0; r < num % parts; ++r) ++share[r];
 }
 
+// The body of fhip_net_feed_pixels / fhip_net_feed_yuv420sp once the arguments are checked: `num` images of `image` bytes (host memory
+// unless on_device) into blob_name as [num][cout][target_h][target_w], each net converting its share with
+// convert(output, device bytes, count, stream).
+template <class Convert>
+static int feed_bytes(fhip_net* n, const char* blob_name, int num, const unsigned char* bytes_in, size_t image, int cout, int target_w,
+                      int target_h, int on_device, const Convert& convert)
+{
+    if (!n->impl.find(blob_name)) return failf(NET_E_IO, "Invalid input blob %s, not found in map.", blob_name);
+    const unsigned char* pixels = bytes_in;
+    if (!on_device)
+    {
+        // one uint8 upload of the whole batch on the net's stream; the replicas then read their shares from the staging buffer
+        const size_t bytes = image * num;
+        if (bytes > n->staging_bytes)
+        {
+            // the old buffer may still be read by conversions queued earlier (every replica's is joined into the net's stream)
+            FHIP_CHECK_HIP(hipStreamSynchronize(n->impl.stream));
+            if (n->staging) FHIP_CHECK_HIP(hipFree(n->staging));
+            n->staging = nullptr;
+            n->staging_bytes = 0;
+            FHIP_CHECK_HIP(hipMalloc((void**)&n->staging, bytes));
+            n->staging_bytes = bytes;
+        }
+        FHIP_CHECK_HIP(hipMemcpyAsync(n->staging, pixels, bytes, hipMemcpyHostToDevice, n->impl.stream));
+        pixels = n->staging;
+    }
+    if (!n->more.empty())
+    {
+        // the shares of fhip_net_feed_input: contiguous, each converted by its replica on its own stream after the fork, joined back
+        deal(num, (int)n->more.size() + 1, n->share);
+        FHIP_CHECK_HIP(hipEventRecord(n->fork, n->impl.stream));
+        size_t first = n->share[0];
+        for (size_t r = 0; r < n->more.size(); ++r)
+        {
+            const int cnt = n->share[r + 1];
+            if (cnt > 0)
+            {
+                FHIP_CHECK_HIP(hipStreamWaitEvent(n->more[r]->impl.stream, n->fork, 0));
+                const int rc = feed_bytes(n->more[r].get(), blob_name, cnt, pixels + first * image, image, cout, target_w, target_h, 1, convert);
+                if (rc) return rc;
+                FHIP_CHECK_HIP(hipEventRecord(n->joins[r], n->more[r]->impl.stream));
+                FHIP_CHECK_HIP(hipStreamWaitEvent(n->impl.stream, n->joins[r], 0));
+            }
+            first += cnt;
+        }
+        num = n->share[0];
+    }
+    Blob* b = n->impl.find(blob_name);
+    if (b->n != num || b->c != cout || b->h != target_h || b->w != target_w)
+    {
+        const float* old = b->data;
+        const int rc = b->reshape(num, cout, target_h, target_w);
+        if (rc) return rc;
+        n->impl.shapes_dirty = true;
+        if (old != b->data) n->impl.drop_graph();
+    }
+    return convert(b->data, pixels, num, n->impl.stream);
+}
+
 #define NET_GUARD(n) \
     if (!(n)) return fail(FHIP_E_BADARG, "null net")
 
@@ -1840,57 +1899,23 @@ int fhip_net_feed_pixels(fhip_net* n, const char* blob_name, int num, const unsi
     if (pixel_channels(type, &cin, &cout)) return fail(FHIP_E_BADARG, "unknown pixel type");
     if (!blob_name || !pixels || num < 1 || w < 1 || h < 1 || target_w < 1 || target_h < 1) return fail(FHIP_E_BADARG, "bad argument");
     if ((w != target_w || h != target_h) && (w < 2 || h < 2)) return fail(FHIP_E_BADARG, "a source 1 pixel wide or high cannot be resized");
-    if (!n->impl.find(blob_name)) return failf(NET_E_IO, "Invalid input blob %s, not found in map.", blob_name);
-    const size_t image = (size_t)h * w * cin;
-    if (!on_device)
-    {
-        // one uint8 upload of the whole batch on the net's stream; the replicas then read their shares from the staging buffer
-        const size_t bytes = image * num;
-        if (bytes > n->staging_bytes)
-        {
-            // the old buffer may still be read by conversions queued earlier (every replica's is joined into the net's stream)
-            FHIP_CHECK_HIP(hipStreamSynchronize(n->impl.stream));
-            if (n->staging) FHIP_CHECK_HIP(hipFree(n->staging));
-            n->staging = nullptr;
-            n->staging_bytes = 0;
-            FHIP_CHECK_HIP(hipMalloc((void**)&n->staging, bytes));
-            n->staging_bytes = bytes;
-        }
-        FHIP_CHECK_HIP(hipMemcpyAsync(n->staging, pixels, bytes, hipMemcpyHostToDevice, n->impl.stream));
-        pixels = n->staging;
-    }
-    if (!n->more.empty())
-    {
-        // the shares of fhip_net_feed_input: contiguous, each converted by its replica on its own stream after the fork, joined back
-        deal(num, (int)n->more.size() + 1, n->share);
-        FHIP_CHECK_HIP(hipEventRecord(n->fork, n->impl.stream));
-        size_t first = n->share[0];
-        for (size_t r = 0; r < n->more.size(); ++r)
-        {
-            const int cnt = n->share[r + 1];
-            if (cnt > 0)
-            {
-                FHIP_CHECK_HIP(hipStreamWaitEvent(n->more[r]->impl.stream, n->fork, 0));
-                const int rc = fhip_net_feed_pixels(n->more[r].get(), blob_name, cnt, pixels + first * image, type, w, h, target_w, target_h,
-                                                    mean, norm, 1);
-                if (rc) return rc;
-                FHIP_CHECK_HIP(hipEventRecord(n->joins[r], n->more[r]->impl.stream));
-                FHIP_CHECK_HIP(hipStreamWaitEvent(n->impl.stream, n->joins[r], 0));
-            }
-            first += cnt;
-        }
-        num = n->share[0];
-    }
-    Blob* b = n->impl.find(blob_name);
-    if (b->n != num || b->c != cout || b->h != target_h || b->w != target_w)
-    {
-        const float* old = b->data;
-        const int rc = b->reshape(num, cout, target_h, target_w);
-        if (rc) return rc;
-        n->impl.shapes_dirty = true;
-        if (old != b->data) n->impl.drop_graph();
-    }
-    return fhip_pixels_to_float(b->data, pixels, num, type, w, h, target_w, target_h, mean, norm, n->impl.stream);
+    return feed_bytes(n, blob_name, num, pixels, (size_t)h * w * cin, cout, target_w, target_h, on_device,
+                      [&](float* out, const unsigned char* px, int cnt, hipStream_t s) {
+                          return fhip_pixels_to_float(out, px, cnt, type, w, h, target_w, target_h, mean, norm, s);
+                      });
+}
+
+int fhip_net_feed_yuv420sp(fhip_net* n, const char* blob_name, int num, const unsigned char* yuv, int w, int h, int target_w, int target_h,
+                           int type, int resize_first, const float* mean, const float* norm, int on_device)
+{
+    NET_GUARD(n);
+    int cout;
+    if (yuv420sp_check(type, w, h, target_w, target_h, resize_first, &cout)) return FHIP_E_BADARG;
+    if (!blob_name || !yuv || num < 1) return fail(FHIP_E_BADARG, "bad argument");
+    return feed_bytes(n, blob_name, num, yuv, (size_t)h * w * 3 / 2, cout, target_w, target_h, on_device,
+                      [&](float* out, const unsigned char* px, int cnt, hipStream_t s) {
+                          return fhip_yuv420sp_to_float(out, px, cnt, type, w, h, target_w, target_h, resize_first, mean, norm, s);
+                      });
 }
 
 int fhip_net_forward(fhip_net* n)

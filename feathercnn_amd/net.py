@@ -101,6 +101,25 @@ class Net:
         del keep, m, s
         return 0
 
+    def FeedYUV420sp(self, input_name: str, frames, ptype: int = 1, target=None, resize_first: bool = True, mean=None, norm=None) -> int:
+        """NV21 camera frames straight into the input blob, on the device (fhip_net_feed_yuv420sp): `frames` is uint8 [N][h*3/2][w] (or
+        [h*3/2][w]), a numpy array (uploaded once as uint8) or a CUDA tensor; ptype PIXEL_RGB (1), PIXEL_RGB2BGR or PIXEL_RGB2GRAY;
+        target = (w, h), default the frame size; resize_first picks the reference's chain (resize_bilinear_yuv420sp before
+        yuv420sp2rgb, or from_pixels_resize after it); mean / norm: one value per output channel, or None."""
+        from .pixels import _frames, _per_channel
+        import torch
+        n, w, h, cout, ptr, dev, keep = _frames(frames, ptype)
+        tw, th = (w, h) if target is None else (int(target[0]), int(target[1]))
+        m, mp = _per_channel(mean, cout, "mean")
+        s, sp = _per_channel(norm, cout, "norm")
+        if dev:
+            torch.cuda.current_stream().synchronize()  # the net's stream may differ from the producer's
+        _check(self._lib.fhip_net_feed_yuv420sp(self._h, input_name.encode(), n, ptr, w, h, tw, th, int(ptype), int(bool(resize_first)), mp,
+                                                sp, dev), "fhip_net_feed_yuv420sp")
+        self.synchronize()  # the host array / device tensor may be freed or overwritten by the caller
+        del keep, m, s
+        return 0
+
     def Forward(self) -> int:
         _check(self._lib.fhip_net_forward(self._h), "fhip_net_forward")
         return 0

@@ -88,3 +88,52 @@ def pixels_to_float(pixels, ptype: int, target=None, mean=None, norm=None, out=N
            "fhip_pixels_to_float")
     del m, s  # read by value at the call
     return out
+
+
+# ---- NV21 (yuv420sp) frames ----------------------------------------------------------------------------------------------------------
+_YUV_TYPES = (PIXEL_RGB, PIXEL_RGB2BGR, PIXEL_RGB2GRAY)
+
+
+def _frames(frames, ptype):
+    """(n, w, h, cout, pointer, on_device, keep-alive) of uint8 NV21 frames [N][h*3/2][w] / [h*3/2][w], numpy array or CUDA tensor."""
+    import torch
+    if ptype not in _YUV_TYPES:
+        raise FeatherHipError(f"pixel type {ptype:#x}: an NV21 frame converts as PIXEL_RGB, PIXEL_RGB2BGR or PIXEL_RGB2GRAY")
+    if isinstance(frames, torch.Tensor):
+        if not frames.is_cuda or frames.dtype != torch.uint8:
+            raise FeatherHipError("frames: a uint8 CUDA tensor or a uint8 numpy array")
+        t = frames.contiguous()
+        shape, ptr, dev = tuple(t.shape), t.data_ptr(), 1
+    else:
+        t = np.ascontiguousarray(frames)
+        if t.dtype != np.uint8:
+            raise FeatherHipError("frames: a uint8 CUDA tensor or a uint8 numpy array")
+        shape, ptr, dev = t.shape, t.ctypes.data, 0
+    if len(shape) == 2:
+        shape = (1,) + tuple(shape)
+    if len(shape) != 3 or shape[1] % 3:
+        raise FeatherHipError(f"frames: NV21 [N][h*3/2][w] or [h*3/2][w], got {tuple(shape)}")
+    n, rows, w = (int(v) for v in shape)
+    return n, w, rows * 2 // 3, 1 if ptype == PIXEL_RGB2GRAY else 3, ctypes.c_void_p(ptr), dev, t
+
+
+def yuv420sp_to_float(frames, ptype: int = PIXEL_RGB, target=None, resize_first: bool = True, mean=None, norm=None, out=None):
+    """NV21 camera frames to the fp32 tensor on the current stream (fhip_yuv420sp_to_float): uint8 CUDA tensor [N][h*3/2][w] (or
+    [h*3/2][w]) -> fp32 CUDA tensor [N][cout][target_h][target_w], bit-identical to the reference's chain
+    resize_bilinear_yuv420sp -> yuv420sp2rgb -> from_pixels (resize_first) or yuv420sp2rgb -> from_pixels_resize (not resize_first).
+    ptype: PIXEL_RGB, PIXEL_RGB2BGR or PIXEL_RGB2GRAY; target = (w, h), default the frame size; mean / norm: cout values or None."""
+    import torch
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+        raise FeatherHipError("yuv420sp_to_float wants a uint8 CUDA tensor (Net.FeedYUV420sp takes host arrays too)")
+    n, w, h, cout, ptr, _, keep = _frames(frames, ptype)
+    tw, th = (w, h) if target is None else (int(target[0]), int(target[1]))
+    m, mp = _per_channel(mean, cout, "mean")
+    s, sp = _per_channel(norm, cout, "norm")
+    if out is None:
+        out = torch.empty((n, cout, th, tw), dtype=torch.float32, device=keep.device)
+    elif tuple(out.shape) != (n, cout, th, tw) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise FeatherHipError(f"out must be a contiguous fp32 tensor of shape {(n, cout, th, tw)}")
+    _check(_lib.load_library().fhip_yuv420sp_to_float(ctypes.c_void_p(out.data_ptr()), ptr, n, int(ptype), w, h, tw, th, int(bool(resize_first)),
+                                                      mp, sp, _stream()), "fhip_yuv420sp_to_float")
+    del m, s  # read by value at the call
+    return out

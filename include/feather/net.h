@@ -12,7 +12,8 @@
 // Differences, all forced by the GPU batch path:
 //   * blobs live in HBM: Extract(name, float**, ...) returns a DEVICE pointer (use ExtractHost for a host copy);
 //   * besides the reference's FeedInput(name, ncnn::Mat&) (N = 1, net.cpp:235-246) there are pointer forms with an explicit batch,
-//     and FeedPixels: ncnn's from_pixels_resize of a batch of uint8 images, done on the device;
+//     FeedPixels: ncnn's from_pixels_resize of a batch of uint8 images, done on the device;
+//     and FeedYUV420sp: a batch of NV21 camera frames through either of the reference's yuv420sp chains, on the device;
 //   * Extract(name, ncnn::Mat&) copies channel by channel like the reference (net.cpp:281-296) -- but every channel, where the
 //     reference copies channel 0 into all of them (its source pointer never advances); a batch > 1 comes back as n*c channels;
 //   * public data members of the reference class are not mirrored: `blob_map` (std::map<std::string, Blob<float>*>, net.h:54)
@@ -94,6 +95,25 @@ class Net
                          const float* mean = NULL, const float* norm = NULL)
     {
         return fhip_net_feed_pixels(net_, input_name, n, device_pixels, type, w, h, target_w, target_h, mean, norm, 1);
+    }
+    // NV21 (yuv420sp) camera frames straight into the input blob, on the device (fhip_net_feed_yuv420sp): `n` frames of w x h
+    // (w*h*3/2 bytes each), host memory (one uint8 upload) or, with FeedYUV420spDevice, device memory.  type: ncnn::Mat::PIXEL_RGB,
+    // PIXEL_RGB2BGR or PIXEL_RGB2GRAY.  resize_first = 1: the reference's resize_bilinear_yuv420sp -> yuv420sp2rgb -> from_pixels (even
+    // target size, frame at least 4x4); 0: yuv420sp2rgb -> from_pixels_resize.  The blob becomes [n][cout][target_h][target_w].
+    int FeedYUV420sp(const char* input_name, const unsigned char* yuv, int w, int h, int target_w, int target_h, int type,
+                     int resize_first = 1, const float* mean = NULL, const float* norm = NULL)
+    {
+        return fhip_net_feed_yuv420sp(net_, input_name, 1, yuv, w, h, target_w, target_h, type, resize_first, mean, norm, 0);
+    }
+    int FeedYUV420sp(const char* input_name, int n, const unsigned char* yuv, int w, int h, int target_w, int target_h, int type,
+                     int resize_first = 1, const float* mean = NULL, const float* norm = NULL)
+    {
+        return fhip_net_feed_yuv420sp(net_, input_name, n, yuv, w, h, target_w, target_h, type, resize_first, mean, norm, 0);
+    }
+    int FeedYUV420spDevice(const char* input_name, int n, const unsigned char* device_yuv, int w, int h, int target_w, int target_h, int type,
+                           int resize_first = 1, const float* mean = NULL, const float* norm = NULL)
+    {
+        return fhip_net_feed_yuv420sp(net_, input_name, n, device_yuv, w, h, target_w, target_h, type, resize_first, mean, norm, 1);
     }
 
     int Forward() { return fhip_net_forward(net_); } // net.cpp:297-334

@@ -64,6 +64,20 @@ enum
 FHIP_API int fhip_pixels_to_float(float* output, const unsigned char* pixels, int batch, int type, int w, int h, int target_w, int target_h,
                                   const float* mean, const float* norm, void* stream);
 
+/* NV21 (yuv420sp) camera frames to the fp32 input tensor, on the device: one of the two chains the reference offers, bit-identical to it.
+ *   yuv: DEVICE, `batch` frames of w x h, dense: each frame is w*h Y bytes, then (w/2)*(h/2) interleaved V,U pairs (w*h*3/2 bytes per
+ *     frame, any byte offset);
+ *   output: DEVICE, [N][cout][target_h][target_w] fp32, 4-byte aligned; cout = 3 (PIXEL_RGB, PIXEL_RGB2BGR) or 1 (PIXEL_RGB2GRAY).
+ *   resize_first = 1: resize_bilinear_yuv420sp (mat_pixel_resize.cpp:1174-1189: Y as c1, VU as c2 at half size), then yuv420sp2rgb at the
+ *     target size, then Mat::from_pixels(rgb, type);
+ *   resize_first = 0: yuv420sp2rgb at the source size, then Mat::from_pixels_resize(rgb, type, w, h, target_w, target_h) (resize in RGB).
+ * yuv420sp2rgb is the reference's C path (mat_pixel.cpp:1266-1320).  mean / norm as in fhip_pixels_to_float.  FHIP_E_BADARG, before any
+ * device call, for a type other than PIXEL_RGB / RGB2BGR / RGB2GRAY, an odd w or h (the reference asserts against it), and with
+ * resize_first an odd target size or a frame narrower or lower than 4 pixels -- deliberate differences: the reference resizes the 1-pair
+ * VU plane of such a frame by reading index -1, even at equal size.  Asynchronous on `stream`, stream-capturable, one launch. */
+FHIP_API int fhip_yuv420sp_to_float(float* output, const unsigned char* yuv, int batch, int type, int w, int h, int target_w, int target_h,
+                                    int resize_first, const float* mean, const float* norm, void* stream);
+
 /* Convolution (+bias, +ReLU as the param says) followed by a 2x2 / stride-2 / unpadded MAX pooling, fused: the pooled
  * tensor [N][K][OH/2][OW/2] is written straight from the Winograd output transform and the full-resolution activation
  * never reaches HBM (VGG: every pooling layer follows a 3x3 convolution).  Same arguments as fhip_conv_forward.  Only the
@@ -236,6 +250,10 @@ FHIP_API int fhip_net_feed_input(fhip_net* net, const char* blob_name, int n, in
  * memory, ordered on the net's stream.  FHIP_E_BADARG for a bad type or size, the error codes of fhip_net_feed_input otherwise. */
 FHIP_API int fhip_net_feed_pixels(fhip_net* net, const char* blob_name, int n, const unsigned char* pixels, int type, int w, int h,
                                   int target_w, int target_h, const float* mean, const float* norm, int on_device);
+/* fhip_net_feed_pixels for `n` NV21 frames: fhip_yuv420sp_to_float (same sizes, type, chain, mean, norm) straight into the input blob,
+ * with the same reshape, stream, replica and staging behaviour; host frames are uploaded as w*h*3/2 bytes each. */
+FHIP_API int fhip_net_feed_yuv420sp(fhip_net* net, const char* blob_name, int n, const unsigned char* yuv, int w, int h, int target_w,
+                                    int target_h, int type, int resize_first, const float* mean, const float* norm, int on_device);
 /* Net::Forward, net.cpp:297-334: Reshape when the input shape changed, Init once, then every layer in file
  * order on the net's stream.  Asynchronous: returns after enqueueing. */
 FHIP_API int fhip_net_forward(fhip_net* net);

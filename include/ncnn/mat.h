@@ -20,6 +20,9 @@
 // source 1 pixel wide or high that must be resized gives an empty Mat (the reference reads index -1 there).  substract_mean_normalize
 // rounds x * norm and the sum separately ("both" form), like the device; build without FMA contraction (-ffp-contract=off, or no
 // -mfma) for bit-equality with it.
+// Mat::to_pixels / to_pixels_resize and the reference's free functions yuv420sp2rgb, resize_bilinear_c1..c4 and
+// resize_bilinear_yuv420sp are host code too, bit-identical to the reference's C paths; feather::Net::FeedYUV420sp converts a batch of
+// NV21 frames on the device.
 #ifndef NCNN_MAT_H
 #define NCNN_MAT_H
 
@@ -30,6 +33,11 @@
 
 namespace ncnn
 {
+
+inline void resize_bilinear_c1(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h);
+inline void resize_bilinear_c2(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h);
+inline void resize_bilinear_c3(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h);
+inline void resize_bilinear_c4(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h);
 
 class Mat
 {
@@ -193,6 +201,49 @@ class Mat
         delete[] dst;
         return m;
     }
+    // the Mat's values as bytes (mat_pixel.cpp:1412-1430): (int) truncation, then clamped to 0..255.  PIXEL_RGB / BGR / GRAY / RGBA write
+    // the channels as they are, PIXEL_RGB2BGR / BGR2RGB in reverse order; any other type writes nothing, as in the reference
+    void to_pixels(unsigned char* pixels, int type) const
+    {
+        int cn;
+        bool reverse = false;
+        if (type == PIXEL_RGB2BGR || type == PIXEL_BGR2RGB)
+        {
+            cn = 3;
+            reverse = true;
+        }
+        else if (type == PIXEL_RGB || type == PIXEL_BGR)
+            cn = 3;
+        else if (type == PIXEL_GRAY)
+            cn = 1;
+        else if (type == PIXEL_RGBA)
+            cn = 4;
+        else
+            return;
+        const size_t size = (size_t)w * h;
+        for (int k = 0; k < cn; ++k)
+        {
+            const float* p = (const float*)data + cstep * (reverse ? cn - 1 - k : k);
+            for (size_t i = 0; i < size; ++i)
+            {
+                const int v = (int)p[i];
+                pixels[i * cn + k] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
+            }
+        }
+    }
+    // to_pixels, then ncnn's bilinear resize in the output format when the size changes (mat_pixel.cpp:1432-1468).  A Mat 1 pixel wide
+    // or high that must be resized writes nothing (the reference reads index -1 there).
+    void to_pixels_resize(unsigned char* pixels, int type, int target_width, int target_height) const
+    {
+        if (w == target_width && h == target_height) return to_pixels(pixels, type);
+        const int to = (type & PIXEL_CONVERT_MASK) ? (int)((unsigned)type >> PIXEL_CONVERT_SHIFT) : (type & PIXEL_FORMAT_MASK);
+        const int cn = (to == PIXEL_RGB || to == PIXEL_BGR) ? 3 : (to == PIXEL_GRAY ? 1 : (to == PIXEL_RGBA ? 4 : 0));
+        if (!cn || w < 2 || h < 2 || target_width < 1 || target_height < 1) return;
+        unsigned char* src = new unsigned char[(size_t)w * h * cn]();
+        to_pixels(src, type);
+        resize_bilinear(src, w, h, cn, pixels, target_width, target_height);
+        delete[] src;
+    }
     // upstream ncnn (mat.cpp): per channel, mean only: x - mean; norm only: x * norm; both: x * norm + (-(mean * norm)).  NULL skips.
     void substract_mean_normalize(const float* mean_vals, const float* norm_vals)
     {
@@ -230,6 +281,10 @@ class Mat
     size_t cstep;
 
   private:
+    friend void resize_bilinear_c1(const unsigned char*, int, int, unsigned char*, int, int);
+    friend void resize_bilinear_c2(const unsigned char*, int, int, unsigned char*, int, int);
+    friend void resize_bilinear_c3(const unsigned char*, int, int, unsigned char*, int, int);
+    friend void resize_bilinear_c4(const unsigned char*, int, int, unsigned char*, int, int);
     static bool pixel_channels(int type, int& cin, int& cout)
     {
         static const int ch[9] = {0, 3, 3, 0, 1, 0, 0, 0, 4};
@@ -323,6 +378,60 @@ class Mat
         data = (unsigned char*)raw + 64;
     }
 };
+
+// ---- free pixel functions (reference mat.h:200-208) ----
+// NV21 (yuv420sp: w*h Y bytes, then w/2 x h/2 interleaved V,U pairs) to w*h RGB bytes, the reference's C path (mat_pixel.cpp:1266-1320).
+// w and h must be even, as the reference asserts.
+inline void yuv420sp2rgb(const unsigned char* yuv420sp, int w, int h, unsigned char* rgb)
+{
+    const unsigned char* vuptr = yuv420sp + (size_t)w * h;
+    for (int y = 0; y < h; y += 2)
+    {
+        const unsigned char* y0 = yuv420sp + (size_t)y * w;
+        const unsigned char* y1 = y0 + w;
+        unsigned char* rgb0 = rgb + (size_t)y * w * 3;
+        unsigned char* rgb1 = rgb0 + (size_t)w * 3;
+        for (int x = 0; x < w; x += 2)
+        {
+            const int v = vuptr[0] - 128, u = vuptr[1] - 128;
+            const int d[3] = {90 * v, -46 * v + -22 * u, 113 * u};
+            const int yy[4] = {y0[x] << 6, y0[x + 1] << 6, y1[x] << 6, y1[x + 1] << 6};
+            unsigned char* out[4] = {rgb0 + x * 3, rgb0 + x * 3 + 3, rgb1 + x * 3, rgb1 + x * 3 + 3};
+            for (int p = 0; p < 4; ++p)
+                for (int k = 0; k < 3; ++k)
+                {
+                    const int r = (yy[p] + d[k]) >> 6;
+                    out[p][k] = (unsigned char)(r < 0 ? 0 : (r > 255 ? 255 : r));
+                }
+            vuptr += 2;
+        }
+    }
+}
+// ncnn's fixed-point bilinear resize of 1 to 4 interleaved channels (mat_pixel_resize.cpp).  A source 1 pixel wide or high writes
+// nothing (the reference reads index -1 there).
+inline void resize_bilinear_c1(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h)
+{
+    if (srcw >= 2 && srch >= 2) Mat::resize_bilinear(src, srcw, srch, 1, dst, w, h);
+}
+inline void resize_bilinear_c2(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h)
+{
+    if (srcw >= 2 && srch >= 2) Mat::resize_bilinear(src, srcw, srch, 2, dst, w, h);
+}
+inline void resize_bilinear_c3(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h)
+{
+    if (srcw >= 2 && srch >= 2) Mat::resize_bilinear(src, srcw, srch, 3, dst, w, h);
+}
+inline void resize_bilinear_c4(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h)
+{
+    if (srcw >= 2 && srch >= 2) Mat::resize_bilinear(src, srcw, srch, 4, dst, w, h);
+}
+// an NV21 frame resized plane by plane (mat_pixel_resize.cpp:1174-1189): Y as c1, the VU plane as c2 at half the sizes.  All four
+// sizes must be even; below 4 source pixels the VU plane is 1 pair wide or high and stays unwritten (see above).
+inline void resize_bilinear_yuv420sp(const unsigned char* src, int srcw, int srch, unsigned char* dst, int w, int h)
+{
+    resize_bilinear_c1(src, srcw, srch, dst, w, h);
+    resize_bilinear_c2(src + (size_t)srcw * srch, srcw / 2, srch / 2, dst + (size_t)w * h, w / 2, h / 2);
+}
 
 } // namespace ncnn
 
