@@ -32,6 +32,11 @@ class fhip_pool_param(ctypes.Structure):
         "pad_top", "pad_bottom", "pooling_type", "global_pooling")]
 
 
+class fhip_pixel_image(ctypes.Structure):
+    """fhip_pixel_image (feather_net.h): one image of a mixed-size batch; stride 0 = w * channels, roi_w = roi_h = 0 = the whole image."""
+    _fields_ = [("data", ctypes.c_void_p)] + [(n, ctypes.c_int) for n in ("w", "h", "stride", "roi_x", "roi_y", "roi_w", "roi_h")]
+
+
 _P = ctypes.POINTER(fhip_conv_param)
 _Q = ctypes.POINTER(fhip_pool_param)
 _PI = ctypes.POINTER(ctypes.c_int)
@@ -80,6 +85,8 @@ SIGNATURES = {
     "fhip_conv_forward_maxpool2": (_I, [_P, _I, _I, _V, _V, _V, _V, _V, _V]),
     "fhip_pixels_to_float": (_I, [_V, _V, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
     "fhip_yuv420sp_to_float": (_I, [_V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_pixel_images_plan": (_I, [_V, _I, _I, _I, _I, _V, ctypes.POINTER(_SZ)]),
+    "fhip_pixels_to_float_images": (_I, [_V, _V, _V, _V, _V, _V]),
     "fhip_pooling_output_dim": (_I, [_Q, _PI, _PI]),
     "fhip_pooling": (_I, [_Q, _I, _V, _V, _V]),
     "fhip_softmax": (_I, [_V, _V, _I, _I, _V]),
@@ -100,6 +107,7 @@ SIGNATURES = {
     "fhip_net_feed_input": (_I, [_V, ctypes.c_char_p, _I, _I, _I, _I, _V, _I]),
     "fhip_net_feed_pixels": (_I, [_V, ctypes.c_char_p, _I, _V, _I, _I, _I, _I, _I, _V, _V, _I]),
     "fhip_net_feed_yuv420sp": (_I, [_V, ctypes.c_char_p, _I, _V, _I, _I, _I, _I, _I, _I, _V, _V, _I]),
+    "fhip_net_feed_pixel_images": (_I, [_V, ctypes.c_char_p, _I, _V, _I, _I, _I, _V, _V, _I]),
     "fhip_net_forward": (_I, [_V]),
     "fhip_net_extract": (_I, [_V, ctypes.c_char_p, ctypes.POINTER(_V), _PI, _PI, _PI, _PI]),
     "fhip_net_extract_host": (_I, [_V, ctypes.c_char_p, _V, _SZ]),

@@ -11,6 +11,8 @@
 // InnerProduct needs no kernel of its own: it is a 1x1 convolution over a 1x1 image with C*H*W input channels and runs
 // through the implicit-GEMM path (split-K takes care of the tiny N = batch).
 #include <float.h>
+#include <stdio.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -86,9 +88,22 @@ struct PlaneSrc
 // that the reference's yuv420sp2rgb makes of them (fhip_yuv420sp_to_float):
 //   yuv = 1: resize_bilinear_yuv420sp first (Y plane as c1, VU plane as c2 at half size), then yuv420sp2rgb at the target size;
 //   yuv = 2: yuv420sp2rgb at the source size, then from_pixels_resize's resize in RGB (c3).
+// With plan != NULL the images are a planned batch (fhip_pixels_to_float_images): image n's layout is plan[n], which stands in for the
+// by-value px + n * image, w, h, resize and scales (the images differ in size, pitch and ROI); type, target and mean / norm stay by value.
+struct PixelPlanEntry
+{
+    const unsigned char* px; // the ROI's first byte
+    size_t pitch;            // bytes from one source row to the next
+    int w, h;                // the ROI's size: the source from_pixels_resize sees
+    int resize;              // w != tw || h != th
+    int reserved;
+    double scale_x, scale_y; // (double)w / tw, (double)h / th, as pixel_src computes them
+};
+
 struct PixelSrc
 {
     const unsigned char* px;
+    const PixelPlanEntry* plan; // NULL but for fhip_pixels_to_float_images (device memory)
     size_t image;   // bytes per image (h*w*cin, or h*w*3/2 for an NV21 frame)
     int w, h, cin, cout, tw, th;
     int resize;     // 0: target size == source size, the bytes are read as they are
@@ -163,32 +178,59 @@ struct PixelSrc
         const int oy = (int)(t % th);
         const size_t nc = t / th;
         const int c = (int)(nc % cout);
+        if (__builtin_expect(plan != nullptr, 0)) // keeps the raw-pixel path (fhip_pixels_to_float) the straight-line one
+        {
+            planned_values<COLS>((int)(nc / cout), c, oy, ox, out);
+            return;
+        }
         const unsigned char* img = px + (nc / cout) * image;
-        if (__builtin_expect(yuv != 0, 0)) // keeps the raw-pixel path (fhip_pixels_to_float) the straight-line one
+        if (__builtin_expect(yuv != 0, 0))
         {
             yuv_values<COLS>(img, c, oy, ox, out);
             return;
         }
-        if (!resize)
+        raw_values<COLS>(img, (size_t)w * cin, w, h, resize, scale_x, scale_y, c, oy, ox, out);
+    }
+    // values() of raw pixels: an image of sw x sh pixels at img, rows `pitch` bytes apart
+    template <int COLS>
+    __device__ __forceinline__ void raw_values(const unsigned char* img, size_t pitch, int sw, int sh, int rs, double sx_scale, double sy_scale,
+                                               int c, int oy, int ox, float* out) const
+    {
+        if (!rs)
         {
 #pragma unroll
             for (int j = 0; j < COLS; ++j)
             {
-                const unsigned char* p = img + ((size_t)oy * w + ox + j) * cin;
+                const unsigned char* p = img + (size_t)oy * pitch + (size_t)(ox + j) * cin;
                 out[j] = convert(c, [&](int k) { return (int)p[k]; });
             }
             return;
         }
         int sy, b0, b1;
-        coef(oy, h, scale_y, sy, b0, b1);
+        coef(oy, sh, sy_scale, sy, b0, b1);
 #pragma unroll
         for (int j = 0; j < COLS; ++j)
         {
             int sx, a0, a1;
-            coef(ox + j, w, scale_x, sx, a0, a1);
-            const unsigned char* p = img + ((size_t)sy * w + sx) * cin;
-            out[j] = convert(c, [&](int k) { return sample(PlaneAt{p + k, (size_t)w * cin, cin}, b0, b1, a0, a1); });
+            coef(ox + j, sw, sx_scale, sx, a0, a1);
+            const unsigned char* p = img + (size_t)sy * pitch + (size_t)sx * cin;
+            out[j] = convert(c, [&](int k) { return sample(PlaneAt{p + k, pitch, cin}, b0, b1, a0, a1); });
         }
+    }
+    // values() of image n of a planned batch.  A wave inside one image (every wave when a plane is a multiple of 256 outputs, 224 x 224
+    // among them) reads the entry at a wave-uniform index, so with scalar loads; a wave across two images reads it per lane.
+    template <int COLS>
+    __device__ __forceinline__ void planned_values(int n, int c, int oy, int ox, float* out) const
+    {
+        const int u = __builtin_amdgcn_readfirstlane(n);
+        if (__builtin_amdgcn_ballot_w64(n != u) == 0)
+        {
+            const PixelPlanEntry& e = plan[u];
+            raw_values<COLS>(e.px, e.pitch, e.w, e.h, e.resize, e.scale_x, e.scale_y, c, oy, ox, out);
+            return;
+        }
+        const PixelPlanEntry& e = plan[n];
+        raw_values<COLS>(e.px, e.pitch, e.w, e.h, e.resize, e.scale_x, e.scale_y, c, oy, ox, out);
     }
     // values() of an NV21 frame; Y at img, the VU plane (w/2 pairs per row) at img + w*h
     template <int COLS>
@@ -560,6 +602,34 @@ static int launch_pixels(float* output, const PixelSrc& src, int batch, void* st
     return FHIP_OK;
 }
 
+// The opaque plan of fhip_pixel_images_plan: this header, then `batch` PixelPlanEntry.  `check` is a hash of the other fields, so a buffer
+// the builder did not write is refused before any launch.
+struct PixelPlanHeader
+{
+    unsigned magic;
+    int batch, type, tw, th, cin, cout, reserved;
+    unsigned long long bytes; // header + entries
+    unsigned long long check;
+};
+static_assert(sizeof(PixelPlanHeader) % 16 == 0 && sizeof(PixelPlanEntry) % 16 == 0, "plan entries stay 16-byte aligned");
+constexpr unsigned kPixelPlanMagic = 0x50504846u; // "FHPP"
+
+static unsigned long long plan_check(const PixelPlanHeader& h)
+{
+    const unsigned long long v[9] = {h.magic, (unsigned)h.batch, (unsigned)h.type, (unsigned)h.tw, (unsigned)h.th, (unsigned)h.cin, (unsigned)h.cout,
+                                     (unsigned)h.reserved, h.bytes};
+    unsigned long long x = 0xcbf29ce484222325ULL; // FNV-1a over the fields
+    for (unsigned long long f : v) x = (x ^ f) * 0x100000001b3ULL;
+    return x;
+}
+
+static int bad_image(int i, const char* what)
+{
+    char msg[160];
+    snprintf(msg, sizeof msg, "image %d: %s", i, what);
+    return fail(FHIP_E_BADARG, msg);
+}
+
 // threads needed: one per float4 plus one per leftover float
 static unsigned ew_grid(size_t n4, size_t n) { return (unsigned)((n4 + (n - n4 * 4) + 255) / 256); }
 
@@ -645,6 +715,80 @@ int fhip_yuv420sp_to_float(float* output, const unsigned char* yuv, int batch, i
     src.uv_scale_x = (double)(w / 2) / (target_w / 2);
     src.uv_scale_y = (double)(h / 2) / (target_h / 2);
     return launch_pixels(output, src, batch, stream);
+}
+
+int fhip_pixel_images_plan(const fhip_pixel_image* images, int batch, int type, int target_w, int target_h, void* plan, size_t* plan_bytes)
+{
+    int cin, cout;
+    if (pixel_channels(type, &cin, &cout)) return fail(FHIP_E_BADARG, "unknown pixel type");
+    if (!images || !plan_bytes || batch < 1 || target_w < 1 || target_h < 1) return fail(FHIP_E_BADARG, "bad argument");
+    for (int i = 0; i < batch; ++i)
+    {
+        const fhip_pixel_image& im = images[i];
+        if (!im.data) return bad_image(i, "null data");
+        if (im.w < 1 || im.h < 1) return bad_image(i, "w and h must be at least 1");
+        if ((long long)im.w * cin > 0x7fffffff) return bad_image(i, "row longer than 2 GiB");
+        if (im.stride != 0 && (long long)im.stride < (long long)im.w * cin) return bad_image(i, "stride below w * channels");
+        const bool whole = im.roi_w == 0 && im.roi_h == 0;
+        const long long rx = whole ? 0 : im.roi_x, ry = whole ? 0 : im.roi_y, rw = whole ? im.w : im.roi_w, rh = whole ? im.h : im.roi_h;
+        if (rw < 1 || rh < 1 || rx < 0 || ry < 0 || rx + rw > im.w || ry + rh > im.h) return bad_image(i, "ROI not inside the image");
+        // the reference's resize reads column / row -1 for a 1-pixel source axis (sx = srcw - 2); refused as in fhip_pixels_to_float
+        if ((rw != target_w || rh != target_h) && (rw < 2 || rh < 2)) return bad_image(i, "a ROI 1 pixel wide or high cannot be resized");
+    }
+    const size_t need = sizeof(PixelPlanHeader) + (size_t)batch * sizeof(PixelPlanEntry);
+    if (!plan)
+    {
+        *plan_bytes = need;
+        return FHIP_OK;
+    }
+    if (*plan_bytes < need) return fail(FHIP_E_BADARG, "plan buffer too small");
+    if ((uintptr_t)plan & 7) return fail(FHIP_E_BADARG, "plan not 8-byte aligned");
+    PixelPlanHeader hd = {};
+    hd.magic = kPixelPlanMagic;
+    hd.batch = batch;
+    hd.type = type;
+    hd.tw = target_w;
+    hd.th = target_h;
+    hd.cin = cin;
+    hd.cout = cout;
+    hd.bytes = need;
+    hd.check = plan_check(hd);
+    memcpy(plan, &hd, sizeof hd);
+    PixelPlanEntry* e = reinterpret_cast<PixelPlanEntry*>((char*)plan + sizeof hd);
+    for (int i = 0; i < batch; ++i)
+    {
+        const fhip_pixel_image& im = images[i];
+        const bool whole = im.roi_w == 0 && im.roi_h == 0;
+        const int rx = whole ? 0 : im.roi_x, ry = whole ? 0 : im.roi_y, rw = whole ? im.w : im.roi_w, rh = whole ? im.h : im.roi_h;
+        const size_t pitch = im.stride ? (size_t)im.stride : (size_t)im.w * cin;
+        PixelPlanEntry en = {};
+        en.px = im.data + (size_t)ry * pitch + (size_t)rx * cin;
+        en.pitch = pitch;
+        en.w = rw;
+        en.h = rh;
+        en.resize = rw != target_w || rh != target_h;
+        en.scale_x = (double)rw / target_w; // IEEE division on the host, as pixel_src
+        en.scale_y = (double)rh / target_h;
+        e[i] = en;
+    }
+    *plan_bytes = need;
+    return FHIP_OK;
+}
+
+int fhip_pixels_to_float_images(float* output, const void* plan, const void* plan_device, const float* mean, const float* norm, void* stream)
+{
+    if (!output || !plan || !plan_device) return fail(FHIP_E_BADARG, "bad argument");
+    if (((uintptr_t)plan | (uintptr_t)plan_device) & 7) return fail(FHIP_E_BADARG, "plan not 8-byte aligned");
+    if ((uintptr_t)output & 3) return fail(FHIP_E_BADARG, "output not 4-byte aligned");
+    PixelPlanHeader hd;
+    memcpy(&hd, plan, sizeof hd);
+    int cin, cout;
+    if (hd.magic != kPixelPlanMagic || hd.check != plan_check(hd) || pixel_channels(hd.type, &cin, &cout) || cin != hd.cin || cout != hd.cout ||
+        hd.batch < 1 || hd.tw < 1 || hd.th < 1 || hd.bytes != sizeof(PixelPlanHeader) + (size_t)hd.batch * sizeof(PixelPlanEntry))
+        return fail(FHIP_E_BADARG, "not a plan written by fhip_pixel_images_plan");
+    PixelSrc src = pixel_src(nullptr, hd.type, cin, cout, hd.tw, hd.th, hd.tw, hd.th, mean, norm);
+    src.plan = reinterpret_cast<const PixelPlanEntry*>((const char*)plan_device + sizeof(PixelPlanHeader));
+    return launch_pixels(output, src, hd.batch, stream);
 }
 
 int fhip_pooling_output_dim(const fhip_pool_param* p, int* out_h, int* out_w)

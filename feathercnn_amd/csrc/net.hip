@@ -1616,11 +1616,14 @@ struct fhip_net
     std::vector<hipEvent_t> joins;
     std::vector<int> share;                    // images per replica at the last FeedInput (index 0 = impl)
     std::map<std::string, DeviceVec> gathered; // Extract: blobs put back together (device pointer API)
-    unsigned char* staging = nullptr;          // FeedPixels from host memory: the uint8 images, uploaded once
+    unsigned char* staging = nullptr;          // FeedPixels from host memory: the uint8 images, uploaded once (FeedPixelImages: + plans)
     size_t staging_bytes = 0;
+    std::vector<unsigned char> plans;          // FeedPixelImages: the host plans, the source of their upload into the staging buffer
+    hipEvent_t plans_read = nullptr;           // recorded after that upload; `plans` is rewritten only once it has passed
     ~fhip_net()
     {
         if (staging) (void)hipFree(staging);
+        if (plans_read) (void)hipEventDestroy(plans_read);
         more.clear();
         for (hipStream_t st : more_streams) (void)hipStreamDestroy(st);
         if (fork) (void)hipEventDestroy(fork);
@@ -1635,9 +1638,64 @@ static void deal(int num, int parts, std::vector<int>& share)
     for (int r = 0; r < num % parts; ++r) ++share[r];
 }
 
+// n's staging buffer holds at least `bytes`
+static int reserve_staging(fhip_net* n, size_t bytes)
+{
+    if (bytes <= n->staging_bytes) return FHIP_OK;
+    // the old buffer may still be read by conversions queued earlier (every replica's is joined into the net's stream)
+    FHIP_CHECK_HIP(hipStreamSynchronize(n->impl.stream));
+    if (n->staging) FHIP_CHECK_HIP(hipFree(n->staging));
+    n->staging = nullptr;
+    n->staging_bytes = 0;
+    FHIP_CHECK_HIP(hipMalloc((void**)&n->staging, bytes));
+    n->staging_bytes = bytes;
+    return FHIP_OK;
+}
+
+// The shares of fhip_net_feed_input for `num` images converted into blob_name as [num][cout][target_h][target_w]: with sub-batch replicas
+// contiguous shares, each converted by its replica on its own stream after a fork from the net's stream and joined back; each net's blob
+// is reshaped (and its graph dropped) only when its shape changes.  convert(output, first image, count, stream).
+template <class Convert>
+static int feed_shares(fhip_net* n, const char* blob_name, int num, int cout, int target_w, int target_h, const Convert& convert)
+{
+    const auto into_blob = [&](fhip_net* m, int first, int cnt) -> int {
+        Blob* b = m->impl.find(blob_name);
+        if (!b) return failf(NET_E_IO, "Invalid input blob %s, not found in map.", blob_name);
+        if (b->n != cnt || b->c != cout || b->h != target_h || b->w != target_w)
+        {
+            const float* old = b->data;
+            const int rc = b->reshape(cnt, cout, target_h, target_w);
+            if (rc) return rc;
+            m->impl.shapes_dirty = true;
+            if (old != b->data) m->impl.drop_graph();
+        }
+        return convert(b->data, first, cnt, m->impl.stream);
+    };
+    if (!n->more.empty())
+    {
+        deal(num, (int)n->more.size() + 1, n->share);
+        FHIP_CHECK_HIP(hipEventRecord(n->fork, n->impl.stream));
+        int first = n->share[0];
+        for (size_t r = 0; r < n->more.size(); ++r)
+        {
+            const int cnt = n->share[r + 1];
+            if (cnt > 0)
+            {
+                FHIP_CHECK_HIP(hipStreamWaitEvent(n->more[r]->impl.stream, n->fork, 0));
+                const int rc = into_blob(n->more[r].get(), first, cnt);
+                if (rc) return rc;
+                FHIP_CHECK_HIP(hipEventRecord(n->joins[r], n->more[r]->impl.stream));
+                FHIP_CHECK_HIP(hipStreamWaitEvent(n->impl.stream, n->joins[r], 0));
+            }
+            first += cnt;
+        }
+        num = n->share[0];
+    }
+    return into_blob(n, 0, num);
+}
+
 // The body of fhip_net_feed_pixels / fhip_net_feed_yuv420sp once the arguments are checked: `num` images of `image` bytes (host memory
-// unless on_device) into blob_name as [num][cout][target_h][target_w], each net converting its share with
-// convert(output, device bytes, count, stream).
+// unless on_device) into blob_name, each net converting its share with convert(output, device bytes, count, stream).
 template <class Convert>
 static int feed_bytes(fhip_net* n, const char* blob_name, int num, const unsigned char* bytes_in, size_t image, int cout, int target_w,
                       int target_h, int on_device, const Convert& convert)
@@ -1647,51 +1705,14 @@ static int feed_bytes(fhip_net* n, const char* blob_name, int num, const unsigne
     if (!on_device)
     {
         // one uint8 upload of the whole batch on the net's stream; the replicas then read their shares from the staging buffer
-        const size_t bytes = image * num;
-        if (bytes > n->staging_bytes)
-        {
-            // the old buffer may still be read by conversions queued earlier (every replica's is joined into the net's stream)
-            FHIP_CHECK_HIP(hipStreamSynchronize(n->impl.stream));
-            if (n->staging) FHIP_CHECK_HIP(hipFree(n->staging));
-            n->staging = nullptr;
-            n->staging_bytes = 0;
-            FHIP_CHECK_HIP(hipMalloc((void**)&n->staging, bytes));
-            n->staging_bytes = bytes;
-        }
-        FHIP_CHECK_HIP(hipMemcpyAsync(n->staging, pixels, bytes, hipMemcpyHostToDevice, n->impl.stream));
+        const int rc = reserve_staging(n, image * num);
+        if (rc) return rc;
+        FHIP_CHECK_HIP(hipMemcpyAsync(n->staging, pixels, image * num, hipMemcpyHostToDevice, n->impl.stream));
         pixels = n->staging;
     }
-    if (!n->more.empty())
-    {
-        // the shares of fhip_net_feed_input: contiguous, each converted by its replica on its own stream after the fork, joined back
-        deal(num, (int)n->more.size() + 1, n->share);
-        FHIP_CHECK_HIP(hipEventRecord(n->fork, n->impl.stream));
-        size_t first = n->share[0];
-        for (size_t r = 0; r < n->more.size(); ++r)
-        {
-            const int cnt = n->share[r + 1];
-            if (cnt > 0)
-            {
-                FHIP_CHECK_HIP(hipStreamWaitEvent(n->more[r]->impl.stream, n->fork, 0));
-                const int rc = feed_bytes(n->more[r].get(), blob_name, cnt, pixels + first * image, image, cout, target_w, target_h, 1, convert);
-                if (rc) return rc;
-                FHIP_CHECK_HIP(hipEventRecord(n->joins[r], n->more[r]->impl.stream));
-                FHIP_CHECK_HIP(hipStreamWaitEvent(n->impl.stream, n->joins[r], 0));
-            }
-            first += cnt;
-        }
-        num = n->share[0];
-    }
-    Blob* b = n->impl.find(blob_name);
-    if (b->n != num || b->c != cout || b->h != target_h || b->w != target_w)
-    {
-        const float* old = b->data;
-        const int rc = b->reshape(num, cout, target_h, target_w);
-        if (rc) return rc;
-        n->impl.shapes_dirty = true;
-        if (old != b->data) n->impl.drop_graph();
-    }
-    return convert(b->data, pixels, num, n->impl.stream);
+    return feed_shares(n, blob_name, num, cout, target_w, target_h, [&](float* out, int first, int cnt, hipStream_t s) {
+        return convert(out, pixels + first * image, cnt, s);
+    });
 }
 
 #define NET_GUARD(n) \
@@ -1916,6 +1937,76 @@ int fhip_net_feed_yuv420sp(fhip_net* n, const char* blob_name, int num, const un
                       [&](float* out, const unsigned char* px, int cnt, hipStream_t s) {
                           return fhip_yuv420sp_to_float(out, px, cnt, type, w, h, target_w, target_h, resize_first, mean, norm, s);
                       });
+}
+
+int fhip_net_feed_pixel_images(fhip_net* n, const char* blob_name, int num, const fhip_pixel_image* images, int type, int target_w,
+                               int target_h, const float* mean, const float* norm, int on_device)
+{
+    NET_GUARD(n);
+    if (!blob_name) return fail(FHIP_E_BADARG, "bad argument");
+    size_t bytes = 0;
+    int rc = fhip_pixel_images_plan(images, num, type, target_w, target_h, nullptr, &bytes); // every descriptor checked here
+    if (rc) return rc;
+    if (!n->impl.find(blob_name)) return failf(NET_E_IO, "Invalid input blob %s, not found in map.", blob_name);
+    int cin, cout;
+    pixel_channels(type, &cin, &cout);
+    // one plan per replica's share (feed_shares deals them the same way), then, from host memory, the ROIs packed dense
+    std::vector<int> share;
+    deal(num, (int)n->more.size() + 1, share);
+    std::vector<size_t> plan_at(share.size(), 0);
+    size_t plans = 0;
+    for (size_t r = 0, first = 0; r < share.size(); first += share[r++])
+    {
+        plan_at[r] = plans;
+        if (!share[r]) continue;
+        rc = fhip_pixel_images_plan(images + first, share[r], type, target_w, target_h, nullptr, &bytes);
+        if (rc) return rc;
+        plans += round_up_sz(bytes, 16);
+    }
+    std::vector<size_t> roi_at(on_device ? 0 : num);
+    size_t total = round_up_sz(plans, 256);
+    for (size_t i = 0; i < roi_at.size(); ++i)
+    {
+        const fhip_pixel_image& im = images[i];
+        const bool whole = im.roi_w == 0 && im.roi_h == 0;
+        const size_t pitch = im.stride ? (size_t)im.stride : (size_t)im.w * cin;
+        roi_at[i] = total;
+        total += (size_t)((whole ? im.h : im.roi_h) - 1) * pitch + (size_t)(whole ? im.w : im.roi_w) * cin; // the ROI's row span
+    }
+    // the previous feed's plan upload reads n->plans until it has run
+    if (n->plans_read) FHIP_CHECK_HIP(hipEventSynchronize(n->plans_read));
+    else FHIP_CHECK_HIP(hipEventCreateWithFlags(&n->plans_read, hipEventDisableTiming));
+    rc = reserve_staging(n, total);
+    if (rc) return rc;
+    // host images: one copy per ROI of its rows, from its first byte to its last, pitch kept (one 2-D copy per ROI of only its columns
+    // measured 0.7 ms per image: DESIGN.md 9.1); described in the staging buffer as images that are their ROI
+    std::vector<fhip_pixel_image> dense(roi_at.size());
+    for (size_t i = 0; i < roi_at.size(); ++i)
+    {
+        const fhip_pixel_image& im = images[i];
+        const bool whole = im.roi_w == 0 && im.roi_h == 0;
+        const int rx = whole ? 0 : im.roi_x, ry = whole ? 0 : im.roi_y, rw = whole ? im.w : im.roi_w, rh = whole ? im.h : im.roi_h;
+        const size_t pitch = im.stride ? (size_t)im.stride : (size_t)im.w * cin;
+        FHIP_CHECK_HIP(hipMemcpyAsync(n->staging + roi_at[i], im.data + (size_t)ry * pitch + (size_t)rx * cin, (size_t)(rh - 1) * pitch + (size_t)rw * cin,
+                                      hipMemcpyHostToDevice, n->impl.stream));
+        dense[i] = fhip_pixel_image{n->staging + roi_at[i], rw, rh, (int)pitch, 0, 0, 0, 0};
+    }
+    const fhip_pixel_image* planned = on_device ? images : dense.data();
+    n->plans.resize(plans);
+    for (size_t r = 0, first = 0; r < share.size(); first += share[r++])
+    {
+        if (!share[r]) continue;
+        bytes = plans - plan_at[r];
+        rc = fhip_pixel_images_plan(planned + first, share[r], type, target_w, target_h, n->plans.data() + plan_at[r], &bytes);
+        if (rc) return rc;
+    }
+    FHIP_CHECK_HIP(hipMemcpyAsync(n->staging, n->plans.data(), plans, hipMemcpyHostToDevice, n->impl.stream));
+    FHIP_CHECK_HIP(hipEventRecord(n->plans_read, n->impl.stream));
+    return feed_shares(n, blob_name, num, cout, target_w, target_h, [&](float* out, int first, int, hipStream_t s) {
+        size_t r = 0; // the share that starts at `first`
+        for (int f = 0; f < first; f += share[r++]) {}
+        return fhip_pixels_to_float_images(out, n->plans.data() + plan_at[r], n->staging + plan_at[r], mean, norm, s);
+    });
 }
 
 int fhip_net_forward(fhip_net* n)

@@ -101,6 +101,26 @@ class Net:
         del keep, m, s
         return 0
 
+    def FeedPixelImages(self, input_name: str, images, ptype: int, target, rois=None, mean=None, norm=None) -> int:
+        """A mixed-size batch straight into the input blob, on the device (fhip_net_feed_pixel_images): `images` a list of uint8 [H][W][C]
+        numpy arrays (each ROI's rows uploaded) or CUDA tensors, all of one kind; row-strided views are read in place.  rois: None or one
+        (x, y, w, h) / None per image; target = (w, h); mean / norm: one value per output channel, or None.  Image i becomes
+        from_pixels_resize of a dense copy of its ROI."""
+        from .pixels import _image_descs, _per_channel, pixel_channels
+        import torch
+        descs, dev, keep = _image_descs(images, ptype, rois)
+        tw, th = int(target[0]), int(target[1])
+        _, cout = pixel_channels(ptype)
+        m, mp = _per_channel(mean, cout, "mean")
+        s, sp = _per_channel(norm, cout, "norm")
+        if dev:
+            torch.cuda.current_stream().synchronize()  # the net's stream may differ from the producer's
+        _check(self._lib.fhip_net_feed_pixel_images(self._h, input_name.encode(), len(descs), descs, int(ptype), tw, th, mp, sp, dev),
+               "fhip_net_feed_pixel_images")
+        self.synchronize()  # the host arrays / device tensors may be freed or overwritten by the caller
+        del keep, m, s
+        return 0
+
     def FeedYUV420sp(self, input_name: str, frames, ptype: int = 1, target=None, resize_first: bool = True, mean=None, norm=None) -> int:
         """NV21 camera frames straight into the input blob, on the device (fhip_net_feed_yuv420sp): `frames` is uint8 [N][h*3/2][w] (or
         [h*3/2][w]), a numpy array (uploaded once as uint8) or a CUDA tensor; ptype PIXEL_RGB (1), PIXEL_RGB2BGR or PIXEL_RGB2GRAY;

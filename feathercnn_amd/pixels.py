@@ -137,3 +137,79 @@ def yuv420sp_to_float(frames, ptype: int = PIXEL_RGB, target=None, resize_first:
                                                       mp, sp, _stream()), "fhip_yuv420sp_to_float")
     del m, s  # read by value at the call
     return out
+
+
+# ---- mixed-size batches: per-image size, pitch and ROI ----------------------------------------------------------------------------
+def _image_descs(images, ptype, rois):
+    """(ctypes array of fhip_pixel_image, on_device, keep-alive) of a list of uint8 [H][W][C] numpy arrays or CUDA tensors, all of one
+    kind.  A view whose pixels are contiguous within a row (img[y0:y1, x0:x1] included) is passed as it is, its row stride as the pitch;
+    anything else is copied.  rois: None, or one (x, y, w, h) or None per image."""
+    import torch
+    cin, _ = pixel_channels(ptype)
+    images = list(images)
+    if not images:
+        raise FeatherHipError("images: an empty list")
+    if rois is not None and len(rois) != len(images):
+        raise FeatherHipError(f"rois: {len(rois)} entries for {len(images)} images")
+    on_device = isinstance(images[0], torch.Tensor)
+    descs = (_lib.fhip_pixel_image * len(images))()
+    keep = []
+    for i, img in enumerate(images):
+        if on_device:
+            if not (isinstance(img, torch.Tensor) and img.is_cuda and img.dtype == torch.uint8):
+                raise FeatherHipError(f"images[{i}]: every image a uint8 CUDA tensor, or every image a uint8 numpy array")
+            if img.dim() != 3 or img.stride(2) != 1 or img.stride(1) != img.shape[2] or img.stride(0) < img.shape[1] * img.shape[2]:
+                img = img.contiguous()
+            shape, pitch, ptr = tuple(img.shape), img.stride(0), img.data_ptr()
+        else:
+            if isinstance(img, torch.Tensor) or not isinstance(img, np.ndarray) or img.dtype != np.uint8:
+                raise FeatherHipError(f"images[{i}]: every image a uint8 CUDA tensor, or every image a uint8 numpy array")
+            if img.ndim != 3 or img.strides[2] != 1 or img.strides[1] != img.shape[2] or img.strides[0] < img.shape[1] * img.shape[2]:
+                img = np.ascontiguousarray(img)
+            shape, pitch, ptr = img.shape, img.strides[0], img.ctypes.data
+        if len(shape) != 3 or shape[2] != cin:
+            raise FeatherHipError(f"images[{i}]: [H][W][{cin}] for pixel type {ptype:#x}, got {tuple(shape)}")
+        keep.append(img)
+        d = descs[i]
+        d.data, d.h, d.w, d.stride = ptr, int(shape[0]), int(shape[1]), int(pitch)
+        if rois is not None and rois[i] is not None:
+            d.roi_x, d.roi_y, d.roi_w, d.roi_h = (int(v) for v in rois[i])
+    return descs, int(on_device), keep
+
+
+def _plan(descs, ptype, tw, th):
+    """The host plan of fhip_pixel_images_plan as a uint8 numpy array (8-byte aligned)."""
+    lib = _lib.load_library()
+    size = ctypes.c_size_t(0)
+    _check(lib.fhip_pixel_images_plan(descs, len(descs), int(ptype), tw, th, None, ctypes.byref(size)), "fhip_pixel_images_plan")
+    buf = np.zeros((size.value + 7) // 8, np.uint64).view(np.uint8)[:size.value]
+    _check(lib.fhip_pixel_images_plan(descs, len(descs), int(ptype), tw, th, buf.ctypes.data_as(ctypes.c_void_p), ctypes.byref(size)),
+           "fhip_pixel_images_plan")
+    return buf
+
+
+def pixels_images_to_float(images, ptype: int, target, rois=None, mean=None, norm=None, out=None):
+    """A mixed-size batch on the current stream (fhip_pixels_to_float_images): `images` a list of uint8 CUDA tensors [H][W][C] (row-strided
+    views are read in place), rois None or one (x, y, w, h) / None per image -> fp32 CUDA tensor [N][cout][target_h][target_w], image i
+    bit-identical to from_pixels_resize of a dense copy of its ROI.  The plan is uploaded as a CUDA tensor on the current stream."""
+    import torch
+    descs, dev, keep = _image_descs(images, ptype, rois)
+    if not dev:
+        raise FeatherHipError("pixels_images_to_float wants uint8 CUDA tensors (Net.FeedPixelImages takes host arrays too)")
+    tw, th = int(target[0]), int(target[1])
+    _, cout = pixel_channels(ptype)
+    m, mp = _per_channel(mean, cout, "mean")
+    s, sp = _per_channel(norm, cout, "norm")
+    plan = _plan(descs, ptype, tw, th)
+    n = len(descs)
+    device = keep[0].device
+    plan_dev = torch.from_numpy(plan).to(device)  # on the current stream; freed into the caching allocator after the launch below
+    if out is None:
+        out = torch.empty((n, cout, th, tw), dtype=torch.float32, device=device)
+    elif tuple(out.shape) != (n, cout, th, tw) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise FeatherHipError(f"out must be a contiguous fp32 tensor of shape {(n, cout, th, tw)}")
+    _check(_lib.load_library().fhip_pixels_to_float_images(ctypes.c_void_p(out.data_ptr()), plan.ctypes.data_as(ctypes.c_void_p),
+                                                           ctypes.c_void_p(plan_dev.data_ptr()), mp, sp, _stream()),
+           "fhip_pixels_to_float_images")
+    del m, s, keep  # read at the call (the plan's bytes are on the device)
+    return out

@@ -12,7 +12,8 @@
 // Differences, all forced by the GPU batch path:
 //   * blobs live in HBM: Extract(name, float**, ...) returns a DEVICE pointer (use ExtractHost for a host copy);
 //   * besides the reference's FeedInput(name, ncnn::Mat&) (N = 1, net.cpp:235-246) there are pointer forms with an explicit batch,
-//     FeedPixels: ncnn's from_pixels_resize of a batch of uint8 images, done on the device;
+//     FeedPixels: ncnn's from_pixels_resize of a batch of uint8 images, done on the device (FeedPixelImages: images of mixed sizes,
+//     pitches and ROIs);
 //     and FeedYUV420sp: a batch of NV21 camera frames through either of the reference's yuv420sp chains, on the device;
 //   * Extract(name, ncnn::Mat&) copies channel by channel like the reference (net.cpp:281-296) -- but every channel, where the
 //     reference copies channel 0 into all of them (its source pointer never advances); a batch > 1 comes back as n*c channels;
@@ -95,6 +96,20 @@ class Net
                          const float* mean = NULL, const float* norm = NULL)
     {
         return fhip_net_feed_pixels(net_, input_name, n, device_pixels, type, w, h, target_w, target_h, mean, norm, 1);
+    }
+    // A mixed-size batch straight into the input blob, on the device (fhip_net_feed_pixel_images): image i is `images[i]` (its own size,
+    // row pitch and optional ROI), converted as ncnn's Mat::from_pixels_resize of a dense copy of its ROI (+ substract_mean_normalize).
+    // The descriptors are host memory; their data is host memory (each ROI's rows uploaded) or, with FeedPixelImagesDevice, device
+    // memory.  The blob becomes [n][cout][target_h][target_w].
+    int FeedPixelImages(const char* input_name, int n, const fhip_pixel_image* images, int type, int target_w, int target_h,
+                        const float* mean = NULL, const float* norm = NULL)
+    {
+        return fhip_net_feed_pixel_images(net_, input_name, n, images, type, target_w, target_h, mean, norm, 0);
+    }
+    int FeedPixelImagesDevice(const char* input_name, int n, const fhip_pixel_image* images, int type, int target_w, int target_h,
+                              const float* mean = NULL, const float* norm = NULL)
+    {
+        return fhip_net_feed_pixel_images(net_, input_name, n, images, type, target_w, target_h, mean, norm, 1);
     }
     // NV21 (yuv420sp) camera frames straight into the input blob, on the device (fhip_net_feed_yuv420sp): `n` frames of w x h
     // (w*h*3/2 bytes each), host memory (one uint8 upload) or, with FeedYUV420spDevice, device memory.  type: ncnn::Mat::PIXEL_RGB,

@@ -78,6 +78,32 @@ FHIP_API int fhip_pixels_to_float(float* output, const unsigned char* pixels, in
 FHIP_API int fhip_yuv420sp_to_float(float* output, const unsigned char* yuv, int batch, int type, int w, int h, int target_w, int target_h,
                                     int resize_first, const float* mean, const float* norm, void* stream);
 
+/* One image of a mixed-size batch: `data` points at pixel (0, 0), rows of w pixels of the type's source channels are `stride` bytes apart
+ * (0: w * cin, dense), and the region (roi_x, roi_y, roi_w, roi_h) is what gets resized (roi_w = roi_h = 0: the whole image).  The ROI
+ * lies inside the image.  Only the ROI's bytes are read. */
+typedef struct fhip_pixel_image
+{
+    const unsigned char* data;
+    int w, h, stride;
+    int roi_x, roi_y, roi_w, roi_h;
+} fhip_pixel_image;
+
+/* The plan of fhip_pixels_to_float_images: every descriptor checked on the host (FHIP_E_BADARG, the image index in fhip_last_error: null
+ * data, w or h < 1, a stride below w * cin, a ROI not inside the image, a ROI axis of 1 pixel that must be resized; an unknown type, a
+ * batch or target < 1), then written to `plan` as an opaque header (batch, type, target) plus one entry per image (the ROI's first byte,
+ * pitch, ROI size, resize flag and the reference's IEEE double scales).  plan = NULL: only *plan_bytes is set, to the size a plan takes;
+ * otherwise *plan_bytes is plan's capacity on entry and the size written on return.  `plan` is 8-byte aligned.  Host only. */
+FHIP_API int fhip_pixel_images_plan(const fhip_pixel_image* images, int batch, int type, int target_w, int target_h, void* plan,
+                                    size_t* plan_bytes);
+/* fhip_pixels_to_float for a planned batch: output image i, of [batch][cout][target_h][target_w] fp32 (4-byte aligned), is
+ * Mat::from_pixels_resize of a dense copy of image i's ROI to the plan's target, then mean / norm as fhip_pixels_to_float applies them.
+ * Batch, type, target and the launch shape come from the HOST plan; the kernel reads `plan_device`, a DEVICE copy of the same bytes
+ * (8-byte aligned) that must stay there until the conversion has run.  The plan's pointers are the descriptors' DEVICE pointers.
+ * One launch; no allocation, no copy: stream-capturable (a replay reads the plan and the images as they are then).  FHIP_E_BADARG,
+ * before any device call, for a host plan fhip_pixel_images_plan did not write. */
+FHIP_API int fhip_pixels_to_float_images(float* output, const void* plan, const void* plan_device, const float* mean, const float* norm,
+                                         void* stream);
+
 /* Convolution (+bias, +ReLU as the param says) followed by a 2x2 / stride-2 / unpadded MAX pooling, fused: the pooled
  * tensor [N][K][OH/2][OW/2] is written straight from the Winograd output transform and the full-resolution activation
  * never reaches HBM (VGG: every pooling layer follows a 3x3 convolution).  Same arguments as fhip_conv_forward.  Only the
@@ -254,6 +280,13 @@ FHIP_API int fhip_net_feed_pixels(fhip_net* net, const char* blob_name, int n, c
  * with the same reshape, stream, replica and staging behaviour; host frames are uploaded as w*h*3/2 bytes each. */
 FHIP_API int fhip_net_feed_yuv420sp(fhip_net* net, const char* blob_name, int n, const unsigned char* yuv, int w, int h, int target_w,
                                     int target_h, int type, int resize_first, const float* mean, const float* norm, int on_device);
+/* fhip_net_feed_pixels for `n` images of their own sizes, pitches and ROIs (fhip_pixel_image): fhip_pixels_to_float_images straight into
+ * the input blob, [n][cout][target_h][target_w], with the same reshape, stream and graph behaviour; each sub-batch replica converts its
+ * contiguous share of the images.  `on_device` = 0: each ROI's rows (from its first byte to its last, one copy per image) are uploaded
+ * back to back into the net's staging buffer together with the plans (the images may be reused once the net's stream has passed the
+ * feed); 1: the descriptors point at device memory and only the plans are uploaded. */
+FHIP_API int fhip_net_feed_pixel_images(fhip_net* net, const char* blob_name, int n, const fhip_pixel_image* images, int type,
+                                        int target_w, int target_h, const float* mean, const float* norm, int on_device);
 /* Net::Forward, net.cpp:297-334: Reshape when the input shape changed, Init once, then every layer in file
  * order on the net's stream.  Asynchronous: returns after enqueueing. */
 FHIP_API int fhip_net_forward(fhip_net* net);
