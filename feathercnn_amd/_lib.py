@@ -6,6 +6,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_PIXOUT = None
 
 STAGE_NAMES = ("wino_input", "wino_gemm", "wino_output", "igemm", "depthwise", "init", "wino_chain")
 
@@ -94,6 +95,7 @@ SIGNATURES = {
     "fhip_net_create": (_I, [ctypes.POINTER(_V)]),
     "fhip_net_destroy": (_I, [_V]),
     "fhip_net_set_stream": (_I, [_V, _V]),
+    "fhip_net_get_stream": (_I, [_V, ctypes.POINTER(_V)]),
     "fhip_net_set_fusion": (_I, [_V, _I]),
     "fhip_net_set_graph": (_I, [_V, _I]),
     "fhip_net_set_tuned_selection": (_I, [_V, _I]),
@@ -122,6 +124,14 @@ SIGNATURES = {
     "fhip_net_memory": (_I, [_V, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
 }
 
+# include/feather_hip/feather_pixout.h -- libfeather_pixout.so, the image output path (a library of its own)
+PIXOUT_SIGNATURES = {
+    "fhip_pixout_channels": (_I, [_I]),
+    "fhip_float_to_pixels": (_I, [_V, _SZ, _V, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_float_to_pixels_host": (_I, [_V, _SZ, _V, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_pixout_last_error": (ctypes.c_char_p, []),
+}
+
 
 def lib_path() -> str:
     return os.environ.get("FEATHER_HIP_LIB", os.path.join(_HERE, "libfeather_hip.so"))
@@ -145,3 +155,25 @@ def load_library():
             fn.argtypes = args
         _LIB = lib
     return _LIB
+
+
+def pixout_path() -> str:
+    return os.path.join(_HERE, "libfeather_pixout.so")
+
+
+def load_pixout_library():
+    """Load libfeather_pixout.so (fhip_float_to_pixels).  Fails loudly like load_library: there is no fallback implementation."""
+    global _PIXOUT
+    if _PIXOUT is None:
+        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
+        path = pixout_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in PIXOUT_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _PIXOUT = lib
+    return _PIXOUT

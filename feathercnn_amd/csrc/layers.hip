@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "feather_hip/feather_net.h"
+#include "pixel_resample.h"
 
 namespace fhip
 {
@@ -100,7 +101,8 @@ struct PixelPlanEntry
     double scale_x, scale_y; // (double)w / tw, (double)h / th, as pixel_src computes them
 };
 
-struct PixelSrc
+// coef() and sample(), the reference's fixed-point bilinear resize, come from PixelResample (pixel_resample.h)
+struct PixelSrc : PixelResample
 {
     const unsigned char* px;
     const PixelPlanEntry* plan; // NULL but for fhip_pixels_to_float_images (device memory)
@@ -114,38 +116,6 @@ struct PixelSrc
     double uv_scale_x, uv_scale_y; // yuv = 1: (double)(w/2) / (tw/2), (double)(h/2) / (th/2), the VU plane's resize_bilinear_c2
     float m[4], a[4];              // output channel c: v * m[c] + a[c], two roundings (see map)
 
-    // ncnn's coefficient of output index d along an axis of `src` source pixels (resize_bilinear_c1, mat_pixel_resize.cpp:46-71):
-    // float / double steps exactly as written there, so no contraction into FMAs
-    static __device__ __forceinline__ void coef(int d, int src, double scale, int& s, int& k0, int& k1)
-    {
-#pragma clang fp contract(off)
-        float f = (float)((d + 0.5) * scale - 0.5);
-        s = (int)floorf(f);
-        f -= (float)s;
-        if (s < 0)
-        {
-            s = 0;
-            f = 0.f;
-        }
-        if (s >= src - 1)
-        {
-            s = src - 2;
-            f = 1.f;
-        }
-        const float c0 = (1.f - f) * 2048.f, c1 = f * 2048.f;
-        k0 = min(max((int)(c0 + (c0 >= 0.f ? 0.5f : -0.5f)), -32768), 32767); // SATURATE_CAST_SHORT
-        k1 = min(max((int)(c1 + (c1 >= 0.f ? 0.5f : -0.5f)), -32768), 32767);
-    }
-    // one channel of the resized source at an output pixel: the horizontal pass ((S0*a0 + S1*a1) >> 4, kept as a short row value) on
-    // rows sy and sy + 1, then the vertical pass of the reference's scalar loop (mat_pixel_resize.cpp:272).  at(dy, dx) is that channel's
-    // byte at source pixel (sy + dy, sx + dx), dy and dx 0 or 1: raw image bytes, a plane of an NV21 frame, or RGB computed from one
-    template <class At>
-    static __device__ __forceinline__ int sample(const At& at, int b0, int b1, int a0, int a1)
-    {
-        const short row0 = (short)((at(0, 0) * a0 + at(0, 1) * a1) >> 4);
-        const short row1 = (short)((at(1, 0) * a0 + at(1, 1) * a1) >> 4);
-        return (unsigned char)(((short)((b0 * row0) >> 16) + (short)((b1 * row1) >> 16) + 2) >> 2);
-    }
     // at() of a plane of `step`-byte pixels, rows of `pitch` bytes, starting at the sample's top-left byte p
     struct PlaneAt
     {
@@ -527,12 +497,11 @@ __global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ y, con
 int pixel_channels(int type, int* cin, int* cout)
 {
     const int from = type & 0xffff, to = (unsigned)type >> 16;
-    const int ch[9] = {0, 3, 3, 0, 1, 0, 0, 0, 4}; // channels of RGB = 1, BGR = 2, GRAY = 4, RGBA = 8
-    if (from < 1 || from > 8 || !ch[from] || to > 8 || (to && !ch[to])) return FHIP_E_BADARG;
+    if (!pixel_format_channels(from) || (to && !pixel_format_channels(to))) return FHIP_E_BADARG;
     // the conversions ncnn's Mat::from_pixels knows (mat_pixel.cpp:1329-1367): none into RGBA, none from a format into itself
     if (to == FHIP_PIXEL_RGBA || to == from) return FHIP_E_BADARG;
-    *cin = ch[from];
-    *cout = to ? ch[to] : ch[from];
+    *cin = pixel_format_channels(from);
+    *cout = pixel_format_channels(to ? to : from);
     return 0;
 }
 

@@ -1771,6 +1771,14 @@ int fhip_net_set_stream(fhip_net* n, void* stream)
     return FHIP_OK;
 }
 
+int fhip_net_get_stream(fhip_net* n, void** stream)
+{
+    NET_GUARD(n);
+    if (!stream) return fail(FHIP_E_BADARG, "null argument");
+    *stream = (void*)n->impl.stream;
+    return FHIP_OK;
+}
+
 int fhip_net_set_fusion(fhip_net* n, int on)
 {
     NET_GUARD(n);

@@ -152,6 +152,30 @@ class Net:
                "fhip_net_extract_host")
         return out
 
+    def ExtractPixels(self, blob_name: str, ptype: int, target=None, mean=None, norm=None) -> np.ndarray:
+        """The blob as uint8 images, converted on the device (fhip_float_to_pixels on the net's stream, after Forward): ncnn's
+        substract_mean_normalize (when mean / norm are given, one value per channel) + Mat::to_pixels_resize of every image ->
+        np.uint8 [N][target_h][target_w][C].  ptype: PIXEL_RGB, PIXEL_BGR, PIXEL_GRAY, PIXEL_RGBA, PIXEL_RGB2BGR or PIXEL_BGR2RGB, whose
+        channels must be the blob's C; target = (w, h), default the blob's size.  Only the bytes cross the bus."""
+        from .pixels import _check_pixout, _per_channel, output_channels
+        cn = output_channels(ptype)
+        ptr, (n, c, h, w) = self.ExtractDevice(blob_name)
+        if c != cn:
+            raise FeatherHipError(f"blob {blob_name} has {c} channels, pixel type {ptype:#x} needs {cn}")
+        if not ptr:
+            raise FeatherHipError(f"blob {blob_name} has no data yet (run Forward first)")
+        tw, th = (w, h) if target is None else (int(target[0]), int(target[1]))
+        m, mp = _per_channel(mean, cn, "mean")
+        s, sp = _per_channel(norm, cn, "norm")
+        stream = ctypes.c_void_p()
+        _check(self._lib.fhip_net_get_stream(self._h, ctypes.byref(stream)), "fhip_net_get_stream")
+        out = np.empty((n, th, tw, cn), dtype=np.uint8)
+        _check_pixout(_lib.load_pixout_library().fhip_float_to_pixels_host(out.ctypes.data_as(ctypes.c_void_p), 0, ctypes.c_void_p(ptr), n,
+                                                                           int(ptype), w, h, tw, th, mp, sp, stream),
+                      "fhip_float_to_pixels_host")
+        del m, s
+        return out
+
     def ExtractDevice(self, blob_name: str):
         """(device pointer, (n, c, h, w)) of a blob -- the float** form of Net::Extract."""
         p = ctypes.c_void_p()

@@ -1,5 +1,6 @@
 """uint8 images to the fp32 input tensor on the device: ncnn's ``Mat::from_pixels_resize`` (+ ``substract_mean_normalize``) for a
-batch, over ``fhip_pixels_to_float`` (include/feather_hip/feather_net.h).  ``PIXEL_*`` are ncnn's codes (reference src/ncnn/mat.h:125-146)."""
+batch, over ``fhip_pixels_to_float`` (include/feather_hip/feather_net.h), and back: ``Mat::to_pixels_resize`` for a batch, over
+``fhip_float_to_pixels`` (include/feather_hip/feather_pixout.h).  ``PIXEL_*`` are ncnn's codes (reference src/ncnn/mat.h:125-146)."""
 from __future__ import annotations
 
 import ctypes
@@ -212,4 +213,60 @@ def pixels_images_to_float(images, ptype: int, target, rois=None, mean=None, nor
                                                            ctypes.c_void_p(plan_dev.data_ptr()), mp, sp, _stream()),
            "fhip_pixels_to_float_images")
     del m, s, keep  # read at the call (the plan's bytes are on the device)
+    return out
+
+
+# ---- the output side: fp32 tensors to uint8 images (libfeather_pixout.so) -------------------------------------------------------------
+_OUT_CHANNELS = {PIXEL_RGB: 3, PIXEL_BGR: 3, PIXEL_GRAY: 1, PIXEL_RGBA: 4, PIXEL_RGB2BGR: 3, PIXEL_BGR2RGB: 3}
+
+
+def output_channels(ptype: int) -> int:
+    """Channels of an OUTPUT pixel type (the six Mat::to_pixels writes anything for); every other type is refused."""
+    if ptype not in _OUT_CHANNELS:
+        raise FeatherHipError(f"pixel type {ptype:#x} is not an output type: PIXEL_RGB, PIXEL_BGR, PIXEL_GRAY, PIXEL_RGBA, PIXEL_RGB2BGR "
+                              "or PIXEL_BGR2RGB")
+    return _OUT_CHANNELS[ptype]
+
+
+def _check_pixout(rc: int, what: str):
+    if rc != 0:
+        msg = _lib.load_pixout_library().fhip_pixout_last_error().decode(errors="replace")
+        raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+
+
+def float_to_pixels(x, ptype: int, target=None, mean=None, norm=None, out=None):
+    """ncnn's Mat::to_pixels_resize (after substract_mean_normalize when mean / norm are given) of a batch on the current stream
+    (fhip_float_to_pixels): fp32 CUDA tensor [N][C][h][w] (or [C][h][w]) -> uint8 CUDA tensor [N][target_h][target_w][C], bit-identical
+    to the reference per image.  ptype: PIXEL_RGB, PIXEL_BGR, PIXEL_GRAY, PIXEL_RGBA, PIXEL_RGB2BGR or PIXEL_BGR2RGB, whose channels must
+    be C; target = (w, h), default the source size; mean / norm: C values (per plane of x) or None.  `out` may be given: a uint8 CUDA
+    tensor of that shape whose pixels and rows are contiguous -- a view into a padded frame works, its row stride is the pitch and the
+    bytes between its rows are not touched."""
+    import torch
+    cn = output_channels(ptype)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise FeatherHipError("float_to_pixels wants an fp32 CUDA tensor")
+    shape = tuple(x.shape)
+    if len(shape) == 3:
+        shape = (1,) + shape
+    if len(shape) != 4 or shape[1] != cn:
+        raise FeatherHipError(f"x: [N][{cn}][h][w] or [{cn}][h][w] for pixel type {ptype:#x}, got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise FeatherHipError("float_to_pixels wants an fp32 CUDA tensor")
+    x = x.contiguous()
+    n, _, h, w = (int(v) for v in shape)
+    tw, th = (w, h) if target is None else (int(target[0]), int(target[1]))
+    m, mp = _per_channel(mean, cn, "mean")
+    s, sp = _per_channel(norm, cn, "norm")
+    pitch = 0
+    if out is None:
+        out = torch.empty((n, th, tw, cn), dtype=torch.uint8, device=x.device)
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n, th, tw, cn)):
+            raise FeatherHipError(f"out must be a uint8 CUDA tensor of shape {(n, th, tw, cn)}")
+        pitch = out.stride(1)
+        if out.stride(3) != 1 or out.stride(2) != cn or pitch < tw * cn or out.stride(0) != th * pitch:
+            raise FeatherHipError("out: pixels and rows must be contiguous, rows `pitch` bytes apart and images target_h * pitch apart")
+    _check_pixout(_lib.load_pixout_library().fhip_float_to_pixels(ctypes.c_void_p(out.data_ptr()), pitch, ctypes.c_void_p(x.data_ptr()), n,
+                                                                  int(ptype), w, h, tw, th, mp, sp, _stream()), "fhip_float_to_pixels")
+    del m, s  # read by value at the call
     return out

@@ -15,6 +15,8 @@
 //     FeedPixels: ncnn's from_pixels_resize of a batch of uint8 images, done on the device (FeedPixelImages: images of mixed sizes,
 //     pitches and ROIs);
 //     and FeedYUV420sp: a batch of NV21 camera frames through either of the reference's yuv420sp chains, on the device;
+//   * ExtractPixels: a blob that is an image comes back as uint8 pixels, ncnn's Mat::to_pixels_resize of every image of the batch done
+//     on the device (libfeather_pixout.so: link it too when this method is used);
 //   * Extract(name, ncnn::Mat&) copies channel by channel like the reference (net.cpp:281-296) -- but every channel, where the
 //     reference copies channel 0 into all of them (its source pointer never advances); a batch > 1 comes back as n*c channels;
 //   * public data members of the reference class are not mirrored: `blob_map` (std::map<std::string, Blob<float>*>, net.h:54)
@@ -33,6 +35,7 @@
 #include <string>
 
 #include "feather_hip/feather_net.h"
+#include "feather_hip/feather_pixout.h"
 #include "ncnn/mat.h"
 
 namespace feather
@@ -156,6 +159,23 @@ class Net
         for (int q = 0; q < c * n; ++q) memcpy((float*)out.data + out.cstep * q, &dense[(size_t)q * plane * sizeof(float)], plane * sizeof(float));
         return 0;
     }
+    // The blob as uint8 images, converted on the device (fhip_float_to_pixels, feather_pixout.h): image i of the batch becomes what the
+    // reference's  m.substract_mean_normalize(mean, norm); m.to_pixels_resize(pixels_i, type, target_w, target_h)  makes of it, bit for
+    // bit; `pixels` is [n][target_h][target_w][cn] in host memory (only these bytes cross the bus; the stream is synchronised) or, with
+    // ExtractPixelsDevice, device memory (enqueued on the net's stream after Forward, no synchronisation).  type: ncnn::Mat::PIXEL_RGB,
+    // PIXEL_BGR, PIXEL_GRAY, PIXEL_RGBA, PIXEL_RGB2BGR or PIXEL_BGR2RGB, whose channels must be the blob's; mean / norm: one value per
+    // channel or NULL; pitch: bytes between output rows, 0 = dense.  *n_out (may be NULL) receives the batch.  Returns Extract's error for
+    // a blob that cannot be extracted, FHIP_E_BADARG (message in LastPixelError()) for a bad type, size or channel count.
+    int ExtractPixels(std::string blob_name, int* n_out, unsigned char* pixels, int type, int target_w, int target_h,
+                      const float* mean = NULL, const float* norm = NULL, size_t pitch = 0)
+    {
+        return extract_pixels(blob_name, n_out, pixels, type, target_w, target_h, mean, norm, pitch, false);
+    }
+    int ExtractPixelsDevice(std::string blob_name, int* n_out, unsigned char* device_pixels, int type, int target_w, int target_h,
+                            const float* mean = NULL, const float* norm = NULL, size_t pitch = 0)
+    {
+        return extract_pixels(blob_name, n_out, device_pixels, type, target_w, target_h, mean, norm, pitch, true);
+    }
     int ExtractHost(std::string blob_name, float* host, size_t capacity_floats) { return fhip_net_extract_host(net_, blob_name.c_str(), host, capacity_floats); }
 
     int SetStream(void* hip_stream) { return fhip_net_set_stream(net_, hip_stream); }
@@ -166,11 +186,29 @@ class Net
     int SetSubBatches(int replicas) { return fhip_net_set_sub_batches(net_, replicas); } // before LoadParam (feather_net.h)
     int LayerCount() { return fhip_net_layer_count(net_); }
     static const char* LastError() { return fhip_last_error(); }
+    static const char* LastPixelError() { return fhip_pixout_last_error(); } // ExtractPixels: the output library keeps its own message
     fhip_net* handle() { return net_; }
 
   private:
     Net(const Net&);
     Net& operator=(const Net&);
+    int extract_pixels(const std::string& blob_name, int* n_out, unsigned char* pixels, int type, int target_w, int target_h,
+                       const float* mean, const float* norm, size_t pitch, bool on_device)
+    {
+        float* dev = NULL;
+        int n = 0, c = 0, h = 0, w = 0;
+        void* stream = NULL;
+        int rc = fhip_net_extract(net_, blob_name.c_str(), &dev, &n, &c, &h, &w); // gathers sub-batch replicas on the net's stream
+        if (rc) return rc;
+        rc = fhip_net_get_stream(net_, &stream);
+        if (rc) return rc;
+        const int cn = fhip_pixout_channels(type);
+        if (cn < 0) return cn;
+        if (cn != c) return FHIP_E_BADARG; // the blob is not an image of this type
+        if (n_out) *n_out = n;
+        return on_device ? fhip_float_to_pixels(pixels, pitch, dev, n, type, w, h, target_w, target_h, mean, norm, stream)
+                         : fhip_float_to_pixels_host(pixels, pitch, dev, n, type, w, h, target_w, target_h, mean, norm, stream);
+    }
     int load_file(FILE* fp, bool param)
     {
         if (!fp) return -1;

@@ -218,6 +218,10 @@ FHIP_API int fhip_net_create(fhip_net** net);
 FHIP_API int fhip_net_destroy(fhip_net* net);
 /* All work of this net is enqueued on `stream` (default: the NULL stream).  Set before the first Forward. */
 FHIP_API int fhip_net_set_stream(fhip_net* net, void* stream);
+/* The stream this net's work is enqueued on as it stands (a hipStream_t as void*; NULL = the NULL stream): the one given to
+ * fhip_net_set_stream, or the net's own after fhip_net_set_graph(1) without one.  Work that reads a blob of fhip_net_extract on this
+ * stream is ordered after Forward (and after the gather of sub-batch replicas) with no synchronisation. */
+FHIP_API int fhip_net_get_stream(fhip_net* net, void** stream);
 /* Fusion level.  Set before the first Forward.
  *   0: none -- every layer of the file runs and every blob can be extracted, like the reference as shipped.
  *   1 (default): the TryFuse pass the reference declares but never calls (layer.cpp:82-101): Conv+ReLU, InnerProduct+ReLU,
