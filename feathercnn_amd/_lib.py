@@ -7,6 +7,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 _PIXOUT = None
+_GCONV = None
 
 STAGE_NAMES = ("wino_input", "wino_gemm", "wino_output", "igemm", "depthwise", "init", "wino_chain")
 
@@ -132,6 +133,16 @@ PIXOUT_SIGNATURES = {
     "fhip_pixout_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_gconv.h -- libfeather_gconv.so, grouped convolution with 1 < group < C (a library of its own)
+GCONV_SIGNATURES = {
+    "fhip_gconv_supported": (_I, [_P]),
+    "fhip_gconv_get_buffer_size": (_I, [_P, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "fhip_gconv_init": (_I, [_P, _V, _V, _V]),
+    "fhip_gconv_forward": (_I, [_P, _I, _V, _V, _V, _V, _V, _V]),
+    "fhip_gconv_route": (_I, [_P, _V, _V, ctypes.c_char_p, _I]),
+    "fhip_gconv_last_error": (ctypes.c_char_p, []),
+}
+
 
 def lib_path() -> str:
     return os.environ.get("FEATHER_HIP_LIB", os.path.join(_HERE, "libfeather_hip.so"))
@@ -177,3 +188,25 @@ def load_pixout_library():
             fn.argtypes = args
         _PIXOUT = lib
     return _PIXOUT
+
+
+def gconv_path() -> str:
+    return os.path.join(_HERE, "libfeather_gconv.so")
+
+
+def load_gconv_library():
+    """Load libfeather_gconv.so (fhip_gconv_forward).  Fails loudly like load_library: there is no fallback implementation."""
+    global _GCONV
+    if _GCONV is None:
+        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
+        path = gconv_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in GCONV_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _GCONV = lib
+    return _GCONV

@@ -15,6 +15,7 @@
 //     so an aliased blob is never modified;
 //   * optional hipGraph replay of the whole forward.
 #include <ctype.h>
+#include <dlfcn.h>
 #include <float.h>
 #include <math.h>
 #include <stdarg.h>
@@ -24,10 +25,12 @@
 #include <algorithm>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_net.h"
 
 namespace fhip
@@ -54,6 +57,60 @@ enum
     NET_E_TOPOLOGY = -300,
     NET_E_BASE_RESHAPE = -400
 };
+
+// ---- libfeather_gconv.so, the route of a Convolution layer with 1 < group < C ------------------------------------
+// Opened lazily from the directory this library was loaded from (then by its bare name, the loader's search path), so that
+// libfeather_hip.so keeps linking and loading without it; a net that holds such a layer and cannot find it fails at Reshape.
+struct GconvApi
+{
+    decltype(&fhip_gconv_supported) supported = nullptr;
+    decltype(&fhip_gconv_get_buffer_size) get_buffer_size = nullptr;
+    decltype(&fhip_gconv_init) init = nullptr;
+    decltype(&fhip_gconv_forward) forward = nullptr;
+    decltype(&fhip_gconv_last_error) last_error = nullptr;
+};
+
+static const GconvApi* gconv_api()
+{
+    static std::mutex mu;
+    static GconvApi api;
+    static bool loaded = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (loaded) return &api;
+    std::string tried;
+    void* h = nullptr;
+    Dl_info self;
+    if (dladdr((void*)&gconv_api, &self) && self.dli_fname)
+    {
+        std::string path = self.dli_fname;
+        const size_t slash = path.rfind('/');
+        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_gconv.so";
+        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        tried = path;
+    }
+    if (!h) h = dlopen("libfeather_gconv.so", RTLD_NOW | RTLD_LOCAL);
+    if (!h)
+    {
+        failf(FHIP_E_UNSUPPORTED, "a convolution with 1 < group < input_channels needs libfeather_gconv.so next to libfeather_hip.so (%s): %s",
+              tried.c_str(), dlerror());
+        return nullptr;
+    }
+    GconvApi a;
+    a.supported = (decltype(a.supported))dlsym(h, "fhip_gconv_supported");
+    a.get_buffer_size = (decltype(a.get_buffer_size))dlsym(h, "fhip_gconv_get_buffer_size");
+    a.init = (decltype(a.init))dlsym(h, "fhip_gconv_init");
+    a.forward = (decltype(a.forward))dlsym(h, "fhip_gconv_forward");
+    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_gconv_last_error");
+    if (!a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
+    {
+        failf(FHIP_E_UNSUPPORTED, "libfeather_gconv.so (%s) does not export the entry points of feather_gconv.h", tried.c_str());
+        dlclose(h);
+        return nullptr;
+    }
+    api = a;
+    loaded = true;
+    return &api;
+}
 
 // ---- ncnn ParamDict (ncnn/paramdict.cpp:92-174): "id=value" pairs, value is float iff it contains '.' or 'e' -----
 struct ParamDict
@@ -414,6 +471,10 @@ struct ConvLayer : Layer
 {
     fhip_conv_param p;
     int algo_ = -1, inited_algo = -2;
+    // 1 < group < input_channels: the layer runs through libfeather_gconv.so (gconv_api) with route code FHIP_NET_ROUTE_GCONV.
+    // p.output_channels then holds the WHOLE layer's K (the library's convention), not K / group as conv_layer.h:69-75 leaves it.
+    // Such a layer fuses a following ReLU and, at level 2, BatchNorm / Scale; every other fusion declines it.
+    bool gconv = false;
     std::vector<float> w_host, b_host;
     std::vector<float> post_mul, post_add; // folded BatchNorm/Scale (fusion level 2)
     DeviceVec packed, bias;
@@ -487,11 +548,13 @@ struct ConvLayer : Layer
         p.output_channels /= p.group;
         if (p.output_channels <= 0 || p.kernel_h <= 0 || p.kernel_w <= 0) return failf(NET_E_SHAPE, "layer %s: bad convolution geometry", name.c_str());
         p.input_channels = weight_data_size / p.output_channels / p.kernel_h / p.kernel_w;
+        gconv = p.group > 1 && p.group < p.input_channels;
+        if (gconv) p.output_channels *= p.group;
         return 0;
     }
     int LoadWeights(ModelBin& mb) override
     {
-        const size_t wsize = (size_t)p.input_channels * p.output_channels * p.kernel_h * p.kernel_w;
+        const size_t wsize = (size_t)p.input_channels * p.output_channels * p.kernel_h * p.kernel_w / (gconv ? p.group : 1);
         inited_algo = -2; // new weights: every packed form is rebuilt at the next Init
         sib_packed_for = nullptr;
         int rc = mb.load(wsize, 0, w_host);
@@ -512,6 +575,17 @@ struct ConvLayer : Layer
             return failf(NET_E_TOPOLOGY, "convolution layer %s has %d input channels while bottom blob has %d channels", name.c_str(), p.input_channels, b->c);
         fhip_conv_assign_output_dim(&p);
         if (p.output_h < 1 || p.output_w < 1) return failf(NET_E_SHAPE, "layer %s: empty output", name.c_str());
+        if (gconv)
+        {
+            const GconvApi* api = gconv_api();
+            if (!api) return FHIP_E_UNSUPPORTED; // message set by gconv_api
+            if (api->supported(&p) != 1) return failf(FHIP_E_UNSUPPORTED, "layer %s: grouped convolution refused: %s", name.c_str(), api->last_error());
+            algo_ = FHIP_NET_ROUTE_GCONV;
+            int rc = tops[0]->reshape(b->n, p.output_channels, p.output_h, p.output_w);
+            if (rc) return rc;
+            if ((rc = api->get_buffer_size(&p, b->n, &buffer_bytes, &packed_bytes))) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+            return 0;
+        }
         int rc = net->tuned_selection ? fhip_conv_select_algo_tuned(&p, &algo_) : fhip_conv_select_algo(&p, &algo_);
         if (rc) return rc;
         if (pw)
@@ -620,7 +694,14 @@ struct ConvLayer : Layer
         if (first_candidate() && (rc = first_raw.upload(w.data(), w.size(), s))) return rc; // 27 floats per output channel
         rc = packed.resize(packed_bytes);
         if (rc) return rc;
-        rc = fhip_conv_init(&p, algo_, packed.d, raw.d, s);
+        if (gconv)
+        {
+            const GconvApi* api = gconv_api();
+            if (!api) return FHIP_E_UNSUPPORTED;
+            if ((rc = api->init(&p, (float*)packed.d, (const float*)raw.d, s))) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+        }
+        else
+            rc = fhip_conv_init(&p, algo_, packed.d, raw.d, s);
         if (rc) return rc;
         if (p.bias_term)
         {
@@ -634,6 +715,13 @@ struct ConvLayer : Layer
     int Forward(hipStream_t s) override
     {
         const float* b = p.bias_term ? bias.d : nullptr;
+        if (gconv)
+        {
+            const GconvApi* api = gconv_api();
+            if (!api) return FHIP_E_UNSUPPORTED;
+            const int rc = api->forward(&p, bottoms[0]->n, tops[0]->data, bottoms[0]->data, (const float*)packed.d, nullptr, b, s);
+            return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+        }
         if (head_of) return 0; // computed inside head_of's input transform
         if (sib_of) return 0;  // computed by the layer before, in the same GEMM
         if (sib)
@@ -711,7 +799,7 @@ struct ConvLayer : Layer
             bottoms.push_back(other); // dependency scans look at THIS layer
             return true;
         }
-        if (fuse_pool || residual || p.activation != FHIP_ACT_NONE) return false;
+        if (gconv || fuse_pool || residual || p.activation != FHIP_ACT_NONE) return false;
         residual = other;
         bottoms.push_back(other); // so that dependency scans (fusion, branch concurrency) see the second input
         return true;
@@ -727,7 +815,7 @@ struct ConvLayer : Layer
     }
     size_t arena_bytes() const override { return std::max(buffer_bytes, chain_bytes); }
     const fhip_conv_param* conv_param() const override { return &p; }
-    int algo() const override { return algo_; }
+    int algo() const override { return gconv ? FHIP_NET_ROUTE_GCONV : algo_; }
     int sibling_state() const override { return sib ? 1 : sib_of ? 2 : 0; }
     int residual_state() const override { return !residual ? 0 : res_fast ? 1 : 2; }
     void chain_state(int* v_from_previous, int* writes_next_v) const override
@@ -983,6 +1071,7 @@ int ConvLayer::Fuse(Layer* next, int level)
 {
     if (pw) return pw->Fuse(next, level) == 1 ? 1 : 0; // behind the absorbed 1x1 convolution: its own fusions
     if (fuse_pool) return 0; // nothing is absorbed behind the pooling
+    if (gconv && next->type != "ReLU" && next->type != "BatchNorm" && next->type != "Scale") return 0; // the grouped route has these epilogues only
     if (level >= 2 && !residual && next->type == "Convolution" && p.group == p.input_channels && p.group > 1 && p.group <= 256 && p.kernel_h == 3 &&
         p.kernel_w == 3 && p.stride_h == p.stride_w && (p.stride_h == 1 || p.stride_h == 2) && p.pad_left == 1 && p.pad_top == 1)
     {

@@ -55,10 +55,10 @@ class GraphBuilder:
     def input(self, name, c, h, w):
         return self.layer("Input", name, [], [name], {0: w, 1: h, 2: c})
 
-    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None):
+    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None):
         fan_in = cin // group * k * k
         wsize = cout * (cin // group) * k * k
-        type_ = "ConvolutionDepthWise" if group > 1 else "Convolution"
+        type_ = type_ or ("ConvolutionDepthWise" if group > 1 else "Convolution")  # what ncnn's converter writes; both load alike
         top = self.layer(type_, name, [bottom], [top or name], {0: cout, 1: k, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group})
         self._tagged(self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in)))
         if bias:
@@ -226,5 +226,50 @@ def tiny_allsorts(seed=7, size=20, dry=False):
     return g.finish() + ("data", "prob")
 
 
+def resnext50_32x4d(seed=1234, classes=1000, size=224, dry=False):
+    """Caffe-style ResNeXt-50 (32x4d): 1x1 reduce, grouped 3x3 (32 groups) with the stage's stride, 1x1 expand, BN + Scale + ReLU after
+    each, projection shortcuts.  Its grouped layers (1 < group < C) run through libfeather_gconv.so."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_relu("conv1", x, 3, 64, 7, 2, 3)
+    x = g.pool("pool1", x, 3, 2)
+    cin = 64
+    for si, (mid, out, blocks, stride) in enumerate([(128, 256, 3, 1), (256, 512, 4, 2), (512, 1024, 6, 2), (1024, 2048, 3, 2)]):
+        for b in range(blocks):
+            s = stride if b == 0 else 1
+            tag = f"resx{si + 2}{chr(ord('a') + b)}"
+            main, short = g.split(tag + "_split", x)
+            if b == 0:
+                short = g.conv_bn_relu(tag + "_branch1", short, cin, out, 1, s, 0, relu=False)
+            y = g.conv_bn_relu(tag + "_branch2a", main, cin, mid, 1, 1, 0)
+            y = g.conv_bn_relu(tag + "_branch2b", y, mid, mid, 3, s, 1, group=32)
+            y = g.conv_bn_relu(tag + "_branch2c", y, mid, out, 1, 1, 0, relu=False)
+            x = g.relu(tag + "_relu", g.eltwise(tag, short, y))
+            cin = out
+    x = g.pool("pool5", x, 7, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc1000", x, 2048, classes))
+    return g.finish() + ("data", "prob")
+
+
+def tiny_grouped(seed=11, size=21, dry=False):
+    """A small net of grouped convolutions (1 < group < C) in every position the Net runtime has to get right: behind a ReLU, behind
+    BatchNorm + Scale + ReLU, in front of an Eltwise sum and of a 2x2 pooling (fusions that must decline a grouped layer)."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.relu("relu1", g.conv("conv1", x, 3, 16, 3, 1, 1))
+    x = g.relu("relu_g1", g.conv("g1", x, 16, 16, 3, 1, 1, group=4))                    # grouped 3x3 / s1, bias + ReLU, odd plane
+    x = g.conv_bn_relu("g2", x, 16, 32, 3, 2, 1, group=2)                                 # grouped 3x3 / s2, no bias, BN + Scale + ReLU
+    a, b = g.split("split1", x)
+    a = g.conv("g3", a, 32, 32, 1, group=4, type_="Convolution")                          # grouped 1x1, then a residual sum
+    x = g.relu("relu_sum", g.eltwise("sum", a, b))
+    x = g.relu("relu_g4", g.conv("g4", x, 32, 10, 3, 1, 0, group=2, bias=False))          # group 2, 16 -> 5 channels, no bias, no pad
+    x = g.pool("pool1", x, 2, 2)
+    x = g.pool("gap", x, 1, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc", x, 10, 10))
+    return g.finish() + ("data", "prob")
+
+
+GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
+
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
-          "tiny_allsorts": tiny_allsorts}
+          "tiny_allsorts": tiny_allsorts, "resnext50_32x4d": resnext50_32x4d, "tiny_grouped": tiny_grouped}

@@ -11,6 +11,11 @@ from . import _lib
 from .booster import ALGO_NAMES, FeatherHipError, _check, _stream
 
 
+# fhip_net_layer_info's route codes: booster::ConvAlgo, plus FHIP_NET_ROUTE_GCONV (feather_net.h) for a layer with 1 < group < C
+ROUTE_GCONV = 100
+ROUTE_NAMES = dict(ALGO_NAMES)
+ROUTE_NAMES[ROUTE_GCONV] = "GCONV"
+
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
                  sub_batches: int = 1):
@@ -195,7 +200,7 @@ class Net:
         for i in range(n):
             t, nm, algo = ctypes.create_string_buffer(64), ctypes.create_string_buffer(256), ctypes.c_int()
             _check(self._lib.fhip_net_layer_info(self._h, i, t, nm, 64, ctypes.byref(algo)), "fhip_net_layer_info")
-            out.append((t.value.decode(), nm.value.decode(), ALGO_NAMES.get(algo.value)))
+            out.append((t.value.decode(), nm.value.decode(), ROUTE_NAMES.get(algo.value)))
         return out
 
     def conv_params(self):

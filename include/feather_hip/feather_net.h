@@ -303,8 +303,12 @@ FHIP_API int fhip_net_extract_host(fhip_net* net, const char* blob_name, float* 
 
 /* Introspection (after LoadParam / fusion). */
 FHIP_API int fhip_net_layer_count(fhip_net* net);
+/* Route code of a Convolution layer with 1 < group < input_channels: it runs through libfeather_gconv.so (feather_gconv.h), which
+ * libfeather_hip.so opens from its own directory when a net holds such a layer (FHIP_E_UNSUPPORTED at the first Reshape if it is not
+ * there).  None of the reference's ConvAlgo values; reported from LoadParam on. */
+#define FHIP_NET_ROUTE_GCONV 100
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
- * convolutions after the first Forward, else -1. */
+ * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);
 /* Geometry of a Convolution / ConvolutionDepthWise layer as it runs (after Reshape: output dims assigned, BatchNorm folded, ...) and
  * the batch of its input blob; FHIP_E_BADARG for any other layer type.  (bench.py prices each layer's kernel against its roofline

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """tools/kernel_resources.py <file.hip> [name filter] [extra hipcc flags...] -- VGPRs / scratch / occupancy / LDS of every kernel of a
 translation unit (hipcc -Rpass-analysis=kernel-resource-usage; cross-compiles, no GPU needed)."""
+import os
 import re
 import subprocess
 import sys
 
-R = "/root/repo"
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # the repository, wherever it is checked out
 
 
 def main():
