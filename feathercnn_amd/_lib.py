@@ -8,6 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 _PIXOUT = None
 _GCONV = None
+_DECONV = None
 
 STAGE_NAMES = ("wino_input", "wino_gemm", "wino_output", "igemm", "depthwise", "init", "wino_chain")
 
@@ -143,6 +144,24 @@ GCONV_SIGNATURES = {
     "fhip_gconv_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_deconv.h -- libfeather_deconv.so, transposed convolution (a library of its own)
+class fhip_deconv_param(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("output_channels", "input_channels", "input_h", "input_w", "kernel_h", "kernel_w", "output_h", "output_w",
+                                            "stride_h", "stride_w", "pad_left", "pad_bottom", "pad_right", "pad_top", "group", "bias_term",
+                                            "activation", "output_pad_right", "output_pad_bottom")]
+
+
+_DP = ctypes.POINTER(fhip_deconv_param)
+DECONV_SIGNATURES = {
+    "fhip_deconv_assign_output_dim": (_I, [_DP]),
+    "fhip_deconv_supported": (_I, [_DP]),
+    "fhip_deconv_get_buffer_size": (_I, [_DP, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "fhip_deconv_init": (_I, [_DP, _V, _V, _V]),
+    "fhip_deconv_forward": (_I, [_DP, _I, _V, _V, _V, _V, _V, _V]),
+    "fhip_deconv_route": (_I, [_DP, ctypes.c_char_p, _I]),
+    "fhip_deconv_last_error": (ctypes.c_char_p, []),
+}
+
 
 def lib_path() -> str:
     return os.environ.get("FEATHER_HIP_LIB", os.path.join(_HERE, "libfeather_hip.so"))
@@ -210,3 +229,25 @@ def load_gconv_library():
             fn.argtypes = args
         _GCONV = lib
     return _GCONV
+
+
+def deconv_path() -> str:
+    return os.path.join(_HERE, "libfeather_deconv.so")
+
+
+def load_deconv_library():
+    """Load libfeather_deconv.so (fhip_deconv_forward).  Fails loudly like load_library: there is no fallback implementation."""
+    global _DECONV
+    if _DECONV is None:
+        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
+        path = deconv_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in DECONV_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _DECONV = lib
+    return _DECONV

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "common.h"
+#include "feather_hip/feather_deconv.h" // declarations only: the library is opened at run time (deconv_api)
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_net.h"
 
@@ -104,6 +105,61 @@ static const GconvApi* gconv_api()
     if (!a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
     {
         failf(FHIP_E_UNSUPPORTED, "libfeather_gconv.so (%s) does not export the entry points of feather_gconv.h", tried.c_str());
+        dlclose(h);
+        return nullptr;
+    }
+    api = a;
+    loaded = true;
+    return &api;
+}
+
+// ---- libfeather_deconv.so, the route of Deconvolution / DeconvolutionDepthWise layers ------------------------------
+// Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name; a net that holds such a layer and
+// cannot find it fails at Reshape.
+struct DeconvApi
+{
+    decltype(&fhip_deconv_assign_output_dim) assign_output_dim = nullptr;
+    decltype(&fhip_deconv_supported) supported = nullptr;
+    decltype(&fhip_deconv_get_buffer_size) get_buffer_size = nullptr;
+    decltype(&fhip_deconv_init) init = nullptr;
+    decltype(&fhip_deconv_forward) forward = nullptr;
+    decltype(&fhip_deconv_last_error) last_error = nullptr;
+};
+
+static const DeconvApi* deconv_api()
+{
+    static std::mutex mu;
+    static DeconvApi api;
+    static bool loaded = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (loaded) return &api;
+    std::string tried;
+    void* h = nullptr;
+    Dl_info self;
+    if (dladdr((void*)&deconv_api, &self) && self.dli_fname)
+    {
+        std::string path = self.dli_fname;
+        const size_t slash = path.rfind('/');
+        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_deconv.so";
+        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        tried = path;
+    }
+    if (!h) h = dlopen("libfeather_deconv.so", RTLD_NOW | RTLD_LOCAL);
+    if (!h)
+    {
+        failf(FHIP_E_UNSUPPORTED, "a Deconvolution layer needs libfeather_deconv.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
+        return nullptr;
+    }
+    DeconvApi a;
+    a.assign_output_dim = (decltype(a.assign_output_dim))dlsym(h, "fhip_deconv_assign_output_dim");
+    a.supported = (decltype(a.supported))dlsym(h, "fhip_deconv_supported");
+    a.get_buffer_size = (decltype(a.get_buffer_size))dlsym(h, "fhip_deconv_get_buffer_size");
+    a.init = (decltype(a.init))dlsym(h, "fhip_deconv_init");
+    a.forward = (decltype(a.forward))dlsym(h, "fhip_deconv_forward");
+    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_deconv_last_error");
+    if (!a.assign_output_dim || !a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
+    {
+        failf(FHIP_E_UNSUPPORTED, "libfeather_deconv.so (%s) does not export the entry points of feather_deconv.h", tried.c_str());
         dlclose(h);
         return nullptr;
     }
@@ -1123,6 +1179,151 @@ int ConvLayer::Fuse(Layer* next, int level)
     return 0;
 }
 
+// ncnn's Deconvolution / DeconvolutionDepthWise (no reference counterpart; the definition is include/feather_hip/feather_deconv.h).
+// Runs through libfeather_deconv.so (deconv_api) with route code FHIP_NET_ROUTE_DECONV.  Fuses a following ReLU and, at level 2,
+// BatchNorm / Scale (weights are [K][C/group][kh][kw], so the fold is the convolution's); it is no "Convolution" to any other fusion
+// (residual add, pooling, depthwise + pointwise, siblings, Winograd chains, first layer, the side stream), which therefore decline it.
+struct DeconvLayer : Layer
+{
+    fhip_deconv_param p;
+    int weight_data_size = 0;
+    std::vector<float> w_host, b_host;
+    std::vector<float> post_mul, post_add; // folded BatchNorm/Scale (fusion level 2)
+    DeviceVec packed, bias;
+    size_t buffer_bytes = 0, packed_bytes = 0;
+    bool inited = false;
+
+    DeconvLayer() { memset(&p, 0, sizeof(p)); }
+
+    int LoadParam(const ParamDict& pd) override
+    {
+        const int dilation_w = pd.get(2, 1), dilation_h = pd.get(12, dilation_w);
+        if (dilation_w > 1 || dilation_h > 1) return failf(NET_E_UNKNOWN_LAYER, "layer %s: dilated deconvolution is not supported", name.c_str());
+        if (pd.get(8, 0)) return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8 deconvolution is not supported", name.c_str());
+        if (pd.get(20, 0) || pd.get(21, 0)) return failf(NET_E_UNKNOWN_LAYER, "layer %s: an explicit deconvolution output size is not supported", name.c_str());
+        if (pd.get(9, 0)) return failf(NET_E_UNKNOWN_LAYER, "layer %s: a built-in activation (param 9) is not supported; use a ReLU layer", name.c_str());
+        p.kernel_w = pd.get(1, 0);
+        p.kernel_h = pd.get(11, p.kernel_w);
+        p.stride_w = pd.get(3, 1);
+        p.stride_h = pd.get(13, p.stride_w);
+        p.pad_left = pd.get(4, 0);
+        p.pad_right = pd.get(15, p.pad_left);
+        p.pad_top = pd.get(14, p.pad_left);
+        p.pad_bottom = pd.get(16, p.pad_top);
+        p.output_pad_right = pd.get(18, 0);
+        p.output_pad_bottom = pd.get(19, 0);
+        p.group = pd.get(7, 1);
+        p.output_channels = pd.get(0, 0);
+        p.bias_term = pd.get(5, 0);
+        p.activation = FHIP_ACT_NONE;
+        weight_data_size = pd.get(6, 0);
+        if (p.group < 1 || p.output_channels < 1 || p.output_channels % p.group)
+            return failf(NET_E_SHAPE, "layer %s: output_channels is not divisible by its group", name.c_str());
+        if (p.kernel_h <= 0 || p.kernel_w <= 0 || p.stride_h <= 0 || p.stride_w <= 0) return failf(NET_E_SHAPE, "layer %s: bad deconvolution geometry", name.c_str());
+        const long long per = (long long)p.output_channels * p.kernel_h * p.kernel_w;
+        if (weight_data_size <= 0 || ((long long)weight_data_size * p.group) % per)
+            return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the deconvolution geometry", name.c_str());
+        p.input_channels = (int)((long long)weight_data_size * p.group / per);
+        if (p.input_channels % p.group) return failf(NET_E_SHAPE, "layer %s: input_channels is not divisible by its group", name.c_str());
+        if (p.pad_left < 0 || p.pad_right < 0 || p.pad_top < 0 || p.pad_bottom < 0)
+            return failf(NET_E_SHAPE, "layer %s: negative (automatic) padding is not supported", name.c_str());
+        if (p.output_pad_right < 0 || p.output_pad_bottom < 0 || p.output_pad_right >= p.stride_w || p.output_pad_bottom >= p.stride_h)
+            return failf(NET_E_SHAPE, "layer %s: output padding must be smaller than the stride", name.c_str());
+        if (p.output_pad_right > p.pad_right || p.output_pad_bottom > p.pad_bottom)
+            return failf(NET_E_SHAPE, "layer %s: output padding larger than the padding of that side is not supported", name.c_str());
+        return 0;
+    }
+    int LoadWeights(ModelBin& mb) override
+    {
+        inited = false; // new weights: the packed form is rebuilt at the next Init
+        int rc = mb.load((size_t)weight_data_size, 0, w_host);
+        if (rc) return rc;
+        if (p.bias_term) rc = mb.load(p.output_channels, 1, b_host);
+        return rc;
+    }
+    int Reshape() override
+    {
+        const Blob* b = bottoms[0];
+        if (p.input_channels != b->c)
+            return failf(NET_E_TOPOLOGY, "deconvolution layer %s has %d input channels while bottom blob has %d channels", name.c_str(), p.input_channels, b->c);
+        const DeconvApi* api = deconv_api();
+        if (!api) return FHIP_E_UNSUPPORTED; // message set by deconv_api
+        p.input_w = b->w;
+        p.input_h = b->h;
+        if (api->assign_output_dim(&p)) return failf(NET_E_SHAPE, "layer %s: %s", name.c_str(), api->last_error());
+        if (api->supported(&p) != 1) return failf(FHIP_E_UNSUPPORTED, "layer %s: deconvolution refused: %s", name.c_str(), api->last_error());
+        int rc = tops[0]->reshape(b->n, p.output_channels, p.output_h, p.output_w);
+        if (rc) return rc;
+        if ((rc = api->get_buffer_size(&p, b->n, &buffer_bytes, &packed_bytes))) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+        return 0;
+    }
+    int Init(hipStream_t s) override
+    {
+        if (inited && packed.bytes == packed_bytes) return 0;
+        const DeconvApi* api = deconv_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        std::vector<float> w = w_host, b = b_host;
+        if (!post_mul.empty())
+        {
+            const int K = p.output_channels;
+            const size_t per = w.size() / K;
+            if (b.empty()) b.assign(K, 0.f);
+            for (int k = 0; k < K; ++k)
+            {
+                for (size_t i = 0; i < per; ++i) w[k * per + i] *= post_mul[k];
+                b[k] = b[k] * post_mul[k] + post_add[k];
+            }
+            p.bias_term = 1;
+        }
+        DeviceVec raw;
+        int rc = raw.upload(w.data(), w.size(), s);
+        if (rc) return rc;
+        if ((rc = packed.resize(packed_bytes))) return rc;
+        if ((rc = api->init(&p, packed.d, raw.d, s))) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+        if (p.bias_term && (rc = bias.upload(b.data(), b.size(), s))) return rc;
+        FHIP_CHECK_HIP(hipStreamSynchronize(s)); // `raw` and the host copies go out of scope
+        inited = true;
+        return 0;
+    }
+    int Forward(hipStream_t s) override
+    {
+        const DeconvApi* api = deconv_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const int rc = api->forward(&p, bottoms[0]->n, tops[0]->data, bottoms[0]->data, packed.d, nullptr, p.bias_term ? bias.d : nullptr, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    int Fuse(Layer* next, int level) override;
+    size_t weight_bytes() const override { return packed.bytes + bias.bytes; }
+    int algo() const override { return FHIP_NET_ROUTE_DECONV; }
+};
+
+int DeconvLayer::Fuse(Layer* next, int level)
+{
+    if (next->type == "ReLU")
+    {
+        p.activation = FHIP_ACT_RELU;
+        return 1;
+    }
+    if (level >= 2 && p.activation == FHIP_ACT_NONE && (next->type == "BatchNorm" || next->type == "Scale"))
+    {
+        AffineLayer* nx = static_cast<AffineLayer*>(next);
+        const int K = p.output_channels;
+        if (nx->channels != K || nx->relu) return 0;
+        if (post_mul.empty())
+        {
+            post_mul.assign(K, 1.f);
+            post_add.assign(K, 0.f);
+        }
+        for (int k = 0; k < K; ++k)
+        {
+            post_mul[k] *= nx->mul[k];
+            post_add[k] = post_add[k] * nx->mul[k] + (nx->has_add ? nx->add[k] : 0.f);
+        }
+        return 1;
+    }
+    return 0;
+}
+
 struct EltwiseLayer : Layer
 {
     bool relu = false;
@@ -1246,6 +1447,7 @@ static Layer* create_layer(const std::string& type) // layer_factory.cpp:55-67
 {
     if (type == "Input") return new InputLayer;
     if (type == "Convolution" || type == "ConvolutionDepthWise") return new ConvLayer;
+    if (type == "Deconvolution" || type == "DeconvolutionDepthWise") return new DeconvLayer;
     if (type == "ReLU") return new ReluLayer;
     if (type == "Pooling") return new PoolingLayer;
     if (type == "InnerProduct") return new InnerProductLayer;

@@ -65,6 +65,28 @@ class GraphBuilder:
             self._raw(self._uniform(cout, -0.1, 0.1))
         return top
 
+    def deconv(self, name, bottom, cin, cout, k, s=1, p=0, op=0, group=1, bias=True):
+        """ncnn's Deconvolution (DeconvolutionDepthWise with a group): weights [cout][cin/group][k][k], not flipped; `op` = output padding
+        on the right / bottom (ids 18 / 19).  He-uniform over the taps that reach one output, ceil(k / s) per axis."""
+        fan_in = cin // group * (-(-k // s)) ** 2
+        wsize = cout * (cin // group) * k * k
+        params = {0: cout, 1: k, 3: s, 4: p, 5: int(bias), 6: wsize}
+        if op:
+            params.update({18: op, 19: op})
+        if group > 1:
+            params[7] = group
+        top = self.layer("DeconvolutionDepthWise" if group > 1 else "Deconvolution", name, [bottom], [name], params)
+        self._tagged(self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in)))
+        if bias:
+            self._raw(self._uniform(cout, -0.1, 0.1))
+        return top
+
+    def deconv_bn_relu(self, name, bottom, cin, cout, k, s=1, p=0, op=0):
+        x = self.deconv(name, bottom, cin, cout, k, s, p, op)
+        x = self.bn(name + "_bn", x, cout)
+        x = self.scale(name + "_scale", x, cout)
+        return self.relu(name + "_relu", x)
+
     def relu(self, name, bottom):
         return self.layer("ReLU", name, [bottom], [name])
 
@@ -269,7 +291,72 @@ def tiny_grouped(seed=11, size=21, dry=False):
     return g.finish() + ("data", "prob")
 
 
+def tiny_deconv(seed=13, size=16, dry=False):
+    """A small net of transposed convolutions in every form the Net runtime has to get right, nothing above 16 px: k4 s2 p1 behind a ReLU,
+    k2 s2 p0 with a BatchNorm + Scale + ReLU tail, a depthwise bilinear-style k4 s2 p1 and a grouped k4 s2 p1 layer, a Concat of the three,
+    k3 s2 p1 with output padding 1, and k3 s1 p1."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.relu("relu1", g.conv("conv1", x, 3, 16, 3, 2, 1))
+    x = g.relu("relu2", g.conv("conv2", x, 16, 32, 3, 2, 1))
+    x = g.relu("relu3", g.conv("conv3", x, 32, 32, 3, 2, 1))
+    x = g.relu("relu_d1", g.deconv("d1", x, 32, 32, 4, 2, 1))                       # k4 s2 p1 + ReLU (the MFMA route)
+    a, b, c = g.split("split1", x, 3)
+    a = g.deconv_bn_relu("d2", a, 32, 32, 2, 2, 0)                                   # k2 s2 p0, BN + Scale + ReLU
+    b = g.deconv("dw_up", b, 32, 32, 4, 2, 1, group=32, bias=False)                  # depthwise, FCN's bilinear up-sampling shape
+    c = g.relu("relu_gd", g.deconv("gd", c, 32, 16, 4, 2, 1, group=4))              # grouped
+    x = g.concat("cat", [a, b, c])
+    x = g.relu("relu_d3", g.deconv("d3", x, 80, 24, 3, 2, 1, op=1))                 # k3 s2 p1, output padding 1
+    x = g.deconv("d4", x, 24, 8, 3, 1, 1)                                            # k3 s1 p1 (the generic kernel)
+    return g.finish() + ("data", "d4")
+
+
+def style_transfer(seed=1234, size=256, dry=False):
+    """Johnson et al.'s feed-forward style-transfer net: 9x9 convolution, two stride-2 convolutions, five 128-channel residual blocks at a
+    quarter of the resolution, two k3 s2 p1 deconvolutions with output padding 1, 9x9 convolution to 3 channels.  BatchNorm + Scale
+    stand where the paper has InstanceNorm (this runtime has no such layer; the arithmetic per layer is the same affine map)."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_relu("conv1", x, 3, 32, 9, 1, 4)
+    x = g.conv_bn_relu("conv2", x, 32, 64, 3, 2, 1)
+    x = g.conv_bn_relu("conv3", x, 64, 128, 3, 2, 1)
+    for i in range(1, 6):
+        a, b = g.split(f"res{i}_split", x)
+        a = g.conv_bn_relu(f"res{i}a", a, 128, 128, 3, 1, 1)
+        a = g.conv_bn_relu(f"res{i}b", a, 128, 128, 3, 1, 1, relu=False)
+        x = g.eltwise(f"res{i}", a, b)
+    x = g.deconv_bn_relu("deconv1", x, 128, 64, 3, 2, 1, op=1)
+    x = g.deconv_bn_relu("deconv2", x, 64, 32, 3, 2, 1, op=1)
+    x = g.conv("out", x, 32, 3, 9, 1, 4)
+    return g.finish() + ("data", "out")
+
+
+def unet_k4(seed=1234, size=256, dry=False):
+    """A five-level pix2pix-style generator: k4 s2 p1 convolutions down (32 .. 256 channels), k4 s2 p1 deconvolutions up, every decoder
+    level concatenated with the encoder level of its size."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    widths = (32, 64, 128, 256, 256)
+    skips, cin = [], 3
+    for i, cw in enumerate(widths, 1):
+        x = g.relu(f"e{i}_relu", g.conv(f"e{i}", x, cin, cw, 4, 2, 1)) if i == 1 else g.conv_bn_relu(f"e{i}", x, cin, cw, 4, 2, 1)
+        cin = cw
+        if i < len(widths):
+            x, skip = g.split(f"e{i}_split", x)
+            skips.append((skip, cw))
+    for i, cw in zip((5, 4, 3, 2), (256, 128, 64, 32)):
+        x = g.deconv_bn_relu(f"d{i}", x, cin, cw, 4, 2, 1)
+        skip, sw = skips.pop()
+        x = g.concat(f"cat{i - 1}", [x, skip])
+        cin = cw + sw
+    x = g.deconv("d1", x, cin, 3, 4, 2, 1)
+    return g.finish() + ("data", "d1")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
-          "tiny_allsorts": tiny_allsorts, "resnext50_32x4d": resnext50_32x4d, "tiny_grouped": tiny_grouped}
+          "tiny_allsorts": tiny_allsorts, "resnext50_32x4d": resnext50_32x4d, "tiny_grouped": tiny_grouped,
+          "tiny_deconv": tiny_deconv, "style_transfer": style_transfer, "unet_k4": unet_k4}
+
+DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}

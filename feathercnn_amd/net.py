@@ -15,6 +15,8 @@ from .booster import ALGO_NAMES, FeatherHipError, _check, _stream
 ROUTE_GCONV = 100
 ROUTE_NAMES = dict(ALGO_NAMES)
 ROUTE_NAMES[ROUTE_GCONV] = "GCONV"
+ROUTE_DECONV = 101  # FHIP_NET_ROUTE_DECONV: a Deconvolution / DeconvolutionDepthWise layer (libfeather_deconv.so)
+ROUTE_NAMES[ROUTE_DECONV] = "DECONV"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,

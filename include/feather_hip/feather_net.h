@@ -307,6 +307,10 @@ FHIP_API int fhip_net_layer_count(fhip_net* net);
  * libfeather_hip.so opens from its own directory when a net holds such a layer (FHIP_E_UNSUPPORTED at the first Reshape if it is not
  * there).  None of the reference's ConvAlgo values; reported from LoadParam on. */
 #define FHIP_NET_ROUTE_GCONV 100
+/* Route code of a Deconvolution / DeconvolutionDepthWise layer: it runs through libfeather_deconv.so (feather_deconv.h), opened the same
+ * way the first time a net holds such a layer.  It fuses a following ReLU and, at fusion level 2, BatchNorm / Scale; no other fusion
+ * takes it.  Reported from LoadParam on. */
+#define FHIP_NET_ROUTE_DECONV 101
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
  * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);
