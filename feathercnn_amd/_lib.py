@@ -9,6 +9,7 @@ _LIB = None
 _PIXOUT = None
 _GCONV = None
 _DECONV = None
+_INORM = None
 
 STAGE_NAMES = ("wino_input", "wino_gemm", "wino_output", "igemm", "depthwise", "init", "wino_chain")
 
@@ -162,6 +163,17 @@ DECONV_SIGNATURES = {
     "fhip_deconv_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_inorm.h -- libfeather_inorm.so, InstanceNorm and the activations of generative nets (a library of its own)
+_FL = ctypes.c_float
+INORM_SIGNATURES = {
+    "fhip_instance_norm_get_buffer_size": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "fhip_instance_norm_forward": (_I, [_I, _I, _I, _I, _V, _V, _V, _V, _FL, _I, _FL, _V, _V]),
+    "fhip_instance_norm_forward_route": (_I, [_I, _I, _I, _I, _I, _V, _V, _V, _V, _FL, _I, _FL, _V, _V]),
+    "fhip_instance_norm_route": (_I, [_I, _I, _I, _I, _V, _V, ctypes.c_char_p, _I]),
+    "fhip_activation_forward": (_I, [_I, _V, _V, _I, _I, _I, _FL, _FL, _V, _V]),
+    "fhip_inorm_last_error": (ctypes.c_char_p, []),
+}
+
 
 def lib_path() -> str:
     return os.environ.get("FEATHER_HIP_LIB", os.path.join(_HERE, "libfeather_hip.so"))
@@ -251,3 +263,26 @@ def load_deconv_library():
             fn.argtypes = args
         _DECONV = lib
     return _DECONV
+
+
+def inorm_path() -> str:
+    return os.path.join(_HERE, "libfeather_inorm.so")
+
+
+def load_inorm_library():
+    """Load libfeather_inorm.so (fhip_instance_norm_forward, fhip_activation_forward).  Fails loudly like load_library: there is no fallback
+    implementation."""
+    global _INORM
+    if _INORM is None:
+        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
+        path = inorm_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in INORM_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _INORM = lib
+    return _INORM

@@ -32,6 +32,7 @@
 #include "common.h"
 #include "feather_hip/feather_deconv.h" // declarations only: the library is opened at run time (deconv_api)
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
+#include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
 #include "feather_hip/feather_net.h"
 
 namespace fhip
@@ -160,6 +161,57 @@ static const DeconvApi* deconv_api()
     if (!a.assign_output_dim || !a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
     {
         failf(FHIP_E_UNSUPPORTED, "libfeather_deconv.so (%s) does not export the entry points of feather_deconv.h", tried.c_str());
+        dlclose(h);
+        return nullptr;
+    }
+    api = a;
+    loaded = true;
+    return &api;
+}
+
+// ---- libfeather_inorm.so, the route of InstanceNorm, PReLU / Sigmoid / TanH / Clip layers and of a ReLU with a slope -----------------
+// Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name; a net that holds such a layer and
+// cannot find it fails at Reshape.
+struct InormApi
+{
+    decltype(&fhip_instance_norm_get_buffer_size) get_buffer_size = nullptr;
+    decltype(&fhip_instance_norm_forward) forward = nullptr;
+    decltype(&fhip_activation_forward) activation = nullptr;
+    decltype(&fhip_inorm_last_error) last_error = nullptr;
+};
+
+static const InormApi* inorm_api()
+{
+    static std::mutex mu;
+    static InormApi api;
+    static bool loaded = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (loaded) return &api;
+    std::string tried;
+    void* h = nullptr;
+    Dl_info self;
+    if (dladdr((void*)&inorm_api, &self) && self.dli_fname)
+    {
+        std::string path = self.dli_fname;
+        const size_t slash = path.rfind('/');
+        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_inorm.so";
+        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        tried = path;
+    }
+    if (!h) h = dlopen("libfeather_inorm.so", RTLD_NOW | RTLD_LOCAL);
+    if (!h)
+    {
+        failf(FHIP_E_UNSUPPORTED, "an InstanceNorm / activation layer needs libfeather_inorm.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
+        return nullptr;
+    }
+    InormApi a;
+    a.get_buffer_size = (decltype(a.get_buffer_size))dlsym(h, "fhip_instance_norm_get_buffer_size");
+    a.forward = (decltype(a.forward))dlsym(h, "fhip_instance_norm_forward");
+    a.activation = (decltype(a.activation))dlsym(h, "fhip_activation_forward");
+    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_inorm_last_error");
+    if (!a.get_buffer_size || !a.forward || !a.activation || !a.last_error)
+    {
+        failf(FHIP_E_UNSUPPORTED, "libfeather_inorm.so (%s) does not export the entry points of feather_inorm.h", tried.c_str());
         dlclose(h);
         return nullptr;
     }
@@ -468,6 +520,10 @@ struct Layer
     virtual int sibling_state() const { return 0; } // 1: launches the GEMM that also computes the NEXT layer; 2: computed by the layer before
     virtual int residual_state() const { return 0; } // 1: an Eltwise SUM operand is added in this layer's GEMM epilogue; 2: absorbed, added by a separate launch
 };
+
+// A ReLU layer without a slope: the only ReLU the fused epilogues of the convolution, deconvolution, InnerProduct, affine and Eltwise
+// layers compute.  A leaky one (ncnn's `ReLU 0=slope`) stays a layer of its own behind them.
+static bool is_plain_relu(const Layer* l);
 
 struct Net
 {
@@ -951,7 +1007,7 @@ struct InnerProductLayer : Layer
     }
     int Fuse(Layer* next, int) override
     {
-        if (next->type == "ReLU")
+        if (is_plain_relu(next))
         {
             p.activation = FHIP_ACT_RELU;
             return 1;
@@ -963,9 +1019,168 @@ struct InnerProductLayer : Layer
     int algo() const override { return FHIP_IM2COL; }
 };
 
+// ncnn's ReLU: 0=slope.  Slope 0 is the reference's layer (fhip_relu); a leaky one runs through libfeather_inorm.so.
 struct ReluLayer : Layer
 {
-    int Forward(hipStream_t s) override { return fhip_relu(tops[0]->data, bottoms[0]->data, bottoms[0]->count(), s); }
+    float slope = 0.f;
+    int LoadParam(const ParamDict& pd) override
+    {
+        slope = pd.get(0, 0.f);
+        return 0;
+    }
+    int Reshape() override
+    {
+        if (slope != 0.f && !inorm_api()) return FHIP_E_UNSUPPORTED; // message set by inorm_api
+        return Layer::Reshape();
+    }
+    int Forward(hipStream_t s) override
+    {
+        if (slope == 0.f) return fhip_relu(tops[0]->data, bottoms[0]->data, bottoms[0]->count(), s);
+        const InormApi* api = inorm_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const Blob* b = bottoms[0];
+        const int rc = api->activation(FHIP_ACTIVATION_LEAKY_RELU, tops[0]->data, b->data, b->n, b->c, b->h * b->w, slope, 0.f, nullptr, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+};
+
+static bool is_plain_relu(const Layer* l) { return l->type == "ReLU" && static_cast<const ReluLayer*>(l)->slope == 0.f; }
+
+// ncnn's InstanceNorm (no reference counterpart; the definition is include/feather_hip/feather_inorm.h): 0=channels, 1=eps, 2=affine,
+// gamma and beta in the .bin when affine.  Runs through libfeather_inorm.so with route code FHIP_NET_ROUTE_INORM; the scratch of the
+// split-plane route comes out of the net's arena, so the layer stays on the main stream.  Absorbs a following ReLU, plain or leaky.
+struct InstanceNormLayer : Layer
+{
+    int channels = 0, affine = 1, act = FHIP_INORM_ACT_NONE;
+    float eps = 0.001f, slope = 0.f;
+    std::vector<float> gamma, beta;
+    DeviceVec d_gamma, d_beta;
+    size_t scratch_bytes = 0;
+    bool inited = false;
+
+    int LoadParam(const ParamDict& pd) override
+    {
+        channels = pd.get(0, 0);
+        eps = pd.get(1, 0.001f);
+        affine = pd.get(2, 1);
+        if (channels < 1) return failf(NET_E_SHAPE, "layer %s: InstanceNorm needs at least one channel", name.c_str());
+        if (!(eps >= 0.f)) return failf(NET_E_SHAPE, "layer %s: InstanceNorm eps must not be negative", name.c_str());
+        return 0;
+    }
+    int LoadWeights(ModelBin& mb) override
+    {
+        inited = false;
+        if (!affine) return 0;
+        const int rc = mb.load(channels, 1, gamma);
+        return rc ? rc : mb.load(channels, 1, beta);
+    }
+    int Reshape() override
+    {
+        const Blob* b = bottoms[0];
+        if (b->c != channels)
+            return failf(NET_E_TOPOLOGY, "InstanceNorm layer %s has %d channels while bottom blob %s has %d", name.c_str(), channels, b->name.c_str(), b->c);
+        const InormApi* api = inorm_api();
+        if (!api) return FHIP_E_UNSUPPORTED; // message set by inorm_api
+        int rc = api->get_buffer_size(b->n, b->c, b->h, b->w, &scratch_bytes);
+        if (rc) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+        return Layer::Reshape();
+    }
+    int Init(hipStream_t s) override
+    {
+        if (inited || !affine) return 0;
+        int rc = d_gamma.upload(gamma.data(), gamma.size(), s);
+        if (rc) return rc;
+        if ((rc = d_beta.upload(beta.data(), beta.size(), s))) return rc;
+        FHIP_CHECK_HIP(hipStreamSynchronize(s));
+        inited = true;
+        return 0;
+    }
+    int Forward(hipStream_t s) override
+    {
+        const InormApi* api = inorm_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const Blob* b = bottoms[0];
+        const int rc = api->forward(b->n, b->c, b->h, b->w, tops[0]->data, b->data, affine ? d_gamma.d : nullptr, affine ? d_beta.d : nullptr, eps, act,
+                                    slope, scratch_bytes ? net->arena.d : nullptr, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    int Fuse(Layer* next, int) override
+    {
+        if (next->type != "ReLU" || act != FHIP_INORM_ACT_NONE) return 0;
+        slope = static_cast<ReluLayer*>(next)->slope;
+        act = slope == 0.f ? FHIP_INORM_ACT_RELU : FHIP_INORM_ACT_LEAKY;
+        return 1;
+    }
+    size_t weight_bytes() const override { return d_gamma.bytes + d_beta.bytes; }
+    size_t arena_bytes() const override { return scratch_bytes; }
+    int algo() const override { return FHIP_NET_ROUTE_INORM; }
+};
+
+// ncnn's PReLU (0=num_slope, slope[num_slope] in the .bin), Sigmoid, TanH and Clip (0=min, 1=max): one element-wise launch of
+// libfeather_inorm.so each; nothing fuses with them.
+struct ActivationLayer : Layer
+{
+    int kind = -1, num_slope = 0;
+    float p0 = 0.f, p1 = 0.f;
+    std::vector<float> slopes;
+    DeviceVec d_slopes;
+    bool inited = false;
+
+    int LoadParam(const ParamDict& pd) override
+    {
+        if (type == "PReLU")
+        {
+            kind = FHIP_ACTIVATION_PRELU;
+            num_slope = pd.get(0, 0);
+            if (num_slope < 1) return failf(NET_E_SHAPE, "layer %s: PReLU needs num_slope >= 1", name.c_str());
+        }
+        else if (type == "Sigmoid")
+            kind = FHIP_ACTIVATION_SIGMOID;
+        else if (type == "TanH")
+            kind = FHIP_ACTIVATION_TANH;
+        else
+        {
+            kind = FHIP_ACTIVATION_CLIP;
+            p0 = pd.get(0, -FLT_MAX);
+            p1 = pd.get(1, FLT_MAX);
+            if (!(p0 <= p1)) return failf(NET_E_SHAPE, "layer %s: Clip needs min <= max", name.c_str());
+        }
+        return 0;
+    }
+    int LoadWeights(ModelBin& mb) override
+    {
+        if (kind != FHIP_ACTIVATION_PRELU) return 0;
+        inited = false;
+        const int rc = mb.load(num_slope, 1, slopes);
+        if (!rc && num_slope == 1) p0 = slopes[0];
+        return rc;
+    }
+    int Reshape() override
+    {
+        if (kind == FHIP_ACTIVATION_PRELU && num_slope != 1 && num_slope != bottoms[0]->c)
+            return failf(NET_E_TOPOLOGY, "PReLU layer %s has %d slopes while bottom blob %s has %d channels", name.c_str(), num_slope,
+                         bottoms[0]->name.c_str(), bottoms[0]->c);
+        if (!inorm_api()) return FHIP_E_UNSUPPORTED; // message set by inorm_api
+        return Layer::Reshape();
+    }
+    int Init(hipStream_t s) override
+    {
+        if (inited || num_slope <= 1) return 0;
+        const int rc = d_slopes.upload(slopes.data(), slopes.size(), s);
+        if (rc) return rc;
+        FHIP_CHECK_HIP(hipStreamSynchronize(s));
+        inited = true;
+        return 0;
+    }
+    int Forward(hipStream_t s) override
+    {
+        const InormApi* api = inorm_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const Blob* b = bottoms[0];
+        const int rc = api->activation(kind, tops[0]->data, b->data, b->n, b->c, b->h * b->w, p0, p1, num_slope > 1 ? d_slopes.d : nullptr, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    size_t weight_bytes() const override { return d_slopes.bytes; }
 };
 
 struct PoolingLayer : Layer
@@ -1055,7 +1270,7 @@ struct AffineLayer : Layer
     }
     int Fuse(Layer* next, int) override
     {
-        if (next->type == "ReLU")
+        if (is_plain_relu(next))
         {
             relu = true;
             return 1;
@@ -1127,7 +1342,7 @@ int ConvLayer::Fuse(Layer* next, int level)
 {
     if (pw) return pw->Fuse(next, level) == 1 ? 1 : 0; // behind the absorbed 1x1 convolution: its own fusions
     if (fuse_pool) return 0; // nothing is absorbed behind the pooling
-    if (gconv && next->type != "ReLU" && next->type != "BatchNorm" && next->type != "Scale") return 0; // the grouped route has these epilogues only
+    if (gconv && !is_plain_relu(next) && next->type != "BatchNorm" && next->type != "Scale") return 0; // the grouped route has these epilogues only
     if (level >= 2 && !residual && next->type == "Convolution" && p.group == p.input_channels && p.group > 1 && p.group <= 256 && p.kernel_h == 3 &&
         p.kernel_w == 3 && p.stride_h == p.stride_w && (p.stride_h == 1 || p.stride_h == 2) && p.pad_left == 1 && p.pad_top == 1)
     {
@@ -1142,7 +1357,7 @@ int ConvLayer::Fuse(Layer* next, int level)
         if (!band_pair && (q.output_channels <= 64 || q.output_channels >= (p.stride_h == 1 ? 160 : 400))) return 0;
         return 2; // the pass hands `next` over (fuse_layers)
     }
-    if (residual && next->type != "ReLU") return 0; // behind the residual add only its ReLU
+    if (residual && !is_plain_relu(next)) return 0; // behind the residual add only its ReLU
     if (level >= 2 && next->type == "Pooling")
     {
         const fhip_pool_param& q = static_cast<PoolingLayer*>(next)->q;
@@ -1153,7 +1368,7 @@ int ConvLayer::Fuse(Layer* next, int level)
         fuse_pool = true;
         return 1;
     }
-    if (next->type == "ReLU")
+    if (is_plain_relu(next))
     {
         p.activation = FHIP_ACT_RELU;
         return 1;
@@ -1299,7 +1514,7 @@ struct DeconvLayer : Layer
 
 int DeconvLayer::Fuse(Layer* next, int level)
 {
-    if (next->type == "ReLU")
+    if (is_plain_relu(next))
     {
         p.activation = FHIP_ACT_RELU;
         return 1;
@@ -1353,7 +1568,7 @@ struct EltwiseLayer : Layer
     }
     int Fuse(Layer* next, int) override
     {
-        if (next->type == "ReLU")
+        if (is_plain_relu(next))
         {
             relu = true;
             return 1;
@@ -1449,6 +1664,8 @@ static Layer* create_layer(const std::string& type) // layer_factory.cpp:55-67
     if (type == "Convolution" || type == "ConvolutionDepthWise") return new ConvLayer;
     if (type == "Deconvolution" || type == "DeconvolutionDepthWise") return new DeconvLayer;
     if (type == "ReLU") return new ReluLayer;
+    if (type == "InstanceNorm") return new InstanceNormLayer;
+    if (type == "PReLU" || type == "Sigmoid" || type == "TanH" || type == "Clip") return new ActivationLayer;
     if (type == "Pooling") return new PoolingLayer;
     if (type == "InnerProduct") return new InnerProductLayer;
     if (type == "Dropout") return new DropoutLayer;
@@ -1814,7 +2031,8 @@ static int prepare(Net& net)
     {
         bool needs = false;
         for (auto& l : net.layers) needs = needs || (l->type != "Input" && l->type != "ReLU" && l->type != "Pooling" && l->type != "Softmax" &&
-                                                     l->type != "Split" && l->type != "Eltwise" && l->type != "Concat" && l->type != "Dropout");
+                                                     l->type != "Split" && l->type != "Eltwise" && l->type != "Concat" && l->type != "Dropout" &&
+                                                     l->type != "Sigmoid" && l->type != "TanH" && l->type != "Clip");
         if (needs) return failf(NET_E_IO, "weights have not been loaded");
     }
     fuse_layers(net);

@@ -87,8 +87,41 @@ class GraphBuilder:
         x = self.scale(name + "_scale", x, cout)
         return self.relu(name + "_relu", x)
 
-    def relu(self, name, bottom):
-        return self.layer("ReLU", name, [bottom], [name])
+    def relu(self, name, bottom, slope=None):
+        """slope: ncnn's leaky ReLU (param 0); None writes no params, the plain layer."""
+        return self.layer("ReLU", name, [bottom], [name], None if slope is None else {0: f"{slope:.6f}"})
+
+    def instance_norm(self, name, bottom, c, eps=1e-3, affine=True):
+        """ncnn's InstanceNorm: gamma U(0.5, 1.5) and beta U(-0.1, 0.1), raw fp32, only when affine."""
+        top = self.layer("InstanceNorm", name, [bottom], [name], {0: c, 1: f"{eps:.6e}", 2: int(affine)})
+        if affine:
+            self._raw(self._uniform(c, 0.5, 1.5))
+            self._raw(self._uniform(c, -0.1, 0.1))
+        return top
+
+    def prelu(self, name, bottom, num_slope):
+        top = self.layer("PReLU", name, [bottom], [name], {0: num_slope})
+        self._raw(self._uniform(num_slope, 0.05, 0.35))
+        return top
+
+    def tanh(self, name, bottom):
+        return self.layer("TanH", name, [bottom], [name])
+
+    def sigmoid(self, name, bottom):
+        return self.layer("Sigmoid", name, [bottom], [name])
+
+    def clip(self, name, bottom, lo, hi):
+        return self.layer("Clip", name, [bottom], [name], {0: f"{lo:.6f}", 1: f"{hi:.6f}"})
+
+    def conv_in_relu(self, name, bottom, cin, cout, k, s=1, p=0, relu=True, slope=None):
+        x = self.conv(name, bottom, cin, cout, k, s, p)
+        x = self.instance_norm(name + "_in", x, cout)
+        return self.relu(name + "_relu", x, slope) if relu else x
+
+    def deconv_in_relu(self, name, bottom, cin, cout, k, s=1, p=0, op=0):
+        x = self.deconv(name, bottom, cin, cout, k, s, p, op)
+        x = self.instance_norm(name + "_in", x, cout)
+        return self.relu(name + "_relu", x)
 
     def pool(self, name, bottom, k=2, s=2, p=0, avg=False, global_=False):
         return self.layer("Pooling", name, [bottom], [name], {0: int(avg), 1: k, 2: s, 3: p, 4: int(global_)})
@@ -314,7 +347,8 @@ def tiny_deconv(seed=13, size=16, dry=False):
 def style_transfer(seed=1234, size=256, dry=False):
     """Johnson et al.'s feed-forward style-transfer net: 9x9 convolution, two stride-2 convolutions, five 128-channel residual blocks at a
     quarter of the resolution, two k3 s2 p1 deconvolutions with output padding 1, 9x9 convolution to 3 channels.  BatchNorm + Scale
-    stand where the paper has InstanceNorm (this runtime has no such layer; the arithmetic per layer is the same affine map)."""
+    stand where the paper has InstanceNorm (the arithmetic per layer is the same affine map, and it folds into the convolutions);
+    `style_transfer_in` is the net as published, with InstanceNorm and a TanH output."""
     g = GraphBuilder(seed, dry)
     x = g.input("data", 3, size, size)
     x = g.conv_bn_relu("conv1", x, 3, 32, 9, 1, 4)
@@ -353,10 +387,72 @@ def unet_k4(seed=1234, size=256, dry=False):
     return g.finish() + ("data", "d1")
 
 
+def tiny_generative(seed=17, size=24, dry=False):
+    """A small generative net with every layer of libfeather_inorm.so, nothing above 24 px: InstanceNorm on a 4-aligned plane (24 x 24) behind
+    a leaky ReLU, without affine weights on 12 x 12 behind a plain ReLU, on an odd plane (5 x 5) and on a 1 x 1 plane; a convolution followed
+    directly by a leaky ReLU (which no convolution epilogue may absorb); PReLU per channel and shared; Sigmoid, Clip and a TanH output.  The
+    1 x 1 branch ends in the blob `gate`, the image branch in `out`."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_in_relu("conv1", x, 3, 16, 3, 1, 1, slope=0.2)                        # InstanceNorm + leaky ReLU
+    x = g.relu("lrelu2", g.conv("conv2", x, 16, 32, 3, 2, 1), slope=0.2)             # Convolution + leaky ReLU: two layers at every level
+    x = g.relu("relu2", g.instance_norm("in2", x, 32, affine=False))                 # no gamma / beta, plain ReLU
+    x = g.prelu("prelu3", g.instance_norm("in3", g.conv("conv3", x, 32, 32, 3, 2, 0), 32, eps=1e-5), 32)  # odd plane, PReLU per channel
+    a, b = g.split("split", x)
+    a = g.pool("gap", a, global_=True, avg=True)
+    a = g.sigmoid("gate", g.prelu("prelu4", g.instance_norm("in4", a, 32), 1))       # a plane of one pixel: y = beta; shared PReLU
+    b = g.deconv_in_relu("d1", b, 32, 16, 4, 2, 1)                                   # Deconvolution + InstanceNorm + ReLU
+    b = g.clip("clip", g.deconv("d2", b, 16, 8, 4, 2, 1), -0.5, 0.75)
+    b = g.tanh("out", g.conv("conv_out", b, 8, 3, 3, 1, 1))
+    return g.finish() + ("data", "out")
+
+
+def style_transfer_in(seed=1234, size=256, dry=False):
+    """Johnson et al.'s style-transfer net as published: `style_transfer` with InstanceNorm (affine) where that one has BatchNorm + Scale,
+    and a TanH on the output."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_in_relu("conv1", x, 3, 32, 9, 1, 4)
+    x = g.conv_in_relu("conv2", x, 32, 64, 3, 2, 1)
+    x = g.conv_in_relu("conv3", x, 64, 128, 3, 2, 1)
+    for i in range(1, 6):
+        a, b = g.split(f"res{i}_split", x)
+        a = g.conv_in_relu(f"res{i}a", a, 128, 128, 3, 1, 1)
+        a = g.conv_in_relu(f"res{i}b", a, 128, 128, 3, 1, 1, relu=False)
+        x = g.eltwise(f"res{i}", a, b)
+    x = g.deconv_in_relu("deconv1", x, 128, 64, 3, 2, 1, op=1)
+    x = g.deconv_in_relu("deconv2", x, 64, 32, 3, 2, 1, op=1)
+    x = g.tanh("out", g.conv("conv_out", x, 32, 3, 9, 1, 4))
+    return g.finish() + ("data", "out")
+
+
+def pix2pix_unet(seed=1234, size=256, dry=False):
+    """`unet_k4` as pix2pix publishes it: leaky ReLU (0.2) in the encoder, InstanceNorm on every level but the first, plain ReLU in the
+    decoder, TanH on the output."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    widths = (32, 64, 128, 256, 256)
+    skips, cin = [], 3
+    for i, cw in enumerate(widths, 1):
+        x = g.relu(f"e{i}_relu", g.conv(f"e{i}", x, cin, cw, 4, 2, 1), 0.2) if i == 1 else g.conv_in_relu(f"e{i}", x, cin, cw, 4, 2, 1, slope=0.2)
+        cin = cw
+        if i < len(widths):
+            x, skip = g.split(f"e{i}_split", x)
+            skips.append((skip, cw))
+    for i, cw in zip((5, 4, 3, 2), (256, 128, 64, 32)):
+        x = g.deconv_in_relu(f"d{i}", x, cin, cw, 4, 2, 1)
+        skip, sw = skips.pop()
+        x = g.concat(f"cat{i - 1}", [x, skip])
+        cin = cw + sw
+    x = g.tanh("out", g.deconv("d1", x, cin, 3, 4, 2, 1))
+    return g.finish() + ("data", "out")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
           "tiny_allsorts": tiny_allsorts, "resnext50_32x4d": resnext50_32x4d, "tiny_grouped": tiny_grouped,
-          "tiny_deconv": tiny_deconv, "style_transfer": style_transfer, "unet_k4": unet_k4}
+          "tiny_deconv": tiny_deconv, "style_transfer": style_transfer, "unet_k4": unet_k4,
+          "tiny_generative": tiny_generative, "style_transfer_in": style_transfer_in, "pix2pix_unet": pix2pix_unet}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}

@@ -17,6 +17,8 @@ ROUTE_NAMES = dict(ALGO_NAMES)
 ROUTE_NAMES[ROUTE_GCONV] = "GCONV"
 ROUTE_DECONV = 101  # FHIP_NET_ROUTE_DECONV: a Deconvolution / DeconvolutionDepthWise layer (libfeather_deconv.so)
 ROUTE_NAMES[ROUTE_DECONV] = "DECONV"
+ROUTE_INORM = 102  # FHIP_NET_ROUTE_INORM: an InstanceNorm layer (libfeather_inorm.so)
+ROUTE_NAMES[ROUTE_INORM] = "INORM"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,

@@ -311,6 +311,10 @@ FHIP_API int fhip_net_layer_count(fhip_net* net);
  * way the first time a net holds such a layer.  It fuses a following ReLU and, at fusion level 2, BatchNorm / Scale; no other fusion
  * takes it.  Reported from LoadParam on. */
 #define FHIP_NET_ROUTE_DECONV 101
+/* Route code of an InstanceNorm layer: it runs through libfeather_inorm.so (feather_inorm.h), opened the same way the first time a net
+ * holds such a layer, a PReLU / Sigmoid / TanH / Clip layer or a ReLU with a slope.  It absorbs a following ReLU (plain or leaky) from
+ * fusion level 1 on; no other fusion takes it.  Reported from LoadParam on. */
+#define FHIP_NET_ROUTE_INORM 102
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
  * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);
