@@ -10,6 +10,7 @@ _PIXOUT = None
 _GCONV = None
 _DECONV = None
 _INORM = None
+_SHUFFLE = None
 
 STAGE_NAMES = ("wino_input", "wino_gemm", "wino_output", "igemm", "depthwise", "init", "wino_chain")
 
@@ -174,6 +175,22 @@ INORM_SIGNATURES = {
     "fhip_inorm_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_shuffle.h -- libfeather_shuffle.so, the channel map: ShuffleChannel, Slice and their chains with Concat
+_PP = ctypes.POINTER(ctypes.c_void_p)
+_IP = ctypes.POINTER(ctypes.c_int)
+SHUFFLE_SIGNATURES = {
+    "fhip_channel_map_supported": (_I, [_I, _I, _I, _I]),
+    "fhip_channel_slice_resolve": (_I, [_I, _IP, _I, _IP]),
+    "fhip_channel_shuffle_forward": (_I, [_V, _V, _I, _I, _I, _I, _I, _I, _V]),
+    "fhip_channel_slice_forward": (_I, [_PP, _V, _I, _I, _I, _I, _IP, _I, _V]),
+    "fhip_channel_map_create": (_I, [_PP, _IP, _I, _IP, _I, _IP]),
+    "fhip_channel_map_destroy": (_I, [_V]),
+    "fhip_channel_map_forward": (_I, [_V, _PP, _PP, _I, _I, _I, _V]),
+    "fhip_channel_map_forward_route": (_I, [_I, _V, _PP, _PP, _I, _I, _I, _V]),
+    "fhip_channel_map_route": (_I, [_I, _I, _I, _PP, _I, ctypes.c_char_p, _I]),
+    "fhip_shuffle_last_error": (ctypes.c_char_p, []),
+}
+
 
 def lib_path() -> str:
     return os.environ.get("FEATHER_HIP_LIB", os.path.join(_HERE, "libfeather_hip.so"))
@@ -286,3 +303,26 @@ def load_inorm_library():
             fn.argtypes = args
         _INORM = lib
     return _INORM
+
+
+def shuffle_path() -> str:
+    return os.path.join(_HERE, "libfeather_shuffle.so")
+
+
+def load_shuffle_library():
+    """Load libfeather_shuffle.so (fhip_channel_shuffle_forward, fhip_channel_slice_forward, fhip_channel_map_forward).  Fails loudly like
+    load_library: there is no fallback implementation."""
+    global _SHUFFLE
+    if _SHUFFLE is None:
+        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
+        path = shuffle_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in SHUFFLE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _SHUFFLE = lib
+    return _SHUFFLE

@@ -34,6 +34,7 @@
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
 #include "feather_hip/feather_net.h"
+#include "feather_hip/feather_shuffle.h" // declarations only: the library is opened at run time (shuffle_api)
 
 namespace fhip
 {
@@ -212,6 +213,59 @@ static const InormApi* inorm_api()
     if (!a.get_buffer_size || !a.forward || !a.activation || !a.last_error)
     {
         failf(FHIP_E_UNSUPPORTED, "libfeather_inorm.so (%s) does not export the entry points of feather_inorm.h", tried.c_str());
+        dlclose(h);
+        return nullptr;
+    }
+    api = a;
+    loaded = true;
+    return &api;
+}
+
+// ---- libfeather_shuffle.so, the route of ShuffleChannel and Slice layers and of the Concat / ShuffleChannel / Slice runs collapsed at
+// fusion level 2.  Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name; a net that holds such a
+// layer and cannot find it fails at Reshape.
+struct ShuffleApi
+{
+    decltype(&fhip_channel_slice_resolve) resolve = nullptr;
+    decltype(&fhip_channel_map_create) create = nullptr;
+    decltype(&fhip_channel_map_destroy) destroy = nullptr;
+    decltype(&fhip_channel_map_forward) forward = nullptr;
+    decltype(&fhip_shuffle_last_error) last_error = nullptr;
+};
+
+static const ShuffleApi* shuffle_api()
+{
+    static std::mutex mu;
+    static ShuffleApi api;
+    static bool loaded = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (loaded) return &api;
+    std::string tried;
+    void* h = nullptr;
+    Dl_info self;
+    if (dladdr((void*)&shuffle_api, &self) && self.dli_fname)
+    {
+        std::string path = self.dli_fname;
+        const size_t slash = path.rfind('/');
+        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_shuffle.so";
+        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        tried = path;
+    }
+    if (!h) h = dlopen("libfeather_shuffle.so", RTLD_NOW | RTLD_LOCAL);
+    if (!h)
+    {
+        failf(FHIP_E_UNSUPPORTED, "a ShuffleChannel / Slice layer needs libfeather_shuffle.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
+        return nullptr;
+    }
+    ShuffleApi a;
+    a.resolve = (decltype(a.resolve))dlsym(h, "fhip_channel_slice_resolve");
+    a.create = (decltype(a.create))dlsym(h, "fhip_channel_map_create");
+    a.destroy = (decltype(a.destroy))dlsym(h, "fhip_channel_map_destroy");
+    a.forward = (decltype(a.forward))dlsym(h, "fhip_channel_map_forward");
+    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_shuffle_last_error");
+    if (!a.resolve || !a.create || !a.destroy || !a.forward || !a.last_error)
+    {
+        failf(FHIP_E_UNSUPPORTED, "libfeather_shuffle.so (%s) does not export the entry points of feather_shuffle.h", tried.c_str());
         dlclose(h);
         return nullptr;
     }
@@ -1613,6 +1667,246 @@ struct ConcatLayer : Layer
     }
 };
 
+// ncnn's ShuffleChannel (0=group, 1=reverse) and Slice (-23300=count,sizes..., 1=axis; channels only): no reference counterpart, the
+// definitions are include/feather_hip/feather_shuffle.h.  Both are channel maps -- every output channel is one channel of one bottom -- and so
+// is every chain of them with Concat: at fusion level 2 collapse_channel_maps() folds such a run into ONE layer of this type whose `steps`
+// are the run in order, whose bottoms are the run's outside inputs and whose tops are the blobs that leave it.  Reshape evaluates the
+// steps symbolically into the (source, source channel) table of every top and hands it to libfeather_shuffle.so, which keeps it on the
+// device; Forward is one launch whatever the number of steps, bottoms and tops.  Route code FHIP_NET_ROUTE_SHUFFLE.
+struct MapStep
+{
+    enum Kind
+    {
+        CONCAT,
+        SHUFFLE,
+        SLICE
+    } kind = SHUFFLE;
+    std::string name;
+    int group = 1, reverse = 0;
+    std::vector<int> sizes;
+    std::vector<Blob*> bottoms, tops;
+};
+
+struct ChannelMapLayer : Layer
+{
+    std::vector<MapStep> steps;
+    fhip_channel_map* map = nullptr;
+    std::vector<int> built_src, built_entries; // what `map` was created from
+
+    ~ChannelMapLayer() override { drop_map(); }
+    void drop_map()
+    {
+        if (map)
+            if (const ShuffleApi* api = shuffle_api()) api->destroy(map);
+        map = nullptr;
+    }
+    int LoadParam(const ParamDict& pd) override
+    {
+        MapStep st;
+        st.name = name;
+        st.bottoms = bottoms;
+        st.tops = tops;
+        if (bottoms.size() != 1) return failf(NET_E_TOPOLOGY, "layer %s: a %s layer has one bottom", name.c_str(), type.c_str());
+        if (type == "ShuffleChannel")
+        {
+            st.kind = MapStep::SHUFFLE;
+            st.group = pd.get(0, 1);
+            st.reverse = pd.get(1, 0);
+            if (st.group < 1) return failf(NET_E_SHAPE, "layer %s: ShuffleChannel needs group >= 1", name.c_str());
+            if (tops.size() != 1) return failf(NET_E_TOPOLOGY, "layer %s: a ShuffleChannel layer has one top", name.c_str());
+        }
+        else
+        {
+            st.kind = MapStep::SLICE;
+            if (pd.get(1, 0) != 0) return failf(NET_E_SHAPE, "layer %s: only slice at axis = 0 (channels) is supported", name.c_str());
+            if (!pd.has_array(0)) return failf(NET_E_SHAPE, "layer %s: Slice needs its sizes (-23300=count,...)", name.c_str());
+            for (float v : pd.e[0].array)
+            {
+                if (v != (float)FHIP_SLICE_SHARE && !(v >= 1.f)) return failf(NET_E_SHAPE, "layer %s: a slice size must be positive or -233", name.c_str());
+                st.sizes.push_back((int)v);
+            }
+            if (st.sizes.size() != tops.size())
+                return failf(NET_E_TOPOLOGY, "layer %s: Slice has %d sizes and %d tops", name.c_str(), (int)st.sizes.size(), (int)tops.size());
+            if (tops.size() > FHIP_CHANNEL_MAP_MAX_BLOBS)
+                return failf(NET_E_SHAPE, "layer %s: a Slice into more than %d tops is not supported", name.c_str(), FHIP_CHANNEL_MAP_MAX_BLOBS);
+        }
+        steps.assign(1, st);
+        return 0;
+    }
+    int Reshape() override
+    {
+        const ShuffleApi* api = shuffle_api();
+        if (!api) return FHIP_E_UNSUPPORTED; // message set by shuffle_api
+        const Blob* a = bottoms[0];
+        typedef std::vector<std::pair<int, int>> Rows; // (bottom index, channel) per channel of a blob
+        std::map<const Blob*, Rows> rows;
+        for (size_t i = 0; i < bottoms.size(); ++i)
+        {
+            const Blob* b = bottoms[i];
+            if (b->w != a->w || b->h != a->h || b->n != a->n)
+                return failf(NET_E_SHAPE, "layer %s: images of different shapes cannot be concatenated together", name.c_str());
+            Rows& r = rows[b];
+            r.clear();
+            for (int ch = 0; ch < b->c; ++ch) r.emplace_back((int)i, ch);
+        }
+        for (const MapStep& st : steps)
+        {
+            if (st.kind == MapStep::CONCAT)
+            {
+                Rows out;
+                for (const Blob* b : st.bottoms) out.insert(out.end(), rows[b].begin(), rows[b].end());
+                rows[st.tops[0]] = out;
+                continue;
+            }
+            const Rows in = rows[st.bottoms[0]];
+            const int c = (int)in.size();
+            if (st.kind == MapStep::SHUFFLE)
+            {
+                if (c % st.group) return failf(NET_E_SHAPE, "layer %s: group %d does not divide the %d channels of its bottom", st.name.c_str(), st.group, c);
+                const int g = st.reverse ? c / st.group : st.group, per = c / g; // the inverse of a shuffle by g is the shuffle by c / g
+                Rows out(c);
+                for (int i = 0; i < per; ++i)
+                    for (int k = 0; k < g; ++k) out[i * g + k] = in[k * per + i];
+                rows[st.tops[0]] = out;
+                continue;
+            }
+            std::vector<int> resolved(st.sizes.size());
+            if (api->resolve(c, st.sizes.data(), (int)st.sizes.size(), resolved.data()))
+                return failf(NET_E_SHAPE, "layer %s (%d channels): %s", st.name.c_str(), c, api->last_error());
+            int at = 0;
+            for (size_t j = 0; j < resolved.size(); ++j)
+            {
+                rows[st.tops[j]] = Rows(in.begin() + at, in.begin() + at + resolved[j]);
+                at += resolved[j];
+            }
+        }
+        std::vector<int> src, out_c, entries;
+        for (const Blob* b : bottoms) src.push_back(b->c);
+        for (Blob* t : tops)
+        {
+            const Rows& r = rows[t];
+            out_c.push_back((int)r.size());
+            for (const auto& e : r)
+            {
+                entries.push_back(e.first);
+                entries.push_back(e.second);
+            }
+            const int rc = t->reshape(a->n, (int)r.size(), a->h, a->w);
+            if (rc) return rc;
+        }
+        if (map && src == built_src && entries == built_entries) return 0;
+        drop_map();
+        if (api->create(&map, src.data(), (int)src.size(), out_c.data(), (int)out_c.size(), entries.data()))
+            return failf(FHIP_E_BADARG, "layer %s: %s", name.c_str(), api->last_error());
+        built_src = src;
+        built_entries = entries;
+        return 0;
+    }
+    int Forward(hipStream_t s) override
+    {
+        const ShuffleApi* api = shuffle_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        float* outs[FHIP_CHANNEL_MAP_MAX_BLOBS];
+        const float* srcs[FHIP_CHANNEL_MAP_MAX_BLOBS];
+        for (size_t j = 0; j < tops.size(); ++j) outs[j] = tops[j]->data;
+        for (size_t i = 0; i < bottoms.size(); ++i) srcs[i] = bottoms[i]->data;
+        const Blob* a = bottoms[0];
+        const int rc = api->forward(map, outs, srcs, a->n, a->h, a->w, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    int algo() const override { return FHIP_NET_ROUTE_SHUFFLE; }
+};
+
+static bool is_channel_map_type(const Layer* l)
+{
+    return l->type == "ShuffleChannel" || l->type == "Slice" || (l->type == "Concat" && static_cast<const ConcatLayer*>(l)->axis == 0);
+}
+
+// Fusion level 2: a run of Concat / ShuffleChannel / Slice layers, in any order, that follow each other in the layer list and are linked
+// by blobs with exactly one consumer becomes one ChannelMapLayer (ShuffleNet v2's Concat -> ShuffleChannel -> Slice: two bottoms, two
+// tops, one launch).  The layer keeps the type and name of the run's first layer; the linking blobs are fused away.  A run of Concat
+// layers alone is left as it is (their copies are not this route's); a run with more bottoms or tops than one map takes is cut
+// back to its longest prefix that fits.
+static void collapse_channel_maps(Net& net)
+{
+    auto uses = [&](const Blob* b) {
+        int u = 0;
+        for (auto& l : net.layers)
+            for (const Blob* x : l->bottoms) u += x == b;
+        return u;
+    };
+    auto holds = [](const std::vector<Blob*>& v, const Blob* b) { return std::find(v.begin(), v.end(), b) != v.end(); };
+    for (size_t i = 0; i < net.layers.size(); ++i)
+    {
+        if (!is_channel_map_type(net.layers[i].get())) continue;
+        std::vector<Blob*> made = net.layers[i]->tops;
+        size_t end = i + 1;
+        for (; end < net.layers.size(); ++end)
+        {
+            const Layer* l = net.layers[end].get();
+            if (!is_channel_map_type(l)) break;
+            bool reads = false, sole = true;
+            for (const Blob* b : l->bottoms)
+                if (holds(made, b))
+                {
+                    reads = true;
+                    sole = sole && uses(b) == 1;
+                }
+            if (!reads || !sole) break;
+            made.insert(made.end(), l->tops.begin(), l->tops.end());
+        }
+        // the longest prefix of the run that moves channels and fits one map
+        std::vector<Blob*> sources, inner, finals;
+        for (; end - i >= 2; --end)
+        {
+            sources.clear();
+            inner.clear();
+            finals.clear();
+            bool moves = false;
+            for (size_t k = i; k < end; ++k)
+            {
+                moves = moves || net.layers[k]->type != "Concat";
+                for (Blob* b : net.layers[k]->bottoms)
+                {
+                    if (holds(made, b))
+                        inner.push_back(b);
+                    else if (!holds(sources, b))
+                        sources.push_back(b);
+                }
+            }
+            for (size_t k = i; k < end; ++k)
+                for (Blob* t : net.layers[k]->tops)
+                    if (!holds(inner, t)) finals.push_back(t);
+            if (moves && sources.size() <= FHIP_CHANNEL_MAP_MAX_BLOBS && finals.size() <= FHIP_CHANNEL_MAP_MAX_BLOBS) break;
+        }
+        if (end - i < 2) continue;
+        std::unique_ptr<ChannelMapLayer> run(new ChannelMapLayer);
+        run->type = net.layers[i]->type;
+        run->name = net.layers[i]->name;
+        run->net = &net;
+        run->bottoms = sources;
+        run->tops = finals;
+        for (size_t k = i; k < end; ++k)
+        {
+            Layer* l = net.layers[k].get();
+            if (l->type == "Concat")
+            {
+                MapStep st;
+                st.kind = MapStep::CONCAT;
+                st.name = l->name;
+                st.bottoms = l->bottoms;
+                st.tops = l->tops;
+                run->steps.push_back(st);
+            }
+            else
+                run->steps.push_back(static_cast<ChannelMapLayer*>(l)->steps[0]);
+        }
+        for (Blob* b : inner) b->fused_away = true;
+        net.layers[i] = std::move(run);
+        net.layers.erase(net.layers.begin() + i + 1, net.layers.begin() + end);
+    }
+}
+
 struct SplitLayer : Layer
 {
     int Reshape() override
@@ -1675,6 +1969,7 @@ static Layer* create_layer(const std::string& type) // layer_factory.cpp:55-67
     if (type == "Split") return new SplitLayer;
     if (type == "Eltwise") return new EltwiseLayer;
     if (type == "Concat") return new ConcatLayer;
+    if (type == "ShuffleChannel" || type == "Slice") return new ChannelMapLayer;
     return nullptr;
 }
 
@@ -1789,6 +2084,7 @@ static void fuse_layers(Net& net)
     if (net.fused) return;
     net.fused = true;
     if (net.fusion <= 0) return;
+    if (net.fusion >= 2) collapse_channel_maps(net);
     for (size_t i = 0; i < net.layers.size(); ++i)
     {
         for (;;)
@@ -2032,7 +2328,8 @@ static int prepare(Net& net)
         bool needs = false;
         for (auto& l : net.layers) needs = needs || (l->type != "Input" && l->type != "ReLU" && l->type != "Pooling" && l->type != "Softmax" &&
                                                      l->type != "Split" && l->type != "Eltwise" && l->type != "Concat" && l->type != "Dropout" &&
-                                                     l->type != "Sigmoid" && l->type != "TanH" && l->type != "Clip");
+                                                     l->type != "Sigmoid" && l->type != "TanH" && l->type != "Clip" && l->type != "ShuffleChannel" &&
+                                                     l->type != "Slice");
         if (needs) return failf(NET_E_IO, "weights have not been loaded");
     }
     fuse_layers(net);

@@ -159,6 +159,16 @@ class GraphBuilder:
     def concat(self, name, bottoms):
         return self.layer("Concat", name, list(bottoms), [name], {0: 0})
 
+    def shuffle(self, name, bottom, group, reverse=False):
+        """ncnn's ShuffleChannel: 0=group, 1=reverse (written only when set)."""
+        return self.layer("ShuffleChannel", name, [bottom], [name], {0: group, 1: 1} if reverse else {0: group})
+
+    def slice(self, name, bottom, sizes):
+        """ncnn's Slice along the channels: -23300=count,sizes (an entry of -233: an equal share of what is left), 1=axis 0."""
+        tops = [f"{name}_{i}" for i in range(len(sizes))]
+        self.layer("Slice", name, [bottom], tops, {-23300: ",".join(map(str, [len(sizes)] + list(sizes))), 1: 0})
+        return tops
+
     def dropout(self, name, bottom, scale=None):
         return self.layer("Dropout", name, [bottom], [name], {} if scale is None else {0: f"{scale:.6f}"})
 
@@ -448,11 +458,111 @@ def pix2pix_unet(seed=1234, size=256, dry=False):
     return g.finish() + ("data", "out")
 
 
+def _v2_basic(g, tag, x, c):
+    """ShuffleNet v2's basic unit on c channels: Slice in two, the second half through 1x1 - depthwise 3x3 - 1x1, Concat, ShuffleChannel(2)."""
+    h = c // 2
+    keep, y = g.slice(tag + "_slice", x, [-233, -233])
+    y = g.conv_bn_relu(tag + "_pw1", y, h, h, 1)
+    y = g.conv_bn_relu(tag + "_dw", y, h, h, 3, 1, 1, group=h, relu=False)
+    y = g.conv_bn_relu(tag + "_pw2", y, h, h, 1)
+    return g.shuffle(tag + "_shuffle", g.concat(tag + "_concat", [keep, y]), 2)
+
+
+def _v2_down(g, tag, x, cin, cout):
+    """ShuffleNet v2's stride-2 unit: both branches see the whole input and halve the plane; Concat, ShuffleChannel(2)."""
+    h = cout // 2
+    a, b = g.split(tag + "_split", x)
+    a = g.conv_bn_relu(tag + "_b1_dw", a, cin, cin, 3, 2, 1, group=cin, relu=False)
+    a = g.conv_bn_relu(tag + "_b1_pw", a, cin, h, 1)
+    b = g.conv_bn_relu(tag + "_b2_pw1", b, cin, h, 1)
+    b = g.conv_bn_relu(tag + "_b2_dw", b, h, h, 3, 2, 1, group=h, relu=False)
+    b = g.conv_bn_relu(tag + "_b2_pw2", b, h, h, 1)
+    return g.shuffle(tag + "_shuffle", g.concat(tag + "_concat", [a, b]), 2)
+
+
+def _v1_unit(g, tag, x, cin, cout, group, stride, first_group=None):
+    """ShuffleNet v1's unit: grouped 1x1 to cout / 4, ShuffleChannel(group), depthwise 3x3, grouped 1x1; stride 1 adds the input, stride 2
+    concatenates a 3x3 / s2 average pooling of it (no pad: the reference's ceil rule gives the depthwise branch's size) and the branch
+    makes up the remaining cout - cin channels."""
+    mid = cout // 4
+    main, short = g.split(tag + "_split", x)
+    y = g.conv_bn_relu(tag + "_g1", main, cin, mid, 1, group=first_group or group)
+    y = g.shuffle(tag + "_shuffle", y, group)
+    y = g.conv_bn_relu(tag + "_dw", y, mid, mid, 3, stride, 1, group=mid, relu=False)
+    if stride == 1:
+        y = g.conv_bn_relu(tag + "_g2", y, mid, cout, 1, group=group, relu=False)
+        return g.relu(tag + "_relu", g.eltwise(tag + "_sum", short, y))
+    y = g.conv_bn_relu(tag + "_g2", y, mid, cout - cin, 1, group=group, relu=False)
+    short = g.pool(tag + "_pool", short, 3, 2, avg=True)
+    return g.relu(tag + "_relu", g.concat(tag + "_concat", [short, y]))
+
+
+def tiny_shuffle(seed=19, size=28, dry=False):
+    """A small ShuffleNet on ShuffleNet's own late plane sizes: a v2 stride-2 unit (28 -> 14 px), a v2 basic unit and an unequal three-way
+    Slice on 14 x 14 (196 floats: 16-byte accesses), a reversed shuffle behind a three-way Concat, a v1 unit with grouped 1x1 convolutions
+    and ShuffleChannel(3), a v1 stride-2 unit (14 -> 7 px, average-pooled shortcut) and a v2 basic unit on 7 x 7 (49 floats: the 4-byte
+    path).  Fusion level 2 collapses u1_concat -> u1_shuffle -> u2_slice, u2_concat -> u2_shuffle -> three, cat3 -> unshuffle and
+    u3_concat -> u3_shuffle."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_relu("conv1", x, 3, 16, 3, 1, 1)
+    x = _v2_down(g, "u1", x, 16, 32)                                     # Concat -> ShuffleChannel, then the next unit's Slice
+    x = _v2_basic(g, "u2", x, 32)                                        # ends in Concat -> ShuffleChannel -> Slice(3) below
+    a, b, c = g.slice("three", x, [5, -233, 14])                         # 5 / 13 / 14 channels: unequal, one share
+    b = g.relu("relu_b", g.conv("conv_b", b, 13, 13, 1))
+    x = g.shuffle("unshuffle", g.concat("cat3", [a, b, c]), 4, reverse=True)  # Concat -> ShuffleChannel(reverse) on 32 channels
+    x = g.conv_bn_relu("conv2", x, 32, 24, 1)
+    x = _v1_unit(g, "v1a", x, 24, 24, 3, 1)                              # grouped 1x1 (24 -> 6, group 3), ShuffleChannel(3), residual sum
+    x = _v1_unit(g, "v1b", x, 24, 60, 3, 2)                              # the stride-2 form: average-pooled shortcut, Concat
+    x = _v2_basic(g, "u3", x, 60)                                        # 7 x 7 planes
+    x = g.pool("gap", x, 1, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc", x, 60, 10))
+    return g.finish() + ("data", "prob")
+
+
+def shufflenet_v2_x1_0(seed=1234, classes=1000, size=224, dry=False):
+    """ShuffleNet v2 1.0x: 24-channel stem, stages of 116 / 232 / 464 channels with 4 / 8 / 4 units (a stride-2 unit, then basic units), a
+    1024-channel 1x1 convolution, global pooling, classifier.  Every basic unit's head is a Slice; its tail is Concat -> ShuffleChannel(2)."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_relu("conv1", x, 3, 24, 3, 2, 1)
+    x = g.pool("pool1", x, 3, 2)
+    cin = 24
+    for si, (c, units) in enumerate([(116, 4), (232, 8), (464, 4)], 2):
+        x = _v2_down(g, f"stage{si}_1", x, cin, c)
+        for u in range(2, units + 1):
+            x = _v2_basic(g, f"stage{si}_{u}", x, c)
+        cin = c
+    x = g.conv_bn_relu("conv5", x, cin, 1024, 1)
+    x = g.pool("gap", x, 7, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc", x, 1024, classes))
+    return g.finish() + ("data", "prob")
+
+
+def shufflenet_v1_g3(seed=1234, classes=1000, size=224, dry=False):
+    """ShuffleNet v1 with 3 groups: 24-channel stem, stages of 240 / 480 / 960 channels with 4 / 8 / 4 units.  The first 1x1 of stage 2 is
+    dense (24 input channels), as published; stride-2 units concatenate a 3x3 / s2 average pooling of their input."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_relu("conv1", x, 3, 24, 3, 2, 1)
+    x = g.pool("pool1", x, 3, 2)
+    cin = 24
+    for si, (c, units) in enumerate([(240, 4), (480, 8), (960, 4)], 2):
+        x = _v1_unit(g, f"stage{si}_1", x, cin, c, 3, 2, first_group=1 if si == 2 else None)
+        for u in range(2, units + 1):
+            x = _v1_unit(g, f"stage{si}_{u}", x, c, c, 3, 1)
+        cin = c
+    x = g.pool("gap", x, 7, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc", x, cin, classes))
+    return g.finish() + ("data", "prob")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
           "tiny_allsorts": tiny_allsorts, "resnext50_32x4d": resnext50_32x4d, "tiny_grouped": tiny_grouped,
           "tiny_deconv": tiny_deconv, "style_transfer": style_transfer, "unet_k4": unet_k4,
-          "tiny_generative": tiny_generative, "style_transfer_in": style_transfer_in, "pix2pix_unet": pix2pix_unet}
+          "tiny_generative": tiny_generative, "style_transfer_in": style_transfer_in, "pix2pix_unet": pix2pix_unet,
+          "tiny_shuffle": tiny_shuffle, "shufflenet_v2_x1_0": shufflenet_v2_x1_0, "shufflenet_v1_g3": shufflenet_v1_g3}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}

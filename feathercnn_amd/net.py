@@ -19,6 +19,8 @@ ROUTE_DECONV = 101  # FHIP_NET_ROUTE_DECONV: a Deconvolution / DeconvolutionDept
 ROUTE_NAMES[ROUTE_DECONV] = "DECONV"
 ROUTE_INORM = 102  # FHIP_NET_ROUTE_INORM: an InstanceNorm layer (libfeather_inorm.so)
 ROUTE_NAMES[ROUTE_INORM] = "INORM"
+ROUTE_SHUFFLE = 103  # FHIP_NET_ROUTE_SHUFFLE: a ShuffleChannel / Slice layer or a collapsed run of them with Concat (libfeather_shuffle.so)
+ROUTE_NAMES[ROUTE_SHUFFLE] = "SHUFFLE"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,

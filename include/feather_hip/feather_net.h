@@ -315,6 +315,11 @@ FHIP_API int fhip_net_layer_count(fhip_net* net);
  * holds such a layer, a PReLU / Sigmoid / TanH / Clip layer or a ReLU with a slope.  It absorbs a following ReLU (plain or leaky) from
  * fusion level 1 on; no other fusion takes it.  Reported from LoadParam on. */
 #define FHIP_NET_ROUTE_INORM 102
+/* Route code of a ShuffleChannel or Slice layer: one channel-map launch of libfeather_shuffle.so (feather_shuffle.h), opened the same way
+ * the first time a net holds such a layer.  At fusion level 2 a run of Concat / ShuffleChannel / Slice layers that follow each other in
+ * the layer list, linked by blobs with one consumer each, is one layer with this route (it keeps the type and name of the run's first
+ * layer; the blobs between them cannot be extracted); no other fusion takes these layers.  Reported from LoadParam on. */
+#define FHIP_NET_ROUTE_SHUFFLE 103
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
  * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);
