@@ -11,6 +11,7 @@ _GCONV = None
 _DECONV = None
 _INORM = None
 _SHUFFLE = None
+_CANVAS = None
 
 STAGE_NAMES = ("wino_input", "wino_gemm", "wino_output", "igemm", "depthwise", "init", "wino_chain")
 
@@ -59,6 +60,8 @@ SIGNATURES = {
     "fhip_conv_init": (_I, [_P, _I, _V, _V, _V]),
     "fhip_conv_forward": (_I, [_P, _I, _I, _V, _V, _V, _V, _V, _V]),
     "fhip_winograd_f63_plan": (_I, [_P, _I, ctypes.POINTER(fhip_winograd_plan)]),
+    "fhip_winograd_f63_plan_canvas": (_I, [_P, _I, _I, ctypes.POINTER(fhip_winograd_plan)]),
+    "fhip_winograd_f63_canvas_param": (_I, [_P, _I, _P]),
     "fhip_winograd_f63_transform_kernel": (_I, [_P, _V, _V, _V]),
     "fhip_winograd_f63_input_transform": (_I, [_P, _I, _V, _V, _V]),
     "fhip_winograd_f63_tile_gemm": (_I, [_P, _I, _V, _V, _V, _V]),
@@ -122,6 +125,7 @@ SIGNATURES = {
     "fhip_net_layer_conv_param": (_I, [_V, _I, _P, _PI]),
     "fhip_net_layer_fused_pointwise": (_I, [_V, _I, _P, _PI]),
     "fhip_net_layer_chain": (_I, [_V, _I, _PI, _PI]),
+    "fhip_net_layer_canvas": (_I, [_V, _I, _PI]),
     "fhip_net_layer_sibling": (_I, [_V, _I, _PI]),
     "fhip_net_layer_residual": (_I, [_V, _I, _PI]),
     "fhip_net_forward_timed": (_I, [_V, ctypes.POINTER(ctypes.c_float)]),
@@ -189,6 +193,14 @@ SHUFFLE_SIGNATURES = {
     "fhip_channel_map_forward_route": (_I, [_I, _V, _PP, _PP, _I, _I, _I, _V]),
     "fhip_channel_map_route": (_I, [_I, _I, _I, _PP, _I, ctypes.c_char_p, _I]),
     "fhip_shuffle_last_error": (ctypes.c_char_p, []),
+}
+
+# include/feather_hip/feather_canvas.h -- libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases
+_PL = ctypes.POINTER(fhip_winograd_plan)
+CANVAS_SIGNATURES = {
+    "fhip_canvas_output_to_next_input": (_I, [_I, _P, _P, _I, _PL, _PL, _V, _V, _V, _V]),
+    "fhip_canvas_output_transform": (_I, [_P, _I, _PL, _V, _V, _V, _I, _V]),
+    "fhip_canvas_last_error": (ctypes.c_char_p, []),
 }
 
 
@@ -326,3 +338,26 @@ def load_shuffle_library():
             fn.argtypes = args
         _SHUFFLE = lib
     return _SHUFFLE
+
+
+def canvas_path() -> str:
+    return os.path.join(_HERE, "libfeather_canvas.so")
+
+
+def load_canvas_library():
+    """Load libfeather_canvas.so (fhip_canvas_output_to_next_input, fhip_canvas_output_transform).  Fails loudly like load_library: there is
+    no fallback implementation."""
+    global _CANVAS
+    if _CANVAS is None:
+        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
+        path = canvas_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in CANVAS_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _CANVAS = lib
+    return _CANVAS

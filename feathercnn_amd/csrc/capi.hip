@@ -354,6 +354,48 @@ int fhip_conv_forward_chained(const fhip_conv_param* p, int batch, float* output
     return winograd_output_transform(*p, batch, output, m, bias, s, pool);
 }
 
+// 2x2 image canvases (feather_canvas.h): the layer as ONE pad-1 image of 2H + 2 pixels per side, four images of a channel with a two-pixel
+// zero seam between them.  14- and 56-pixel planes (square, even, the canvas whole tiles: (2H + 2) % 6 == 0, within a block's LDS with a
+// lane per tile), batches that are a multiple of 4, layers the F(6,3) transforms take.
+#ifndef FHIP_CANVAS_PLANES
+#define FHIP_CANVAS_PLANES 3
+#endif
+static bool winograd_canvas_param(const fhip_conv_param& p, int batch, fhip_conv_param* canvas)
+{
+    if (p.kernel_h != 3 || p.kernel_w != 3 || p.stride_h > 1 || p.stride_w > 1 || p.group > 1) return false;
+    if (p.pad_left != 1 || p.pad_right != 1 || p.pad_top != 1 || p.pad_bottom != 1) return false;
+    const int h = p.input_h;
+    if (batch < 4 || (batch & 3) || h != p.input_w || h < 2 || (h & 1) || (2 * h + 2) % 6 != 0) return false;
+    // The rule is on for the two plane sizes it was measured on: other sides with (2H + 2) % 6 == 0 (26, 38, 50) would leave
+    // through boundaries (26 -> pool -> 13) nobody has measured or tested.  FHIP_CANVAS_PLANES (build-time, per-stage A/B runs) is a mask:
+    // bit 0 = 14-pixel planes, bit 1 = 56-pixel planes.
+    if (!((h == 14 && (FHIP_CANVAS_PLANES & 1)) || (h == 56 && (FHIP_CANVAS_PLANES & 2)))) return false;
+    const int side = 2 * h + 2, tiles = side / 6;
+    if (tiles * tiles > 512 || (size_t)(side + 2) * (side + 4) * sizeof(float) > 64 * 1024) return false;
+    fhip_conv_param q = p;
+    q.input_h = q.input_w = q.output_h = q.output_w = side;
+    fhip_winograd_plan own;
+    if (winograd_plan(p, batch, &own) != FHIP_OK || own.frequency_points != 64) return false; // planes the F(4x4,3x3) route takes stay plain
+    if (canvas) *canvas = q;
+    return true;
+}
+
+int fhip_winograd_f63_canvas_param(const fhip_conv_param* p, int batch, fhip_conv_param* canvas)
+{
+    if (!valid_param(p) || !canvas) return fail(FHIP_E_BADARG, "bad argument");
+    if (!winograd_canvas_param(*p, batch, canvas)) return fail(FHIP_E_UNSUPPORTED, "this layer and batch do not run on 2x2 image canvases");
+    return FHIP_OK;
+}
+
+int fhip_winograd_f63_plan_canvas(const fhip_conv_param* p, int batch, int canvas, fhip_winograd_plan* plan)
+{
+    if (!valid_param(p) || !plan || (canvas != 1 && canvas != 2)) return fail(FHIP_E_BADARG, "bad argument");
+    if (canvas == 1) return winograd_plan(*p, batch, plan);
+    fhip_conv_param q;
+    if (!winograd_canvas_param(*p, batch, &q)) return fail(FHIP_E_UNSUPPORTED, "this layer and batch do not run on 2x2 image canvases");
+    return winograd_plan(q, batch / 4, plan);
+}
+
 int fhip_winograd_f63_output_to_next_input(const fhip_conv_param* p, const fhip_conv_param* next, int batch, float* v_next, const float* m,
                                            const float* bias, int pool, void* stream)
 {

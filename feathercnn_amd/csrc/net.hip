@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "common.h"
+#include "feather_hip/feather_canvas.h" // declarations only: the library is opened at run time (canvas_api)
 #include "feather_hip/feather_deconv.h" // declarations only: the library is opened at run time (deconv_api)
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
@@ -266,6 +267,56 @@ static const ShuffleApi* shuffle_api()
     if (!a.resolve || !a.create || !a.destroy || !a.forward || !a.last_error)
     {
         failf(FHIP_E_UNSUPPORTED, "libfeather_shuffle.so (%s) does not export the entry points of feather_shuffle.h", tried.c_str());
+        dlclose(h);
+        return nullptr;
+    }
+    api = a;
+    loaded = true;
+    return &api;
+}
+
+// ---- libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases (plan_chains) -----------------------
+// Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name.  The canvas form is a faster way to run
+// the same run of layers, not a layer type: a net that qualifies and cannot find the library fails at plan_chains like the others.
+struct CanvasApi
+{
+    decltype(&fhip_canvas_output_to_next_input) chain = nullptr;
+    decltype(&fhip_canvas_output_transform) output = nullptr;
+    decltype(&fhip_canvas_last_error) last_error = nullptr;
+};
+
+static const CanvasApi* canvas_api()
+{
+    static std::mutex mu;
+    static CanvasApi api;
+    static bool loaded = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (loaded) return &api;
+    std::string tried;
+    void* h = nullptr;
+    Dl_info self;
+    if (dladdr((void*)&canvas_api, &self) && self.dli_fname)
+    {
+        std::string path = self.dli_fname;
+        const size_t slash = path.rfind('/');
+        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_canvas.so";
+        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        tried = path;
+    }
+    if (!h) h = dlopen("libfeather_canvas.so", RTLD_NOW | RTLD_LOCAL);
+    if (!h)
+    {
+        failf(FHIP_E_UNSUPPORTED, "a chained Winograd run on 2x2 image canvases needs libfeather_canvas.so next to libfeather_hip.so (%s): %s",
+              tried.c_str(), dlerror());
+        return nullptr;
+    }
+    CanvasApi a;
+    a.chain = (decltype(a.chain))dlsym(h, "fhip_canvas_output_to_next_input");
+    a.output = (decltype(a.output))dlsym(h, "fhip_canvas_output_transform");
+    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_canvas_last_error");
+    if (!a.chain || !a.output || !a.last_error)
+    {
+        failf(FHIP_E_UNSUPPORTED, "libfeather_canvas.so (%s) does not export the entry points of feather_canvas.h", tried.c_str());
         dlclose(h);
         return nullptr;
     }
@@ -571,6 +622,7 @@ struct Layer
     virtual const fhip_conv_param* conv_param() const { return nullptr; }
     virtual const fhip_conv_param* fused_pointwise(int*) const { return nullptr; } // the 1x1 convolution a depthwise layer absorbed
     virtual void chain_state(int* v_from_previous, int* writes_next_v) const { *v_from_previous = *writes_next_v = 0; }
+    virtual int canvas_state() const { return 0; }
     virtual int sibling_state() const { return 0; } // 1: launches the GEMM that also computes the NEXT layer; 2: computed by the layer before
     virtual int residual_state() const { return 0; } // 1: an Eltwise SUM operand is added in this layer's GEMM epilogue; 2: absorbed, added by a separate launch
 };
@@ -665,6 +717,11 @@ struct ConvLayer : Layer
     bool chain_in = false;
     int chain_pos = 0;
     size_t chain_bytes = 0; // arena the run needs (reported instead of buffer_bytes)
+    // fusion level 3 (plan_chains): this chained layer's V and M hold 2x2 image canvases (feather_canvas.h): its tile GEMM runs on
+    // canvas_p -- the layer as one (2H + 2)-pixel image -- at a quarter of the batch, its boundaries through libfeather_canvas.so
+    bool canvas = false;
+    fhip_conv_param canvas_p;
+    fhip_winograd_plan run_plan; // the plan this chained layer runs with (plain or canvas), set by plan_chains
     // fusion level 3 (plan_chains): a first layer (3x3 / s1 / p1, 2 .. 4 input channels) whose only consumer is a Winograd layer is computed
     // inside that layer's input transform (fhip_winograd_f63_input_from_first): `head_of` = the consumer (this layer then launches nothing,
     // its top has no storage), `head` = the absorbed first layer (on the consumer); first_raw = this layer's filters as loaded
@@ -927,6 +984,7 @@ struct ConvLayer : Layer
                                                                   head->p.bias_term ? head->bias.d : nullptr, s);
                 if (rc) return rc;
             }
+            if (canvas || (chain_next && chain_next->canvas)) return forward_canvas(n, in, v, m, vn, b, s);
             if (chain_next) return fhip_conv_forward_chained(&p, n, nullptr, in, packed.d, v, m, b, &chain_next->p, vn, fuse_pool ? 1 : 0, s);
             if (!fuse_pool || pool_fast) return fhip_conv_forward_chained(&p, n, tops[0]->data, in, packed.d, v, m, b, nullptr, nullptr, fuse_pool ? 1 : 0, s);
             const int rc = fhip_conv_forward_chained(&p, n, pre_pool.d, in, packed.d, v, m, b, nullptr, nullptr, 0, s);
@@ -951,6 +1009,30 @@ struct ConvLayer : Layer
         const int rc = fhip_conv_forward(&p, algo_, bottoms[0]->n, pre_pool.d, bottoms[0]->data, packed.d, (float*)net->arena.d, b, s);
         if (rc) return rc;
         return fhip_pooling(&poolq, bottoms[0]->n, tops[0]->data, pre_pool.d, s);
+    }
+    // One layer of a chained run that is, or is followed by, a canvas layer: input transform (a plain first layer only) -> tile GEMM on the
+    // geometry the layer runs with -> the boundary's form of the chained transform, or the canvas output transform at the end of the run.
+    int forward_canvas(int n, const float* in, float* v, float* m, float* vn, const float* b, hipStream_t s)
+    {
+        const CanvasApi* api = canvas_api();
+        if (!api) return FHIP_E_UNSUPPORTED; // message set by canvas_api
+        int rc;
+        if (in)
+        {
+            // plan_chains enters a canvas stretch through a chained boundary only: a layer that transforms its own input is plain
+            if (canvas) return failf(FHIP_E_UNSUPPORTED, "layer %s: a canvas layer takes its input from the chained transform before it", name.c_str());
+            if ((rc = fhip_winograd_f63_input_transform(&p, n, v, in, s))) return rc;
+        }
+        rc = canvas ? fhip_winograd_f63_tile_gemm(&canvas_p, n / 4, m, packed.d, v, s) : fhip_winograd_f63_tile_gemm(&p, n, m, packed.d, v, s);
+        if (rc) return rc;
+        if (chain_next)
+        {
+            const int form = !canvas ? FHIP_CANVAS_ENTRY : chain_next->canvas ? FHIP_CANVAS_INSIDE : FHIP_CANVAS_EXIT;
+            rc = api->chain(form, &p, &chain_next->p, n, &run_plan, &chain_next->run_plan, vn, m, b, s);
+        }
+        else
+            rc = api->output(&p, n, &run_plan, tops[0]->data, m, b, fuse_pool ? 1 : 0, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
     }
     int Fuse(Layer* next, int level) override;
     // absorb `elt` = Eltwise SUM of this layer's top and `other` (a blob produced earlier in the layer list)
@@ -989,6 +1071,7 @@ struct ConvLayer : Layer
         *v_from_previous = head ? 2 : chain_in ? 1 : 0;
         *writes_next_v = head_of ? 2 : chain_next ? 1 : 0;
     }
+    int canvas_state() const override { return canvas ? 1 : 0; }
 };
 
 // feather::InnerProductLayer, layers/inner_product_layer.h:28-171: y = W x + b, W [out][in].  On the device it is a
@@ -2184,6 +2267,7 @@ static int plan_chains(Net& net)
             conv[i]->chain_in = false;
             conv[i]->chain_pos = 0;
             conv[i]->chain_bytes = 0;
+            conv[i]->canvas = false;
             conv[i]->head = conv[i]->head_of = nullptr;
         }
     for (auto& kv : net.blobs) kv.second->chained = false;
@@ -2206,6 +2290,43 @@ static int plan_chains(Net& net)
         b->chain_pos = a->chain_pos + 1;
         a->tops[0]->chained = true;
         a->tops[0]->drop_storage();
+    }
+    // 2x2 image canvases (feather_canvas.h): a maximal sub-run of chained layers on one plane size, entered through a pooled boundary, whose
+    // planes are whole tiles as canvases (14 and 56 pixels: 0.69 x and 0.90 x the tiles) runs with four images of a channel per "image".
+    // It ends in a pooled boundary to a plain layer, or with the run (the canvas output transform; a pooling that is not fused stays plain).
+    for (size_t i = 0; i < L; ++i)
+    {
+        ConvLayer* c = conv[i];
+        if (!c || !c->chain_in || c->canvas) continue;
+        ConvLayer* prev = nullptr;
+        for (size_t j = 0; j < i; ++j)
+            if (conv[j] && conv[j]->chain_next == c) prev = conv[j];
+        if (!prev || prev->canvas || !prev->fuse_pool || prev->head) continue; // a sub-run starts behind a plain layer's pooled boundary
+        const int n = c->bottoms[0]->n;
+        fhip_conv_param q;
+        if (fhip_winograd_f63_canvas_param(&prev->p, n, &q) == FHIP_OK) continue; // (never: a pooled consumer of a canvas plane is not one)
+        if (prev->p.kernel_h != 3 || prev->p.pad_left != 1 || prev->p.pad_right != 1 || prev->p.pad_top != 1 || prev->p.pad_bottom != 1 ||
+            prev->p.output_h != prev->p.output_w || prev->p.output_h != prev->p.input_h)
+            continue;
+        std::vector<ConvLayer*> run;
+        for (ConvLayer* x = c; x; x = x->chain_next)
+        {
+            if (x->p.input_h != c->p.input_h || x->p.input_w != c->p.input_w || fhip_winograd_f63_canvas_param(&x->p, n, &q) != FHIP_OK) break;
+            if (x->p.activation != FHIP_ACT_NONE && x->p.activation != FHIP_ACT_RELU) break;
+            run.push_back(x);
+            if (x->fuse_pool) break; // the plane size changes behind it
+        }
+        if (run.empty()) continue;
+        ConvLayer* last = run.back();
+        // the sub-run must be the whole stretch on this plane size, and leave through a form that exists: EXIT (pooled), or the end of the run
+        if (last->chain_next && !last->fuse_pool) continue;
+        if (!last->chain_next && last->fuse_pool && !last->pool_fast) continue;
+        if (!canvas_api()) return FHIP_E_UNSUPPORTED; // message set by canvas_api
+        for (ConvLayer* x : run)
+        {
+            x->canvas = true;
+            (void)fhip_winograd_f63_canvas_param(&x->p, n, &x->canvas_p);
+        }
     }
     // a first layer in front of a Winograd layer (VGG-16: conv1_1 -> conv1_2) is computed inside that layer's input transform
     for (size_t i = 0; i + 1 < L; ++i)
@@ -2241,8 +2362,9 @@ static int plan_chains(Net& net)
         ConvLayer* c = conv[i];
         if (!c || (!c->chain_in && !c->chain_next && !c->head)) continue;
         fhip_winograd_plan pl;
-        const int rc = fhip_winograd_f63_plan(&c->p, c->bottoms[0]->n, &pl);
+        const int rc = fhip_winograd_f63_plan_canvas(&c->p, c->bottoms[0]->n, c->canvas ? 2 : 1, &pl);
         if (rc) return rc;
+        c->run_plan = pl;
         slot[c->chain_pos & 1] = std::max(slot[c->chain_pos & 1], up(pl.v_bytes));
         msz = std::max(msz, up(pl.m_bytes));
     }
@@ -2974,6 +3096,14 @@ int fhip_net_layer_chain(fhip_net* n, int index, int* v_from_previous, int* writ
     NET_GUARD(n);
     if (index < 0 || index >= (int)n->impl.layers.size() || !v_from_previous || !writes_next_v) return fail(FHIP_E_BADARG, "layer index out of range");
     n->impl.layers[index]->chain_state(v_from_previous, writes_next_v);
+    return FHIP_OK;
+}
+
+int fhip_net_layer_canvas(fhip_net* n, int index, int* canvas)
+{
+    NET_GUARD(n);
+    if (index < 0 || index >= (int)n->impl.layers.size() || !canvas) return fail(FHIP_E_BADARG, "layer index out of range");
+    *canvas = n->impl.layers[index]->canvas_state();
     return FHIP_OK;
 }
 

@@ -261,6 +261,15 @@ class Net:
                     out[i] = (a.value == 1, b.value == 1)
         return out
 
+    def canvases(self):
+        """[layer index] of the chained Winograd layers that run on 2x2 image canvases (fhip_net_layer_canvas; fusion level 3)."""
+        out = []
+        for i in range(self._lib.fhip_net_layer_count(self._h)):
+            c = ctypes.c_int()
+            if self._lib.fhip_net_layer_canvas(self._h, i, ctypes.byref(c)) == 0 and c.value:
+                out.append(i)
+        return out
+
     def forward_timed(self):
         """One eager forward with HIP events around every layer: [(type, name, algo, ms)]."""
         n = self._lib.fhip_net_layer_count(self._h)

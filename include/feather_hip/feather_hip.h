@@ -144,6 +144,16 @@ typedef struct fhip_winograd_plan
 } fhip_winograd_plan;
 
 FHIP_API int fhip_winograd_f63_plan(const fhip_conv_param* param, int batch, fhip_winograd_plan* plan);
+/* The plan of a layer that runs on 2x2 IMAGE CANVASES (feather_canvas.h): four images of one channel on one pad-1 "image" of 2H + 2 pixels
+ * per side, a two-pixel zero seam between them -- 14 + 2 + 14 = 30 pixels are exactly 5 tiles (25 for four images instead of 4 x 9),
+ * 56 + 2 + 56 = 114 exactly 19 (361 instead of 4 x 100).  canvas = 1: fhip_winograd_f63_plan.  canvas = 2: tiles_x = tiles_y = (2H + 2) / 6
+ * count the tiles of a CANVAS, columns = (batch / 4) * tiles_per_image, column p = canvas * T + ty * tiles_x + tx, image n is quadrant
+ * n % 4 (row n % 4 / 2, column n % 2) of canvas n / 4; v_bytes / m_bytes size the canvas-form V and M.  FHIP_E_UNSUPPORTED unless the
+ * layer is 3x3 / stride 1 / pad 1 on 14 x 14 or 56 x 56 planes (the sizes the form was measured on) and batch % 4 == 0.
+ *   fhip_winograd_f63_canvas_param fills `canvas` with the geometry of that (2H + 2)-pixel image: fhip_winograd_f63_tile_gemm(canvas,
+ *   batch / 4, ...) is the tile GEMM of the canvas layer, and the plain stage entry points on host-assembled canvases are its definition. */
+FHIP_API int fhip_winograd_f63_plan_canvas(const fhip_conv_param* param, int batch, int canvas, fhip_winograd_plan* plan);
+FHIP_API int fhip_winograd_f63_canvas_param(const fhip_conv_param* param, int batch, fhip_conv_param* canvas);
 
 /* transformKernel_F6x6_3x3, include/booster/winograd_kernels.h:33, avx/winograd_kernels_F63.cpp:256-271 */
 FHIP_API int fhip_winograd_f63_transform_kernel(const fhip_conv_param* param, float* u, const float* kernel,

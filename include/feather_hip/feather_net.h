@@ -337,6 +337,10 @@ FHIP_API int fhip_net_layer_fused_pointwise(fhip_net* net, int index, fhip_conv_
  * is 2 for the pair "first layer computed inside the next layer's input transform" (fhip_winograd_f63_input_from_first): writes_next_v =
  * 2 on the first layer (it launches nothing), v_from_previous = 2 on the Winograd layer behind it. */
 FHIP_API int fhip_net_layer_chain(fhip_net* net, int index, int* v_from_previous, int* writes_next_v);
+/* Fusion level 3: *canvas = 1 when this chained Winograd layer runs on 2x2 image canvases (feather_canvas.h: four images of a channel as
+ * one (2H + 2)-pixel image, fhip_winograd_f63_plan_canvas(.., 2) sizes its V and M), 0 otherwise.  VGG-16 at a batch that is a multiple
+ * of 4: conv3_1 .. conv3_3 (56 pixels) and conv5_1 .. conv5_3 (14 pixels). */
+FHIP_API int fhip_net_layer_canvas(fhip_net* net, int index, int* canvas);
 /* Fusion level 2: *state = 1 when this 1x1 convolution's launch also computes the NEXT layer of the list (a 1x1 convolution of the same
  * input: fhip_conv_forward_siblings), 2 when this layer is that next one (it launches nothing), 0 otherwise. */
 FHIP_API int fhip_net_layer_sibling(fhip_net* net, int index, int* state);
