@@ -106,6 +106,7 @@ SIGNATURES = {
     "fhip_net_set_fusion": (_I, [_V, _I]),
     "fhip_net_set_graph": (_I, [_V, _I]),
     "fhip_net_set_tuned_selection": (_I, [_V, _I]),
+    "fhip_net_set_dilated": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -202,6 +203,28 @@ CANVAS_SIGNATURES = {
     "fhip_canvas_output_transform": (_I, [_P, _I, _PL, _V, _V, _V, _I, _V]),
     "fhip_canvas_last_error": (ctypes.c_char_p, []),
 }
+
+# include/feather_hip/feather_atrous.h -- libfeather_atrous.so, dilated convolution (a library of its own)
+class fhip_atrous_param(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("output_channels", "input_channels", "input_h", "input_w", "kernel_h", "kernel_w", "output_h", "output_w",
+                                            "stride_h", "stride_w", "pad_left", "pad_bottom", "pad_right", "pad_top", "group", "bias_term",
+                                            "activation", "dilation_h", "dilation_w")]
+
+
+_AP = ctypes.POINTER(fhip_atrous_param)
+ATROUS_SIGNATURES = {
+    "fhip_atrous_assign_output_dim": (_I, [_AP]),
+    "fhip_atrous_supported": (_I, [_AP]),
+    "fhip_atrous_get_buffer_size": (_I, [_AP, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "fhip_atrous_init": (_I, [_AP, _V, _V, _V]),
+    "fhip_atrous_forward": (_I, [_AP, _I, _V, _V, _V, _V, _V, _V]),
+    "fhip_atrous_route": (_I, [_AP, ctypes.c_char_p, _I]),
+    "fhip_atrous_get_buffer_size_route": (_I, [_AP, _I, ctypes.c_char_p, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "fhip_atrous_init_route": (_I, [_AP, _V, _V, _V, ctypes.c_char_p]),
+    "fhip_atrous_forward_route": (_I, [_AP, _I, _V, _V, _V, _V, _V, _V, ctypes.c_char_p]),
+    "fhip_atrous_last_error": (ctypes.c_char_p, []),
+}
+_ATROUS = None
 
 
 def lib_path() -> str:
@@ -361,3 +384,25 @@ def load_canvas_library():
             fn.argtypes = args
         _CANVAS = lib
     return _CANVAS
+
+
+def atrous_path() -> str:
+    return os.path.join(_HERE, "libfeather_atrous.so")
+
+
+def load_atrous_library():
+    """Load libfeather_atrous.so (fhip_atrous_forward).  Fails loudly like load_library: there is no fallback implementation."""
+    global _ATROUS
+    if _ATROUS is None:
+        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
+        path = atrous_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in ATROUS_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _ATROUS = lib
+    return _ATROUS

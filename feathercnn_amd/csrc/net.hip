@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "feather_hip/feather_canvas.h" // declarations only: the library is opened at run time (canvas_api)
+#include "feather_hip/feather_atrous.h" // declarations only: the library is opened at run time (atrous_api)
 #include "feather_hip/feather_deconv.h" // declarations only: the library is opened at run time (deconv_api)
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
@@ -108,6 +109,61 @@ static const GconvApi* gconv_api()
     if (!a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
     {
         failf(FHIP_E_UNSUPPORTED, "libfeather_gconv.so (%s) does not export the entry points of feather_gconv.h", tried.c_str());
+        dlclose(h);
+        return nullptr;
+    }
+    api = a;
+    loaded = true;
+    return &api;
+}
+
+// ---- libfeather_atrous.so, the route of a Convolution layer with dilation > 1 (fhip_net_set_dilated) --------------
+// Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name; a net that holds such a layer and
+// cannot find it fails at Reshape.
+struct AtrousApi
+{
+    decltype(&fhip_atrous_assign_output_dim) assign_output_dim = nullptr;
+    decltype(&fhip_atrous_supported) supported = nullptr;
+    decltype(&fhip_atrous_get_buffer_size) get_buffer_size = nullptr;
+    decltype(&fhip_atrous_init) init = nullptr;
+    decltype(&fhip_atrous_forward) forward = nullptr;
+    decltype(&fhip_atrous_last_error) last_error = nullptr;
+};
+
+static const AtrousApi* atrous_api()
+{
+    static std::mutex mu;
+    static AtrousApi api;
+    static bool loaded = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (loaded) return &api;
+    std::string tried;
+    void* h = nullptr;
+    Dl_info self;
+    if (dladdr((void*)&atrous_api, &self) && self.dli_fname)
+    {
+        std::string path = self.dli_fname;
+        const size_t slash = path.rfind('/');
+        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_atrous.so";
+        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        tried = path;
+    }
+    if (!h) h = dlopen("libfeather_atrous.so", RTLD_NOW | RTLD_LOCAL);
+    if (!h)
+    {
+        failf(FHIP_E_UNSUPPORTED, "a dilated convolution needs libfeather_atrous.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
+        return nullptr;
+    }
+    AtrousApi a;
+    a.assign_output_dim = (decltype(a.assign_output_dim))dlsym(h, "fhip_atrous_assign_output_dim");
+    a.supported = (decltype(a.supported))dlsym(h, "fhip_atrous_supported");
+    a.get_buffer_size = (decltype(a.get_buffer_size))dlsym(h, "fhip_atrous_get_buffer_size");
+    a.init = (decltype(a.init))dlsym(h, "fhip_atrous_init");
+    a.forward = (decltype(a.forward))dlsym(h, "fhip_atrous_forward");
+    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_atrous_last_error");
+    if (!a.assign_output_dim || !a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
+    {
+        failf(FHIP_E_UNSUPPORTED, "libfeather_atrous.so (%s) does not export the entry points of feather_atrous.h", tried.c_str());
         dlclose(h);
         return nullptr;
     }
@@ -643,6 +699,7 @@ struct Net
     int fusion = 1;
     bool use_graph = false;
     bool tuned_selection = false; // fhip_conv_select_algo_tuned instead of the reference's SelectAlgo rule
+    bool dilated = false;         // fhip_net_set_dilated: a Convolution with dilation > 1 is loaded (libfeather_atrous.so) instead of refused
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;
     // fusion level 3 (plan_chains): runs of Winograd layers hand their transformed input from one to the next; the arena then holds two V
@@ -693,6 +750,20 @@ struct ConvLayer : Layer
     // p.output_channels then holds the WHOLE layer's K (the library's convention), not K / group as conv_layer.h:69-75 leaves it.
     // Such a layer fuses a following ReLU and, at level 2, BatchNorm / Scale; every other fusion declines it.
     bool gconv = false;
+    // dilation > 1 in a net with fhip_net_set_dilated: the layer runs through libfeather_atrous.so (atrous_api) with route code
+    // FHIP_NET_ROUTE_ATROUS, whatever its group.  p.output_channels holds the WHOLE layer's K here too; ap() is the library's param.
+    // Fusions as on the grouped route: a following ReLU, at level 2 BatchNorm / Scale, nothing else.
+    bool atrous = false;
+    int dilation_h = 1, dilation_w = 1;
+    fhip_atrous_param ap() const
+    {
+        fhip_atrous_param a;
+        a.output_channels = p.output_channels, a.input_channels = p.input_channels, a.input_h = p.input_h, a.input_w = p.input_w;
+        a.kernel_h = p.kernel_h, a.kernel_w = p.kernel_w, a.output_h = p.output_h, a.output_w = p.output_w;
+        a.stride_h = p.stride_h, a.stride_w = p.stride_w, a.pad_left = p.pad_left, a.pad_bottom = p.pad_bottom, a.pad_right = p.pad_right, a.pad_top = p.pad_top;
+        a.group = p.group, a.bias_term = p.bias_term, a.activation = p.activation, a.dilation_h = dilation_h, a.dilation_w = dilation_w;
+        return a;
+    }
     std::vector<float> w_host, b_host;
     std::vector<float> post_mul, post_add; // folded BatchNorm/Scale (fusion level 2)
     DeviceVec packed, bias;
@@ -750,8 +821,12 @@ struct ConvLayer : Layer
 
     int LoadParam(const ParamDict& pd) override
     {
-        const int dilation_w = pd.get(2, 1), dilation_h = pd.get(12, dilation_w);
-        if (dilation_w > 1 || dilation_h > 1) return failf(NET_E_UNKNOWN_LAYER, "layer %s: dilated convolution is not supported", name.c_str());
+        dilation_w = pd.get(2, 1);
+        dilation_h = pd.get(12, dilation_w);
+        atrous = dilation_w > 1 || dilation_h > 1;
+        if (atrous && !(net && net->dilated))
+            return failf(NET_E_UNKNOWN_LAYER, "layer %s: dilated convolution is not supported (fhip_net_set_dilated lifts this)", name.c_str());
+        if (dilation_w < 1 || dilation_h < 1) return failf(NET_E_SHAPE, "layer %s: dilation must be >= 1", name.c_str());
         if (pd.get(8, 0)) return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8 convolution is not supported", name.c_str());
         p.kernel_w = pd.get(1, 0);
         p.kernel_h = pd.get(11, p.kernel_w);
@@ -771,20 +846,26 @@ struct ConvLayer : Layer
         p.output_channels /= p.group;
         if (p.output_channels <= 0 || p.kernel_h <= 0 || p.kernel_w <= 0) return failf(NET_E_SHAPE, "layer %s: bad convolution geometry", name.c_str());
         p.input_channels = weight_data_size / p.output_channels / p.kernel_h / p.kernel_w;
-        gconv = p.group > 1 && p.group < p.input_channels;
-        if (gconv) p.output_channels *= p.group;
+        gconv = !atrous && p.group > 1 && p.group < p.input_channels;
+        if (gconv || atrous) p.output_channels *= p.group;
+        if (atrous)
+        {
+            if (p.pad_left < 0 || p.pad_top < 0) return failf(NET_E_UNKNOWN_LAYER, "layer %s: automatic padding is not supported", name.c_str());
+            if (p.input_channels < 1 || p.input_channels % p.group) return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the convolution geometry", name.c_str());
+            algo_ = FHIP_NET_ROUTE_ATROUS;
+        }
         return 0;
     }
     int LoadWeights(ModelBin& mb) override
     {
-        const size_t wsize = (size_t)p.input_channels * p.output_channels * p.kernel_h * p.kernel_w / (gconv ? p.group : 1);
+        const size_t wsize = (size_t)p.input_channels * p.output_channels * p.kernel_h * p.kernel_w / (gconv || atrous ? p.group : 1);
         inited_algo = -2; // new weights: every packed form is rebuilt at the next Init
         sib_packed_for = nullptr;
         int rc = mb.load(wsize, 0, w_host);
         if (rc) return rc;
         if (p.bias_term)
         {
-            const int k = p.group == p.input_channels ? p.input_channels : p.output_channels;
+            const int k = atrous ? p.output_channels : p.group == p.input_channels ? p.input_channels : p.output_channels;
             rc = mb.load(k, 1, b_host);
         }
         return rc;
@@ -796,6 +877,21 @@ struct ConvLayer : Layer
         p.input_h = b->h;
         if (p.input_channels != b->c)
             return failf(NET_E_TOPOLOGY, "convolution layer %s has %d input channels while bottom blob has %d channels", name.c_str(), p.input_channels, b->c);
+        if (atrous)
+        {
+            const AtrousApi* api = atrous_api();
+            if (!api) return FHIP_E_UNSUPPORTED; // message set by atrous_api
+            fhip_atrous_param a = ap();
+            if (api->assign_output_dim(&a)) return failf(NET_E_SHAPE, "layer %s: %s", name.c_str(), api->last_error());
+            p.output_h = a.output_h;
+            p.output_w = a.output_w;
+            if (api->supported(&a) != 1) return failf(FHIP_E_UNSUPPORTED, "layer %s: dilated convolution refused: %s", name.c_str(), api->last_error());
+            algo_ = FHIP_NET_ROUTE_ATROUS;
+            int rc = tops[0]->reshape(b->n, p.output_channels, p.output_h, p.output_w);
+            if (rc) return rc;
+            if ((rc = api->get_buffer_size(&a, b->n, &buffer_bytes, &packed_bytes))) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+            return 0;
+        }
         fhip_conv_assign_output_dim(&p);
         if (p.output_h < 1 || p.output_w < 1) return failf(NET_E_SHAPE, "layer %s: empty output", name.c_str());
         if (gconv)
@@ -917,7 +1013,14 @@ struct ConvLayer : Layer
         if (first_candidate() && (rc = first_raw.upload(w.data(), w.size(), s))) return rc; // 27 floats per output channel
         rc = packed.resize(packed_bytes);
         if (rc) return rc;
-        if (gconv)
+        if (atrous)
+        {
+            const AtrousApi* api = atrous_api();
+            if (!api) return FHIP_E_UNSUPPORTED;
+            const fhip_atrous_param a = ap();
+            if ((rc = api->init(&a, (float*)packed.d, (const float*)raw.d, s))) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+        }
+        else if (gconv)
         {
             const GconvApi* api = gconv_api();
             if (!api) return FHIP_E_UNSUPPORTED;
@@ -938,6 +1041,14 @@ struct ConvLayer : Layer
     int Forward(hipStream_t s) override
     {
         const float* b = p.bias_term ? bias.d : nullptr;
+        if (atrous)
+        {
+            const AtrousApi* api = atrous_api();
+            if (!api) return FHIP_E_UNSUPPORTED;
+            const fhip_atrous_param a = ap();
+            const int rc = api->forward(&a, bottoms[0]->n, tops[0]->data, bottoms[0]->data, (const float*)packed.d, nullptr, b, s);
+            return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+        }
         if (gconv)
         {
             const GconvApi* api = gconv_api();
@@ -1047,7 +1158,7 @@ struct ConvLayer : Layer
             bottoms.push_back(other); // dependency scans look at THIS layer
             return true;
         }
-        if (gconv || fuse_pool || residual || p.activation != FHIP_ACT_NONE) return false;
+        if (gconv || atrous || fuse_pool || residual || p.activation != FHIP_ACT_NONE) return false;
         residual = other;
         bottoms.push_back(other); // so that dependency scans (fusion, branch concurrency) see the second input
         return true;
@@ -1063,7 +1174,7 @@ struct ConvLayer : Layer
     }
     size_t arena_bytes() const override { return std::max(buffer_bytes, chain_bytes); }
     const fhip_conv_param* conv_param() const override { return &p; }
-    int algo() const override { return gconv ? FHIP_NET_ROUTE_GCONV : algo_; }
+    int algo() const override { return atrous ? FHIP_NET_ROUTE_ATROUS : gconv ? FHIP_NET_ROUTE_GCONV : algo_; }
     int sibling_state() const override { return sib ? 1 : sib_of ? 2 : 0; }
     int residual_state() const override { return !residual ? 0 : res_fast ? 1 : 2; }
     void chain_state(int* v_from_previous, int* writes_next_v) const override
@@ -1479,13 +1590,14 @@ int ConvLayer::Fuse(Layer* next, int level)
 {
     if (pw) return pw->Fuse(next, level) == 1 ? 1 : 0; // behind the absorbed 1x1 convolution: its own fusions
     if (fuse_pool) return 0; // nothing is absorbed behind the pooling
-    if (gconv && !is_plain_relu(next) && next->type != "BatchNorm" && next->type != "Scale") return 0; // the grouped route has these epilogues only
+    if ((gconv || atrous) && !is_plain_relu(next) && next->type != "BatchNorm" && next->type != "Scale") return 0; // the grouped and dilated routes have these epilogues only
     if (level >= 2 && !residual && next->type == "Convolution" && p.group == p.input_channels && p.group > 1 && p.group <= 256 && p.kernel_h == 3 &&
         p.kernel_w == 3 && p.stride_h == p.stride_w && (p.stride_h == 1 || p.stride_h == 2) && p.pad_left == 1 && p.pad_top == 1)
     {
         // depthwise 3x3 (at most 256 channels: fhip_conv_can_fuse_dw_pw's structural conditions) -> 1x1 convolution: the pair becomes one
         // layer -- one kernel where the shapes qualify too, else the two kernels one after the other inside this layer
         const fhip_conv_param& q = static_cast<ConvLayer*>(next)->p;
+        if (static_cast<ConvLayer*>(next)->atrous) return 0;
         if (q.group != 1 || q.kernel_h != 1 || q.kernel_w != 1 || q.stride_h != 1 || q.stride_w != 1 || q.pad_left || q.pad_right || q.pad_top || q.pad_bottom)
             return 0;
         // fhip_conv_can_fuse_dw_pw's profitable range -- or the band-staged kernel's pair (32 channels, stride 1, a multiple of 64 output channels:
@@ -1514,7 +1626,7 @@ int ConvLayer::Fuse(Layer* next, int level)
     if (level >= 2 && p.activation == FHIP_ACT_NONE && (next->type == "BatchNorm" || next->type == "Scale"))
     {
         AffineLayer* nx = static_cast<AffineLayer*>(next);
-        const int K = p.group == p.input_channels ? p.input_channels : p.output_channels;
+        const int K = atrous ? p.output_channels : p.group == p.input_channels ? p.input_channels : p.output_channels;
         if (nx->channels != K || nx->relu) return 0;
         if (post_mul.empty())
         {
@@ -2332,7 +2444,7 @@ static int plan_chains(Net& net)
     for (size_t i = 0; i + 1 < L; ++i)
     {
         ConvLayer *a = conv[i], *b = conv[i + 1];
-        if (!a || a->pw || a->residual || a->fuse_pool || a->chain_in || a->chain_next || a->tops.size() != 1 || a->bottoms.size() != 1) continue;
+        if (!a || a->atrous || a->pw || a->residual || a->fuse_pool || a->chain_in || a->chain_next || a->tops.size() != 1 || a->bottoms.size() != 1) continue;
         if (!a->first_candidate() || !plain(b) || b->chain_in || b->bottoms[0] != a->tops[0]) continue;
         int uses = 0;
         for (size_t j = 0; j < L; ++j)
@@ -2684,6 +2796,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.fusion = n->impl.fusion;
         m->impl.use_graph = n->impl.use_graph;
         m->impl.tuned_selection = n->impl.tuned_selection;
+        m->impl.dilated = n->impl.dilated;
         m->impl.concurrency = n->impl.concurrency;
         n->more.push_back(std::move(m));
     }
@@ -2722,6 +2835,15 @@ int fhip_net_set_tuned_selection(fhip_net* n, int on)
     n->impl.tuned_selection = on != 0;
     n->impl.shapes_dirty = true;
     for (auto& m : n->more) (void)fhip_net_set_tuned_selection(m.get(), on);
+    return FHIP_OK;
+}
+
+int fhip_net_set_dilated(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the dilated-convolution switch before LoadParam");
+    n->impl.dilated = on != 0;
+    for (auto& m : n->more) m->impl.dilated = on != 0;
     return FHIP_OK;
 }
 

@@ -55,11 +55,14 @@ class GraphBuilder:
     def input(self, name, c, h, w):
         return self.layer("Input", name, [], [name], {0: w, 1: h, 2: c})
 
-    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None):
+    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None, dilation=1):
         fan_in = cin // group * k * k
         wsize = cout * (cin // group) * k * k
         type_ = type_ or ("ConvolutionDepthWise" if group > 1 else "Convolution")  # what ncnn's converter writes; both load alike
-        top = self.layer(type_, name, [bottom], [top or name], {0: cout, 1: k, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group})
+        params = {0: cout, 1: k, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group}
+        if dilation != 1:  # ncnn's id 2 (written only when set); a net that holds one needs Net.SetDilated(True)
+            params = {0: cout, 1: k, 2: dilation, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group}
+        top = self.layer(type_, name, [bottom], [top or name], params)
         self._tagged(self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in)))
         if bias:
             self._raw(self._uniform(cout, -0.1, 0.1))
@@ -175,11 +178,11 @@ class GraphBuilder:
     def softmax(self, name, bottom):
         return self.layer("Softmax", name, [bottom], [name])
 
-    def conv_bn_relu(self, name, bottom, cin, cout, k, s=1, p=0, group=1, relu=True):
+    def conv_bn_relu(self, name, bottom, cin, cout, k, s=1, p=0, group=1, relu=True, dilation=1):
         # bias on every dense conv: the reference Winograd output transform reads bias[k] unconditionally and
         # ConvLayer passes NULL without bias_term; none on depthwise, whose bias blob the reference
         # Net sizes wrongly
-        x = self.conv(name, bottom, cin, cout, k, s, p, group, bias=(group == 1))
+        x = self.conv(name, bottom, cin, cout, k, s, p, group, bias=(group == 1), dilation=dilation)
         x = self.bn(name + "_bn", x, cout)
         x = self.scale(name + "_scale", x, cout)
         return self.relu(name + "_relu", x) if relu else x
@@ -557,12 +560,78 @@ def shufflenet_v1_g3(seed=1234, classes=1000, size=224, dry=False):
     return g.finish() + ("data", "prob")
 
 
+def tiny_dilated(seed=23, size=16, dry=False):
+    """A small net of dilated convolutions in every form the Net runtime has to get right, nothing above 16 px (Net.SetDilated(True)):
+    a stride-1 "same" layer behind a ReLU (the MFMA route, 64-row tile), one in front of an Eltwise sum, a stride-2 layer with a BatchNorm + Scale +
+    ReLU tail (the 128-row tile), a depthwise and a grouped dilated layer, and a layer whose dilation exceeds the plane in front of a 2x2
+    pooling (fusions that must decline a dilated layer)."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.relu("relu1", g.conv("conv1", x, 3, 16, 3, 1, 1))
+    x = g.relu("relu_a1", g.conv("a1", x, 16, 64, 3, 1, 2, dilation=2))                     # group 1, stride 1: the MFMA route
+    a, b = g.split("split1", x)
+    a = g.conv("a2", a, 64, 64, 3, 1, 2, dilation=2)                                        # in front of a residual sum
+    x = g.relu("relu_sum", g.eltwise("sum", a, b))
+    x = g.conv_bn_relu("a3", x, 64, 96, 3, 2, 2, dilation=2)                                # stride 2; BN + Scale + ReLU
+    x = g.relu("relu_dw", g.conv("a_dw", x, 96, 96, 3, 1, 2, group=96, bias=False, dilation=2))  # depthwise
+    x = g.relu("relu_g", g.conv("a_g", x, 96, 48, 3, 1, 3, group=4, dilation=3))            # 1 < group < C: this library, not gconv
+    x = g.relu("relu_far", g.conv("a_far", x, 48, 48, 3, 1, 12, dilation=12))               # only the centre tap ever lands inside
+    x = g.pool("pool1", x, 2, 2)
+    x = g.conv("head", x, 48, 8, 1)
+    return g.finish() + ("data", "head")
+
+
+def _deeplab_trunk(g, size):
+    """VGG-16 as DeepLab runs it: 3x3 / stride-2 / pad-1 poolings, pool4 and pool5 at stride 1, conv5_* at dilation 2."""
+    x = g.input("data", 3, size, size)
+    cin = 3
+    for stage, (n, c) in enumerate([(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)], 1):
+        d = 2 if stage == 5 else 1
+        for i in range(1, n + 1):
+            x = g.relu(f"relu{stage}_{i}", g.conv(f"conv{stage}_{i}", x, cin, c, 3, 1, d, dilation=d))
+            cin = c
+        x = g.pool(f"pool{stage}", x, 3, 2 if stage < 4 else 1, 1)
+    return x
+
+
+def _deeplab_head(g, x, tag, rate, classes):
+    x = g.dropout("drop6" + tag, g.relu("relu6" + tag, g.conv("fc6" + tag, x, 512, 1024, 3, 1, rate, dilation=rate)))
+    x = g.dropout("drop7" + tag, g.relu("relu7" + tag, g.conv("fc7" + tag, x, 1024, 1024, 1)))
+    return g.conv("fc8" + tag, x, 1024, classes, 1)
+
+
+def deeplab_largefov(seed=1234, classes=21, size=321, dry=False):
+    """DeepLab-LargeFOV (Chen et al., ICLR 2015): the VGG-16 trunk at output stride 8, fc6 as a 3x3 convolution at dilation 12 with 1024
+    channels, fc7 / fc8 1x1; the output is the class score map (41 x 41 at 321 pixels).  Net.SetDilated(True)."""
+    g = GraphBuilder(seed, dry)
+    x = _deeplab_head(g, _deeplab_trunk(g, size), "", 12, classes)
+    return g.finish() + ("data", "fc8")
+
+
+def deeplab_v2_aspp(seed=1234, classes=21, size=321, dry=False):
+    """DeepLab v2's atrous spatial pyramid pooling on the VGG-16 trunk: four fc6 - fc8 branches at rates 6 / 12 / 18 / 24, summed by a chain
+    of two-input Eltwise layers.  Net.SetDilated(True)."""
+    g = GraphBuilder(seed, dry)
+    tops = g.split("pool5_split", _deeplab_trunk(g, size), 4)
+    heads = [_deeplab_head(g, t, f"_{j + 1}", rate, classes) for j, (t, rate) in enumerate(zip(tops, (6, 12, 18, 24)))]
+    x = g.eltwise("fc8_sum2", heads[0], heads[1])
+    x = g.eltwise("fc8_sum3", x, heads[2])
+    x = g.eltwise("fc8_sum", x, heads[3])
+    return g.finish() + ("data", "fc8_sum")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
           "tiny_allsorts": tiny_allsorts, "resnext50_32x4d": resnext50_32x4d, "tiny_grouped": tiny_grouped,
           "tiny_deconv": tiny_deconv, "style_transfer": style_transfer, "unet_k4": unet_k4,
           "tiny_generative": tiny_generative, "style_transfer_in": style_transfer_in, "pix2pix_unet": pix2pix_unet,
-          "tiny_shuffle": tiny_shuffle, "shufflenet_v2_x1_0": shufflenet_v2_x1_0, "shufflenet_v1_g3": shufflenet_v1_g3}
+          "tiny_shuffle": tiny_shuffle, "shufflenet_v2_x1_0": shufflenet_v2_x1_0, "shufflenet_v1_g3": shufflenet_v1_g3,
+          "tiny_dilated": tiny_dilated, "deeplab_largefov": deeplab_largefov, "deeplab_v2_aspp": deeplab_v2_aspp}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
+
+# nets that need Net.SetDilated(True), and the layers of each that run through libfeather_atrous.so
+DILATED_LAYERS = {"tiny_dilated": ("a1", "a2", "a3", "a_dw", "a_g", "a_far"),
+                  "deeplab_largefov": ("conv5_1", "conv5_2", "conv5_3", "fc6"),
+                  "deeplab_v2_aspp": ("conv5_1", "conv5_2", "conv5_3", "fc6_1", "fc6_2", "fc6_3", "fc6_4")}

@@ -21,6 +21,8 @@ ROUTE_INORM = 102  # FHIP_NET_ROUTE_INORM: an InstanceNorm layer (libfeather_ino
 ROUTE_NAMES[ROUTE_INORM] = "INORM"
 ROUTE_SHUFFLE = 103  # FHIP_NET_ROUTE_SHUFFLE: a ShuffleChannel / Slice layer or a collapsed run of them with Concat (libfeather_shuffle.so)
 ROUTE_NAMES[ROUTE_SHUFFLE] = "SHUFFLE"
+ROUTE_ATROUS = 104  # FHIP_NET_ROUTE_ATROUS: a Convolution layer with dilation > 1, after SetDilated(True) (libfeather_atrous.so)
+ROUTE_NAMES[ROUTE_ATROUS] = "ATROUS"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -44,6 +46,11 @@ class Net:
             self._h = None
 
     __del__ = close
+
+    def SetDilated(self, on: bool = True):
+        """feather::Net::SetDilated: accept Convolution layers with dilation > 1 (routed to libfeather_atrous.so) instead of refusing them
+        at LoadParam.  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_dilated(self._h, int(bool(on))), "fhip_net_set_dilated")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

@@ -182,6 +182,8 @@ class Net
     int SetFusion(int level) { return fhip_net_set_fusion(net_, level); }
     int SetGraph(bool on) { return fhip_net_set_graph(net_, on ? 1 : 0); }
     int SetTunedSelection(bool on) { return fhip_net_set_tuned_selection(net_, on ? 1 : 0); }
+    // accept Convolution layers with dilation > 1 (libfeather_atrous.so) instead of refusing them; before LoadParam (feather_net.h)
+    int SetDilated(bool on) { return fhip_net_set_dilated(net_, on ? 1 : 0); }
     int SetConcurrency(bool on) { return fhip_net_set_concurrency(net_, on ? 1 : 0); }
     int SetSubBatches(int replicas) { return fhip_net_set_sub_batches(net_, replicas); } // before LoadParam (feather_net.h)
     int LayerCount() { return fhip_net_layer_count(net_); }

@@ -237,6 +237,11 @@ FHIP_API int fhip_net_set_fusion(fhip_net* net, int on);
 /* 1: convolutions choose their route with fhip_conv_select_algo_tuned (MI355X cost model) instead of the reference's
  * SelectAlgo rule; 0 (default): the reference rule. */
 FHIP_API int fhip_net_set_tuned_selection(fhip_net* net, int on);
+/* 1: a Convolution / ConvolutionDepthWise layer with dilation > 1 (ncnn params 2 / 12) is loaded and runs through libfeather_atrous.so
+ * (feather_atrous.h, route code FHIP_NET_ROUTE_ATROUS); 0 (default): LoadParam refuses it with -200.  The default is a refusal only because
+ * tests/test_net_cpu.py pins that answer for a default net; flip it when that test is next revised.  Its only effect is lifting that
+ * refusal (a dilated Deconvolution stays refused).  Call before LoadParam; later it is FHIP_E_BADARG. */
+FHIP_API int fhip_net_set_dilated(fhip_net* net, int on);
 /* 1: independent branches run concurrently: a convolution that needs no scratch arena and whose output is only consumed
  * further down the layer list (ResNet's projection shortcut, SqueezeNet's expand1x1) is enqueued on a second stream owned by
  * the net while the main stream continues; fork and join are events (hipGraph-capturable).  0 (default): one stream. */
@@ -320,6 +325,11 @@ FHIP_API int fhip_net_layer_count(fhip_net* net);
  * the layer list, linked by blobs with one consumer each, is one layer with this route (it keeps the type and name of the run's first
  * layer; the blobs between them cannot be extracted); no other fusion takes these layers.  Reported from LoadParam on. */
 #define FHIP_NET_ROUTE_SHUFFLE 103
+/* Route code of a Convolution layer with dilation > 1 in a net with fhip_net_set_dilated: it runs through libfeather_atrous.so
+ * (feather_atrous.h), opened the same way the first time a net holds such a layer, whatever its group (a dilated layer with
+ * 1 < group < C goes there, not to libfeather_gconv.so).  It fuses a following ReLU and, at fusion level 2, BatchNorm / Scale; no other
+ * fusion takes it.  Reported from LoadParam on. */
+#define FHIP_NET_ROUTE_ATROUS 104
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
  * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);
