@@ -226,6 +226,19 @@ ATROUS_SIGNATURES = {
 }
 _ATROUS = None
 
+# include/feather_hip/feather_gate.h -- libfeather_gate.so, squeeze-and-excitation channel gating, Swish, HardSigmoid (a library of its own)
+GATE_SIGNATURES = {
+    "fhip_channel_gate_forward": (_I, [_I, _I, _I, _I, _V, _V, _V, _V, _I, _V]),
+    "fhip_squeeze_get_buffer_size": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "fhip_squeeze_forward": (_I, [_I, _I, _I, _I, _V, _V, _V, _V]),
+    "fhip_excite_forward": (_I, [_I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _I, _FL, _FL, _V]),
+    "fhip_excite_forward_slices": (_I, [_I, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _I, _FL, _FL, _V]),
+    "fhip_gate_activation_forward": (_I, [_I, _V, _V, _I, _I, _I, _FL, _FL, _V]),
+    "fhip_gate_route": (_I, [_I, _I, _I, _I, _I, _V, _V, _V, ctypes.c_char_p, _I]),
+    "fhip_gate_last_error": (ctypes.c_char_p, []),
+}
+_GATE = None
+
 
 def lib_path() -> str:
     return os.environ.get("FEATHER_HIP_LIB", os.path.join(_HERE, "libfeather_hip.so"))
@@ -406,3 +419,26 @@ def load_atrous_library():
             fn.argtypes = args
         _ATROUS = lib
     return _ATROUS
+
+
+def gate_path() -> str:
+    return os.path.join(_HERE, "libfeather_gate.so")
+
+
+def load_gate_library():
+    """Load libfeather_gate.so (fhip_channel_gate_forward, fhip_squeeze_forward, fhip_excite_forward, fhip_gate_activation_forward).  Fails
+    loudly like load_library: there is no fallback implementation."""
+    global _GATE
+    if _GATE is None:
+        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
+        path = gate_path()
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in GATE_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        _GATE = lib
+    return _GATE

@@ -33,6 +33,7 @@
 #include "feather_hip/feather_canvas.h" // declarations only: the library is opened at run time (canvas_api)
 #include "feather_hip/feather_atrous.h" // declarations only: the library is opened at run time (atrous_api)
 #include "feather_hip/feather_deconv.h" // declarations only: the library is opened at run time (deconv_api)
+#include "feather_hip/feather_gate.h" // declarations only: the library is opened at run time (gate_api)
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
 #include "feather_hip/feather_net.h"
@@ -323,6 +324,61 @@ static const ShuffleApi* shuffle_api()
     if (!a.resolve || !a.create || !a.destroy || !a.forward || !a.last_error)
     {
         failf(FHIP_E_UNSUPPORTED, "libfeather_shuffle.so (%s) does not export the entry points of feather_shuffle.h", tried.c_str());
+        dlclose(h);
+        return nullptr;
+    }
+    api = a;
+    loaded = true;
+    return &api;
+}
+
+// ---- libfeather_gate.so, the route of the squeeze-and-excitation layers: a two-bottom BinaryOp (mul) or Scale, Swish, HardSigmoid, and the
+// whole SE block collapsed at fusion level 2 (collapse_gate_blocks).  Opened like libfeather_gconv.so: lazily, from this library's
+// directory, then by its bare name; a net that holds such a layer and cannot find it fails at Reshape.
+struct GateApi
+{
+    decltype(&fhip_channel_gate_forward) apply = nullptr;
+    decltype(&fhip_squeeze_get_buffer_size) squeeze_buffer_size = nullptr;
+    decltype(&fhip_squeeze_forward) squeeze = nullptr;
+    decltype(&fhip_excite_forward) excite = nullptr;
+    decltype(&fhip_gate_activation_forward) activation = nullptr;
+    decltype(&fhip_gate_last_error) last_error = nullptr;
+};
+
+static const GateApi* gate_api()
+{
+    static std::mutex mu;
+    static GateApi api;
+    static bool loaded = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (loaded) return &api;
+    std::string tried;
+    void* h = nullptr;
+    Dl_info self;
+    if (dladdr((void*)&gate_api, &self) && self.dli_fname)
+    {
+        std::string path = self.dli_fname;
+        const size_t slash = path.rfind('/');
+        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_gate.so";
+        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        tried = path;
+    }
+    if (!h) h = dlopen("libfeather_gate.so", RTLD_NOW | RTLD_LOCAL);
+    if (!h)
+    {
+        failf(FHIP_E_UNSUPPORTED, "a channel-gate / Swish / HardSigmoid layer needs libfeather_gate.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
+        return nullptr;
+    }
+    GateApi a;
+    a.apply = (decltype(a.apply))dlsym(h, "fhip_channel_gate_forward");
+    a.squeeze_buffer_size = (decltype(a.squeeze_buffer_size))dlsym(h, "fhip_squeeze_get_buffer_size");
+    a.squeeze = (decltype(a.squeeze))dlsym(h, "fhip_squeeze_forward");
+    a.excite = (decltype(a.excite))dlsym(h, "fhip_excite_forward");
+    a.activation = (decltype(a.activation))dlsym(h, "fhip_gate_activation_forward");
+    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_gate_last_error");
+    if (!a.apply || !a.squeeze_buffer_size || !a.squeeze || !a.excite || !a.activation || !a.last_error)
+    {
+        failf(FHIP_E_UNSUPPORTED, "libfeather_gate.so (%s) does not export the entry points of feather_gate.h", tried.c_str());
         dlclose(h);
         return nullptr;
     }
@@ -1480,6 +1536,7 @@ struct AffineLayer : Layer
     int channels = 0;
     std::vector<float> mul, add;
     bool has_add = false, relu = false;
+    bool gated = false; // a Scale whose scale is its second bottom (ScaleLayer): no affine map, no fold absorbs it
     DeviceVec d_mul, d_add;
     bool inited = false;
 
@@ -1526,7 +1583,7 @@ struct AffineLayer : Layer
         if (!relu && type == "BatchNorm" && next->type == "Scale") // BN-Scale(-ReLU), batchnorm_layer.h:107-131
         {
             AffineLayer* nx = static_cast<AffineLayer*>(next);
-            if (nx->channels != channels) return 0;
+            if (nx->gated || nx->channels != channels) return 0;
             compose(*nx);
             return 1;
         }
@@ -1562,6 +1619,27 @@ struct BatchNormLayer : AffineLayer
     }
 };
 
+// y[n][c][:] = x[n][c][:] * g[n][c] for a gate blob g of shape [n][c][1][1]: what a two-bottom `BinaryOp 0=2` and a two-bottom
+// `Scale 0=-233` both say (include/feather_hip/feather_gate.h).  Shared by the two layers; route code FHIP_NET_ROUTE_GATE.
+static int gate_reshape(const Layer* l, const Blob* x, const Blob* g)
+{
+    if (g->n != x->n || g->c != x->c || g->h != 1 || g->w != 1)
+        return failf(NET_E_SHAPE, "layer %s: a channel gate needs bottoms of shapes [n][c][h][w] and [n][c][1][1], got %s [%d][%d][%d][%d] and %s [%d][%d][%d][%d]",
+                     l->name.c_str(), x->name.c_str(), x->n, x->c, x->h, x->w, g->name.c_str(), g->n, g->c, g->h, g->w);
+    if (!gate_api()) return FHIP_E_UNSUPPORTED; // message set by gate_api
+    return l->tops[0]->reshape(x->n, x->c, x->h, x->w);
+}
+
+static int gate_forward(const Layer* l, const Blob* x, const Blob* g, hipStream_t s)
+{
+    const GateApi* api = gate_api();
+    if (!api) return FHIP_E_UNSUPPORTED;
+    const int rc = api->apply(x->n, x->c, x->h, x->w, l->tops[0]->data, x->data, g->data, nullptr, FHIP_GATE_ACT_NONE, s);
+    return rc ? failf(rc, "layer %s: %s", l->name.c_str(), api->last_error()) : 0;
+}
+
+// Scale, scale_layer.h:33-98.  ncnn's `0=-233` with two bottoms takes the scale from the second bottom: the channel gate above (`gated`);
+// such a layer is no per-channel affine map to any fusion.
 struct ScaleLayer : AffineLayer
 {
     int bias_term = 0, scale_data_size = 0;
@@ -1569,12 +1647,20 @@ struct ScaleLayer : AffineLayer
     {
         scale_data_size = pd.get(0, 0);
         bias_term = pd.get(1, 0);
+        if (scale_data_size == -233 && bottoms.size() == 2)
+        {
+            if (bias_term) return failf(NET_E_SHAPE, "layer %s: a Scale that takes its scale from a second bottom (0=-233) cannot have a bias term", name.c_str());
+            if (tops.size() != 1) return failf(NET_E_SHAPE, "layer %s: a two-bottom Scale has one top", name.c_str());
+            gated = true;
+            return 0;
+        }
         if (scale_data_size < 0) return failf(NET_E_SHAPE, "layer %s: negative scale data size is not accepted (scale_layer.h:37-41)", name.c_str());
         channels = scale_data_size;
         return 0;
     }
     int LoadWeights(ModelBin& mb) override
     {
+        if (gated) return 0;
         int rc = mb.load(scale_data_size, 1, mul);
         if (rc) return rc;
         if (bias_term)
@@ -1584,6 +1670,157 @@ struct ScaleLayer : AffineLayer
         }
         return rc;
     }
+    int Reshape() override { return gated ? gate_reshape(this, bottoms[0], bottoms[1]) : AffineLayer::Reshape(); }
+    int Init(hipStream_t s) override { return gated ? 0 : AffineLayer::Init(s); }
+    int Forward(hipStream_t s) override { return gated ? gate_forward(this, bottoms[0], bottoms[1], s) : AffineLayer::Forward(s); }
+    int Fuse(Layer* next, int level) override { return gated ? 0 : AffineLayer::Fuse(next, level); }
+    int algo() const override { return gated ? FHIP_NET_ROUTE_GATE : -1; }
+};
+
+// ncnn's BinaryOp: only 0=2 (mul) of a tensor and a per-plane scalar, in either order -- the multiply of a squeeze-and-excitation block
+// as ncnn's converters write it.
+struct BinaryOpLayer : Layer
+{
+    int LoadParam(const ParamDict& pd) override
+    {
+        if (pd.get(0, 0) != 2) return failf(NET_E_SHAPE, "layer %s: only BinaryOp mul (0=2) is supported", name.c_str());
+        if (pd.get(1, 0)) return failf(NET_E_SHAPE, "layer %s: BinaryOp with a scalar operand is not supported", name.c_str());
+        if (bottoms.size() != 2 || tops.size() != 1) return failf(NET_E_SHAPE, "layer %s: BinaryOp needs two bottoms and one top", name.c_str());
+        return 0;
+    }
+    // the gate is the bottom with the 1 x 1 plane; two such bottoms: the second is the gate
+    bool gate_first() const { return bottoms[0]->h == 1 && bottoms[0]->w == 1 && !(bottoms[1]->h == 1 && bottoms[1]->w == 1); }
+    int Reshape() override { return gate_first() ? gate_reshape(this, bottoms[1], bottoms[0]) : gate_reshape(this, bottoms[0], bottoms[1]); }
+    int Forward(hipStream_t s) override { return gate_first() ? gate_forward(this, bottoms[1], bottoms[0], s) : gate_forward(this, bottoms[0], bottoms[1], s); }
+    int algo() const override { return FHIP_NET_ROUTE_GATE; }
+};
+
+// ncnn's Swish (no params) and HardSigmoid (0=alpha, 1=beta; defaults 0.2 and 0.5): one element-wise launch of libfeather_gate.so each.
+struct GateActivationLayer : Layer
+{
+    int kind = FHIP_GATE_SWISH;
+    float alpha = 0.2f, beta = 0.5f;
+    int LoadParam(const ParamDict& pd) override
+    {
+        if (type == "Swish") return 0;
+        kind = FHIP_GATE_HARDSIGMOID;
+        alpha = pd.get(0, 0.2f);
+        beta = pd.get(1, 0.5f);
+        if (!std::isfinite(alpha) || !std::isfinite(beta)) return failf(NET_E_SHAPE, "layer %s: HardSigmoid needs finite alpha and beta", name.c_str());
+        return 0;
+    }
+    int Reshape() override
+    {
+        if (!gate_api()) return FHIP_E_UNSUPPORTED; // message set by gate_api
+        return Layer::Reshape();
+    }
+    int Forward(hipStream_t s) override
+    {
+        const GateApi* api = gate_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const Blob* b = bottoms[0];
+        const int rc = api->activation(kind, tops[0]->data, b->data, b->n, b->c, b->h * b->w, alpha, beta, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    int algo() const override { return FHIP_NET_ROUTE_GATE; }
+};
+
+// Fusion level 2 (collapse_gate_blocks): a whole squeeze-and-excitation block as one layer -- squeeze, excite, and the apply with the
+// residual add and its ReLU folded in: at most three launches (four when the plane is large enough for the squeeze's split route) and
+// four tensor-sized passes through HBM where the layers one by one make six.  It keeps the type and name of the block's Pooling layer and
+// IS a PoolingLayer (q unchanged: global, average), so that whatever looks at a "Pooling" layer's parameters finds them.
+// bottoms: the squeezed blob, the gated blob (two tops of one Split), then the shortcut if an Eltwise SUM was absorbed.
+//
+// The saving grows with the plane (two passes over n x C x HW floats) and the excite kernel's cost with n x C x R, where the dense layers
+// of the block as written run on the GEMM: measured, the collapsed form loses where the hidden width is large against
+// the plane (2048 x 7 x 7 with R = 128, 1152 x 7 x 7 with R = 48).  So the layer keeps the block's own layers in `parts` and, where
+// 2 R > HW at Reshape, runs them one after the other as they were written (`stepwise`): the parent's pooling, dense layers, add and ReLU
+// and the gate's multiply.  The blobs inside the block refuse Extract either way.
+struct GateBlockLayer : PoolingLayer
+{
+    int C = 0, R = 0, mact = FHIP_EXCITE_MACT_NONE, gact = FHIP_EXCITE_GACT_SIGMOID, act = FHIP_GATE_ACT_NONE;
+    float alpha = 0.2f, beta = 0.5f;
+    bool has_b1 = false, has_b2 = false, inited = false, stepwise = false;
+    std::vector<float> w1, b1, w2, b2;
+    DeviceVec d_w1, d_b1, d_w2, d_b2, mean, gate;
+    size_t scratch_bytes = 0;
+    std::vector<std::unique_ptr<Layer>> parts; // the block's layers in the order of the list
+
+    int Reshape() override
+    {
+        const Blob* x = bottoms[0];
+        const Blob* y = bottoms[1];
+        if (x->c != C) return failf(NET_E_TOPOLOGY, "squeeze-and-excitation block %s has %d channels while bottom blob %s has %d", name.c_str(), C, x->name.c_str(), x->c);
+        for (size_t i = 1; i < bottoms.size(); ++i)
+            if (bottoms[i]->n != x->n || bottoms[i]->c != x->c || bottoms[i]->h != x->h || bottoms[i]->w != x->w)
+                return failf(NET_E_SHAPE, "Shape mismatch among bottoms of layer %s.", name.c_str());
+        stepwise = 2ll * R > (long long)x->h * x->w;
+        if (stepwise)
+        {
+            scratch_bytes = 0;
+            for (auto& l : parts)
+            {
+                const int rc = l->Reshape();
+                if (rc) return rc;
+                scratch_bytes = std::max(scratch_bytes, l->arena_bytes());
+            }
+            return 0;
+        }
+        const GateApi* api = gate_api();
+        if (!api) return FHIP_E_UNSUPPORTED; // message set by gate_api
+        int rc = api->squeeze_buffer_size(x->n, x->c, x->h, x->w, &scratch_bytes);
+        if (rc) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+        if ((rc = mean.resize((size_t)x->n * C * sizeof(float))) || (rc = gate.resize((size_t)x->n * C * sizeof(float)))) return rc;
+        return tops[0]->reshape(y->n, y->c, y->h, y->w);
+    }
+    int Init(hipStream_t s) override
+    {
+        if (stepwise)
+        {
+            for (auto& l : parts)
+            {
+                const int rc = l->Init(s);
+                if (rc) return rc;
+            }
+            return 0;
+        }
+        if (inited) return 0;
+        int rc;
+        if ((rc = d_w1.upload(w1.data(), w1.size(), s)) || (rc = d_w2.upload(w2.data(), w2.size(), s))) return rc;
+        if (has_b1 && (rc = d_b1.upload(b1.data(), b1.size(), s))) return rc;
+        if (has_b2 && (rc = d_b2.upload(b2.data(), b2.size(), s))) return rc;
+        FHIP_CHECK_HIP(hipStreamSynchronize(s));
+        inited = true;
+        return 0;
+    }
+    int Forward(hipStream_t s) override
+    {
+        if (stepwise)
+        {
+            for (auto& l : parts)
+            {
+                const int rc = l->Forward(s);
+                if (rc) return rc;
+            }
+            return 0;
+        }
+        const GateApi* api = gate_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const Blob* x = bottoms[0];
+        int rc = api->squeeze(x->n, x->c, x->h, x->w, mean.d, x->data, scratch_bytes ? net->arena.d : nullptr, s);
+        if (!rc) rc = api->excite(x->n, C, R, gate.d, mean.d, d_w1.d, has_b1 ? d_b1.d : nullptr, d_w2.d, has_b2 ? d_b2.d : nullptr, mact, gact, alpha, beta, s);
+        if (!rc) rc = api->apply(x->n, x->c, x->h, x->w, tops[0]->data, bottoms[1]->data, gate.d, bottoms.size() > 2 ? bottoms[2]->data : nullptr, act, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    size_t weight_bytes() const override
+    {
+        size_t b = d_w1.bytes + d_b1.bytes + d_w2.bytes + d_b2.bytes;
+        if (stepwise)
+            for (auto& l : parts) b += l->weight_bytes();
+        return b;
+    }
+    size_t arena_bytes() const override { return scratch_bytes; }
+    int algo() const override { return FHIP_NET_ROUTE_GATE; }
 };
 
 int ConvLayer::Fuse(Layer* next, int level)
@@ -1627,7 +1864,7 @@ int ConvLayer::Fuse(Layer* next, int level)
     {
         AffineLayer* nx = static_cast<AffineLayer*>(next);
         const int K = atrous ? p.output_channels : p.group == p.input_channels ? p.input_channels : p.output_channels;
-        if (nx->channels != K || nx->relu) return 0;
+        if (nx->gated || nx->channels != K || nx->relu) return 0;
         if (post_mul.empty())
         {
             post_mul.assign(K, 1.f);
@@ -1772,7 +2009,7 @@ int DeconvLayer::Fuse(Layer* next, int level)
     {
         AffineLayer* nx = static_cast<AffineLayer*>(next);
         const int K = p.output_channels;
-        if (nx->channels != K || nx->relu) return 0;
+        if (nx->gated || nx->channels != K || nx->relu) return 0;
         if (post_mul.empty())
         {
             post_mul.assign(K, 1.f);
@@ -2147,6 +2384,144 @@ struct DropoutLayer : Layer
     }
 };
 
+// Fusion level 2: a squeeze-and-excitation block,
+//
+//   Split(x) -> Pooling(global, average) -> {InnerProduct | Convolution 1x1, group 1} -> [ReLU | Swish]
+//            -> {InnerProduct | Convolution 1x1, group 1} -> {Sigmoid | HardSigmoid}
+//            -> {BinaryOp mul | Scale -233}(x, gate)   [-> Eltwise SUM with another blob [-> plain ReLU]]
+//
+// where every linking blob has exactly one consumer, becomes one GateBlockLayer.  The pass runs BEFORE the pairwise Fuse pass of
+// fuse_layers: afterwards the first excite layer would already have absorbed its ReLU and the block would no longer read as written.
+// The layer keeps the Pooling layer's type and name and takes the place of the block's LAST layer in the list: the shortcut of a residual
+// block may be produced between the Pooling layer and the Eltwise layer, and everything the block reads is ready where its last layer
+// stood.  A block that does not match (a linking blob with a second consumer, a grouped, strided or padded excite convolution, a pooling
+// that is not global average, operands that are not two tops of one Split) stays layer by layer.
+static void collapse_gate_blocks(Net& net)
+{
+    auto sole_consumer = [&](const Blob* b) -> int { // index of the only layer that reads b (once), or -1
+        int uses = 0, at = -1;
+        for (size_t j = 0; j < net.layers.size(); ++j)
+            for (const Blob* x : net.layers[j]->bottoms)
+                if (x == b)
+                {
+                    ++uses;
+                    at = (int)j;
+                }
+        return uses == 1 ? at : -1;
+    };
+    auto one_to_one = [](const Layer* l) { return l->bottoms.size() == 1 && l->tops.size() == 1; };
+    // W [out][in] and bias of an InnerProduct or of a plain 1x1 convolution
+    auto dense = [&](Layer* l, int& in, int& out, std::vector<float>& w, std::vector<float>& b, bool& has_b) {
+        if (!one_to_one(l)) return false;
+        if (l->type == "InnerProduct")
+        {
+            InnerProductLayer* ip = static_cast<InnerProductLayer*>(l);
+            if (ip->p.activation != FHIP_ACT_NONE || ip->w_host.size() != ip->input_size * ip->output_size) return false;
+            in = (int)ip->input_size, out = (int)ip->output_size, w = ip->w_host, b = ip->b_host, has_b = ip->p.bias_term != 0;
+            return true;
+        }
+        if (l->type != "Convolution") return false;
+        ConvLayer* cv = static_cast<ConvLayer*>(l);
+        const fhip_conv_param& p = cv->p;
+        if (cv->gconv || cv->atrous || p.group != 1 || p.kernel_h != 1 || p.kernel_w != 1 || p.stride_h != 1 || p.stride_w != 1 || p.pad_left || p.pad_right ||
+            p.pad_top || p.pad_bottom || p.activation != FHIP_ACT_NONE || !cv->post_mul.empty() || cv->w_host.size() != (size_t)p.input_channels * p.output_channels)
+            return false;
+        in = p.input_channels, out = p.output_channels, w = cv->w_host, b = cv->b_host, has_b = p.bias_term != 0;
+        return true;
+    };
+    for (size_t i = 0; i < net.layers.size(); ++i)
+    {
+        Layer* pool = net.layers[i].get();
+        if (pool->type != "Pooling" || !one_to_one(pool)) continue;
+        const fhip_pool_param& q = static_cast<PoolingLayer*>(pool)->q;
+        if (!q.global_pooling || q.pooling_type == 0) continue;
+        std::vector<int> gone(1, (int)i);
+        std::vector<Blob*> inner;
+        std::unique_ptr<GateBlockLayer> blk(new GateBlockLayer);
+        auto step = [&](Blob* top) -> Layer* { // the layer behind a linking blob
+            const int j = sole_consumer(top);
+            if (j < 0) return nullptr;
+            gone.push_back(j);
+            inner.push_back(top);
+            return net.layers[j].get();
+        };
+        Layer* l = step(pool->tops[0]);
+        int in2 = 0, out2 = 0;
+        if (!l || !dense(l, blk->C, blk->R, blk->w1, blk->b1, blk->has_b1)) continue;
+        if (!(l = step(l->tops[0]))) continue;
+        if (one_to_one(l) && (is_plain_relu(l) || l->type == "Swish"))
+        {
+            blk->mact = l->type == "Swish" ? FHIP_EXCITE_MACT_SWISH : FHIP_EXCITE_MACT_RELU;
+            if (!(l = step(l->tops[0]))) continue;
+        }
+        if (!dense(l, in2, out2, blk->w2, blk->b2, blk->has_b2) || in2 != blk->R || out2 != blk->C) continue;
+        if (!(l = step(l->tops[0])) || !one_to_one(l)) continue;
+        if (l->type == "HardSigmoid")
+        {
+            blk->gact = FHIP_EXCITE_GACT_HARDSIGMOID;
+            blk->alpha = static_cast<GateActivationLayer*>(l)->alpha;
+            blk->beta = static_cast<GateActivationLayer*>(l)->beta;
+        }
+        else if (l->type != "Sigmoid")
+            continue;
+        Blob* g = l->tops[0];
+        if (!(l = step(g)) || l->bottoms.size() != 2 || l->tops.size() != 1) continue;
+        Blob* x = nullptr;
+        if (l->type == "BinaryOp")
+            x = l->bottoms[0] == g ? l->bottoms[1] : l->bottoms[0];
+        else if (l->type == "Scale" && static_cast<ScaleLayer*>(l)->gated && l->bottoms[1] == g)
+            x = l->bottoms[0];
+        if (!x || x == g || x == pool->bottoms[0]) continue;
+        bool siblings = false; // the squeezed and the gated blob are two tops of one Split: the same tensor
+        for (auto& s : net.layers)
+            if (s->type == "Split")
+            {
+                bool a = false, b = false;
+                for (const Blob* t : s->tops) a = a || t == pool->bottoms[0], b = b || t == x;
+                siblings = siblings || (a && b);
+            }
+        if (!siblings) continue;
+        blk->bottoms.push_back(pool->bottoms[0]);
+        blk->bottoms.push_back(x);
+        Blob* out = l->tops[0];
+        const int jsum = sole_consumer(out);
+        if (jsum >= 0)
+        {
+            Layer* sum = net.layers[jsum].get();
+            if (sum->type == "Eltwise" && sum->bottoms.size() == 2 && sum->tops.size() == 1 && sum->bottoms[0] != sum->bottoms[1])
+            {
+                blk->bottoms.push_back(sum->bottoms[0] == out ? sum->bottoms[1] : sum->bottoms[0]);
+                gone.push_back(jsum);
+                inner.push_back(out);
+                out = sum->tops[0];
+                const int jrelu = sole_consumer(out);
+                if (static_cast<EltwiseLayer*>(sum)->relu)
+                    blk->act = FHIP_GATE_ACT_RELU;
+                else if (jrelu >= 0 && one_to_one(net.layers[jrelu].get()) && is_plain_relu(net.layers[jrelu].get()))
+                {
+                    blk->act = FHIP_GATE_ACT_RELU;
+                    gone.push_back(jrelu);
+                    inner.push_back(out);
+                    out = net.layers[jrelu]->tops[0];
+                }
+            }
+        }
+        bool forward = true; // the chain runs down the list
+        for (size_t k = 1; k < gone.size(); ++k) forward = forward && gone[k] > gone[k - 1];
+        if (!forward) continue;
+        blk->type = pool->type;
+        blk->name = pool->name;
+        blk->net = &net;
+        blk->q = q;
+        blk->tops.assign(1, out);
+        for (Blob* b : inner) b->fused_away = true;
+        for (int j : gone) blk->parts.push_back(std::move(net.layers[j])); // kept for the shapes that run stepwise
+        net.layers[gone.back()] = std::move(blk);
+        for (size_t k = gone.size() - 1; k-- > 0;) net.layers.erase(net.layers.begin() + gone[k]);
+        --i; // the layer that moved into slot i has not been looked at
+    }
+}
+
 static Layer* create_layer(const std::string& type) // layer_factory.cpp:55-67
 {
     if (type == "Input") return new InputLayer;
@@ -2165,6 +2540,8 @@ static Layer* create_layer(const std::string& type) // layer_factory.cpp:55-67
     if (type == "Eltwise") return new EltwiseLayer;
     if (type == "Concat") return new ConcatLayer;
     if (type == "ShuffleChannel" || type == "Slice") return new ChannelMapLayer;
+    if (type == "BinaryOp") return new BinaryOpLayer;
+    if (type == "Swish" || type == "HardSigmoid") return new GateActivationLayer;
     return nullptr;
 }
 
@@ -2280,6 +2657,7 @@ static void fuse_layers(Net& net)
     net.fused = true;
     if (net.fusion <= 0) return;
     if (net.fusion >= 2) collapse_channel_maps(net);
+    if (net.fusion >= 2) collapse_gate_blocks(net);
     for (size_t i = 0; i < net.layers.size(); ++i)
     {
         for (;;)
@@ -2563,7 +2941,8 @@ static int prepare(Net& net)
         for (auto& l : net.layers) needs = needs || (l->type != "Input" && l->type != "ReLU" && l->type != "Pooling" && l->type != "Softmax" &&
                                                      l->type != "Split" && l->type != "Eltwise" && l->type != "Concat" && l->type != "Dropout" &&
                                                      l->type != "Sigmoid" && l->type != "TanH" && l->type != "Clip" && l->type != "ShuffleChannel" &&
-                                                     l->type != "Slice");
+                                                     l->type != "Slice" && l->type != "BinaryOp" && l->type != "Swish" && l->type != "HardSigmoid" &&
+                                                     !(l->type == "Scale" && static_cast<ScaleLayer*>(l.get())->gated));
         if (needs) return failf(NET_E_IO, "weights have not been loaded");
     }
     fuse_layers(net);

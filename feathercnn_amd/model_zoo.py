@@ -55,7 +55,7 @@ class GraphBuilder:
     def input(self, name, c, h, w):
         return self.layer("Input", name, [], [name], {0: w, 1: h, 2: c})
 
-    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None, dilation=1):
+    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None, dilation=1, gain=1.0):
         fan_in = cin // group * k * k
         wsize = cout * (cin // group) * k * k
         type_ = type_ or ("ConvolutionDepthWise" if group > 1 else "Convolution")  # what ncnn's converter writes; both load alike
@@ -63,7 +63,7 @@ class GraphBuilder:
         if dilation != 1:  # ncnn's id 2 (written only when set); a net that holds one needs Net.SetDilated(True)
             params = {0: cout, 1: k, 2: dilation, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group}
         top = self.layer(type_, name, [bottom], [top or name], params)
-        self._tagged(self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in)))
+        self._tagged(self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in) * gain))
         if bias:
             self._raw(self._uniform(cout, -0.1, 0.1))
         return top
@@ -129,9 +129,9 @@ class GraphBuilder:
     def pool(self, name, bottom, k=2, s=2, p=0, avg=False, global_=False):
         return self.layer("Pooling", name, [bottom], [name], {0: int(avg), 1: k, 2: s, 3: p, 4: int(global_)})
 
-    def fc(self, name, bottom, cin, cout, bias=True):
+    def fc(self, name, bottom, cin, cout, bias=True, gain=1.0):
         top = self.layer("InnerProduct", name, [bottom], [name], {0: cout, 1: int(bias), 2: cin * cout})
-        self._tagged(self._uniform(cin * cout, -1, 1, np.sqrt(6.0 / cin)))
+        self._tagged(self._uniform(cin * cout, -1, 1, np.sqrt(6.0 / cin) * gain))
         if bias:
             self._raw(self._uniform(cout, -0.1, 0.1))
         return top
@@ -171,6 +171,48 @@ class GraphBuilder:
         tops = [f"{name}_{i}" for i in range(len(sizes))]
         self.layer("Slice", name, [bottom], tops, {-23300: ",".join(map(str, [len(sizes)] + list(sizes))), 1: 0})
         return tops
+
+    def swish(self, name, bottom):
+        """ncnn's Swish: y = x / (1 + exp(-x)), no params."""
+        return self.layer("Swish", name, [bottom], [name])
+
+    def hard_sigmoid(self, name, bottom, alpha=0.2, beta=0.5):
+        """ncnn's HardSigmoid: y = min(max(alpha * x + beta, 0), 1); 0=alpha, 1=beta."""
+        return self.layer("HardSigmoid", name, [bottom], [name], {0: f"{alpha:.6f}", 1: f"{beta:.6f}"})
+
+    def binary_mul(self, name, a, b):
+        """ncnn's BinaryOp 0=2 (mul) with two bottoms: a tensor and a [c][1][1] gate, in either order (the converters' SE multiply)."""
+        return self.layer("BinaryOp", name, [a, b], [name], {0: 2})
+
+    def scale_by(self, name, bottom, gate):
+        """ncnn's Scale 0=-233 with two bottoms: the scale comes from the second one (Caffe's two-bottom Scale, SENet's multiply)."""
+        return self.layer("Scale", name, [bottom, gate], [name], {0: -233})
+
+    def se_block(self, name, bottom, c, r, spelling="caffe", mact="relu", gact="sigmoid", alpha=0.2, beta=0.5, gate_first=False, gain=1.0):
+        """A squeeze-and-excitation block on `bottom` ([c] channels, reduction to r): Split, global average Pooling, two dense layers with
+        `mact` ("relu", "swish" or None) between them, `gact` ("sigmoid" or "hard_sigmoid"), and the multiply.  spelling "caffe":
+        InnerProduct layers and Scale 0=-233 (SENet as published); "converter": 1x1 Convolution layers and BinaryOp mul (what ncnn's
+        converters write for EfficientNet and RegNetY).  gate_first puts the gate first among BinaryOp's bottoms.  `gain` scales the first dense layer's
+        weights: the gate's logits scale with the squeezed activations, and a net whose activations grow with depth passes the inverse of
+        that growth, so that the logits stay of order one as in a trained net and the gate does not saturate.  Returns the gated top."""
+        keep, sq = self.split(name + "_split", bottom)
+        g = self.pool(name + "_gap", sq, 1, 1, avg=True, global_=True)
+        dense = (lambda nm, x, i, o, gain=1.0: self.fc(nm, x, i, o, gain=gain)) if spelling == "caffe" else \
+                (lambda nm, x, i, o, gain=1.0: self.conv(nm, x, i, o, 1, type_="Convolution", gain=gain))
+        g = dense(name + ("_fc1" if spelling == "caffe" else "_conv1"), g, c, r, gain)
+        if mact == "relu":
+            g = self.relu(name + "_relu", g)
+        elif mact == "swish":
+            g = self.swish(name + "_swish", g)
+        g = dense(name + ("_fc2" if spelling == "caffe" else "_conv2"), g, r, c)
+        g = self.sigmoid(name + "_sigmoid", g) if gact == "sigmoid" else self.hard_sigmoid(name + "_hsigmoid", g, alpha, beta)
+        if spelling == "caffe":
+            return self.scale_by(name + "_scale", keep, g)
+        return self.binary_mul(name + "_mul", g, keep) if gate_first else self.binary_mul(name + "_mul", keep, g)
+
+    def conv_bn_swish(self, name, bottom, cin, cout, k, s=1, p=0, group=1, swish=True):
+        x = self.conv_bn_relu(name, bottom, cin, cout, k, s, p, group, relu=False)
+        return self.swish(name + "_swish", x) if swish else x
 
     def dropout(self, name, bottom, scale=None):
         return self.layer("Dropout", name, [bottom], [name], {} if scale is None else {0: f"{scale:.6f}"})
@@ -620,6 +662,94 @@ def deeplab_v2_aspp(seed=1234, classes=21, size=321, dry=False):
     return g.finish() + ("data", "fc8_sum")
 
 
+def tiny_se(seed=29, size=24, dry=False):
+    """A small net of squeeze-and-excitation blocks in every form the Net runtime has to get right, nothing above 24 px: block `a` in
+    Caffe's spelling (InnerProduct, ReLU, Sigmoid, Scale 0=-233; R = 4) inside a residual unit, followed by Eltwise + ReLU; block `b` in
+    the converters' spelling (1x1 Convolution, Swish, Sigmoid, BinaryOp mul; C = 24, R = 6, no multiple of 4) on a 12 x 12 plane behind a
+    Swish; block `c` with no activation between its 1x1 convolutions, a HardSigmoid gate and the gate first among BinaryOp's bottoms, on
+    an odd 5 x 5 plane (R = 5), followed by nothing; block `d` whose gate blob is also read by a classifier of its own (`aux`), so that
+    fusion level 2 must leave it layer by layer."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.relu("relu1", g.conv("conv1", x, 3, 16, 3, 1, 1))
+    short, y = g.split("res_split", x)
+    y = g.conv_bn_relu("conv2", y, 16, 16, 3, 1, 1, relu=False)
+    y = g.se_block("a", y, 16, 4, "caffe")
+    x = g.relu("res_relu", g.eltwise("res", short, y))
+    x = g.conv_bn_swish("conv3", x, 16, 24, 3, 2, 1)                                   # 12 x 12, Swish as a layer of its own
+    x = g.se_block("b", x, 24, 6, "converter", mact="swish")
+    x = g.relu("relu4", g.conv("conv4", x, 24, 20, 3, 2, 0))                            # 5 x 5
+    x = g.se_block("c", x, 20, 5, "converter", mact=None, gact="hard_sigmoid", alpha=1.0 / 6, beta=0.5, gate_first=True)
+    keep, sq = g.split("d_split", x)
+    gate = g.sigmoid("d_sigmoid", g.conv("d_conv2", g.relu("d_relu", g.conv("d_conv1", g.pool("d_gap", sq, 1, 1, avg=True, global_=True), 20, 5, 1)), 5, 20, 1))
+    g0, g1 = g.split("d_gate_split", gate)
+    x = g.scale_by("d_scale", keep, g0)
+    g.fc("aux", g1, 20, 4)                                                              # the gate's second consumer
+    x = g.pool("gap", x, 1, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc", x, 20, 10))
+    return g.finish() + ("data", "prob")
+
+
+def se_resnet50(seed=1234, classes=1000, size=224, dry=False):
+    """SE-ResNet-50 (Hu et al.) in Caffe's spelling: `resnet50` with a squeeze-and-excitation block (InnerProduct, ReLU, InnerProduct,
+    Sigmoid, Scale 0=-233; reduction 16) behind the last 1x1 of every bottleneck, then the residual Eltwise and its ReLU.  With these random
+    weights every residual sum about doubles the variance of the activations; a ReLU net does not mind, but the gate's logits would reach
+    several hundred by the last stage, where a Sigmoid turns the fp32 rounding of its input (1e-6 of several hundred) into a gate error of
+    1e-3.  So the first excite layer of unit k is scaled by 2^(-k/2) and the logits stay of order one, as in the published net."""
+    g = GraphBuilder(seed, dry)
+    unit = 0
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_relu("conv1", x, 3, 64, 7, 2, 3)
+    x = g.pool("pool1", x, 3, 2)
+    cin = 64
+    for si, (mid, out, blocks, stride) in enumerate([(64, 256, 3, 1), (128, 512, 4, 2), (256, 1024, 6, 2), (512, 2048, 3, 2)]):
+        for b in range(blocks):
+            s = stride if b == 0 else 1
+            tag = f"res{si + 2}{chr(ord('a') + b)}"
+            main, short = g.split(tag + "_split", x)
+            if b == 0:
+                short = g.conv_bn_relu(tag + "_branch1", short, cin, out, 1, s, 0, relu=False)
+            y = g.conv_bn_relu(tag + "_branch2a", main, cin, mid, 1, s, 0)
+            y = g.conv_bn_relu(tag + "_branch2b", y, mid, mid, 3, 1, 1)
+            y = g.conv_bn_relu(tag + "_branch2c", y, mid, out, 1, 1, 0, relu=False)
+            y = g.se_block(tag + "_se", y, out, out // 16, "caffe", gain=2.0 ** (-0.5 * unit))
+            unit += 1
+            x = g.relu(tag + "_relu", g.eltwise(tag, short, y))
+            cin = out
+    x = g.pool("pool5", x, 7, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc1000", x, 2048, classes))
+    return g.finish() + ("data", "prob")
+
+
+def efficientnet_b0(seed=1234, classes=1000, size=224, dry=False):
+    """EfficientNet-B0 (Tan & Le) in the converters' spelling: MBConv units of a 1x1 expansion, a 3x3 or 5x5 depthwise convolution, a
+    squeeze-and-excitation block (1x1 Convolution, Swish, 1x1 Convolution, Sigmoid, BinaryOp mul; reduction to a quarter of the unit's
+    input channels) and a 1x1 projection, Swish everywhere else, a residual Eltwise where the unit keeps its shape.  BatchNorm + Scale
+    behind every convolution outside the SE blocks, as in the other zoo nets."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_swish("stem", x, 3, 32, 3, 2, 1)
+    cin, unit = 32, 0
+    for expand, k, stride, cout, repeats in [(1, 3, 1, 16, 1), (6, 3, 2, 24, 2), (6, 5, 2, 40, 2), (6, 3, 2, 80, 3), (6, 5, 1, 112, 3), (6, 5, 2, 192, 4),
+                                             (6, 3, 1, 320, 1)]:
+        for rep in range(repeats):
+            unit += 1
+            tag, s, mid = f"mb{unit}", (stride if rep == 0 else 1), cin * expand
+            residual = s == 1 and cin == cout
+            if residual:
+                x, short = g.split(tag + "_split", x)
+            y = g.conv_bn_swish(tag + "_expand", x, cin, mid, 1) if expand != 1 else x
+            y = g.conv_bn_swish(tag + "_dw", y, mid, mid, k, s, k // 2, group=mid)
+            y = g.se_block(tag + "_se", y, mid, max(1, cin // 4), "converter", mact="swish")
+            y = g.conv_bn_swish(tag + "_project", y, mid, cout, 1, swish=False)
+            x = g.eltwise(tag + "_add", short, y) if residual else y
+            cin = cout
+    x = g.conv_bn_swish("head", x, cin, 1280, 1)
+    x = g.pool("gap", x, 1, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc", x, 1280, classes))
+    return g.finish() + ("data", "prob")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
@@ -627,7 +757,8 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_deconv": tiny_deconv, "style_transfer": style_transfer, "unet_k4": unet_k4,
           "tiny_generative": tiny_generative, "style_transfer_in": style_transfer_in, "pix2pix_unet": pix2pix_unet,
           "tiny_shuffle": tiny_shuffle, "shufflenet_v2_x1_0": shufflenet_v2_x1_0, "shufflenet_v1_g3": shufflenet_v1_g3,
-          "tiny_dilated": tiny_dilated, "deeplab_largefov": deeplab_largefov, "deeplab_v2_aspp": deeplab_v2_aspp}
+          "tiny_dilated": tiny_dilated, "deeplab_largefov": deeplab_largefov, "deeplab_v2_aspp": deeplab_v2_aspp,
+          "tiny_se": tiny_se, "se_resnet50": se_resnet50, "efficientnet_b0": efficientnet_b0}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -635,3 +766,7 @@ DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_
 DILATED_LAYERS = {"tiny_dilated": ("a1", "a2", "a3", "a_dw", "a_g", "a_far"),
                   "deeplab_largefov": ("conv5_1", "conv5_2", "conv5_3", "fc6"),
                   "deeplab_v2_aspp": ("conv5_1", "conv5_2", "conv5_3", "fc6_1", "fc6_2", "fc6_3", "fc6_4")}
+
+# the squeeze-and-excitation blocks of each net (the name fusion level 2 keeps: the block's Pooling layer) that collapse into one layer,
+# and those that must not
+SE_BLOCKS = {"tiny_se": (("a_gap", "b_gap", "c_gap"), ("d_gap",))}

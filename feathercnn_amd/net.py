@@ -23,6 +23,8 @@ ROUTE_SHUFFLE = 103  # FHIP_NET_ROUTE_SHUFFLE: a ShuffleChannel / Slice layer or
 ROUTE_NAMES[ROUTE_SHUFFLE] = "SHUFFLE"
 ROUTE_ATROUS = 104  # FHIP_NET_ROUTE_ATROUS: a Convolution layer with dilation > 1, after SetDilated(True) (libfeather_atrous.so)
 ROUTE_NAMES[ROUTE_ATROUS] = "ATROUS"
+ROUTE_GATE = 105  # FHIP_NET_ROUTE_GATE: a two-bottom BinaryOp mul / Scale -233, Swish, HardSigmoid, or a collapsed SE block (libfeather_gate.so)
+ROUTE_NAMES[ROUTE_GATE] = "GATE"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,

@@ -25,7 +25,11 @@
 //   * Forward only enqueues work on the net's HIP stream (SetStream); ExtractHost / Synchronize wait for it;
 //   * SetFusion: 0 = none (what the reference actually does: TryFuse is never called),
 //     1 = the reference's declared Conv-ReLU / BN-Scale-ReLU / InnerProduct-ReLU patterns (default), 2 = also fold
-//     BatchNorm/Scale into the preceding convolution's weights.
+//     BatchNorm/Scale into the preceding convolution's weights, and run a squeeze-and-excitation block (global average Pooling, two
+//     InnerProduct / 1x1 Convolution layers, Sigmoid / HardSigmoid, BinaryOp mul or two-bottom Scale, the residual Eltwise and its ReLU)
+//     as one layer of libfeather_gate.so (FHIP_NET_ROUTE_GATE, feather_net.h);
+//   * layer types beyond the reference's factory are loaded too: see feather_net.h's route codes (BinaryOp mul, Scale 0=-233, Swish and
+//     HardSigmoid are the newest).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 

@@ -228,7 +228,8 @@ FHIP_API int fhip_net_get_stream(fhip_net* net, void** stream);
  *      BatchNorm+Scale(+ReLU), Scale+ReLU, Eltwise+ReLU.
  *   2: + BatchNorm / Scale folded into the convolution before them, Conv + 2x2 max pooling, Conv + Eltwise SUM (+ReLU), a 3x3
  *      depthwise layer + the 1x1 convolution behind it as one layer (fhip_conv_forward_dw_pw where the pair qualifies), and two 1x1
- *      convolutions of the same input that follow each other as one GEMM (fhip_conv_forward_siblings; both blobs keep their storage).
+ *      convolutions of the same input that follow each other as one GEMM (fhip_conv_forward_siblings; both blobs keep their storage);
+ *      a squeeze-and-excitation block as one layer (FHIP_NET_ROUTE_GATE).
  *   3: + runs of Winograd layers chained (fhip_conv_forward_chained): the blob between two chained layers has a shape but no storage;
  *      a first layer (3x3 / stride 1 / pad 1, 2 .. 4 input channels) in front of a Winograd layer is computed inside that layer's input
  *      transform (fhip_winograd_f63_input_from_first): its top has no storage either.
@@ -330,6 +331,14 @@ FHIP_API int fhip_net_layer_count(fhip_net* net);
  * 1 < group < C goes there, not to libfeather_gconv.so).  It fuses a following ReLU and, at fusion level 2, BatchNorm / Scale; no other
  * fusion takes it.  Reported from LoadParam on. */
 #define FHIP_NET_ROUTE_ATROUS 104
+/* Route code of the squeeze-and-excitation layers: a `BinaryOp 0=2` or a `Scale 0=-233` with two bottoms of shapes [n][c][h][w] and
+ * [n][c][1][1] (the channel gate), Swish and HardSigmoid.  They run through libfeather_gate.so (feather_gate.h), opened the same way the
+ * first time a net holds such a layer.  At fusion level 2 a whole block -- Split -> global average Pooling -> {InnerProduct | 1x1
+ * Convolution} -> [ReLU | Swish] -> {InnerProduct | 1x1 Convolution} -> {Sigmoid | HardSigmoid} -> the multiply [-> Eltwise SUM [-> ReLU]],
+ * linked by blobs with one consumer each -- is one layer with this route: squeeze, excite and apply, three launches.  It keeps the type
+ * and name of the block's Pooling layer and stands where the block's last layer stood; the blobs between them cannot be extracted.  The
+ * pass runs before the pairwise fusions, so the excite layers are matched as written.  Reported from LoadParam on. */
+#define FHIP_NET_ROUTE_GATE 105
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
  * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);

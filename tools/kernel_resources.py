@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/kernel_resources.py <file.hip> [name filter] [extra hipcc flags...] -- VGPRs / scratch / occupancy / LDS of every kernel of a
 translation unit (hipcc -Rpass-analysis=kernel-resource-usage; cross-compiles, no GPU needed).  <file.hip> may lie in any of the source
-directories (feathercnn_amd/csrc, csrc_pixout, csrc_gconv, csrc_deconv, csrc_inorm, csrc_shuffle, csrc_canvas, csrc_atrous): headers of feathercnn_amd/csrc (gemm_core.h) are on the include path."""
+directories (feathercnn_amd/csrc, csrc_pixout, csrc_gconv, csrc_deconv, csrc_inorm, csrc_shuffle, csrc_canvas, csrc_atrous, csrc_gate): headers of feathercnn_amd/csrc (gemm_core.h) are on the include path."""
 import os
 import re
 import subprocess
