@@ -16,10 +16,13 @@
 //   * optional hipGraph replay of the whole forward.
 #include <ctype.h>
 #include <dlfcn.h>
+#include <errno.h>
 #include <float.h>
+#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -486,11 +489,15 @@ struct ParamDict
     int parse(const std::string& tok)
     {
         const size_t eq = tok.find('=');
-        int id = atoi(tok.substr(0, eq).c_str());
+        // a file may hold any digits: the id is read wide, and its range is checked before any arithmetic on it
+        errno = 0;
+        const long long raw_id = strtoll(tok.substr(0, eq).c_str(), nullptr, 10);
         const std::string val = tok.substr(eq + 1);
-        const bool is_array = id <= -23300;
-        if (is_array) id = -id - 23300;
-        if (id < 0 || id >= kMax) return failf(FHIP_E_BADARG, "param id %d out of range", id);
+        const bool is_array = raw_id <= -23300;
+        if (errno == ERANGE || raw_id <= -23300 - kMax || raw_id >= kMax || (raw_id < 0 && !is_array))
+            return failf(FHIP_E_BADARG, "param id %.24s out of range", tok.c_str());
+        const long long wide_id = is_array ? -raw_id - 23300 : raw_id;
+        const int id = (int)wide_id;
         if (is_array)
         {
             std::vector<std::string> parts;
@@ -503,13 +510,13 @@ struct ParamDict
                 a = b + 1;
             }
             const int len = atoi(parts[0].c_str());
-            if (len < 0 || (int)parts.size() != len + 1) return failf(FHIP_E_BADARG, "ParamDict read array element fail");
+            if (len < 0 || parts.size() != (size_t)len + 1) return failf(NET_E_IO, "ParamDict read array element fail"); // paramdict.cpp:124-128
             e[id].array.resize(len);
             for (int j = 0; j < len; ++j) e[id].array[j] = (float)atof(parts[j + 1].c_str());
         }
         else
         {
-            if (val.empty()) return failf(FHIP_E_BADARG, "ParamDict read value fail");
+            if (val.empty()) return failf(NET_E_IO, "ParamDict read value fail"); // paramdict.cpp:153-157
             if (is_float(val))
             {
                 const float f = (float)atof(val.c_str());
@@ -572,6 +579,13 @@ struct ModelBin
     // type 0: 4-byte tag then payload (raw fp32 / fp16 / 256-entry table); type 1: raw fp32 (modelbin.cpp:52-189)
     int load(size_t w, int type, std::vector<float>& out)
     {
+        // every payload form holds at least one byte per weight: a count the rest of the file cannot hold is refused before anything of
+        // that size is allocated (counts are products of file values: negative ones arrive here as huge ones)
+        if (w > (size_t)(end - p))
+        {
+            out.clear();
+            return failf(NET_E_SHAPE, "ModelBin read weight_data failed (file too short for %zu weights)", w);
+        }
         out.assign(w, 0.f);
         if (type == 1)
         {
@@ -898,10 +912,16 @@ struct ConvLayer : Layer
         p.activation = FHIP_ACT_NONE;
         const int weight_data_size = pd.get(6, 0);
         // conv_layer.h:69-75: output_channels is divided by group (AssignOutputDim restores it for depthwise)
-        if (p.group == 0 || p.output_channels % p.group) return failf(NET_E_SHAPE, "layer %s: output_channels is not divisible by its group", name.c_str());
+        if (p.group < 1 || p.output_channels % p.group) return failf(NET_E_SHAPE, "layer %s: output_channels is not divisible by its group", name.c_str());
         p.output_channels /= p.group;
         if (p.output_channels <= 0 || p.kernel_h <= 0 || p.kernel_w <= 0) return failf(NET_E_SHAPE, "layer %s: bad convolution geometry", name.c_str());
-        p.input_channels = weight_data_size / p.output_channels / p.kernel_h / p.kernel_w;
+        // the reference truncates here (conv_layer.h:75); a size that is no whole number of input channels would leave the weight stream
+        // out of step with the file for every later layer
+        long long per_channel = (long long)p.output_channels * p.kernel_h; // three ints: the product is taken in two steps, each below 2^62
+        if (per_channel <= INT_MAX) per_channel *= p.kernel_w;
+        if (weight_data_size < 0 || per_channel > INT_MAX || weight_data_size % per_channel)
+            return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the convolution geometry", name.c_str());
+        p.input_channels = (int)(weight_data_size / per_channel);
         gconv = !atrous && p.group > 1 && p.group < p.input_channels;
         if (gconv || atrous) p.output_channels *= p.group;
         if (atrous)
@@ -1259,7 +1279,9 @@ struct InnerProductLayer : Layer
         output_size = pd.get(0, 0);
         p.bias_term = pd.get(1, 0);
         weight_data_size = pd.get(2, 0);
-        if (output_size == 0) return failf(NET_E_SHAPE, "layer %s: num_output is 0", name.c_str());
+        if (pd.get(0, 0) < 1) return failf(NET_E_SHAPE, "layer %s: num_output must be positive", name.c_str());
+        if (pd.get(2, 0) < 0 || weight_data_size % output_size)
+            return failf(NET_E_SHAPE, "layer %s: weight_data_size is no whole number of rows of num_output", name.c_str());
         input_size = weight_data_size / output_size;
         p.input_channels = (int)input_size;
         p.output_channels = (int)output_size;
@@ -1599,6 +1621,7 @@ struct BatchNormLayer : AffineLayer
     {
         channels = pd.get(0, 0);
         eps = pd.get(1, 0.f);
+        if (channels < 0) return failf(NET_E_SHAPE, "layer %s: negative channel count", name.c_str());
         return 0;
     }
     int LoadWeights(ModelBin& mb) override // slope, mean, var, bias -> alpha/beta (batchnorm_layer.h:43-75)
@@ -1900,6 +1923,7 @@ struct DeconvLayer : Layer
     {
         const int dilation_w = pd.get(2, 1), dilation_h = pd.get(12, dilation_w);
         if (dilation_w > 1 || dilation_h > 1) return failf(NET_E_UNKNOWN_LAYER, "layer %s: dilated deconvolution is not supported", name.c_str());
+        if (dilation_w < 1 || dilation_h < 1) return failf(NET_E_SHAPE, "layer %s: dilation must be >= 1", name.c_str());
         if (pd.get(8, 0)) return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8 deconvolution is not supported", name.c_str());
         if (pd.get(20, 0) || pd.get(21, 0)) return failf(NET_E_UNKNOWN_LAYER, "layer %s: an explicit deconvolution output size is not supported", name.c_str());
         if (pd.get(9, 0)) return failf(NET_E_UNKNOWN_LAYER, "layer %s: a built-in activation (param 9) is not supported; use a ReLU layer", name.c_str());
@@ -1921,8 +1945,9 @@ struct DeconvLayer : Layer
         if (p.group < 1 || p.output_channels < 1 || p.output_channels % p.group)
             return failf(NET_E_SHAPE, "layer %s: output_channels is not divisible by its group", name.c_str());
         if (p.kernel_h <= 0 || p.kernel_w <= 0 || p.stride_h <= 0 || p.stride_w <= 0) return failf(NET_E_SHAPE, "layer %s: bad deconvolution geometry", name.c_str());
-        const long long per = (long long)p.output_channels * p.kernel_h * p.kernel_w;
-        if (weight_data_size <= 0 || ((long long)weight_data_size * p.group) % per)
+        long long per = (long long)p.output_channels * p.kernel_h; // three ints: the product is taken in two steps, each below 2^62
+        if (per <= INT_MAX) per *= p.kernel_w;
+        if (weight_data_size <= 0 || per > INT_MAX || ((long long)weight_data_size * p.group) % per)
             return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the deconvolution geometry", name.c_str());
         p.input_channels = (int)((long long)weight_data_size * p.group / per);
         if (p.input_channels % p.group) return failf(NET_E_SHAPE, "layer %s: input_channels is not divisible by its group", name.c_str());
@@ -2032,6 +2057,7 @@ struct EltwiseLayer : Layer
     {
         if (pd.has_array(1)) return failf(NET_E_SHAPE, "layer %s: coeffs in eltwise layer are not supported", name.c_str());
         if (pd.get(0, 0) != 1) return failf(NET_E_SHAPE, "layer %s: only eltwise SUM is supported", name.c_str());
+        if (bottoms.size() < 2) return failf(NET_E_TOPOLOGY, "layer %s: eltwise needs two bottoms", name.c_str());
         return 0;
     }
     int Reshape() override
@@ -2069,6 +2095,7 @@ struct ConcatLayer : Layer
     int LoadParam(const ParamDict& pd) override
     {
         axis = pd.get(0, 0);
+        if (axis != 0) return failf(NET_E_SHAPE, "layer %s: only concat at axis = 0 (channels) is supported", name.c_str()); // concat_layer.h:70-73, at Reshape there
         return 0;
     }
     int Reshape() override // concat_layer.h:50-80
@@ -2154,7 +2181,8 @@ struct ChannelMapLayer : Layer
             if (!pd.has_array(0)) return failf(NET_E_SHAPE, "layer %s: Slice needs its sizes (-23300=count,...)", name.c_str());
             for (float v : pd.e[0].array)
             {
-                if (v != (float)FHIP_SLICE_SHARE && !(v >= 1.f)) return failf(NET_E_SHAPE, "layer %s: a slice size must be positive or -233", name.c_str());
+                if (v != (float)FHIP_SLICE_SHARE && !(v >= 1.f && v <= 16777216.f)) // the floats that hold every integer: no cast of inf or 1e30 to int
+                    return failf(NET_E_SHAPE, "layer %s: a slice size must be positive or -233", name.c_str());
                 st.sizes.push_back((int)v);
             }
             if (st.sizes.size() != tops.size())
@@ -2585,6 +2613,9 @@ static int load_param_text(Net& net, const char* text, size_t len)
         layer->name = name;
         layer->net = &net;
         const int bottom_count = atoi(nb.c_str()), top_count = atoi(nt.c_str());
+        // the reference uses both counts as read (net.cpp:98-137) and a layer without bottoms or tops faults at its first Reshape
+        if (bottom_count < 0 || top_count < 1 || (bottom_count == 0 && type != "Input"))
+            return failf(NET_E_TOPOLOGY, "Topology error: layer %s type %s has %d bottoms and %d tops.", name.c_str(), type.c_str(), bottom_count, top_count);
         for (int j = 0; j < bottom_count; ++j)
         {
             std::string bn;

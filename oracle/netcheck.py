@@ -113,7 +113,10 @@ def parse_param(text: bytes):
         pd = {}
         while t < len(tok) and "=" in tok[t] and tok[t].split("=")[0].lstrip("-").isdigit():
             k, v = tok[t].split("=", 1)
-            pd[int(k)] = float(v) if ("." in v or "e" in v.lower()) else int(v)
+            if int(k) <= -23300:  # paramdict.cpp:131-158: "-233xx=len,v0,v1,..." is the array form of id xx
+                pd[-int(k) - 23300] = [float(e) if ("." in e or "e" in e.lower()) else int(e) for e in v.split(",")[1:]]
+            else:
+                pd[int(k)] = float(v) if ("." in v or "e" in v.lower()) else int(v)
             t += 1
         layers.append((type_, name, bottoms, tops, pd))
     return layers
@@ -168,13 +171,17 @@ class PortNet:
         self.layers = parse_param(param)
         mb = _Bin(weights)
         self.w = {}
-        for type_, name, _, _, pd in self.layers:
+        self.blocks = []  # (layer name, first byte, one past the last byte) of every layer that reads the .bin, in stream order
+        for type_, name, bottoms, _, pd in self.layers:
+            start = mb.o
             if type_ in ("Convolution", "ConvolutionDepthWise"):  # conv_layer.h:41-131
                 group, kw = pd.get(7, 1), pd.get(1, 0)
                 kh = pd.get(11, kw)
                 oc = pd.get(0, 0) // group
                 ic = pd.get(6, 0) // oc // kh // kw
                 k_out = ic if group == ic and group != 1 else oc
+                if 1 < group < ic or pd.get(2, 1) > 1 or pd.get(12, 1) > 1:  # the grouped and dilated routes (no reference counterpart): K biases
+                    k_out = pd.get(0, 0)
                 wgt = mb.load(ic * oc * kh * kw, True)
                 b = mb.load(k_out, False) if pd.get(5, 0) else None
                 self.w[name] = (wgt, b, ic, oc, group)
@@ -187,10 +194,21 @@ class PortNet:
                 slope, mean, var, bias = (mb.load(c, False) for _ in range(4))
                 sq = np.sqrt(var + np.float32(pd.get(1, 0.0)), dtype=np.float32)
                 self.w[name] = (slope / sq, bias - slope * mean / sq)  # beta, alpha
-            elif type_ == "Scale":  # scale_layer.h:45-69
+            elif type_ == "Scale" and not (pd.get(0, 0) == -233 and len(bottoms) == 2):  # scale_layer.h:45-69; a two-bottom Scale reads nothing
                 c = pd.get(0, 0)
                 s = mb.load(c, False)
                 self.w[name] = (s, mb.load(c, False) if pd.get(1, 0) else None)
+            # layer types the reference does not have (ncnn's definitions): read, so that the stream stays aligned, but not run
+            elif type_ in ("Deconvolution", "DeconvolutionDepthWise"):
+                wgt = mb.load(pd.get(6, 0), True)
+                self.w[name] = (wgt, mb.load(pd.get(0, 0), False) if pd.get(5, 0) else None)
+            elif type_ == "InstanceNorm" and pd.get(2, 1):
+                self.w[name] = (mb.load(pd.get(0, 0), False), mb.load(pd.get(0, 0), False))
+            elif type_ == "PReLU":
+                self.w[name] = (mb.load(pd.get(0, 0), False),)
+            if mb.o > start:
+                self.blocks.append((name, start, mb.o))
+        self.consumed = mb.o
 
     def run(self, input_name: str, x: np.ndarray, output_name: str, keep: bool = False):
         blobs = {input_name: np.ascontiguousarray(x, np.float32)}
