@@ -5,13 +5,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = None
-_PIXOUT = None
-_GCONV = None
-_DECONV = None
-_INORM = None
-_SHUFFLE = None
-_CANVAS = None
+_LOADED = {}  # path -> ctypes.CDLL with every symbol of its table typed
 
 STAGE_NAMES = ("wino_input", "wino_gemm", "wino_output", "igemm", "depthwise", "init", "wino_chain")
 
@@ -224,7 +218,6 @@ ATROUS_SIGNATURES = {
     "fhip_atrous_forward_route": (_I, [_AP, _I, _V, _V, _V, _V, _V, _V, ctypes.c_char_p]),
     "fhip_atrous_last_error": (ctypes.c_char_p, []),
 }
-_ATROUS = None
 
 # include/feather_hip/feather_gate.h -- libfeather_gate.so, squeeze-and-excitation channel gating, Swish, HardSigmoid (a library of its own)
 GATE_SIGNATURES = {
@@ -237,7 +230,25 @@ GATE_SIGNATURES = {
     "fhip_gate_route": (_I, [_I, _I, _I, _I, _I, _V, _V, _V, ctypes.c_char_p, _I]),
     "fhip_gate_last_error": (ctypes.c_char_p, []),
 }
-_GATE = None
+
+
+def _load(path, signatures):
+    """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
+    lib = _LOADED.get(path)
+    if lib is None:
+        # PyTorch bundles its own HIP/HSA runtime; it must be the one already mapped when our library (linked against
+        # libamdhip64.so.7 by SONAME) is loaded, or the process ends up with two HSA runtimes and no visible device.
+        import torch  # noqa: F401  (device memory + stream provider of this host mirror)
+        if not os.path.exists(path):
+            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
+                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
+        lib = ctypes.CDLL(path)
+        for name, (res, args) in signatures.items():
+            fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
+            fn.restype = res
+            fn.argtypes = args
+        _LOADED[path] = lib
+    return lib
 
 
 def lib_path() -> str:
@@ -246,22 +257,7 @@ def lib_path() -> str:
 
 def load_library():
     """Load libfeather_hip.so.  Fails loudly: there is no fallback implementation."""
-    global _LIB
-    if _LIB is None:
-        # PyTorch bundles its own HIP/HSA runtime; it must be the one already mapped when our library (linked against
-        # libamdhip64.so.7 by SONAME) is loaded, or the process ends up with two HSA runtimes and no visible device.
-        import torch  # noqa: F401  (device memory + stream provider of this host mirror)
-        path = lib_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
-            fn.restype = res
-            fn.argtypes = args
-        _LIB = lib
-    return _LIB
+    return _load(lib_path(), SIGNATURES)
 
 
 def pixout_path() -> str:
@@ -270,20 +266,7 @@ def pixout_path() -> str:
 
 def load_pixout_library():
     """Load libfeather_pixout.so (fhip_float_to_pixels).  Fails loudly like load_library: there is no fallback implementation."""
-    global _PIXOUT
-    if _PIXOUT is None:
-        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
-        path = pixout_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in PIXOUT_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _PIXOUT = lib
-    return _PIXOUT
+    return _load(pixout_path(), PIXOUT_SIGNATURES)
 
 
 def gconv_path() -> str:
@@ -292,20 +275,7 @@ def gconv_path() -> str:
 
 def load_gconv_library():
     """Load libfeather_gconv.so (fhip_gconv_forward).  Fails loudly like load_library: there is no fallback implementation."""
-    global _GCONV
-    if _GCONV is None:
-        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
-        path = gconv_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in GCONV_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _GCONV = lib
-    return _GCONV
+    return _load(gconv_path(), GCONV_SIGNATURES)
 
 
 def deconv_path() -> str:
@@ -314,20 +284,7 @@ def deconv_path() -> str:
 
 def load_deconv_library():
     """Load libfeather_deconv.so (fhip_deconv_forward).  Fails loudly like load_library: there is no fallback implementation."""
-    global _DECONV
-    if _DECONV is None:
-        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
-        path = deconv_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in DECONV_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _DECONV = lib
-    return _DECONV
+    return _load(deconv_path(), DECONV_SIGNATURES)
 
 
 def inorm_path() -> str:
@@ -337,20 +294,7 @@ def inorm_path() -> str:
 def load_inorm_library():
     """Load libfeather_inorm.so (fhip_instance_norm_forward, fhip_activation_forward).  Fails loudly like load_library: there is no fallback
     implementation."""
-    global _INORM
-    if _INORM is None:
-        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
-        path = inorm_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in INORM_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _INORM = lib
-    return _INORM
+    return _load(inorm_path(), INORM_SIGNATURES)
 
 
 def shuffle_path() -> str:
@@ -360,20 +304,7 @@ def shuffle_path() -> str:
 def load_shuffle_library():
     """Load libfeather_shuffle.so (fhip_channel_shuffle_forward, fhip_channel_slice_forward, fhip_channel_map_forward).  Fails loudly like
     load_library: there is no fallback implementation."""
-    global _SHUFFLE
-    if _SHUFFLE is None:
-        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
-        path = shuffle_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in SHUFFLE_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _SHUFFLE = lib
-    return _SHUFFLE
+    return _load(shuffle_path(), SHUFFLE_SIGNATURES)
 
 
 def canvas_path() -> str:
@@ -383,20 +314,7 @@ def canvas_path() -> str:
 def load_canvas_library():
     """Load libfeather_canvas.so (fhip_canvas_output_to_next_input, fhip_canvas_output_transform).  Fails loudly like load_library: there is
     no fallback implementation."""
-    global _CANVAS
-    if _CANVAS is None:
-        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
-        path = canvas_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in CANVAS_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _CANVAS = lib
-    return _CANVAS
+    return _load(canvas_path(), CANVAS_SIGNATURES)
 
 
 def atrous_path() -> str:
@@ -405,20 +323,7 @@ def atrous_path() -> str:
 
 def load_atrous_library():
     """Load libfeather_atrous.so (fhip_atrous_forward).  Fails loudly like load_library: there is no fallback implementation."""
-    global _ATROUS
-    if _ATROUS is None:
-        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
-        path = atrous_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in ATROUS_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _ATROUS = lib
-    return _ATROUS
+    return _load(atrous_path(), ATROUS_SIGNATURES)
 
 
 def gate_path() -> str:
@@ -428,17 +333,4 @@ def gate_path() -> str:
 def load_gate_library():
     """Load libfeather_gate.so (fhip_channel_gate_forward, fhip_squeeze_forward, fhip_excite_forward, fhip_gate_activation_forward).  Fails
     loudly like load_library: there is no fallback implementation."""
-    global _GATE
-    if _GATE is None:
-        import torch  # noqa: F401  (its HIP runtime must be the one mapped first, as in load_library)
-        path = gate_path()
-        if not os.path.exists(path):
-            raise RuntimeError(f"feathercnn_amd: HIP library {path} is missing -- run `python -c 'import __graft_entry__ as g; "
-                               "g.build()'` (or `make -C feathercnn_amd/csrc`). There is no CPU fallback.")
-        lib = ctypes.CDLL(path)
-        for name, (res, args) in GATE_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _GATE = lib
-    return _GATE
+    return _load(gate_path(), GATE_SIGNATURES)

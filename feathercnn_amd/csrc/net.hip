@@ -67,9 +67,74 @@ enum
     NET_E_BASE_RESHAPE = -400
 };
 
-// ---- libfeather_gconv.so, the route of a Convolution layer with 1 < group < C ------------------------------------
-// Opened lazily from the directory this library was loaded from (then by its bare name, the loader's search path), so that
-// libfeather_hip.so keeps linking and loading without it; a net that holds such a layer and cannot find it fails at Reshape.
+// ---- the side libraries: libfeather_<x>.so next to libfeather_hip.so, one per layer family added after the first release ----------------
+// Each is opened lazily from the directory this library was loaded from (then by its bare name, the loader's search path), so that
+// libfeather_hip.so keeps linking and loading without it; a net that needs one and cannot find it fails at Reshape (canvas: at
+// plan_chains).  A typed struct per library holds its entry points and describes itself once (library()); side_api<X>() opens and
+// caches it.
+struct SideSymbol
+{
+    void* slot; // the function pointer of the Api struct that receives the address
+    const char* name;
+};
+
+struct SideLibrary
+{
+    const char *file, *needs, *header; // libfeather_<x>.so, what needs it (for the message), feather_<x>.h
+    std::vector<SideSymbol> symbols;
+};
+
+// Opens the library and fills every slot; false, with the message set and nothing left open, if the file or one entry point is missing.
+static bool open_side_library(const SideLibrary& lib)
+{
+    std::string tried;
+    Dl_info self;
+    if (dladdr((void*)&open_side_library, &self) && self.dli_fname)
+    {
+        tried = self.dli_fname;
+        const size_t slash = tried.rfind('/');
+        tried = (slash == std::string::npos ? std::string() : tried.substr(0, slash + 1)) + lib.file;
+    }
+    void* h = nullptr;
+    for (const char* path : {tried.c_str(), lib.file})
+        if (*path && (h = dlopen(path, RTLD_NOW | RTLD_LOCAL))) break;
+    if (!h)
+    {
+        failf(FHIP_E_UNSUPPORTED, "%s needs %s next to libfeather_hip.so (%s): %s", lib.needs, lib.file, tried.c_str(), dlerror());
+        return false;
+    }
+    bool all = true;
+    for (const SideSymbol& s : lib.symbols)
+    {
+        void* f = dlsym(h, s.name);
+        memcpy(s.slot, &f, sizeof(f));
+        all = all && f;
+    }
+    if (!all)
+    {
+        failf(FHIP_E_UNSUPPORTED, "%s (%s) does not export the entry points of %s", lib.file, tried.c_str(), lib.header);
+        dlclose(h);
+    }
+    return all;
+}
+
+// One table, mutex and `loaded` flag per library; a failed open leaves them untouched and is tried again at the next call.
+template <class Api>
+static const Api* side_api()
+{
+    static std::mutex mu;
+    static Api api;
+    static bool loaded = false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (loaded) return &api;
+    Api a;
+    if (!open_side_library(a.library())) return nullptr;
+    api = a;
+    loaded = true;
+    return &api;
+}
+
+// libfeather_gconv.so, the route of a Convolution layer with 1 < group < C
 struct GconvApi
 {
     decltype(&fhip_gconv_supported) supported = nullptr;
@@ -77,53 +142,16 @@ struct GconvApi
     decltype(&fhip_gconv_init) init = nullptr;
     decltype(&fhip_gconv_forward) forward = nullptr;
     decltype(&fhip_gconv_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_gconv.so", "a convolution with 1 < group < input_channels", "feather_gconv.h",
+                {{&supported, "fhip_gconv_supported"}, {&get_buffer_size, "fhip_gconv_get_buffer_size"}, {&init, "fhip_gconv_init"},
+                 {&forward, "fhip_gconv_forward"}, {&last_error, "fhip_gconv_last_error"}}};
+    }
 };
+static const GconvApi* gconv_api() { return side_api<GconvApi>(); }
 
-static const GconvApi* gconv_api()
-{
-    static std::mutex mu;
-    static GconvApi api;
-    static bool loaded = false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (loaded) return &api;
-    std::string tried;
-    void* h = nullptr;
-    Dl_info self;
-    if (dladdr((void*)&gconv_api, &self) && self.dli_fname)
-    {
-        std::string path = self.dli_fname;
-        const size_t slash = path.rfind('/');
-        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_gconv.so";
-        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        tried = path;
-    }
-    if (!h) h = dlopen("libfeather_gconv.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-    {
-        failf(FHIP_E_UNSUPPORTED, "a convolution with 1 < group < input_channels needs libfeather_gconv.so next to libfeather_hip.so (%s): %s",
-              tried.c_str(), dlerror());
-        return nullptr;
-    }
-    GconvApi a;
-    a.supported = (decltype(a.supported))dlsym(h, "fhip_gconv_supported");
-    a.get_buffer_size = (decltype(a.get_buffer_size))dlsym(h, "fhip_gconv_get_buffer_size");
-    a.init = (decltype(a.init))dlsym(h, "fhip_gconv_init");
-    a.forward = (decltype(a.forward))dlsym(h, "fhip_gconv_forward");
-    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_gconv_last_error");
-    if (!a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
-    {
-        failf(FHIP_E_UNSUPPORTED, "libfeather_gconv.so (%s) does not export the entry points of feather_gconv.h", tried.c_str());
-        dlclose(h);
-        return nullptr;
-    }
-    api = a;
-    loaded = true;
-    return &api;
-}
-
-// ---- libfeather_atrous.so, the route of a Convolution layer with dilation > 1 (fhip_net_set_dilated) --------------
-// Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name; a net that holds such a layer and
-// cannot find it fails at Reshape.
+// libfeather_atrous.so, the route of a Convolution layer with dilation > 1 (fhip_net_set_dilated)
 struct AtrousApi
 {
     decltype(&fhip_atrous_assign_output_dim) assign_output_dim = nullptr;
@@ -132,53 +160,17 @@ struct AtrousApi
     decltype(&fhip_atrous_init) init = nullptr;
     decltype(&fhip_atrous_forward) forward = nullptr;
     decltype(&fhip_atrous_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_atrous.so", "a dilated convolution", "feather_atrous.h",
+                {{&assign_output_dim, "fhip_atrous_assign_output_dim"}, {&supported, "fhip_atrous_supported"},
+                 {&get_buffer_size, "fhip_atrous_get_buffer_size"}, {&init, "fhip_atrous_init"}, {&forward, "fhip_atrous_forward"},
+                 {&last_error, "fhip_atrous_last_error"}}};
+    }
 };
+static const AtrousApi* atrous_api() { return side_api<AtrousApi>(); }
 
-static const AtrousApi* atrous_api()
-{
-    static std::mutex mu;
-    static AtrousApi api;
-    static bool loaded = false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (loaded) return &api;
-    std::string tried;
-    void* h = nullptr;
-    Dl_info self;
-    if (dladdr((void*)&atrous_api, &self) && self.dli_fname)
-    {
-        std::string path = self.dli_fname;
-        const size_t slash = path.rfind('/');
-        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_atrous.so";
-        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        tried = path;
-    }
-    if (!h) h = dlopen("libfeather_atrous.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-    {
-        failf(FHIP_E_UNSUPPORTED, "a dilated convolution needs libfeather_atrous.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
-        return nullptr;
-    }
-    AtrousApi a;
-    a.assign_output_dim = (decltype(a.assign_output_dim))dlsym(h, "fhip_atrous_assign_output_dim");
-    a.supported = (decltype(a.supported))dlsym(h, "fhip_atrous_supported");
-    a.get_buffer_size = (decltype(a.get_buffer_size))dlsym(h, "fhip_atrous_get_buffer_size");
-    a.init = (decltype(a.init))dlsym(h, "fhip_atrous_init");
-    a.forward = (decltype(a.forward))dlsym(h, "fhip_atrous_forward");
-    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_atrous_last_error");
-    if (!a.assign_output_dim || !a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
-    {
-        failf(FHIP_E_UNSUPPORTED, "libfeather_atrous.so (%s) does not export the entry points of feather_atrous.h", tried.c_str());
-        dlclose(h);
-        return nullptr;
-    }
-    api = a;
-    loaded = true;
-    return &api;
-}
-
-// ---- libfeather_deconv.so, the route of Deconvolution / DeconvolutionDepthWise layers ------------------------------
-// Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name; a net that holds such a layer and
-// cannot find it fails at Reshape.
+// libfeather_deconv.so, the route of Deconvolution / DeconvolutionDepthWise layers
 struct DeconvApi
 {
     decltype(&fhip_deconv_assign_output_dim) assign_output_dim = nullptr;
@@ -187,104 +179,34 @@ struct DeconvApi
     decltype(&fhip_deconv_init) init = nullptr;
     decltype(&fhip_deconv_forward) forward = nullptr;
     decltype(&fhip_deconv_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_deconv.so", "a Deconvolution layer", "feather_deconv.h",
+                {{&assign_output_dim, "fhip_deconv_assign_output_dim"}, {&supported, "fhip_deconv_supported"},
+                 {&get_buffer_size, "fhip_deconv_get_buffer_size"}, {&init, "fhip_deconv_init"}, {&forward, "fhip_deconv_forward"},
+                 {&last_error, "fhip_deconv_last_error"}}};
+    }
 };
+static const DeconvApi* deconv_api() { return side_api<DeconvApi>(); }
 
-static const DeconvApi* deconv_api()
-{
-    static std::mutex mu;
-    static DeconvApi api;
-    static bool loaded = false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (loaded) return &api;
-    std::string tried;
-    void* h = nullptr;
-    Dl_info self;
-    if (dladdr((void*)&deconv_api, &self) && self.dli_fname)
-    {
-        std::string path = self.dli_fname;
-        const size_t slash = path.rfind('/');
-        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_deconv.so";
-        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        tried = path;
-    }
-    if (!h) h = dlopen("libfeather_deconv.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-    {
-        failf(FHIP_E_UNSUPPORTED, "a Deconvolution layer needs libfeather_deconv.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
-        return nullptr;
-    }
-    DeconvApi a;
-    a.assign_output_dim = (decltype(a.assign_output_dim))dlsym(h, "fhip_deconv_assign_output_dim");
-    a.supported = (decltype(a.supported))dlsym(h, "fhip_deconv_supported");
-    a.get_buffer_size = (decltype(a.get_buffer_size))dlsym(h, "fhip_deconv_get_buffer_size");
-    a.init = (decltype(a.init))dlsym(h, "fhip_deconv_init");
-    a.forward = (decltype(a.forward))dlsym(h, "fhip_deconv_forward");
-    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_deconv_last_error");
-    if (!a.assign_output_dim || !a.supported || !a.get_buffer_size || !a.init || !a.forward || !a.last_error)
-    {
-        failf(FHIP_E_UNSUPPORTED, "libfeather_deconv.so (%s) does not export the entry points of feather_deconv.h", tried.c_str());
-        dlclose(h);
-        return nullptr;
-    }
-    api = a;
-    loaded = true;
-    return &api;
-}
-
-// ---- libfeather_inorm.so, the route of InstanceNorm, PReLU / Sigmoid / TanH / Clip layers and of a ReLU with a slope -----------------
-// Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name; a net that holds such a layer and
-// cannot find it fails at Reshape.
+// libfeather_inorm.so, the route of InstanceNorm, PReLU / Sigmoid / TanH / Clip layers and of a ReLU with a slope
 struct InormApi
 {
     decltype(&fhip_instance_norm_get_buffer_size) get_buffer_size = nullptr;
     decltype(&fhip_instance_norm_forward) forward = nullptr;
     decltype(&fhip_activation_forward) activation = nullptr;
     decltype(&fhip_inorm_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_inorm.so", "an InstanceNorm / activation layer", "feather_inorm.h",
+                {{&get_buffer_size, "fhip_instance_norm_get_buffer_size"}, {&forward, "fhip_instance_norm_forward"},
+                 {&activation, "fhip_activation_forward"}, {&last_error, "fhip_inorm_last_error"}}};
+    }
 };
+static const InormApi* inorm_api() { return side_api<InormApi>(); }
 
-static const InormApi* inorm_api()
-{
-    static std::mutex mu;
-    static InormApi api;
-    static bool loaded = false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (loaded) return &api;
-    std::string tried;
-    void* h = nullptr;
-    Dl_info self;
-    if (dladdr((void*)&inorm_api, &self) && self.dli_fname)
-    {
-        std::string path = self.dli_fname;
-        const size_t slash = path.rfind('/');
-        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_inorm.so";
-        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        tried = path;
-    }
-    if (!h) h = dlopen("libfeather_inorm.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-    {
-        failf(FHIP_E_UNSUPPORTED, "an InstanceNorm / activation layer needs libfeather_inorm.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
-        return nullptr;
-    }
-    InormApi a;
-    a.get_buffer_size = (decltype(a.get_buffer_size))dlsym(h, "fhip_instance_norm_get_buffer_size");
-    a.forward = (decltype(a.forward))dlsym(h, "fhip_instance_norm_forward");
-    a.activation = (decltype(a.activation))dlsym(h, "fhip_activation_forward");
-    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_inorm_last_error");
-    if (!a.get_buffer_size || !a.forward || !a.activation || !a.last_error)
-    {
-        failf(FHIP_E_UNSUPPORTED, "libfeather_inorm.so (%s) does not export the entry points of feather_inorm.h", tried.c_str());
-        dlclose(h);
-        return nullptr;
-    }
-    api = a;
-    loaded = true;
-    return &api;
-}
-
-// ---- libfeather_shuffle.so, the route of ShuffleChannel and Slice layers and of the Concat / ShuffleChannel / Slice runs collapsed at
-// fusion level 2.  Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name; a net that holds such a
-// layer and cannot find it fails at Reshape.
+// libfeather_shuffle.so, the route of ShuffleChannel and Slice layers and of the Concat / ShuffleChannel / Slice runs collapsed at
+// fusion level 2
 struct ShuffleApi
 {
     decltype(&fhip_channel_slice_resolve) resolve = nullptr;
@@ -292,52 +214,17 @@ struct ShuffleApi
     decltype(&fhip_channel_map_destroy) destroy = nullptr;
     decltype(&fhip_channel_map_forward) forward = nullptr;
     decltype(&fhip_shuffle_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_shuffle.so", "a ShuffleChannel / Slice layer", "feather_shuffle.h",
+                {{&resolve, "fhip_channel_slice_resolve"}, {&create, "fhip_channel_map_create"}, {&destroy, "fhip_channel_map_destroy"},
+                 {&forward, "fhip_channel_map_forward"}, {&last_error, "fhip_shuffle_last_error"}}};
+    }
 };
+static const ShuffleApi* shuffle_api() { return side_api<ShuffleApi>(); }
 
-static const ShuffleApi* shuffle_api()
-{
-    static std::mutex mu;
-    static ShuffleApi api;
-    static bool loaded = false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (loaded) return &api;
-    std::string tried;
-    void* h = nullptr;
-    Dl_info self;
-    if (dladdr((void*)&shuffle_api, &self) && self.dli_fname)
-    {
-        std::string path = self.dli_fname;
-        const size_t slash = path.rfind('/');
-        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_shuffle.so";
-        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        tried = path;
-    }
-    if (!h) h = dlopen("libfeather_shuffle.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-    {
-        failf(FHIP_E_UNSUPPORTED, "a ShuffleChannel / Slice layer needs libfeather_shuffle.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
-        return nullptr;
-    }
-    ShuffleApi a;
-    a.resolve = (decltype(a.resolve))dlsym(h, "fhip_channel_slice_resolve");
-    a.create = (decltype(a.create))dlsym(h, "fhip_channel_map_create");
-    a.destroy = (decltype(a.destroy))dlsym(h, "fhip_channel_map_destroy");
-    a.forward = (decltype(a.forward))dlsym(h, "fhip_channel_map_forward");
-    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_shuffle_last_error");
-    if (!a.resolve || !a.create || !a.destroy || !a.forward || !a.last_error)
-    {
-        failf(FHIP_E_UNSUPPORTED, "libfeather_shuffle.so (%s) does not export the entry points of feather_shuffle.h", tried.c_str());
-        dlclose(h);
-        return nullptr;
-    }
-    api = a;
-    loaded = true;
-    return &api;
-}
-
-// ---- libfeather_gate.so, the route of the squeeze-and-excitation layers: a two-bottom BinaryOp (mul) or Scale, Swish, HardSigmoid, and the
-// whole SE block collapsed at fusion level 2 (collapse_gate_blocks).  Opened like libfeather_gconv.so: lazily, from this library's
-// directory, then by its bare name; a net that holds such a layer and cannot find it fails at Reshape.
+// libfeather_gate.so, the route of the squeeze-and-excitation layers: a two-bottom BinaryOp (mul) or Scale, Swish, HardSigmoid, and the
+// whole SE block collapsed at fusion level 2 (collapse_gate_blocks)
 struct GateApi
 {
     decltype(&fhip_channel_gate_forward) apply = nullptr;
@@ -346,99 +233,29 @@ struct GateApi
     decltype(&fhip_excite_forward) excite = nullptr;
     decltype(&fhip_gate_activation_forward) activation = nullptr;
     decltype(&fhip_gate_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_gate.so", "a channel-gate / Swish / HardSigmoid layer", "feather_gate.h",
+                {{&apply, "fhip_channel_gate_forward"}, {&squeeze_buffer_size, "fhip_squeeze_get_buffer_size"}, {&squeeze, "fhip_squeeze_forward"},
+                 {&excite, "fhip_excite_forward"}, {&activation, "fhip_gate_activation_forward"}, {&last_error, "fhip_gate_last_error"}}};
+    }
 };
+static const GateApi* gate_api() { return side_api<GateApi>(); }
 
-static const GateApi* gate_api()
-{
-    static std::mutex mu;
-    static GateApi api;
-    static bool loaded = false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (loaded) return &api;
-    std::string tried;
-    void* h = nullptr;
-    Dl_info self;
-    if (dladdr((void*)&gate_api, &self) && self.dli_fname)
-    {
-        std::string path = self.dli_fname;
-        const size_t slash = path.rfind('/');
-        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_gate.so";
-        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        tried = path;
-    }
-    if (!h) h = dlopen("libfeather_gate.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-    {
-        failf(FHIP_E_UNSUPPORTED, "a channel-gate / Swish / HardSigmoid layer needs libfeather_gate.so next to libfeather_hip.so (%s): %s", tried.c_str(), dlerror());
-        return nullptr;
-    }
-    GateApi a;
-    a.apply = (decltype(a.apply))dlsym(h, "fhip_channel_gate_forward");
-    a.squeeze_buffer_size = (decltype(a.squeeze_buffer_size))dlsym(h, "fhip_squeeze_get_buffer_size");
-    a.squeeze = (decltype(a.squeeze))dlsym(h, "fhip_squeeze_forward");
-    a.excite = (decltype(a.excite))dlsym(h, "fhip_excite_forward");
-    a.activation = (decltype(a.activation))dlsym(h, "fhip_gate_activation_forward");
-    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_gate_last_error");
-    if (!a.apply || !a.squeeze_buffer_size || !a.squeeze || !a.excite || !a.activation || !a.last_error)
-    {
-        failf(FHIP_E_UNSUPPORTED, "libfeather_gate.so (%s) does not export the entry points of feather_gate.h", tried.c_str());
-        dlclose(h);
-        return nullptr;
-    }
-    api = a;
-    loaded = true;
-    return &api;
-}
-
-// ---- libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases (plan_chains) -----------------------
-// Opened like libfeather_gconv.so: lazily, from this library's directory, then by its bare name.  The canvas form is a faster way to run
-// the same run of layers, not a layer type: a net that qualifies and cannot find the library fails at plan_chains like the others.
+// libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases (plan_chains).  The canvas form is a
+// faster way to run the same run of layers, not a layer type: a net that qualifies and cannot find the library fails at plan_chains.
 struct CanvasApi
 {
     decltype(&fhip_canvas_output_to_next_input) chain = nullptr;
     decltype(&fhip_canvas_output_transform) output = nullptr;
     decltype(&fhip_canvas_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_canvas.so", "a chained Winograd run on 2x2 image canvases", "feather_canvas.h",
+                {{&chain, "fhip_canvas_output_to_next_input"}, {&output, "fhip_canvas_output_transform"}, {&last_error, "fhip_canvas_last_error"}}};
+    }
 };
-
-static const CanvasApi* canvas_api()
-{
-    static std::mutex mu;
-    static CanvasApi api;
-    static bool loaded = false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (loaded) return &api;
-    std::string tried;
-    void* h = nullptr;
-    Dl_info self;
-    if (dladdr((void*)&canvas_api, &self) && self.dli_fname)
-    {
-        std::string path = self.dli_fname;
-        const size_t slash = path.rfind('/');
-        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "libfeather_canvas.so";
-        h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        tried = path;
-    }
-    if (!h) h = dlopen("libfeather_canvas.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-    {
-        failf(FHIP_E_UNSUPPORTED, "a chained Winograd run on 2x2 image canvases needs libfeather_canvas.so next to libfeather_hip.so (%s): %s",
-              tried.c_str(), dlerror());
-        return nullptr;
-    }
-    CanvasApi a;
-    a.chain = (decltype(a.chain))dlsym(h, "fhip_canvas_output_to_next_input");
-    a.output = (decltype(a.output))dlsym(h, "fhip_canvas_output_transform");
-    a.last_error = (decltype(a.last_error))dlsym(h, "fhip_canvas_last_error");
-    if (!a.chain || !a.output || !a.last_error)
-    {
-        failf(FHIP_E_UNSUPPORTED, "libfeather_canvas.so (%s) does not export the entry points of feather_canvas.h", tried.c_str());
-        dlclose(h);
-        return nullptr;
-    }
-    api = a;
-    loaded = true;
-    return &api;
-}
+static const CanvasApi* canvas_api() { return side_api<CanvasApi>(); }
 
 // ---- ncnn ParamDict (ncnn/paramdict.cpp:92-174): "id=value" pairs, value is float iff it contains '.' or 'e' -----
 struct ParamDict
@@ -811,6 +628,29 @@ struct InputLayer : Layer
     int Forward(hipStream_t) override { return 0; }
 };
 
+// A BatchNorm / Scale folded into the convolution or deconvolution before it (fusion level 2): y = y * mul[k] + add[k] per output
+// channel k, applied to the filters and the bias at Init.  K is the caller's business: the layers count their channels differently.
+struct AffineLayer;
+struct AffineFold
+{
+    std::vector<float> mul, add;
+    bool empty() const { return mul.empty(); }
+    // composes nx behind what is folded already; false, with nothing changed, if nx is no plain affine map over K channels
+    bool absorb(const AffineLayer& nx, int K);
+    // w = [K][...] filters, b = K biases or none (then a zero bias is created); does nothing while no layer was absorbed
+    void apply(std::vector<float>& w, std::vector<float>& b, int K) const
+    {
+        if (mul.empty()) return;
+        const size_t per = w.size() / K;
+        if (b.empty()) b.assign(K, 0.f);
+        for (int k = 0; k < K; ++k)
+        {
+            for (size_t i = 0; i < per; ++i) w[k * per + i] *= mul[k];
+            b[k] = b[k] * mul[k] + add[k];
+        }
+    }
+};
+
 // feather::ConvLayer, layers/conv_layer.h:26-193 (also registered as ConvolutionDepthWise, layer_factory.cpp)
 struct ConvLayer : Layer
 {
@@ -835,7 +675,7 @@ struct ConvLayer : Layer
         return a;
     }
     std::vector<float> w_host, b_host;
-    std::vector<float> post_mul, post_add; // folded BatchNorm/Scale (fusion level 2)
+    AffineFold fold; // folded BatchNorm/Scale (fusion level 2)
     DeviceVec packed, bias;
     size_t buffer_bytes = 0, packed_bytes = 0;
     // fusion level 2: a following 2x2 / stride-2 max pooling is absorbed (fhip_conv_forward_maxpool2 when the route can,
@@ -1028,15 +868,7 @@ struct ConvLayer : Layer
     {
         w = w_host;
         b = b_host;
-        if (post_mul.empty()) return;
-        const int K = p.output_channels;
-        const size_t per = w.size() / K;
-        if (b.empty()) b.assign(K, 0.f);
-        for (int k = 0; k < K; ++k)
-        {
-            for (size_t i = 0; i < per; ++i) w[k * per + i] *= post_mul[k];
-            b[k] = b[k] * post_mul[k] + post_add[k];
-        }
+        fold.apply(w, b, p.output_channels);
     }
     int init_siblings(hipStream_t s)
     {
@@ -1082,7 +914,7 @@ struct ConvLayer : Layer
         if (inited_algo == algo_ && packed.bytes == packed_bytes) return 0;
         std::vector<float> w, b;
         folded(w, b);
-        if (!post_mul.empty()) p.bias_term = 1;
+        if (!fold.empty()) p.bias_term = 1;
         DeviceVec raw;
         int rc = raw.upload(w.data(), w.size(), s);
         if (rc) return rc;
@@ -1614,6 +1446,22 @@ struct AffineLayer : Layer
     size_t weight_bytes() const override { return d_mul.bytes + d_add.bytes; }
 };
 
+bool AffineFold::absorb(const AffineLayer& nx, int K)
+{
+    if (nx.gated || nx.channels != K || nx.relu) return false;
+    if (mul.empty())
+    {
+        mul.assign(K, 1.f);
+        add.assign(K, 0.f);
+    }
+    for (int k = 0; k < K; ++k)
+    {
+        mul[k] *= nx.mul[k];
+        add[k] = add[k] * nx.mul[k] + (nx.has_add ? nx.add[k] : 0.f);
+    }
+    return true;
+}
+
 struct BatchNormLayer : AffineLayer
 {
     float eps = 0.f;
@@ -1885,20 +1733,8 @@ int ConvLayer::Fuse(Layer* next, int level)
     // level 2 (beyond the reference): fold a following BatchNorm / Scale into the weights and bias
     if (level >= 2 && p.activation == FHIP_ACT_NONE && (next->type == "BatchNorm" || next->type == "Scale"))
     {
-        AffineLayer* nx = static_cast<AffineLayer*>(next);
         const int K = atrous ? p.output_channels : p.group == p.input_channels ? p.input_channels : p.output_channels;
-        if (nx->gated || nx->channels != K || nx->relu) return 0;
-        if (post_mul.empty())
-        {
-            post_mul.assign(K, 1.f);
-            post_add.assign(K, 0.f);
-        }
-        for (int k = 0; k < K; ++k)
-        {
-            post_mul[k] *= nx->mul[k];
-            post_add[k] = post_add[k] * nx->mul[k] + (nx->has_add ? nx->add[k] : 0.f);
-        }
-        return 1;
+        return fold.absorb(*static_cast<AffineLayer*>(next), K) ? 1 : 0;
     }
     return 0;
 }
@@ -1912,7 +1748,7 @@ struct DeconvLayer : Layer
     fhip_deconv_param p;
     int weight_data_size = 0;
     std::vector<float> w_host, b_host;
-    std::vector<float> post_mul, post_add; // folded BatchNorm/Scale (fusion level 2)
+    AffineFold fold; // folded BatchNorm/Scale (fusion level 2)
     DeviceVec packed, bias;
     size_t buffer_bytes = 0, packed_bytes = 0;
     bool inited = false;
@@ -1989,18 +1825,8 @@ struct DeconvLayer : Layer
         const DeconvApi* api = deconv_api();
         if (!api) return FHIP_E_UNSUPPORTED;
         std::vector<float> w = w_host, b = b_host;
-        if (!post_mul.empty())
-        {
-            const int K = p.output_channels;
-            const size_t per = w.size() / K;
-            if (b.empty()) b.assign(K, 0.f);
-            for (int k = 0; k < K; ++k)
-            {
-                for (size_t i = 0; i < per; ++i) w[k * per + i] *= post_mul[k];
-                b[k] = b[k] * post_mul[k] + post_add[k];
-            }
-            p.bias_term = 1;
-        }
+        fold.apply(w, b, p.output_channels);
+        if (!fold.empty()) p.bias_term = 1;
         DeviceVec raw;
         int rc = raw.upload(w.data(), w.size(), s);
         if (rc) return rc;
@@ -2031,22 +1857,7 @@ int DeconvLayer::Fuse(Layer* next, int level)
         return 1;
     }
     if (level >= 2 && p.activation == FHIP_ACT_NONE && (next->type == "BatchNorm" || next->type == "Scale"))
-    {
-        AffineLayer* nx = static_cast<AffineLayer*>(next);
-        const int K = p.output_channels;
-        if (nx->gated || nx->channels != K || nx->relu) return 0;
-        if (post_mul.empty())
-        {
-            post_mul.assign(K, 1.f);
-            post_add.assign(K, 0.f);
-        }
-        for (int k = 0; k < K; ++k)
-        {
-            post_mul[k] *= nx->mul[k];
-            post_add[k] = post_add[k] * nx->mul[k] + (nx->has_add ? nx->add[k] : 0.f);
-        }
-        return 1;
-    }
+        return fold.absorb(*static_cast<AffineLayer*>(next), p.output_channels) ? 1 : 0;
     return 0;
 }
 
@@ -2452,7 +2263,7 @@ static void collapse_gate_blocks(Net& net)
         ConvLayer* cv = static_cast<ConvLayer*>(l);
         const fhip_conv_param& p = cv->p;
         if (cv->gconv || cv->atrous || p.group != 1 || p.kernel_h != 1 || p.kernel_w != 1 || p.stride_h != 1 || p.stride_w != 1 || p.pad_left || p.pad_right ||
-            p.pad_top || p.pad_bottom || p.activation != FHIP_ACT_NONE || !cv->post_mul.empty() || cv->w_host.size() != (size_t)p.input_channels * p.output_channels)
+            p.pad_top || p.pad_bottom || p.activation != FHIP_ACT_NONE || !cv->fold.empty() || cv->w_host.size() != (size_t)p.input_channels * p.output_channels)
             return false;
         in = p.input_channels, out = p.output_channels, w = cv->w_host, b = cv->b_host, has_b = p.bias_term != 0;
         return true;
