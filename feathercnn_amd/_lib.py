@@ -51,6 +51,7 @@ SIGNATURES = {
     "fhip_conv_select_algo": (_I, [_P, ctypes.POINTER(_I)]),
     "fhip_conv_select_algo_tuned": (_I, [_P, ctypes.POINTER(_I)]),
     "fhip_conv_get_buffer_size": (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    "fhip_conv_packed_layout": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int)]),
     "fhip_conv_init": (_I, [_P, _I, _V, _V, _V]),
     "fhip_conv_forward": (_I, [_P, _I, _I, _V, _V, _V, _V, _V, _V]),
     "fhip_winograd_f63_plan": (_I, [_P, _I, ctypes.POINTER(fhip_winograd_plan)]),

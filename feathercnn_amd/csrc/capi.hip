@@ -38,6 +38,7 @@ int igemm_forward(const fhip_conv_param& p, int batch, float* out, const float* 
                   float* buffer, bool force_no_act, hipStream_t s, const float* residual = nullptr);
 size_t igemm_buffer_bytes(const fhip_conv_param& p, int batch);
 size_t igemm_packed_floats(const fhip_conv_param& p);
+int igemm_packed_layout(const fhip_conv_param& p);
 bool igemm_streams(const fhip_conv_param& p, int batch);
 int depthwise_forward(const fhip_conv_param& p, int batch, float* out, const float* in, const float* kernel, const float* bias,
                       hipStream_t s);
@@ -226,6 +227,26 @@ int fhip_conv_get_buffer_size(const fhip_conv_param* p, int algo, int batch, siz
             return FHIP_OK;
         }
         default: return fail(FHIP_E_UNSUPPORTED, "This algo is not supported on gfx950 (nor on AVX2, avx/booster.cpp:348-354)");
+    }
+}
+
+int fhip_conv_packed_layout(const fhip_conv_param* p, int algo, int* layout)
+{
+    if (!valid_param(p) || !layout) return fail(FHIP_E_BADARG, "bad argument");
+    switch (algo)
+    {
+        case FHIP_NAIVE:
+        case FHIP_IM2COL: *layout = igemm_packed_layout(*p); return FHIP_OK; // which weight images follow the panels
+        case FHIP_DEPTHWISE: *layout = 0; return FHIP_OK;                      // the filters and their 12-float copies: no plane in it
+        case FHIP_WINOGRADF63:
+        {
+            fhip_winograd_plan pl;
+            const int rc = winograd_plan(*p, 1, &pl);
+            if (rc) return rc;
+            *layout = pl.frequency_points; // U of F(6,3) or of F(4,3)
+            return FHIP_OK;
+        }
+        default: return fail(FHIP_E_UNSUPPORTED, "This algo is not supported on gfx950");
     }
 }
 

@@ -101,6 +101,10 @@ size_t igemm_packed_floats(const fhip_conv_param& p)
     return (size_t)kdp * kp + (stream_eligible(p) ? (size_t)p.output_channels * p.input_channels : 0) + (ip_eligible(p) ? ip_packed_floats(p) : 0);
 }
 
+// Which of the optional weight images igemm_init writes behind the panels (fhip_conv_packed_layout): the two have the same size for a layer
+// both routes can take, so a caller that keeps packed weights across input sizes cannot go by the byte count.
+int igemm_packed_layout(const fhip_conv_param& p) { return (stream_eligible(p) ? 1 : 0) | (ip_eligible(p) ? 2 : 0); }
+
 void igemm_packed_dims(const fhip_conv_param& p, int* kd_padded, int* k_padded)
 {
     const int Kd = p.input_channels * p.kernel_h * p.kernel_w;

@@ -656,6 +656,9 @@ struct ConvLayer : Layer
 {
     fhip_conv_param p;
     int algo_ = -1, inited_algo = -2;
+    // what the packed weights' content depends on besides the route and the byte count (fhip_conv_packed_layout): a new input size packs
+    // again when it changes -- a 1x1 layer's streamed image and its InnerProduct image have the same size
+    int layout = 0, inited_layout = -1;
     // 1 < group < input_channels: the layer runs through libfeather_gconv.so (gconv_api) with route code FHIP_NET_ROUTE_GCONV.
     // p.output_channels then holds the WHOLE layer's K (the library's convention), not K / group as conv_layer.h:69-75 leaves it.
     // Such a layer fuses a following ReLU and, at level 2, BatchNorm / Scale; every other fusion declines it.
@@ -842,7 +845,7 @@ struct ConvLayer : Layer
             size_t bb = 0;
             if ((rc = fhip_conv_get_buffer_size(&p, algo_, b->n, &bb, &packed_bytes))) return rc;
             buffer_bytes = std::max(bb, pw->buffer_bytes);
-            return 0;
+            return fhip_conv_packed_layout(&p, algo_, &layout);
         }
         res_fast = residual && fhip_conv_can_fuse_residual(&p, algo_) != 0;
         if (residual && (residual->n != b->n || residual->c != p.output_channels || residual->h != p.output_h || residual->w != p.output_w))
@@ -861,7 +864,8 @@ struct ConvLayer : Layer
         else
             rc = tops[0]->reshape(b->n, p.output_channels, p.output_h, p.output_w);
         if (rc) return rc;
-        return fhip_conv_get_buffer_size(&p, algo_, b->n, &buffer_bytes, &packed_bytes);
+        if ((rc = fhip_conv_get_buffer_size(&p, algo_, b->n, &buffer_bytes, &packed_bytes))) return rc;
+        return fhip_conv_packed_layout(&p, algo_, &layout);
     }
     // filters and bias with the folded BatchNorm / Scale (fusion level 2) applied
     void folded(std::vector<float>& w, std::vector<float>& b) const
@@ -911,7 +915,7 @@ struct ConvLayer : Layer
             const int rc = init_siblings(s);
             if (rc) return rc;
         }
-        if (inited_algo == algo_ && packed.bytes == packed_bytes) return 0;
+        if (inited_algo == algo_ && packed.bytes == packed_bytes && inited_layout == layout) return 0;
         std::vector<float> w, b;
         folded(w, b);
         if (!fold.empty()) p.bias_term = 1;
@@ -944,6 +948,7 @@ struct ConvLayer : Layer
         }
         FHIP_CHECK_HIP(hipStreamSynchronize(s)); // `raw` and the host copies go out of scope
         inited_algo = algo_;
+        inited_layout = layout;
         return 0;
     }
     int Forward(hipStream_t s) override

@@ -57,6 +57,14 @@ class Net:
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")
 
+    def set_tuned(self, on: bool):
+        """fhip_net_set_tuned_selection, legal between Forwards: the routes are chosen again at the next Forward."""
+        _check(self._lib.fhip_net_set_tuned_selection(self._h, int(bool(on))), "fhip_net_set_tuned_selection")
+
+    def set_concurrency(self, on: bool):
+        """fhip_net_set_concurrency, legal between Forwards: the side stream is planned again (and a captured graph dropped) at the next Forward."""
+        _check(self._lib.fhip_net_set_concurrency(self._h, int(bool(on))), "fhip_net_set_concurrency")
+
     def use_current_stream(self):
         """Enqueue on torch's current stream (so torch events and tensors order against the net's work)."""
         _check(self._lib.fhip_net_set_stream(self._h, _stream()), "fhip_net_set_stream")

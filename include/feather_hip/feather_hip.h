@@ -106,6 +106,13 @@ FHIP_API int fhip_conv_select_algo_tuned(const fhip_conv_param* param, int* algo
 FHIP_API int fhip_conv_get_buffer_size(const fhip_conv_param* param, int algo, int batch, size_t* buffer_bytes,
                                        size_t* processed_kernel_bytes);
 
+/* What the CONTENT of the packed weights depends on beyond the filters and the byte count: *layout is the same for two geometries of one
+ * layer (the same filters, another input size) exactly when fhip_conv_init writes the same bytes for both.  A caller that keeps packed
+ * weights across input sizes packs again when (algo, processed_kernel_bytes, layout) changes -- the byte count alone does not tell: a 1x1
+ * layer's second weight image is the streamed kernel's on planes of at least 4 pixels and the InnerProduct stream's, of the same size, on a
+ * 1x1 plane.  Pure. */
+FHIP_API int fhip_conv_packed_layout(const fhip_conv_param* param, int algo, int* layout);
+
 /* INIT_FUNC, include/booster/booster.h:152; bodies avx/booster.cpp:35-39,73-81,130-134,199-203.
  * One-time weight pre-processing on the device: Winograd U = G g G^T (transformKernel_F6x6_3x3,
  * avx/winograd_kernels_F63.cpp:256-271), GEMM weight packing (packed_sgemm_init, avx/sgemm.cpp:312-346),
