@@ -37,6 +37,7 @@ int igemm_init(const fhip_conv_param& p, float* packed, const float* kernel, hip
 int igemm_forward(const fhip_conv_param& p, int batch, float* out, const float* in, const float* packed, const float* bias,
                   float* buffer, bool force_no_act, hipStream_t s, const float* residual = nullptr);
 size_t igemm_buffer_bytes(const fhip_conv_param& p, int batch);
+int igemm_check_columns(const fhip_conv_param& p, int batch);
 size_t igemm_packed_floats(const fhip_conv_param& p);
 int igemm_packed_layout(const fhip_conv_param& p);
 bool igemm_streams(const fhip_conv_param& p, int batch);
@@ -209,11 +210,13 @@ int fhip_conv_get_buffer_size(const fhip_conv_param* p, int algo, int batch, siz
         case FHIP_IM2COL:
         {
             if (p->group > 1) return fail(FHIP_E_UNSUPPORTED, "implicit GEMM handles group == 1 only");
+            if (const int rc = igemm_check_columns(*p, batch)) return rc; // what igemm_forward refuses
             *buffer_bytes = igemm_buffer_bytes(*p, batch); // no column matrix; split-K partial sums for under-filled grids only
             *packed_bytes = igemm_packed_floats(*p) * sizeof(float);
             return FHIP_OK;
         }
         case FHIP_DEPTHWISE:
+            if ((long long)batch * p->input_channels > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*C too large: 2^31 planes or more"); // as depthwise_forward
             *buffer_bytes = 0; // no padded copy
             *packed_bytes = depthwise_packed_floats(*p, nullptr) * sizeof(float);
             return FHIP_OK;

@@ -788,7 +788,7 @@ int depthwise_forward(const fhip_conv_param& p, int batch, float* out, const flo
     q.PL = p.pad_left;
     q.PT = p.pad_top;
     const long long planes = (long long)batch * q.C;
-    if (planes > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*C too large");
+    if (planes > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*C too large: 2^31 planes or more");
     q.planes = (int)planes;
     q.has_bias = p.bias_term != 0;
     q.relu = p.activation == FHIP_ACT_RELU;
@@ -823,7 +823,7 @@ int depthwise_forward(const fhip_conv_param& p, int batch, float* out, const flo
         const int tile_floats = round_up(cp * HW, 4);
         const size_t lds = (size_t)(tile_floats + cp * 12) * sizeof(float);
         const long long chunks = (planes + cp - 1) / cp;
-        if (chunks > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*C too large");
+        if (chunks > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*C too large: 2^31 chunks of planes or more");
         // (small_plane implies stride 2: stride-1 planes never reach this kernel, so only its stride-2 form is instantiated)
         hipLaunchKernelGGL(depthwise3x3_chunk_kernel<2>, dim3((unsigned)chunks), dim3(256), lds, s, q, cp, tile_floats);
     }

@@ -173,6 +173,14 @@ static int igemm_tail(const fhip_conv_param& p, int batch, int* pieces)
 
 bool igemm_streams(const fhip_conv_param& p, int batch) { return stream_profitable(p, batch); }
 
+// The column limit of igemm_forward, for fhip_conv_get_buffer_size: the query refuses what the launch refuses.
+int igemm_check_columns(const fhip_conv_param& p, int batch)
+{
+    if ((long long)batch * p.output_h * p.output_w > 0x7fffff00LL || igemm_columns(p, batch) > 0x7fffff00LL)
+        return fail(FHIP_E_BADARG, "N*Ho*Wo exceeds 32-bit column indices: more than 0x7fffff00 GEMM columns");
+    return FHIP_OK;
+}
+
 size_t igemm_buffer_bytes(const fhip_conv_param& p, int batch)
 {
     if (ip_profitable(p, batch)) // [ xq: the re-packed activations | partial sums of the pieces ]
@@ -642,7 +650,7 @@ int igemm_forward(const fhip_conv_param& p, int batch, float* out, const float* 
     g.HW = g.H * g.W;
     g.KHW = g.KH * g.KW;
     const long long ntot = (long long)batch * g.OHW;
-    if (ntot > 0x7fffff00LL) return fail(FHIP_E_BADARG, "N*Ho*Wo exceeds 32-bit column indices");
+    if (ntot > 0x7fffff00LL) return fail(FHIP_E_BADARG, "N*Ho*Wo exceeds 32-bit column indices: more than 0x7fffff00 GEMM columns");
     g.Ntot = (int)ntot;
     g.rag_gpi = 0;
     g.has_bias = p.bias_term != 0;
@@ -732,7 +740,7 @@ int igemm_forward(const fhip_conv_param& p, int batch, float* out, const float* 
         mode = 5;
         g.rag_gpi = (g.OHW + 3) / 4;
         const long long slots = igemm_columns(p, batch);
-        if (slots > 0x7fffff00LL) return fail(FHIP_E_BADARG, "N*Ho*Wo exceeds 32-bit column indices");
+        if (slots > 0x7fffff00LL) return fail(FHIP_E_BADARG, "N*Ho*Wo exceeds 32-bit column indices: more than 0x7fffff00 GEMM columns");
         g.Ntot = (int)slots;
     }
     const bool small = conv_small_m(g.K);
@@ -803,7 +811,7 @@ bool igemm_twin_applicable(const fhip_conv_param& a, const fhip_conv_param& b, i
 int igemm_twin_forward(const fhip_conv_param& a, const fhip_conv_param& b, int batch, float* out_a, float* out_b, const float* in, const float* packed,
                        const float* bias, hipStream_t s)
 {
-    if (!igemm_twin_applicable(a, b, batch)) return fail(FHIP_E_UNSUPPORTED, "these two layers cannot run as one GEMM (fhip_conv_can_fuse_siblings)");
+    if (!igemm_twin_applicable(a, b, batch)) return fail(FHIP_E_UNSUPPORTED, "these two layers cannot run as one GEMM (fhip_conv_can_fuse_siblings): their geometry, or more than 0x7fffff00 GEMM columns");
     const fhip_conv_param p = igemm_twin_geometry(a, b);
     if (p.bias_term && !bias) return fail(FHIP_E_BADARG, "one of the layers has a bias but the concatenated bias is NULL");
     ConvGemmParams g;
@@ -879,7 +887,7 @@ static int dwpw_band_launch(const DwPwBandParams& q, int batch, hipStream_t s)
     DwPwBandParams qq = q;
     qq.m_tiles = q.K / (32 * SH::CW);
     const long long items = (long long)batch * q.groups * qq.m_tiles;
-    if (items > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N * row groups too large");
+    if (items > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N * row groups too large: 2^31 work items or more");
     qq.bands = (int)items;
     // persistent: SH::BPC blocks per CU, each with a contiguous share of the (image, row group, channel block) items
     const int grid = (int)std::min<long long>(items, (long long)device_compute_units() * SH::BPC);
@@ -913,7 +921,7 @@ bool dwpw_applicable(const fhip_conv_param& dw, const fhip_conv_param& pw, int b
 int dwpw_forward(const fhip_conv_param& dw, const fhip_conv_param& pw, int batch, float* out, const float* in, const float* dw_packed,
                  const float* dw_bias, const float* pw_packed, const float* pw_bias, hipStream_t s)
 {
-    if (!dwpw_applicable(dw, pw, batch)) return fail(FHIP_E_UNSUPPORTED, "this depthwise + pointwise pair cannot be fused (fhip_conv_can_fuse_dw_pw)");
+    if (!dwpw_applicable(dw, pw, batch)) return fail(FHIP_E_UNSUPPORTED, "this depthwise + pointwise pair cannot be fused (fhip_conv_can_fuse_dw_pw): its geometry, or more than 0x7fffff00 GEMM columns");
     if (dw.bias_term && !dw_bias) return fail(FHIP_E_BADARG, "depthwise bias_term set but its bias is NULL");
     if (pw.bias_term && !pw_bias) return fail(FHIP_E_BADARG, "pointwise bias_term set but its bias is NULL");
     ConvGemmParams g;

@@ -560,7 +560,7 @@ static int launch_pixels(float* output, const PixelSrc& src, int batch, void* st
     const size_t count = (size_t)batch * src.cout * hw;
     const bool vec = (src.tw % 4) == 0 && ((uintptr_t)output & 15) == 0;
     const size_t total = vec ? count / 4 : count;
-    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large");
+    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large: 2^31 blocks of 256 lanes or more");
     const dim3 grid((unsigned)((total + 255) / 256));
     hipStream_t s = (hipStream_t)stream;
     if (vec)
@@ -599,8 +599,13 @@ static int bad_image(int i, const char* what)
     return fail(FHIP_E_BADARG, msg);
 }
 
-// threads needed: one per float4 plus one per leftover float
-static unsigned ew_grid(size_t n4, size_t n) { return (unsigned)((n4 + (n - n4 * 4) + 255) / 256); }
+// blocks needed: a thread per float4 plus one per leftover float; 0 = more than a grid holds (2^31 - 1 blocks)
+static unsigned ew_grid(size_t n4, size_t n)
+{
+    const size_t blocks = (n4 + (n - n4 * 4) + 255) / 256;
+    return blocks > 0x7fffffffULL ? 0u : (unsigned)blocks;
+}
+static const char* const kEwTooLarge = "tensor too large: 2^31 blocks of 256 lanes or more";
 
 } // namespace fhip
 
@@ -615,7 +620,9 @@ int fhip_relu(float* y, const float* x, size_t count, void* stream)
     if (count == 0) return FHIP_OK;
     const bool vec = (((uintptr_t)y | (uintptr_t)x) & 15) == 0;
     const size_t n4 = vec ? count / 4 : 0;
-    hipLaunchKernelGGL(relu_kernel, dim3(ew_grid(n4, count)), dim3(256), 0, (hipStream_t)stream, y, x, n4, count);
+    const unsigned grid = ew_grid(n4, count);
+    if (!grid) return fail(FHIP_E_BADARG, kEwTooLarge);
+    hipLaunchKernelGGL(relu_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, y, x, n4, count);
     FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
@@ -626,7 +633,9 @@ int fhip_add(float* y, const float* a, const float* b, size_t count, int relu, v
     if (count == 0) return FHIP_OK;
     const bool vec = (((uintptr_t)y | (uintptr_t)a | (uintptr_t)b) & 15) == 0;
     const size_t n4 = vec ? count / 4 : 0;
-    const dim3 grid(ew_grid(n4, count));
+    const unsigned blocks = ew_grid(n4, count);
+    if (!blocks) return fail(FHIP_E_BADARG, kEwTooLarge);
+    const dim3 grid(blocks);
     if (relu)
         hipLaunchKernelGGL(add_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, y, a, b, n4, count);
     else
@@ -641,7 +650,7 @@ int fhip_affine(float* y, const float* x, const float* mul, const float* add, in
     const size_t count = (size_t)batch * channels * hw;
     const bool vec = (hw % 4) == 0 && (((uintptr_t)y | (uintptr_t)x) & 15) == 0;
     const size_t total = vec ? count / 4 : count;
-    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large");
+    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large: 2^31 blocks of 256 lanes or more");
     const dim3 grid((unsigned)((total + 255) / 256));
     hipStream_t s = (hipStream_t)stream;
     if (relu && vec)
@@ -784,6 +793,11 @@ int fhip_pooling(const fhip_pool_param* p, int batch, float* y, const float* x, 
     int rc = fhip_pooling_output_dim(p, &oh, &ow);
     if (rc) return rc;
     if (oh < 1 || ow < 1) return fail(FHIP_E_BADARG, "empty pooling output");
+    // the kernels index planes and the pixels of one plane in int
+    // (0x7fffff00, the column limit of the convolutions: the grids round the plane count up in int)
+    if ((long long)batch * p->channels > 0x7fffff00LL) return fail(FHIP_E_BADARG, "N*C too large: more than 0x7fffff00 planes");
+    if ((long long)oh * ow > 0x7fffffffLL) return fail(FHIP_E_BADARG, "output plane too large: 2^31 elements or more");
+    if ((long long)p->input_h * p->input_w > 0x7fffffffLL) return fail(FHIP_E_BADARG, "plane too large: 2^31 elements or more");
     q.planes = batch * p->channels;
     q.H = p->input_h;
     q.W = p->input_w;

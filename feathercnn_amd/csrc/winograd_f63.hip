@@ -933,7 +933,7 @@ int winograd_plan(const fhip_conv_param& p, int batch, fhip_winograd_plan* plan)
     const int nxi = plan->frequency_points;
     plan->tiles_per_image = plan->tiles_x * plan->tiles_y;
     const long long P = (long long)plan->tiles_per_image * batch;
-    if (P > 0x7fffff00LL) return fail(FHIP_E_BADARG, "too many Winograd tiles for 32-bit column indices");
+    if (P > 0x7fffff00LL) return fail(FHIP_E_BADARG, "too many Winograd tiles for 32-bit column indices: N * tiles per image above 0x7fffff00");
     plan->columns = (int)P;
     plan->column_block = wino_col_block(p, (int)P);
     plan->columns_padded = round_up((int)P, std::max(kWinoColTile, plan->column_block));
@@ -1049,7 +1049,7 @@ int winograd_input_transform(const fhip_conv_param& p, int batch, float* v, cons
     const WinoXformParams q = xform_params(p, batch, pl);
     StageTimer tm(FHIP_STAGE_WINO_INPUT, s);
     const long long work = (long long)q.C * q.P;
-    if ((work + 255) / 256 > 0x7fffffffLL) return fail(FHIP_E_BADARG, "input transform grid too large");
+    if ((work + 255) / 256 > 0x7fffffffLL) return fail(FHIP_E_BADARG, "input transform grid too large: 2^31 blocks of 256 (channel, tile) pairs or more");
     dim3 grid((unsigned)((work + 255) / 256));
     if (pl.frequency_points == 36)
         hipLaunchKernelGGL(wino43_input_transform_kernel, grid, dim3(256), 0, s, v, input, q);
@@ -1080,7 +1080,7 @@ int winograd_input_from_first(const fhip_conv_param& first, const fhip_conv_para
                               const float* first_kernel, const float* first_bias, hipStream_t s)
 {
     if (!winograd_can_fuse_first(first, next, batch))
-        return fail(FHIP_E_UNSUPPORTED, "this first layer cannot be computed inside the next layer's input transform (fhip_conv_can_fuse_first_winograd)");
+        return fail(FHIP_E_UNSUPPORTED, "this first layer cannot be computed inside the next layer's input transform (fhip_conv_can_fuse_first_winograd): its geometry, 2^30 input bytes or more, or more than 65535 output channels");
     if (first.bias_term && !first_bias) return fail(FHIP_E_BADARG, "bias_term set but bias_arr is NULL");
     fhip_winograd_plan pl;
     const int rc = winograd_plan(next, batch, &pl);
@@ -1383,7 +1383,7 @@ int winograd_output_to_next_input(const fhip_conv_param& p, const fhip_conv_para
     g.Lm = wino_layout(g.K, g.Pp, pl.column_block);
     g.Lv2 = wino_layout(g.K, g.Pp2, pn.column_block);
     const long long planes = (long long)batch * g.K;
-    if (planes > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*K too large");
+    if (planes > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*K too large: 2^31 planes or more");
     g.planes = (int)planes;
     g.LDH = 6 * pn.tiles_y + 2;
     g.LDW = 6 * pn.tiles_x + 4;

@@ -653,7 +653,7 @@ static int do_init(const fhip_atrous_param* param, float* packed, const float* k
     if (!aligned(packed, 16) || !aligned(kernel, 4)) return fail(FHIP_E_BADARG, "packed must be 16-byte aligned, kernel 4-byte aligned");
     const fhip_atrous_param& p = *param;
     const size_t total = packed_floats(p, r);
-    if (total > 0x7fffffffULL) return fail(FHIP_E_BADARG, "filter tensor too large");
+    if (total > 0x7fffffffULL) return fail(FHIP_E_BADARG, "filter tensor too large: 2^31 packed floats or more");
     const dim3 grid((unsigned)((total + 255) / 256));
     const int taps = p.kernel_h * p.kernel_w;
     if (is_dw(r))
@@ -725,7 +725,7 @@ static int do_forward(const fhip_atrous_param* param, int batch, float* out, con
         {
             const size_t total = (size_t)p.output_h * a.strips;
             const size_t gy = (total + 255) / 256;
-            if (gy > 65535) return fail(FHIP_E_BADARG, "output plane too large for the depthwise route");
+            if (gy > 65535) return fail(FHIP_E_BADARG, "output plane too large for the depthwise route: more than 65535 blocks of 256 lanes");
             a.total = (unsigned)total;
             const dim3 grid((unsigned)((size_t)batch * p.input_channels), (unsigned)gy);
             switch (r)
@@ -808,7 +808,7 @@ int fhip_atrous_assign_output_dim(fhip_atrous_param* param)
     const long long nw = (long long)param->input_w + param->pad_left + param->pad_right - ((long long)param->dilation_w * (param->kernel_w - 1) + 1);
     if (nh < 0 || nw < 0) return fail(FHIP_E_BADARG, "the dilated kernel extent is larger than the padded input");
     const long long oh = nh / param->stride_h + 1, ow = nw / param->stride_w + 1;
-    if (oh > 0x7fffffffLL || ow > 0x7fffffffLL) return fail(FHIP_E_BADARG, "absurdly large output");
+    if (oh > 0x7fffffffLL || ow > 0x7fffffffLL) return fail(FHIP_E_BADARG, "absurdly large output: 2^31 or more per side");
     param->output_h = (int)oh;
     param->output_w = (int)ow;
     return FHIP_OK;

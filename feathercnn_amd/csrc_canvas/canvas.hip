@@ -357,7 +357,7 @@ static int canvas_chain(int form, const fhip_conv_param& p, const fhip_conv_para
     g.Lm = wino_layout(g.K, pp.columns_padded, pp.column_block);
     g.Lv2 = wino_layout(g.K, pn.columns_padded, pn.column_block);
     const long long planes = (long long)nc * g.K;
-    if (planes > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*K too large");
+    if (planes > 0x7fffffffLL) return fail(FHIP_E_BADARG, "N*K too large: 2^31 canvas planes or more");
     g.planes = (int)planes;
     g.LDH = 6 * pn.tiles_y + 2;
     g.LDW = 6 * pn.tiles_x + 4;

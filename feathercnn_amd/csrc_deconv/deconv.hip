@@ -360,7 +360,7 @@ static int check_geometry(const fhip_deconv_param* p)
     if (p->activation != FHIP_ACT_NONE && p->activation != FHIP_ACT_RELU) return fail(FHIP_E_BADARG, "activation must be None or ReLU");
     const long long oh = (long long)(p->input_h - 1) * p->stride_h + p->kernel_h - p->pad_top - p->pad_bottom + p->output_pad_bottom;
     const long long ow = (long long)(p->input_w - 1) * p->stride_w + p->kernel_w - p->pad_left - p->pad_right + p->output_pad_right;
-    if (oh < 1 || ow < 1 || oh > 0x7fffffffLL || ow > 0x7fffffffLL) return fail(FHIP_E_BADARG, "empty (or absurdly large) output");
+    if (oh < 1 || ow < 1 || oh > 0x7fffffffLL || ow > 0x7fffffffLL) return fail(FHIP_E_BADARG, "empty (or absurdly large: 2^31 or more per side) output");
     return FHIP_OK;
 }
 
@@ -518,7 +518,7 @@ int fhip_deconv_assign_output_dim(fhip_deconv_param* param)
         return fail(FHIP_E_BADARG, "input size, kernel size and stride must be >= 1");
     const long long oh = (long long)(param->input_h - 1) * param->stride_h + param->kernel_h - param->pad_top - param->pad_bottom + param->output_pad_bottom;
     const long long ow = (long long)(param->input_w - 1) * param->stride_w + param->kernel_w - param->pad_left - param->pad_right + param->output_pad_right;
-    if (oh < 1 || ow < 1 || oh > 0x7fffffffLL || ow > 0x7fffffffLL) return fail(FHIP_E_BADARG, "empty (or absurdly large) output");
+    if (oh < 1 || ow < 1 || oh > 0x7fffffffLL || ow > 0x7fffffffLL) return fail(FHIP_E_BADARG, "empty (or absurdly large: 2^31 or more per side) output");
     param->output_h = (int)oh;
     param->output_w = (int)ow;
     return FHIP_OK;
@@ -545,7 +545,7 @@ int fhip_deconv_init(const fhip_deconv_param* param, float* packed, const float*
     const fhip_deconv_param& p = *param;
     const RouteKind r = select(p);
     const size_t total = packed_floats(p);
-    if (total > 0x7fffffffULL) return fail(FHIP_E_BADARG, "filter tensor too large");
+    if (total > 0x7fffffffULL) return fail(FHIP_E_BADARG, "filter tensor too large: 2^31 packed floats or more");
     const dim3 grid((unsigned)((total + 255) / 256));
     if (r == ROUTE_GENERIC)
     {

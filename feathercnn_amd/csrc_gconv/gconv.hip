@@ -354,7 +354,7 @@ int fhip_gconv_init(const fhip_conv_param* param, float* packed, const float* ke
     if (!aligned(packed, 4) || !aligned(kernel, 4)) return fail(FHIP_E_BADARG, "device pointers must be 4-byte aligned");
     const Plan pl = plan_of(*param);
     const size_t total = packed_floats(*param, pl);
-    if (total > 0x7fffffffULL) return fail(FHIP_E_BADARG, "filter tensor too large");
+    if (total > 0x7fffffffULL) return fail(FHIP_E_BADARG, "filter tensor too large: 2^31 packed floats or more");
     hipLaunchKernelGGL(gconv_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, packed, kernel, pl.Cg, pl.Kg,
                        pl.taps, pl.kt, pl.chunks, (unsigned)total);
     GCONV_CHECK_HIP(hipGetLastError());
@@ -392,7 +392,7 @@ int fhip_gconv_forward(const fhip_conv_param* param, int batch, float* out, cons
     a.relu = p.activation == FHIP_ACT_RELU;
     const size_t total = (size_t)batch * p.output_h * a.strips;
     const size_t gy = (size_t)p.group * pl.chunks;
-    if (total > 0x7fffffffULL || gy > 65535) return fail(FHIP_E_BADARG, "tensor too large: more than 2^31 lanes or 65535 channel chunks");
+    if (total > 0x7fffffffULL || gy > 65535) return fail(FHIP_E_BADARG, "tensor too large: 2^31 lanes or more, or more than 65535 channel chunks");
     a.total = (unsigned)total;
     const Route r = select(p, pl, out, in);
     hipLaunchKernelGGL(r.fn, dim3((unsigned)((total + 255) / 256), (unsigned)gy), dim3(256), 0, (hipStream_t)stream, a);

@@ -243,7 +243,7 @@ static int launch(unsigned char* pixels, size_t pitch, const float* x, int batch
     q.per_row = vec ? (target_w + 3) / 4 : target_w;
     q.load4 = vec && !q.resize && (w % 4) == 0 && ((uintptr_t)x & 15) == 0;
     const size_t total = (size_t)batch * target_h * q.per_row;
-    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large");
+    if ((total + 255) / 256 > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large: 2^31 blocks of 256 lanes or more");
     const dim3 grid((unsigned)((total + 255) / 256));
     hipStream_t s = (hipStream_t)stream;
     if (cn == 1)

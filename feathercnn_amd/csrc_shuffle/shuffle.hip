@@ -313,7 +313,7 @@ int fhip_channel_map_create(fhip_channel_map** map, const int* src_channels, int
         if (out_channels[j] < 1) return fail(FHIP_E_BADARG, "every output needs at least one channel");
         rows += out_channels[j];
     }
-    if (rows >= (1L << 24)) return fail(FHIP_E_BADARG, "too many output channels");
+    if (rows >= (1L << 24)) return fail(FHIP_E_BADARG, "too many output channels: 2^24 or more");
     std::vector<int4> table((size_t)rows);
     size_t r = 0;
     for (int j = 0; j < n_out; ++j)

@@ -336,6 +336,26 @@ def tiny_allsorts(seed=7, size=20, dry=False):
     return g.finish() + ("data", "prob")
 
 
+def tiny_plain(seed=31, size=8, dry=False):
+    """A small net of main-library layers only -- Convolution (3x3 on RGB, 1x1, depthwise), Pooling, ReLU, Split, Eltwise, Concat, InnerProduct,
+    Softmax -- whose largest blob (conv1: 32 x size x size) sits right behind the input and whose planes stay too small for Winograd: a batch
+    that takes that blob past 2^31 floats needs no Winograd scratch and about 22 GB in all at size 8."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.relu("relu1", g.conv("conv1", x, 3, 32, 3, 1, 1))
+    x = g.pool("pool1", x, 2, 2)
+    a, b = g.split("split1", x)
+    a = g.relu("relu_a", g.conv("pw_a", a, 32, 32, 1))
+    b = g.conv("dw_b", b, 32, 32, 3, 1, 1, group=32)
+    x = g.relu("relu_sum", g.eltwise("sum", a, b))
+    c, d = g.split("split2", x)
+    c = g.conv("pw_c", c, 32, 16, 1)
+    x = g.concat("cat", [c, d])
+    x = g.pool("gap", x, 1, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc", x, 48, 10))
+    return g.finish() + ("data", "prob")
+
+
 def resnext50_32x4d(seed=1234, classes=1000, size=224, dry=False):
     """Caffe-style ResNeXt-50 (32x4d): 1x1 reduce, grouped 3x3 (32 groups) with the stage's stride, 1x1 expand, BN + Scale + ReLU after
     each, projection shortcuts.  Its grouped layers (1 < group < C) run through libfeather_gconv.so."""

@@ -75,6 +75,10 @@ FHIP_ATROUS_API int fhip_atrous_init(const fhip_atrous_param* param, float* pack
  * no allocation, no copy, no synchronisation: hipGraph-capturable.  `scratch` is unused (may be NULL); `bias` is [K], read only with
  * bias_term.  FHIP_E_BADARG: a refused param, batch < 1, NULL out / in / packed, NULL bias with bias_term, a pointer that is not 4-byte
  * aligned (packed: 16-byte), a tensor of 2^31 elements or more.  FHIP_E_HIP: the launch failed. */
+/* Size limits: FHIP_E_BADARG for 2^31 elements or more in one image (every entry point: fhip_atrous_supported is 0) or in a whole tensor, for
+ * 2^30 GEMM columns or more on an MFMA route, for more than 65535 chunks of 4 output channels on the generic route, for an output plane of more
+ * than 65535 blocks of 256 lanes on the depthwise routes; fhip_atrous_init for 2^31 packed floats or more; fhip_atrous_assign_output_dim for an
+ * output side of 2^31 or more. */
 FHIP_ATROUS_API int fhip_atrous_forward(const fhip_atrous_param* param, int batch, float* out, const float* in, const float* packed, float* scratch,
                                         const float* bias, void* stream);
 

@@ -52,6 +52,8 @@ enum fhip_canvas_form
  * are the plans the two layers RUN with: fhip_winograd_f63_plan(layer, batch) for a plain one, fhip_winograd_f63_plan_canvas(layer,
  * batch, 2) for a canvas one (ENTRY: plain, canvas; INSIDE: canvas, canvas; EXIT: canvas, plain).  One launch on `stream`, no allocation.
  * FHIP_E_BADARG: NULL pointers, plans that do not belong to the layers.  FHIP_E_UNSUPPORTED: a pair this form does not take. */
+/* Size limits: FHIP_E_BADARG at 2^31 canvas planes or more (batch / 4 * output_channels); fhip_canvas_output_transform returns FHIP_E_UNSUPPORTED
+ * for more than 65535 output channels. */
 FHIP_CANVAS_API int fhip_canvas_output_to_next_input(int form, const fhip_conv_param* param, const fhip_conv_param* next, int batch,
                                                      const fhip_winograd_plan* plan, const fhip_winograd_plan* plan_next, float* v_next,
                                                      const float* m, const float* bias, void* stream);

@@ -76,6 +76,9 @@ FHIP_DECONV_API int fhip_deconv_init(const fhip_deconv_param* param, float* pack
  * void*), no allocation, no copy, no synchronisation: hipGraph-capturable.  `scratch` is unused (may be NULL); `bias` is [K], read only
  * with bias_term.  FHIP_E_BADARG: a refused param, batch < 1, NULL out / in / packed, NULL bias with bias_term, a pointer that is not
  * 4-byte aligned (packed: 16-byte), a tensor of 2^31 elements or more.  FHIP_E_HIP: the launch failed. */
+/* Size limits: FHIP_E_BADARG for an input or output tensor of 2^31 elements or more, for 2^30 GEMM columns or more on the MFMA routes (not
+ * reachable: the element limit refuses first), for more than 65535 chunks of 4 output channels on the generic route; fhip_deconv_init for 2^31
+ * packed floats or more; fhip_deconv_assign_output_dim for an output side of 2^31 or more. */
 FHIP_DECONV_API int fhip_deconv_forward(const fhip_deconv_param* param, int batch, float* out, const float* in, const float* packed, float* scratch,
                                         const float* bias, void* stream);
 

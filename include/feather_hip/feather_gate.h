@@ -74,6 +74,8 @@ enum fhip_gate_op
  * are 16-byte aligned, 4-byte accesses otherwise.
  * FHIP_E_BADARG: a dimension < 1, 2^31 elements or more, NULL out / in / gate, a pointer that is not 4-byte aligned, an unknown act.
  * FHIP_E_HIP: a launch failed. */
+/* Size limit (every entry point of this header): FHIP_E_BADARG for a tensor of 2^31 elements or more (n * c * h * w; n * c and c * r for
+ * fhip_excite_forward, whose n is at most 65535).  The kernels index elements in unsigned 32-bit arithmetic up to that limit. */
 FHIP_GATE_API int fhip_channel_gate_forward(int n, int c, int h, int w, float* out, const float* in, const float* gate, const float* residual, int act,
                                             void* stream);
 

@@ -42,6 +42,9 @@ FHIP_GCONV_API int fhip_gconv_init(const fhip_conv_param* param, float* packed, 
  * no allocation, no copy, no synchronisation: hipGraph-capturable.  `scratch` is unused (may be NULL); `bias` is [K], read only with
  * bias_term.  FHIP_E_BADARG: a refused param, batch < 1, NULL out / in / packed, NULL bias with bias_term, a pointer that is not 4-byte
  * aligned, more than 2^31 lanes.  FHIP_E_HIP: the launch failed. */
+/* Size limits: FHIP_E_BADARG at 2^31 lanes or more (batch * Ho * strips of the output row: 4 outputs per strip on the tuned routes, 1 on the
+ * generic one) and for more than 65535 channel chunks; fhip_gconv_init for 2^31 packed floats or more.  Tensors beyond 2^31 elements are
+ * supported within that (64-bit offsets). */
 FHIP_GCONV_API int fhip_gconv_forward(const fhip_conv_param* param, int batch, float* out, const float* in, const float* packed, float* scratch,
                                       const float* bias, void* stream);
 

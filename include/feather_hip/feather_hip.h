@@ -103,6 +103,9 @@ FHIP_API int fhip_conv_select_algo_tuned(const fhip_conv_param* param, int* algo
 /* GET_BUFFER_SIZE_FUNC, include/booster/booster.h:151; per-algo bodies avx/booster.cpp:28-33,64-71,121-128,178-197.
  * Pure and cheap (callers invoke it on every Net::Forward, src/layers/conv_layer.h:105-112).
  * buffer_bytes: scratch for ONE in-flight forward of `batch` images; processed_kernel_bytes: packed weights. */
+/* Size limits, refused with FHIP_E_BADARG here exactly as by fhip_conv_forward: IM2COL / NAIVE beyond 0x7fffff00 GEMM columns (batch * Ho * Wo; for
+ * a 1x1 layer on planes that are no multiple of 4 pixels, batch * 4 * ceil(Ho * Wo / 4) pixel slots), DEPTHWISE at batch * channels of 2^31 planes
+ * or more, WINOGRADF63 beyond 0x7fffff00 tiles (batch * tiles per image). */
 FHIP_API int fhip_conv_get_buffer_size(const fhip_conv_param* param, int algo, int batch, size_t* buffer_bytes,
                                        size_t* processed_kernel_bytes);
 
@@ -124,6 +127,8 @@ FHIP_API int fhip_conv_init(const fhip_conv_param* param, int algo, float* proce
  * input [batch][C][H][W] -> output [batch][K][Ho][Wo]; bias_arr [K] (may be NULL when !bias_term);
  * fused bias / ReLU epilogue selected by param->bias_term / param->activation.  Asynchronous on `stream`;
  * never allocates.  One in-flight forward per `buffer`. */
+/* Size limits: see fhip_conv_get_buffer_size (FHIP_E_BADARG, before any launch).  Tensors and Winograd scratch beyond 2^31 floats are supported
+ * within them. */
 FHIP_API int fhip_conv_forward(const fhip_conv_param* param, int algo, int batch, float* output, const float* input,
                                const float* processed_kernel, float* buffer, const float* bias_arr, void* stream);
 
@@ -150,6 +155,7 @@ typedef struct fhip_winograd_plan
     size_t u_bytes;                 /* U[64][Cp][Kp] = processed kernel                 */
 } fhip_winograd_plan;
 
+/* Size limit: FHIP_E_BADARG beyond 0x7fffff00 tiles (batch * tiles_per_image: the GEMM columns); the stage-level entry points below refuse the same. */
 FHIP_API int fhip_winograd_f63_plan(const fhip_conv_param* param, int batch, fhip_winograd_plan* plan);
 /* The plan of a layer that runs on 2x2 IMAGE CANVASES (feather_canvas.h): four images of one channel on one pad-1 "image" of 2H + 2 pixels
  * per side, a two-pixel zero seam between them -- 14 + 2 + 14 = 30 pixels are exactly 5 tiles (25 for four images instead of 4 x 9),
@@ -166,6 +172,7 @@ FHIP_API int fhip_winograd_f63_canvas_param(const fhip_conv_param* param, int ba
 FHIP_API int fhip_winograd_f63_transform_kernel(const fhip_conv_param* param, float* u, const float* kernel,
                                                 void* stream);
 /* pad_input + winogradInputFrameTransformSeq, avx/generic_kernels.cpp:31-48 + avx/winograd_kernels_F63.cpp:327-513 */
+/* Size limit of its own: FHIP_E_BADARG at 2^31 blocks of 256 (channel, tile) pairs or more (input_channels * tiles >= 2^39 - 255). */
 FHIP_API int fhip_winograd_f63_input_transform(const fhip_conv_param* param, int batch, float* v, const float* input,
                                                void* stream);
 /* TensorGEMM, avx/winograd_kernels_F63.cpp:518-692: M_xi[K x P] = U_xi[K x C] * V_xi[C x P] for 64 xi */

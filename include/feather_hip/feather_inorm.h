@@ -62,6 +62,7 @@ FHIP_INORM_API int fhip_instance_norm_get_buffer_size(int n, int c, int h, int w
  * accesses when h * w is a multiple of 4 and out and in are 16-byte aligned, 4-byte accesses otherwise.
  * FHIP_E_BADARG: a dimension < 1, 2^31 elements or more, NULL out / in, NULL scratch where some is needed, a pointer that is not 4-byte
  * aligned, eps < 0 or not finite, an unknown act.  FHIP_E_HIP: a launch failed. */
+/* Size limit (every entry point of this header): FHIP_E_BADARG for a tensor of 2^31 elements or more (n * c * h * w). */
 FHIP_INORM_API int fhip_instance_norm_forward(int n, int c, int h, int w, float* out, const float* in, const float* gamma, const float* beta,
                                               float eps, int act, float slope, float* scratch, void* stream);
 

@@ -17,6 +17,8 @@ extern "C" {
 /* ---- layer kernels ---------------------------------------------------------------------------------- */
 
 /* ReluLayer::Forward, layers/relu_layer.h:29-41: y = x > 0 ? x : 0 over `count` floats. */
+/* Size limit (fhip_relu, fhip_add): FHIP_E_BADARG at 2^31 blocks of 256 lanes or more -- a lane per float4 on 16-byte aligned pointers, per
+ * float otherwise: about 2^39 floats.  Indices are 64-bit below that. */
 FHIP_API int fhip_relu(float* y, const float* x, size_t count, void* stream);
 
 /* EltwiseLayer::Forward (SUM only) -> booster::add_relu<fuse_relu>, layers/eltwise_layer.h:69-80,
@@ -26,6 +28,7 @@ FHIP_API int fhip_add(float* y, const float* a, const float* b, size_t count, in
 /* booster::scale<bias> (generic_kernels.cpp:203-233) and booster::batchnorm<bias,scale,relu>
  * (generic_kernels.cpp:237-279) are both per-channel affine maps: y[n][c][i] = x[n][c][i]*mul[c] + add[c],
  * optionally followed by ReLU.  mul/add are device vectors of `channels` floats; add may be NULL. */
+/* Size limit: FHIP_E_BADARG at 2^31 blocks of 256 lanes or more (a lane per float4 when hw % 4 == 0 and y, x are 16-byte aligned, else per float). */
 FHIP_API int fhip_affine(float* y, const float* x, const float* mul, const float* add, int batch, int channels, int hw,
                          int relu, void* stream);
 
@@ -61,6 +64,8 @@ enum
  *   mean / norm: HOST arrays of cout floats, or NULL (upstream ncnn's substract_mean_normalize, compiled out of the reference build):
  *     mean only: x - mean; norm only: x * norm; both: x * norm + (-(mean * norm)), rounded after the product and after the sum (no FMA).
  * Asynchronous on `stream` and stream-capturable: no allocation, no copy, everything the kernel needs is passed by value.  One launch. */
+/* Size limit: FHIP_E_BADARG at 2^31 blocks of 256 lanes or more (a lane per output float4 when target_w % 4 == 0 and output is 16-byte aligned,
+ * else per float). */
 FHIP_API int fhip_pixels_to_float(float* output, const unsigned char* pixels, int batch, int type, int w, int h, int target_w, int target_h,
                                   const float* mean, const float* norm, void* stream);
 
@@ -93,6 +98,7 @@ typedef struct fhip_pixel_image
  * batch or target < 1), then written to `plan` as an opaque header (batch, type, target) plus one entry per image (the ROI's first byte,
  * pitch, ROI size, resize flag and the reference's IEEE double scales).  plan = NULL: only *plan_bytes is set, to the size a plan takes;
  * otherwise *plan_bytes is plan's capacity on entry and the size written on return.  `plan` is 8-byte aligned.  Host only. */
+/* Size limit: FHIP_E_BADARG for an image whose row (w * channels) is 2 GiB (2^31 bytes) or longer. */
 FHIP_API int fhip_pixel_images_plan(const fhip_pixel_image* images, int batch, int type, int target_w, int target_h, void* plan,
                                     size_t* plan_bytes);
 /* fhip_pixels_to_float for a planned batch: output image i, of [batch][cout][target_h][target_w] fp32 (4-byte aligned), is
@@ -134,6 +140,7 @@ FHIP_API int fhip_conv_forward_residual(const fhip_conv_param* param, int algo, 
  * -- the range in which one kernel beats two on this chip.  Otherwise fhip_conv_forward_dw_pw returns FHIP_E_UNSUPPORTED (run the two
  * layers one after the other). */
 FHIP_API int fhip_conv_can_fuse_dw_pw(const fhip_conv_param* dw, const fhip_conv_param* pw, int batch);
+/* Size limit: fhip_conv_can_fuse_dw_pw is 0 (and the call FHIP_E_UNSUPPORTED) beyond 0x7fffff00 GEMM columns (batch * Ho * Wo). */
 FHIP_API int fhip_conv_forward_dw_pw(const fhip_conv_param* dw, const fhip_conv_param* pw, int batch, float* output, const float* input,
                                      const float* dw_packed, const float* dw_bias, const float* pw_packed, const float* pw_bias, void* stream);
 
@@ -153,10 +160,13 @@ FHIP_API int fhip_pooling_output_dim(const fhip_pool_param* p, int* out_h, int* 
 /* PoolingLayer::Forward, pooling_layer.h:37-88.  Reference semantics kept exactly: the window origin is
  * j*stride - pad_top - pad_bottom (both pads, :56,:67), windows are clipped to the image, the average
  * divides by the number of in-range taps, an empty window yields -FLT_MAX (max) or NaN (average). */
+/* Size limits: FHIP_E_BADARG for more than 0x7fffff00 planes (batch * channels), and for an input plane (input_h * input_w) or an output plane of 2^31
+ * elements or more (the kernels keep these in int); planes * H * W beyond 2^31 is supported. */
 FHIP_API int fhip_pooling(const fhip_pool_param* p, int batch, float* y, const float* x, void* stream);
 
 /* SoftmaxLayer::Forward, layers/softmax_layer.h:33-53: max-subtracted exp / sum over all
  * `count_per_image` values of each image. */
+/* No size limit below int batch and int count_per_image: a block per row, 64-bit row offsets. */
 FHIP_API int fhip_softmax(float* y, const float* x, int batch, int count_per_image, void* stream);
 
 /* Consecutive Winograd layers without the activation between them.  When layer `p` (WINOGRADF63: 3x3, stride 1) is followed -- directly,
@@ -177,6 +187,7 @@ FHIP_API int fhip_softmax(float* y, const float* x, int batch, int count_per_ima
 FHIP_API int fhip_conv_can_chain_winograd(const fhip_conv_param* param, int algo, const fhip_conv_param* next, int next_algo, int pool);
 FHIP_API int fhip_conv_forward_chained(const fhip_conv_param* param, int batch, float* output, const float* input, const float* packed, float* v,
                                        float* m, const float* bias, const fhip_conv_param* next, float* v_next, int pool, void* stream);
+/* Size limit: FHIP_E_BADARG at batch * output_channels of 2^31 planes or more (and what fhip_winograd_f63_plan refuses). */
 FHIP_API int fhip_winograd_f63_output_to_next_input(const fhip_conv_param* param, const fhip_conv_param* next, int batch, float* v_next,
                                                     const float* m, const float* bias, int pool, void* stream);
 
@@ -192,6 +203,7 @@ FHIP_API int fhip_winograd_f63_output_to_next_input(const fhip_conv_param* param
  *   fhip_conv_forward_siblings: the launch.  Results equal the two layers run on the LDS-tiled route (same tile, same k order). */
 FHIP_API int fhip_conv_can_fuse_siblings(const fhip_conv_param* a, int algo_a, const fhip_conv_param* b, int algo_b, int batch);
 FHIP_API int fhip_conv_siblings_geometry(const fhip_conv_param* a, const fhip_conv_param* b, fhip_conv_param* both);
+/* Size limit: fhip_conv_can_fuse_siblings is 0 (and the call FHIP_E_UNSUPPORTED) beyond 0x7fffff00 GEMM columns (batch * Ho * Wo). */
 FHIP_API int fhip_conv_forward_siblings(const fhip_conv_param* a, const fhip_conv_param* b, int batch, float* output_a, float* output_b,
                                         const float* input, const float* packed_both, const float* bias_both, void* stream);
 
@@ -205,6 +217,9 @@ FHIP_API int fhip_conv_forward_siblings(const fhip_conv_param* a, const fhip_con
  *   fhip_conv_can_fuse_first_winograd: 1 when the pair qualifies at this batch.
  *   fhip_winograd_f63_input_from_first writes next's V (fhip_winograd_plan(next).v_bytes); run the rest of `next` with
  *     fhip_conv_forward_chained(next, ..., input = NULL, v = that buffer, ...). */
+/* Size limits: the pair qualifies while the input holds fewer than 2^30 bytes (4 * batch * c * h * w: 1783 images of 3 x 224 x 224) and the first
+ * layer has at most 65535 output channels; beyond, the query is 0 and fhip_winograd_f63_input_from_first returns FHIP_E_UNSUPPORTED.  Where V of
+ * `next` passes 2^31 bytes (batch 91 of 64 x 224 x 224) another form of the kernel runs: nothing for the caller to do. */
 FHIP_API int fhip_conv_can_fuse_first_winograd(const fhip_conv_param* first, const fhip_conv_param* next, int next_algo, int batch);
 FHIP_API int fhip_winograd_f63_input_from_first(const fhip_conv_param* first, const fhip_conv_param* next, int batch, float* v_next,
                                                 const float* input, const float* first_kernel, const float* first_bias, void* stream);

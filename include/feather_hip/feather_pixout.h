@@ -43,6 +43,8 @@ FHIP_PIXOUT_API int fhip_pixout_channels(int type);
  * +inf and anything above 255 give 255.
  * FHIP_E_BADARG: NULL pixels / x, a misaligned x, batch / sizes < 1, a type fhip_pixout_channels refuses, a pitch smaller than a row,
  * a 1-pixel source axis with a resize, more than 2^31 * 256 lanes.  FHIP_E_HIP: the launch failed. */
+/* Size limit: FHIP_E_BADARG at 2^31 blocks of 256 lanes or more (batch * target_h * lanes per row: 4 pixels per lane where the rows take vector
+ * stores, else one). */
 FHIP_PIXOUT_API int fhip_float_to_pixels(unsigned char* pixels, size_t pitch, const float* x, int batch, int type, int w, int h, int target_w,
                                          int target_h, const float* mean, const float* norm, void* stream);
 

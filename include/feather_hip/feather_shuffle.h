@@ -66,6 +66,8 @@ FHIP_SHUFFLE_API int fhip_channel_slice_resolve(int c, const int* sizes, int cou
 
 /* out[n][c][h][w] = ShuffleChannel(in) as defined above.  FHIP_E_BADARG: an unsupported shape, group < 1, c % group != 0, NULL or
  * misaligned (4 bytes) pointers.  FHIP_E_HIP: the launch failed. */
+/* Size limit (every forward entry point of this header and fhip_channel_map_supported): a tensor of 2^31 elements or more (n * c * h * w, of any
+ * source or output, and n * rows * h * w of a map) is refused with FHIP_E_BADARG; fhip_channel_map_create refuses 2^24 output channels or more. */
 FHIP_SHUFFLE_API int fhip_channel_shuffle_forward(float* out, const float* in, int n, int c, int h, int w, int group, int reverse, void* stream);
 
 /* outs[j][n][sizes_j][h][w] = the j-th slice of in[n][c][h][w]; sizes as in the .param (-233 allowed), count <= FHIP_CHANNEL_MAP_MAX_BLOBS;
