@@ -102,6 +102,7 @@ SIGNATURES = {
     "fhip_net_set_graph": (_I, [_V, _I]),
     "fhip_net_set_tuned_selection": (_I, [_V, _I]),
     "fhip_net_set_dilated": (_I, [_V, _I]),
+    "fhip_net_set_extended_layers": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -232,6 +233,16 @@ GATE_SIGNATURES = {
     "fhip_gate_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_resample.h -- libfeather_resample.so, Interp (nearest / bilinear resize) and HardSwish (a library of its own)
+RESAMPLE_SIGNATURES = {
+    "fhip_interp_output_dim": (_I, [_I, _I, _FL, _FL, _I, _I, _PI, _PI]),
+    "fhip_interp_forward": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _FL, _FL, _V, _V, _V, _I, _V]),
+    "fhip_interp_route": (_I, [_I, _I, _I, _I, _I, _I, _I, _FL, _FL, _V, _V, _V, ctypes.c_char_p, _I]),
+    "fhip_hardswish_forward": (_I, [_V, _V, _I, _I, _I, _FL, _FL, _V]),
+    "fhip_hardswish_route": (_I, [_V, _V, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_resample_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -335,3 +346,13 @@ def load_gate_library():
     """Load libfeather_gate.so (fhip_channel_gate_forward, fhip_squeeze_forward, fhip_excite_forward, fhip_gate_activation_forward).  Fails
     loudly like load_library: there is no fallback implementation."""
     return _load(gate_path(), GATE_SIGNATURES)
+
+
+def resample_path() -> str:
+    return os.path.join(_HERE, "libfeather_resample.so")
+
+
+def load_resample_library():
+    """Load libfeather_resample.so (fhip_interp_forward, fhip_hardswish_forward).  Fails loudly like load_library: there is no fallback
+    implementation."""
+    return _load(resample_path(), RESAMPLE_SIGNATURES)

@@ -40,6 +40,7 @@
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
 #include "feather_hip/feather_net.h"
+#include "feather_hip/feather_resample.h" // declarations only: the library is opened at run time (resample_api)
 #include "feather_hip/feather_shuffle.h" // declarations only: the library is opened at run time (shuffle_api)
 
 namespace fhip
@@ -241,6 +242,23 @@ struct GateApi
     }
 };
 static const GateApi* gate_api() { return side_api<GateApi>(); }
+
+// libfeather_resample.so, the route of the Interp and HardSwish layers of a net with fhip_net_set_extended_layers, and of an Interp
+// collapsed with the Eltwise SUM (and ReLU) behind it at fusion level 2 (collapse_upsample_adds)
+struct ResampleApi
+{
+    decltype(&fhip_interp_output_dim) output_dim = nullptr;
+    decltype(&fhip_interp_forward) interp = nullptr;
+    decltype(&fhip_hardswish_forward) hardswish = nullptr;
+    decltype(&fhip_resample_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_resample.so", "an Interp / HardSwish layer", "feather_resample.h",
+                {{&output_dim, "fhip_interp_output_dim"}, {&interp, "fhip_interp_forward"}, {&hardswish, "fhip_hardswish_forward"},
+                 {&last_error, "fhip_resample_last_error"}}};
+    }
+};
+static const ResampleApi* resample_api() { return side_api<ResampleApi>(); }
 
 // libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases (plan_chains).  The canvas form is a
 // faster way to run the same run of layers, not a layer type: a net that qualifies and cannot find the library fails at plan_chains.
@@ -587,6 +605,7 @@ struct Net
     bool use_graph = false;
     bool tuned_selection = false; // fhip_conv_select_algo_tuned instead of the reference's SelectAlgo rule
     bool dilated = false;         // fhip_net_set_dilated: a Convolution with dilation > 1 is loaded (libfeather_atrous.so) instead of refused
+    bool extended = false;        // fhip_net_set_extended_layers: Interp and HardSwish are loaded (libfeather_resample.so) instead of refused
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;
     // fusion level 3 (plan_chains): runs of Winograd layers hand their transformed input from one to the next; the arena then holds two V
@@ -1699,6 +1718,120 @@ struct GateBlockLayer : PoolingLayer
     int algo() const override { return FHIP_NET_ROUTE_GATE; }
 };
 
+// ncnn's Interp in a net with fhip_net_set_extended_layers (feather_resample.h has the definition): 0 = resize_type (1 nearest, 2
+// bilinear), 1 / 2 = height / width scale, 3 / 4 = output height / width, 6 = align_corner.  A second bottom gives the output size (its
+// height and width) and the params 1 .. 4 are not looked at.  One launch of libfeather_resample.so; nothing is uploaded, so Forward
+// only launches.
+// Fusion level 2 (collapse_upsample_adds): the layer takes over the two-bottom Eltwise SUM that is the sole consumer of its top, and the
+// plain ReLU behind that: `residual_at` is the bottom added after the resize, `relu` the ReLU after the sum -- FPN's upsample-and-add as
+// one launch, the up-sampled tensor never written.
+struct InterpLayer : Layer
+{
+    int mode = 0, out_h = 0, out_w = 0, align = 0;
+    float hs = 1.f, ws = 1.f;
+    size_t sized_by = 0;  // 0: the params; else the index of the bottom whose height and width the output takes
+    int residual_at = -1; // index of the absorbed Eltwise operand among the bottoms, or -1
+    bool relu = false;
+    int LoadParam(const ParamDict& pd) override
+    {
+        if ((bottoms.size() != 1 && bottoms.size() != 2) || tops.size() != 1)
+            return failf(NET_E_SHAPE, "layer %s: Interp needs one or two bottoms and one top, got %zu and %zu", name.c_str(), bottoms.size(), tops.size());
+        mode = pd.get(0, 0);
+        if (mode == 3) return failf(NET_E_SHAPE, "layer %s: Interp resize_type 3 (bicubic) is not supported", name.c_str());
+        if (mode != FHIP_INTERP_NEAREST && mode != FHIP_INTERP_BILINEAR)
+            return failf(NET_E_SHAPE, "layer %s: Interp resize_type %d is not supported (1 nearest, 2 bilinear)", name.c_str(), mode);
+        if (pd.get(5, 0)) return failf(NET_E_SHAPE, "layer %s: Interp dynamic_target_size %d is not supported", name.c_str(), pd.get(5, 0));
+        align = pd.get(6, 0) != 0;
+        if (bottoms.size() == 2)
+        {
+            sized_by = 1;
+            return 0;
+        }
+        hs = pd.get(1, 1.f);
+        ws = pd.get(2, 1.f);
+        out_h = pd.get(3, 0);
+        out_w = pd.get(4, 0);
+        if (out_h < 0 || out_w < 0) return failf(NET_E_SHAPE, "layer %s: Interp output size %d x %d: every dimension must be at least 1", name.c_str(), out_h, out_w);
+        if ((long long)out_h * out_w >= (1ll << 31))
+            return failf(NET_E_SHAPE, "layer %s: Interp output size %d x %d: tensors of 2^31 elements or more are not supported", name.c_str(), out_h, out_w);
+        const float scale[2] = {hs, ws};
+        const int given[2] = {out_h, out_w};
+        for (int a = 0; a < 2; ++a)
+        {
+            if (given[a]) continue;
+            if (!std::isfinite(scale[a]) || !(scale[a] > 0.f))
+                return failf(NET_E_SHAPE, "layer %s: Interp %s scale %g must be finite and positive", name.c_str(), a ? "width" : "height", (double)scale[a]);
+            if (!(scale[a] < 2147483648.f))
+                return failf(NET_E_SHAPE, "layer %s: Interp %s scale %g gives an output dimension of 2^31 or more", name.c_str(), a ? "width" : "height", (double)scale[a]);
+        }
+        return 0;
+    }
+    int Reshape() override
+    {
+        const ResampleApi* api = resample_api();
+        if (!api) return FHIP_E_UNSUPPORTED; // message set by resample_api
+        const Blob* x = bottoms[0];
+        int oh = 0, ow = 0;
+        if (sized_by)
+            oh = bottoms[sized_by]->h, ow = bottoms[sized_by]->w;
+        else if (api->output_dim(x->h, x->w, hs, ws, out_h, out_w, &oh, &ow))
+            return failf(NET_E_SHAPE, "layer %s: %s", name.c_str(), api->last_error());
+        if (x->n < 1 || x->c < 1 || x->h < 1 || x->w < 1 || oh < 1 || ow < 1)
+            return failf(NET_E_SHAPE, "layer %s: Interp %d x %d -> %d x %d: every dimension must be at least 1", name.c_str(), x->h, x->w, oh, ow);
+        if ((long long)x->n * x->c * oh * ow >= (1ll << 31) || x->count() >= ((size_t)1 << 31))
+            return failf(NET_E_SHAPE, "layer %s: Interp to %d x %d: tensors of 2^31 elements or more are not supported", name.c_str(), oh, ow);
+        if (residual_at >= 0)
+        {
+            const Blob* r = bottoms[residual_at];
+            if (r->n != x->n || r->c != x->c || r->h != oh || r->w != ow) return failf(NET_E_SHAPE, "Shape mismatch among bottoms of layer %s.", name.c_str());
+        }
+        return tops[0]->reshape(x->n, x->c, oh, ow);
+    }
+    int Forward(hipStream_t s) override
+    {
+        const ResampleApi* api = resample_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const Blob* x = bottoms[0];
+        const Blob* t = tops[0];
+        // a scale is handed on only where it decided the size
+        const int rc = api->interp(mode, align, x->n, x->c, x->h, x->w, t->h, t->w, sized_by || out_h ? 0.f : hs, sized_by || out_w ? 0.f : ws, t->data, x->data,
+                                   residual_at >= 0 ? bottoms[residual_at]->data : nullptr, relu, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    int algo() const override { return FHIP_NET_ROUTE_RESAMPLE; }
+};
+
+// ncnn's HardSwish in a net with fhip_net_set_extended_layers: 0 = alpha, 1 = beta (defaults 0.2 and 0.5; MobileNet-V3 writes 1/6 and
+// 0.5).  One element-wise launch of libfeather_resample.so.
+struct HardSwishLayer : Layer
+{
+    float alpha = 0.2f, beta = 0.5f;
+    int LoadParam(const ParamDict& pd) override
+    {
+        if (bottoms.size() != 1 || tops.size() != 1)
+            return failf(NET_E_SHAPE, "layer %s: HardSwish needs one bottom and one top, got %zu and %zu", name.c_str(), bottoms.size(), tops.size());
+        alpha = pd.get(0, 0.2f);
+        beta = pd.get(1, 0.5f);
+        if (!std::isfinite(alpha) || !std::isfinite(beta) || alpha == 0.f)
+            return failf(NET_E_SHAPE, "layer %s: HardSwish needs finite alpha and beta and alpha != 0, got %g and %g", name.c_str(), (double)alpha, (double)beta);
+        return 0;
+    }
+    int Reshape() override
+    {
+        if (!resample_api()) return FHIP_E_UNSUPPORTED; // message set by resample_api
+        return Layer::Reshape();
+    }
+    int Forward(hipStream_t s) override
+    {
+        const ResampleApi* api = resample_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const Blob* b = bottoms[0];
+        const int rc = api->hardswish(tops[0]->data, b->data, b->n, b->c, b->h * b->w, alpha, beta, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    int algo() const override { return FHIP_NET_ROUTE_RESAMPLE; }
+};
+
 int ConvLayer::Fuse(Layer* next, int level)
 {
     if (pw) return pw->Fuse(next, level) == 1 ? 1 : 0; // behind the absorbed 1x1 convolution: its own fusions
@@ -2366,6 +2499,76 @@ static void collapse_gate_blocks(Net& net)
     }
 }
 
+// Fusion level 2: FPN's upsample-and-add,
+//
+//   Interp(x [, size]) -> Eltwise SUM (two bottoms, no coefficients) with another blob [-> plain ReLU]
+//
+// where the Interp's top -- and the sum's, if a ReLU follows -- has exactly one consumer, becomes the InterpLayer alone: the other operand is
+// its last bottom (residual_at) and the whole chain is one launch that never writes the up-sampled tensor.  Like collapse_gate_blocks the
+// pass runs before the pairwise Fuse pass and the layer takes the place of the chain's LAST layer in the list: the other operand (FPN's
+// lateral convolution) may be produced between the Interp and the Eltwise layer.  The layer keeps its type and name; the blobs inside the
+// chain refuse Extract.  An Interp whose top has a second consumer stays as written.
+static void collapse_upsample_adds(Net& net)
+{
+    auto sole_consumer = [&](const Blob* b) -> int { // index of the only layer that reads b (once), or -1
+        int uses = 0, at = -1;
+        for (size_t j = 0; j < net.layers.size(); ++j)
+            for (const Blob* x : net.layers[j]->bottoms)
+                if (x == b)
+                {
+                    ++uses;
+                    at = (int)j;
+                }
+        return uses == 1 ? at : -1;
+    };
+    for (size_t i = 0; i < net.layers.size(); ++i)
+    {
+        if (net.layers[i]->type != "Interp") continue;
+        InterpLayer* up = static_cast<InterpLayer*>(net.layers[i].get());
+        if (up->residual_at >= 0 || up->tops.size() != 1) continue;
+        Blob* top = up->tops[0];
+        const int jsum = sole_consumer(top);
+        if (jsum <= (int)i) continue;
+        Layer* sum = net.layers[jsum].get();
+        if (sum->type != "Eltwise" || sum->bottoms.size() != 2 || sum->tops.size() != 1 || sum->bottoms[0] == sum->bottoms[1]) continue;
+        Blob* other = sum->bottoms[0] == top ? sum->bottoms[1] : sum->bottoms[0];
+        Blob* out = sum->tops[0];
+        int last = jsum;
+        bool relu = static_cast<EltwiseLayer*>(sum)->relu;
+        std::vector<Blob*> inner(1, top);
+        if (!relu)
+        {
+            const int jrelu = sole_consumer(out);
+            if (jrelu > jsum && net.layers[jrelu]->bottoms.size() == 1 && net.layers[jrelu]->tops.size() == 1 && is_plain_relu(net.layers[jrelu].get()))
+            {
+                relu = true;
+                inner.push_back(out);
+                out = net.layers[jrelu]->tops[0];
+                last = jrelu;
+            }
+        }
+        up->bottoms.push_back(other);
+        up->residual_at = (int)up->bottoms.size() - 1;
+        up->relu = relu;
+        up->tops[0] = out;
+        for (Blob* b : inner) b->fused_away = true;
+        std::unique_ptr<Layer> moved = std::move(net.layers[i]);
+        net.layers[last] = std::move(moved); // the ReLU (or the Eltwise) is dropped, the Interp stands in its place
+        if (last != jsum) net.layers.erase(net.layers.begin() + jsum);
+        net.layers.erase(net.layers.begin() + i);
+        --i; // the layer that moved into slot i has not been looked at
+    }
+}
+
+// The layer types of a net with fhip_net_set_extended_layers (Net::extended); load_param_text asks here only when create_layer knows no
+// such type and the switch is on.
+static Layer* create_extended_layer(const std::string& type)
+{
+    if (type == "Interp") return new InterpLayer;
+    if (type == "HardSwish") return new HardSwishLayer;
+    return nullptr;
+}
+
 static Layer* create_layer(const std::string& type) // layer_factory.cpp:55-67
 {
     if (type == "Input") return new InputLayer;
@@ -2424,7 +2627,12 @@ static int load_param_text(Net& net, const char* text, size_t len)
         std::string type, name, nb, nt;
         if (!next(type) || !next(name) || !next(nb) || !next(nt)) return failf(NET_E_IO, "param file ends after %d of %d layers", i, layer_count);
         std::unique_ptr<Layer> layer(create_layer(type));
-        if (!layer) return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered", type.c_str());
+        if (!layer && net.extended) layer.reset(create_extended_layer(type));
+        if (!layer)
+        {
+            std::unique_ptr<Layer> opt_in(create_extended_layer(type));
+            return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered%s", type.c_str(), opt_in ? " (fhip_net_set_extended_layers lifts this)" : "");
+        }
         layer->type = type;
         layer->name = name;
         layer->net = &net;
@@ -2505,6 +2713,7 @@ static void fuse_layers(Net& net)
     if (net.fusion <= 0) return;
     if (net.fusion >= 2) collapse_channel_maps(net);
     if (net.fusion >= 2) collapse_gate_blocks(net);
+    if (net.fusion >= 2) collapse_upsample_adds(net);
     for (size_t i = 0; i < net.layers.size(); ++i)
     {
         for (;;)
@@ -2789,6 +2998,7 @@ static int prepare(Net& net)
                                                      l->type != "Split" && l->type != "Eltwise" && l->type != "Concat" && l->type != "Dropout" &&
                                                      l->type != "Sigmoid" && l->type != "TanH" && l->type != "Clip" && l->type != "ShuffleChannel" &&
                                                      l->type != "Slice" && l->type != "BinaryOp" && l->type != "Swish" && l->type != "HardSigmoid" &&
+                                                     l->type != "Interp" && l->type != "HardSwish" &&
                                                      !(l->type == "Scale" && static_cast<ScaleLayer*>(l.get())->gated));
         if (needs) return failf(NET_E_IO, "weights have not been loaded");
     }
@@ -3023,6 +3233,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.use_graph = n->impl.use_graph;
         m->impl.tuned_selection = n->impl.tuned_selection;
         m->impl.dilated = n->impl.dilated;
+        m->impl.extended = n->impl.extended;
         m->impl.concurrency = n->impl.concurrency;
         n->more.push_back(std::move(m));
     }
@@ -3070,6 +3281,15 @@ int fhip_net_set_dilated(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the dilated-convolution switch before LoadParam");
     n->impl.dilated = on != 0;
     for (auto& m : n->more) m->impl.dilated = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_extended_layers(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the extended-layers switch before LoadParam");
+    n->impl.extended = on != 0;
+    for (auto& m : n->more) m->impl.extended = on != 0;
     return FHIP_OK;
 }
 

@@ -210,6 +210,25 @@ class GraphBuilder:
             return self.scale_by(name + "_scale", keep, g)
         return self.binary_mul(name + "_mul", g, keep) if gate_first else self.binary_mul(name + "_mul", keep, g)
 
+    def hard_swish(self, name, bottom, alpha=None, beta=None):
+        """ncnn's HardSwish: y = x * min(max(alpha * x + beta, 0), 1); 0=alpha, 1=beta, written only when given (defaults 0.2 and 0.5).  A
+        net that holds one needs Net.SetExtendedLayers(True)."""
+        return self.layer("HardSwish", name, [bottom], [name], None if alpha is None else {0: f"{alpha:.6f}", 1: f"{0.5 if beta is None else beta:.6f}"})
+
+    def interp(self, name, bottom, mode="bilinear", scale=None, size=None, align_corner=False, like=None):
+        """ncnn's Interp: 0=resize_type (1 nearest, 2 bilinear), 1 / 2 = height / width scale, 3 / 4 = output height / width, 6=align_corner.
+        scale: one value or (height, width); size: (height, width); like: a second bottom whose height and width the output takes.  A net
+        that holds one needs Net.SetExtendedLayers(True)."""
+        params = {0: {"nearest": 1, "bilinear": 2}[mode]}
+        if like is None and size is not None:
+            params.update({3: int(size[0]), 4: int(size[1])})
+        elif like is None:
+            hs, ws = scale if isinstance(scale, (tuple, list)) else (scale, scale)
+            params.update({1: f"{hs:.6f}", 2: f"{ws:.6f}"})
+        if align_corner:
+            params[6] = 1
+        return self.layer("Interp", name, [bottom] + ([like] if like is not None else []), [name], params)
+
     def conv_bn_swish(self, name, bottom, cin, cout, k, s=1, p=0, group=1, swish=True):
         x = self.conv_bn_relu(name, bottom, cin, cout, k, s, p, group, relu=False)
         return self.swish(name + "_swish", x) if swish else x
@@ -770,6 +789,170 @@ def efficientnet_b0(seed=1234, classes=1000, size=224, dry=False):
     return g.finish() + ("data", "prob")
 
 
+def tiny_resample(seed=37, size=24, dry=False):
+    """A small net of Interp and HardSwish layers in every form the Net runtime has to get right, nothing above 24 px
+    (Net.SetExtendedLayers(True)): HardSwish with ncnn's defaults and with MobileNet-V3's 1/6 and 0.5; `up1`, a nearest x2 whose top is read
+    by the Eltwise `sum1` alone, with a ReLU behind it (fusion level 2 makes the three one layer; the sum's other operand, `lat`, is produced
+    between them); `up2`, a second nearest x2 whose top has two readers and must stay as written; `shrink` and `aligned`, bilinear layers
+    with a scale per axis that turn the 12 x 12 plane into 5 x 7 and (align_corner) 9 x 13; `to_ref`, bilinear to the size of a second
+    bottom (5 x 7 -> 9 x 13); `down`, nearest from 12 x 12 to a given 5 x 5.  Every size but the last follows the input's."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.hard_swish("hs1", g.conv("conv1", x, 3, 8, 3, 1, 1))                          # ncnn's defaults, 24 x 24
+    big, x = g.split("split0", x)
+    x = g.hard_swish("hs2", g.conv("conv2", x, 8, 16, 3, 2, 1), 1.0 / 6, 0.5)           # 12 x 12
+    lat_in, down_in, odd_in = g.split("split1", x, 3)
+    y = g.relu("relu3", g.conv("conv3", down_in, 16, 16, 3, 2, 1))                      # 6 x 6
+    up1 = g.interp("up1", y, "nearest", scale=2.0)                                      # 12 x 12
+    lat = g.conv("lat", lat_in, 16, 16, 1)                                              # produced between up1 and sum1
+    x = g.relu("sum1_relu", g.eltwise("sum1", lat, up1))                                # up1 -> sum1 -> sum1_relu: one layer at level 2
+    s_a, s_b, s_c = g.split("split2", x, 3)
+    up2 = g.interp("up2", s_a, "nearest", scale=2.0)                                    # 24 x 24, read by `side` and by `sum2`
+    side = g.conv("side", up2, 16, 8, 1)
+    t = g.eltwise("sum2", up2, g.conv("big_pw", big, 8, 16, 1))
+    head_a = g.pool("gap_a", g.concat("cat_a", [t, side]), 1, 1, avg=True, global_=True)
+    q = g.interp("shrink", odd_in, "bilinear", scale=(0.45, 0.6))                       # 12 x 12 -> 5 x 7
+    ref_a, ref_b = g.split("split3", g.interp("aligned", s_b, "bilinear", scale=(0.75, 1.1), align_corner=True))  # 12 x 12 -> 9 x 13
+    q = g.relu("q_relu", g.conv("q_conv", q, 16, 16, 3, 1, 1))
+    z = g.interp("to_ref", q, "bilinear", like=ref_a)                                   # 5 x 7 -> 9 x 13, the size of its second bottom
+    head_b = g.pool("gap_b", g.concat("cat_b", [z, ref_b]), 1, 1, avg=True, global_=True)
+    d = g.interp("down", s_c, "nearest", size=(5, 5))                                   # 12 x 12 -> 5 x 5, the size given
+    head_c = g.pool("gap_c", g.relu("d_relu", g.conv("d_conv", d, 16, 8, 3, 1, 0)), 1, 1, avg=True, global_=True)
+    x = g.concat("heads", [head_a, head_b, head_c])
+    x = g.softmax("prob", g.fc("fc", x, 64, 10))
+    return g.finish() + ("data", "prob")
+
+
+def _divisible(v, d=8):
+    """MobileNet's channel rounding: to the nearest multiple of d, at least d and never below 90 % of v."""
+    n = max(d, int(v + d / 2) // d * d)
+    return n + d if n < 0.9 * v else n
+
+
+def _mobilenet_v3(g, rows, last, hidden, classes, size, se_gain=lambda unit: 1.0):
+    """The layers both MobileNet-V3 nets share; rows: (kernel, expansion, out, SE, activation, stride).  se_gain(unit) scales the first
+    excite layer of that unit (se_block's `gain`)."""
+    hs = lambda nm, t: g.hard_swish(nm + "_hs", t, 1.0 / 6, 0.5)
+    x = g.input("data", 3, size, size)
+    x = hs("conv1", g.conv_bn_relu("conv1", x, 3, 16, 3, 2, 1, relu=False))
+    cin = 16
+    for i, (k, exp, cout, se, act, s) in enumerate(rows, 1):
+        tag = f"b{i}"
+        nl = hs if act == "HS" else (lambda nm, t: g.relu(nm + "_relu", t))
+        residual = s == 1 and cin == cout
+        if residual:
+            x, short = g.split(tag + "_split", x)
+        y = x
+        if exp != cin:
+            y = nl(tag + "_expand", g.conv_bn_relu(tag + "_expand", y, cin, exp, 1, relu=False))
+        y = nl(tag + "_dw", g.conv_bn_relu(tag + "_dw", y, exp, exp, k, s, k // 2, group=exp, relu=False))
+        if se:
+            y = g.se_block(tag + "_se", y, exp, _divisible(exp / 4), "converter", mact="relu", gact="hard_sigmoid", alpha=1.0 / 6, beta=0.5, gain=se_gain(i))
+        y = g.conv_bn_relu(tag + "_project", y, exp, cout, 1, relu=False)
+        x = g.eltwise(tag + "_add", short, y) if residual else y
+        cin = cout
+    x = hs("conv_last", g.conv_bn_relu("conv_last", x, cin, last, 1, relu=False))
+    x = g.pool("gap", x, 1, 1, avg=True, global_=True)
+    x = hs("fc1", g.conv("fc1", x, last, hidden, 1, type_="Convolution"))
+    x = g.softmax("prob", g.conv("fc2", x, hidden, classes, 1, type_="Convolution"))
+    return g.finish() + ("data", "prob")
+
+
+def mobilenet_v3_large(seed=1234, classes=1000, size=224, dry=False):
+    """MobileNet-V3-Large (Howard et al. 2019) in the converters' spelling: inverted-residual units of a 1x1 expansion, a 3x3 or 5x5
+    depthwise convolution, a squeeze-and-excitation block (reduction to a quarter, rounded to a multiple of 8; ReLU inside, a
+    HardSigmoid(1/6, 0.5) gate, BinaryOp mul) and a 1x1 projection; ReLU in the early units, HardSwish(1/6, 0.5) in the stem, the late units
+    and the tail; residuals as Eltwise.  BatchNorm + Scale behind every convolution outside the SE blocks and the classifier.  With these
+    random weights the activations grow by about the square root of two per unit, and the gate's logits with them: by the late units every
+    HardSigmoid gate would be a step function of its logit's sign, which turns the fp32 rounding of a logit next to zero into a gate error
+    of one.  So the first excite layer of unit k is scaled by 2^(-k/2), as in `se_resnet50`, and the gates stay inside their ramp as in a
+    trained net.  Net.SetExtendedLayers(True)."""
+    rows = [(3, 16, 16, 0, "RE", 1), (3, 64, 24, 0, "RE", 2), (3, 72, 24, 0, "RE", 1), (5, 72, 40, 1, "RE", 2), (5, 120, 40, 1, "RE", 1),
+            (5, 120, 40, 1, "RE", 1), (3, 240, 80, 0, "HS", 2), (3, 200, 80, 0, "HS", 1), (3, 184, 80, 0, "HS", 1), (3, 184, 80, 0, "HS", 1),
+            (3, 480, 112, 1, "HS", 1), (3, 672, 112, 1, "HS", 1), (5, 672, 160, 1, "HS", 2), (5, 960, 160, 1, "HS", 1), (5, 960, 160, 1, "HS", 1)]
+    return _mobilenet_v3(GraphBuilder(seed, dry), rows, 960, 1280, classes, size, se_gain=lambda unit: 2.0 ** (-0.5 * unit))
+
+
+def mobilenet_v3_small(seed=1234, classes=1000, size=224, dry=False):
+    """MobileNet-V3-Small: `mobilenet_v3_large`'s units in the paper's small configuration.  Net.SetExtendedLayers(True)."""
+    rows = [(3, 16, 16, 1, "RE", 2), (3, 72, 24, 0, "RE", 2), (3, 88, 24, 0, "RE", 1), (5, 96, 40, 1, "HS", 2), (5, 240, 40, 1, "HS", 1),
+            (5, 240, 40, 1, "HS", 1), (5, 120, 48, 1, "HS", 1), (5, 144, 48, 1, "HS", 1), (5, 288, 96, 1, "HS", 2), (5, 576, 96, 1, "HS", 1),
+            (5, 576, 96, 1, "HS", 1)]
+    return _mobilenet_v3(GraphBuilder(seed, dry), rows, 576, 1024, classes, size)
+
+
+def deeplab_largefov_full(seed=1234, classes=21, size=321, dry=False):
+    """`deeplab_largefov` with its last layer: the class scores (1/8 resolution) resized to the input's size by a bilinear Interp.
+    Net.SetDilated(True) and Net.SetExtendedLayers(True)."""
+    g = GraphBuilder(seed, dry)
+    x = _deeplab_head(g, _deeplab_trunk(g, size), "", 12, classes)
+    g.interp("fc8_interp", x, "bilinear", size=(size, size))
+    return g.finish() + ("data", "fc8_interp")
+
+
+def unet_bilinear(seed=1234, size=256, dry=False):
+    """`unet_k4` with a bilinear Interp x2 and a 3x3 convolution where that net has a k4 s2 p1 Deconvolution: the decoder of U-Nets that
+    avoid the checkerboard of transposed convolutions.  Net.SetExtendedLayers(True)."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    widths = (32, 64, 128, 256, 256)
+    skips, cin = [], 3
+    for i, cw in enumerate(widths, 1):
+        x = g.relu(f"e{i}_relu", g.conv(f"e{i}", x, cin, cw, 4, 2, 1)) if i == 1 else g.conv_bn_relu(f"e{i}", x, cin, cw, 4, 2, 1)
+        cin = cw
+        if i < len(widths):
+            x, skip = g.split(f"e{i}_split", x)
+            skips.append((skip, cw))
+    for i, cw in zip((5, 4, 3, 2), (256, 128, 64, 32)):
+        x = g.conv_bn_relu(f"d{i}", g.interp(f"u{i}", x, "bilinear", scale=2.0), cin, cw, 3, 1, 1)
+        skip, sw = skips.pop()
+        x = g.concat(f"cat{i - 1}", [x, skip])
+        cin = cw + sw
+    x = g.conv("d1", g.interp("u1", x, "bilinear", scale=2.0), cin, 3, 3, 1, 1)
+    return g.finish() + ("data", "d1")
+
+
+FPN_OUTPUTS = ("fpn_p2", "fpn_p3", "fpn_p4", "fpn_p5")
+
+
+def fpn_resnet50(seed=1234, size=224, dry=False):
+    """A feature pyramid network (Lin et al. 2017) on `resnet50`'s stages: C2 .. C5 (256 .. 2048 channels at strides 4 .. 32), a 1x1 lateral
+    convolution to 256 channels on each, the top-down path -- a nearest Interp of the level above to the lateral's size (x2), added to it --
+    and a 3x3 output convolution per level.  The outputs are FPN_OUTPUTS; the builder names the finest.  Net.SetExtendedLayers(True)."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_relu("conv1", x, 3, 64, 7, 2, 3)
+    x = g.pool("pool1", x, 3, 2)
+    cin, feats = 64, []
+    for si, (mid, out, blocks, stride) in enumerate([(64, 256, 3, 1), (128, 512, 4, 2), (256, 1024, 6, 2), (512, 2048, 3, 2)]):
+        for b in range(blocks):
+            s = stride if b == 0 else 1
+            tag = f"res{si + 2}{chr(ord('a') + b)}"
+            main, short = g.split(tag + "_split", x)
+            if b == 0:
+                short = g.conv_bn_relu(tag + "_branch1", short, cin, out, 1, s, 0, relu=False)
+            y = g.conv_bn_relu(tag + "_branch2a", main, cin, mid, 1, s, 0)
+            y = g.conv_bn_relu(tag + "_branch2b", y, mid, mid, 3, 1, 1)
+            y = g.conv_bn_relu(tag + "_branch2c", y, mid, out, 1, 1, 0, relu=False)
+            x = g.relu(tag + "_relu", g.eltwise(tag, short, y))
+            cin = out
+        if si < 3:
+            x, c = g.split(f"c{si + 2}_split", x)
+        else:
+            c = x
+        feats.append((c, out))
+    top = None
+    for level in (5, 4, 3, 2):
+        c, width = feats[level - 2]
+        m = g.conv(f"fpn_lat{level}", c, width, 256, 1)
+        if top is not None:
+            m = g.eltwise(f"fpn_sum{level}", m, g.interp(f"fpn_up{level}", top, "nearest", like=m))
+        if level > 2:
+            m, top = g.split(f"fpn_m{level}_split", m)
+        g.conv(f"fpn_p{level}", m, 256, 256, 3, 1, 1)
+    return g.finish() + ("data", "fpn_p2")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
@@ -778,14 +961,24 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_generative": tiny_generative, "style_transfer_in": style_transfer_in, "pix2pix_unet": pix2pix_unet,
           "tiny_shuffle": tiny_shuffle, "shufflenet_v2_x1_0": shufflenet_v2_x1_0, "shufflenet_v1_g3": shufflenet_v1_g3,
           "tiny_dilated": tiny_dilated, "deeplab_largefov": deeplab_largefov, "deeplab_v2_aspp": deeplab_v2_aspp,
-          "tiny_se": tiny_se, "se_resnet50": se_resnet50, "efficientnet_b0": efficientnet_b0}
+          "tiny_se": tiny_se, "se_resnet50": se_resnet50, "efficientnet_b0": efficientnet_b0,
+          "tiny_resample": tiny_resample, "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small,
+          "deeplab_largefov_full": deeplab_largefov_full, "unet_bilinear": unet_bilinear, "fpn_resnet50": fpn_resnet50}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
 # nets that need Net.SetDilated(True), and the layers of each that run through libfeather_atrous.so
 DILATED_LAYERS = {"tiny_dilated": ("a1", "a2", "a3", "a_dw", "a_g", "a_far"),
                   "deeplab_largefov": ("conv5_1", "conv5_2", "conv5_3", "fc6"),
-                  "deeplab_v2_aspp": ("conv5_1", "conv5_2", "conv5_3", "fc6_1", "fc6_2", "fc6_3", "fc6_4")}
+                  "deeplab_v2_aspp": ("conv5_1", "conv5_2", "conv5_3", "fc6_1", "fc6_2", "fc6_3", "fc6_4"),
+                  "deeplab_largefov_full": ("conv5_1", "conv5_2", "conv5_3", "fc6")}
+
+# nets that need Net.SetExtendedLayers(True) (Interp, HardSwish: libfeather_resample.so)
+EXTENDED_NETS = ("tiny_resample", "mobilenet_v3_large", "mobilenet_v3_small", "deeplab_largefov_full", "unet_bilinear", "fpn_resnet50")
+
+# the Interp layers of each net that fusion level 2 collapses with the Eltwise SUM (and ReLU) behind them, and those that must stay
+UPSAMPLE_ADDS = {"tiny_resample": (("up1",), ("up2", "shrink", "aligned", "to_ref", "down")),
+                 "fpn_resnet50": (("fpn_up4", "fpn_up3", "fpn_up2"), ())}
 
 # the squeeze-and-excitation blocks of each net (the name fusion level 2 keeps: the block's Pooling layer) that collapse into one layer,
 # and those that must not

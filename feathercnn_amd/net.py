@@ -25,6 +25,8 @@ ROUTE_ATROUS = 104  # FHIP_NET_ROUTE_ATROUS: a Convolution layer with dilation >
 ROUTE_NAMES[ROUTE_ATROUS] = "ATROUS"
 ROUTE_GATE = 105  # FHIP_NET_ROUTE_GATE: a two-bottom BinaryOp mul / Scale -233, Swish, HardSigmoid, or a collapsed SE block (libfeather_gate.so)
 ROUTE_NAMES[ROUTE_GATE] = "GATE"
+ROUTE_RESAMPLE = 106  # FHIP_NET_ROUTE_RESAMPLE: an Interp or HardSwish layer, after SetExtendedLayers(True) (libfeather_resample.so)
+ROUTE_NAMES[ROUTE_RESAMPLE] = "RESAMPLE"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -53,6 +55,11 @@ class Net:
         """feather::Net::SetDilated: accept Convolution layers with dilation > 1 (routed to libfeather_atrous.so) instead of refusing them
         at LoadParam.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_dilated(self._h, int(bool(on))), "fhip_net_set_dilated")
+
+    def SetExtendedLayers(self, on: bool = True):
+        """feather::Net::SetExtendedLayers: accept Interp and HardSwish layers (routed to libfeather_resample.so) instead of refusing them
+        at LoadParam.  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_extended_layers(self._h, int(bool(on))), "fhip_net_set_extended_layers")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

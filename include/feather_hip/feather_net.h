@@ -244,7 +244,8 @@ FHIP_API int fhip_net_get_stream(fhip_net* net, void** stream);
  *   2: + BatchNorm / Scale folded into the convolution before them, Conv + 2x2 max pooling, Conv + Eltwise SUM (+ReLU), a 3x3
  *      depthwise layer + the 1x1 convolution behind it as one layer (fhip_conv_forward_dw_pw where the pair qualifies), and two 1x1
  *      convolutions of the same input that follow each other as one GEMM (fhip_conv_forward_siblings; both blobs keep their storage);
- *      a squeeze-and-excitation block as one layer (FHIP_NET_ROUTE_GATE).
+ *      a squeeze-and-excitation block as one layer (FHIP_NET_ROUTE_GATE); Interp + Eltwise SUM (+ReLU) as one layer
+ *      (FHIP_NET_ROUTE_RESAMPLE).
  *   3: + runs of Winograd layers chained (fhip_conv_forward_chained): the blob between two chained layers has a shape but no storage;
  *      a first layer (3x3 / stride 1 / pad 1, 2 .. 4 input channels) in front of a Winograd layer is computed inside that layer's input
  *      transform (fhip_winograd_f63_input_from_first): its top has no storage either.
@@ -258,6 +259,12 @@ FHIP_API int fhip_net_set_tuned_selection(fhip_net* net, int on);
  * tests/test_net_cpu.py pins that answer for a default net; flip it when that test is next revised.  Its only effect is lifting that
  * refusal (a dilated Deconvolution stays refused).  Call before LoadParam; later it is FHIP_E_BADARG. */
 FHIP_API int fhip_net_set_dilated(fhip_net* net, int on);
+/* 1: the layer types Interp (nearest / bilinear resize; one bottom, or two where the second gives the output size) and HardSwish are loaded
+ * and run through libfeather_resample.so (feather_resample.h has their definitions; route code FHIP_NET_ROUTE_RESAMPLE); 0 (default):
+ * LoadParam refuses them with -200, as tests/test_inorm_cpu.py and tests/test_gate_cpu.py pin for a default net.  Its only effect is
+ * lifting that refusal: PixelShuffle stays -200 and a bicubic Interp -100.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to
+ * sub-batch replicas. */
+FHIP_API int fhip_net_set_extended_layers(fhip_net* net, int on);
 /* 1: independent branches run concurrently: a convolution that needs no scratch arena and whose output is only consumed
  * further down the layer list (ResNet's projection shortcut, SqueezeNet's expand1x1) is enqueued on a second stream owned by
  * the net while the main stream continues; fork and join are events (hipGraph-capturable).  0 (default): one stream. */
@@ -354,6 +361,13 @@ FHIP_API int fhip_net_layer_count(fhip_net* net);
  * and name of the block's Pooling layer and stands where the block's last layer stood; the blobs between them cannot be extracted.  The
  * pass runs before the pairwise fusions, so the excite layers are matched as written.  Reported from LoadParam on. */
 #define FHIP_NET_ROUTE_GATE 105
+/* Route code of an Interp or HardSwish layer in a net with fhip_net_set_extended_layers: one launch of libfeather_resample.so
+ * (feather_resample.h), opened the same way the first time a net holds such a layer.  At fusion level 2 an Interp whose top has a sole
+ * consumer, a two-bottom Eltwise SUM, takes that sum over, and the plain ReLU behind it if that is the sum's sole consumer (FPN's
+ * upsample-and-add): one layer of one launch that keeps the Interp's type and name, has the sum's other operand as its last bottom and
+ * stands where the chain's last layer stood; the up-sampled tensor is never written and the blobs inside the chain cannot be extracted.
+ * No other fusion takes these layers.  Reported from LoadParam on. */
+#define FHIP_NET_ROUTE_RESAMPLE 106
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
  * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);

@@ -13,10 +13,19 @@ from feathercnn_amd import model_zoo  # noqa: E402
 from feathercnn_amd.net import Net  # noqa: E402
 
 
+def switches(net, name):
+    """The opt-in layer families a zoo net needs (Net.SetDilated, Net.SetExtendedLayers), set before LoadParam."""
+    if name in model_zoo.DILATED_LAYERS:
+        net.SetDilated(True)
+    if name in model_zoo.EXTENDED_NETS:
+        net.SetExtendedLayers(True)
+
+
 def run(name, batch, fusion, steps=10):
     t0 = time.time()
     p, b, i, o = model_zoo.MODELS[name]()
     net = Net(fusion=fusion, graph=False, tuned=True)
+    switches(net, name)
     net.LoadParam(p)
     net.LoadWeights(b)
     del b
@@ -47,6 +56,7 @@ def run(name, batch, fusion, steps=10):
     print("   slowest:", ", ".join(f"{nm}({typ[:4]}) {ms:.3f}" for typ, nm, algo, ms in worst))
     net.close()
     net = Net(fusion=fusion, graph=True, tuned=True)
+    switches(net, name)
     net.LoadParam(p)
     net.LoadWeights(model_zoo.MODELS[name]()[1])
     net.FeedInput(i, x)
