@@ -243,6 +243,17 @@ RESAMPLE_SIGNATURES = {
     "fhip_resample_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_lrn.h -- libfeather_lrn.so, local response normalisation alone and with the Pooling layer behind it (a library
+# of its own)
+LRN_SIGNATURES = {
+    "fhip_lrn_forward": (_I, [_I, _I, _FL, _FL, _FL, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_lrn_forward_chunked": (_I, [_I, _FL, _FL, _FL, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_lrn_route": (_I, [_I, _I, _I, _I, _I, _I, _V, _V, ctypes.c_char_p, _I]),
+    "fhip_lrn_pool_forward": (_I, [_I, _I, _FL, _FL, _FL, _I, _I, _I, _I, _Q, _V, _V, _V]),
+    "fhip_lrn_pool_route": (_I, [_I, _I, _I, _I, _I, _I, _Q, _V, _V, ctypes.c_char_p, _I]),
+    "fhip_lrn_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -356,3 +367,13 @@ def load_resample_library():
     """Load libfeather_resample.so (fhip_interp_forward, fhip_hardswish_forward).  Fails loudly like load_library: there is no fallback
     implementation."""
     return _load(resample_path(), RESAMPLE_SIGNATURES)
+
+
+def lrn_path() -> str:
+    return os.path.join(_HERE, "libfeather_lrn.so")
+
+
+def load_lrn_library():
+    """Load libfeather_lrn.so (fhip_lrn_forward, fhip_lrn_pool_forward).  Fails loudly like load_library: there is no fallback
+    implementation."""
+    return _load(lrn_path(), LRN_SIGNATURES)

@@ -39,6 +39,7 @@
 #include "feather_hip/feather_gate.h" // declarations only: the library is opened at run time (gate_api)
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
+#include "feather_hip/feather_lrn.h" // declarations only: the library is opened at run time (lrn_api)
 #include "feather_hip/feather_net.h"
 #include "feather_hip/feather_resample.h" // declarations only: the library is opened at run time (resample_api)
 #include "feather_hip/feather_shuffle.h" // declarations only: the library is opened at run time (shuffle_api)
@@ -259,6 +260,21 @@ struct ResampleApi
     }
 };
 static const ResampleApi* resample_api() { return side_api<ResampleApi>(); }
+
+// libfeather_lrn.so, the route of the LRN layers of a net with fhip_net_set_extended_layers, alone or with the Pooling layer behind them
+// (LRNLayer::Fuse at fusion level 2)
+struct LrnApi
+{
+    decltype(&fhip_lrn_forward) forward = nullptr;
+    decltype(&fhip_lrn_pool_forward) pool_forward = nullptr;
+    decltype(&fhip_lrn_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_lrn.so", "an LRN layer", "feather_lrn.h",
+                {{&forward, "fhip_lrn_forward"}, {&pool_forward, "fhip_lrn_pool_forward"}, {&last_error, "fhip_lrn_last_error"}}};
+    }
+};
+static const LrnApi* lrn_api() { return side_api<LrnApi>(); }
 
 // libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases (plan_chains).  The canvas form is a
 // faster way to run the same run of layers, not a layer type: a net that qualifies and cannot find the library fails at plan_chains.
@@ -605,7 +621,7 @@ struct Net
     bool use_graph = false;
     bool tuned_selection = false; // fhip_conv_select_algo_tuned instead of the reference's SelectAlgo rule
     bool dilated = false;         // fhip_net_set_dilated: a Convolution with dilation > 1 is loaded (libfeather_atrous.so) instead of refused
-    bool extended = false;        // fhip_net_set_extended_layers: Interp and HardSwish are loaded (libfeather_resample.so) instead of refused
+    bool extended = false;        // fhip_net_set_extended_layers: Interp, HardSwish (libfeather_resample.so) and LRN (libfeather_lrn.so) are loaded instead of refused
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;
     // fusion level 3 (plan_chains): runs of Winograd layers hand their transformed input from one to the next; the arena then holds two V
@@ -1832,6 +1848,91 @@ struct HardSwishLayer : Layer
     int algo() const override { return FHIP_NET_ROUTE_RESAMPLE; }
 };
 
+// ncnn's LRN in a net with fhip_net_set_extended_layers (feather_lrn.h has the definition): 0 = region_type (0 across channels, 1 within
+// channel), 1 = local_size (5), 2 = alpha (1), 3 = beta (0.75), 4 = bias (1).  One launch of libfeather_lrn.so; nothing is uploaded, so
+// Forward only launches.
+// Fusion level 2 (Fuse): the layer takes over the non-global Pooling layer that alone reads its top -- AlexNet's and GoogLeNet's norm -> pool
+// -- and its top becomes the pooled tensor; the normalised one has no blob.  Up to kLrnOneLaunchMax elements it runs fhip_lrn_pool_forward:
+// one launch, the normalised tensor never written.  Above, where that kernel measured slower than the two, and where the
+// pooling window covers the whole unpadded plane (fhip_pooling's plane-reduce route, which the one launch does not restate), it runs
+// fhip_lrn_forward into the net's scratch arena and fhip_pooling from there.  Both are bit for bit the two layers.
+// GoogLeNet's conv2/norm2 at batch 4, the largest of the six measured tensors (0.19 M .. 2.4 M elements) at which one launch was faster than
+// the pair; the next larger one measured (6.0 M, AlexNet's norm2 at batch 32) was slower
+constexpr size_t kLrnOneLaunchMax = 4 * 192 * 56 * 56;
+struct LRNLayer : Layer
+{
+    int region = 0, local_size = 5;
+    float alpha = 1.f, beta = 0.75f, bias = 1.f;
+    bool pooled = false; // q is the absorbed Pooling layer's
+    size_t scratch_bytes = 0; // pooled, and too large for one launch to pay: the normalised tensor goes through the arena
+    fhip_pool_param q;
+    LRNLayer() { memset(&q, 0, sizeof(q)); }
+    int LoadParam(const ParamDict& pd) override
+    {
+        if (bottoms.size() != 1 || tops.size() != 1)
+            return failf(NET_E_SHAPE, "layer %s: LRN needs one bottom and one top, got %zu and %zu", name.c_str(), bottoms.size(), tops.size());
+        region = pd.get(0, 0);
+        local_size = pd.get(1, 5);
+        alpha = pd.get(2, 1.f);
+        beta = pd.get(3, 0.75f);
+        bias = pd.get(4, 1.f);
+        if (region != FHIP_LRN_ACROSS_CHANNELS && region != FHIP_LRN_WITHIN_CHANNEL)
+            return failf(NET_E_SHAPE, "layer %s: LRN region_type %d is not supported (0 across channels, 1 within channel)", name.c_str(), region);
+        if (local_size < 1 || local_size % 2 == 0)
+            return failf(NET_E_SHAPE, "layer %s: LRN local_size %d must be odd and at least 1", name.c_str(), local_size);
+        if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(bias))
+            return failf(NET_E_SHAPE, "layer %s: LRN needs finite alpha, beta and bias, got %g, %g and %g", name.c_str(), (double)alpha, (double)beta, (double)bias);
+        if (!(bias > 0.f) || alpha < 0.f)
+            return failf(NET_E_SHAPE, "layer %s: LRN needs bias > 0 and alpha >= 0 (else bias + alpha * sum could be 0 or negative), got %g and %g", name.c_str(),
+                         (double)bias, (double)alpha);
+        return 0;
+    }
+    int Reshape() override
+    {
+        if (!lrn_api()) return FHIP_E_UNSUPPORTED; // message set by lrn_api
+        const Blob* b = bottoms[0];
+        if (b->n < 1 || b->c < 1 || b->h < 1 || b->w < 1) return failf(NET_E_SHAPE, "layer %s: LRN of an empty blob", name.c_str());
+        if (b->count() >= ((size_t)1 << 31)) return failf(NET_E_SHAPE, "layer %s: LRN: tensors of 2^31 elements or more are not supported", name.c_str());
+        scratch_bytes = 0;
+        if (!pooled) return tops[0]->reshape(b->n, b->c, b->h, b->w);
+        q.channels = b->c;
+        q.input_h = b->h;
+        q.input_w = b->w;
+        int oh, ow;
+        const int rc = fhip_pooling_output_dim(&q, &oh, &ow);
+        if (rc) return rc;
+        if (oh < 1 || ow < 1) return failf(NET_E_SHAPE, "layer %s: empty pooling output", name.c_str());
+        // a window that covers the unpadded plane: fhip_pooling sums it in its plane-reduce order, which fhip_lrn_pool_forward does not restate
+        // (and refuses): the pair, so that the layer keeps the bits of levels 0 and 1
+        const bool whole_plane = oh == 1 && ow == 1 && q.pad_top + q.pad_bottom == 0 && q.pad_left + q.pad_right == 0 && q.kernel_h >= b->h && q.kernel_w >= b->w;
+        if (b->count() > kLrnOneLaunchMax || whole_plane) scratch_bytes = b->count() * sizeof(float);
+        return tops[0]->reshape(b->n, b->c, oh, ow);
+    }
+    int Forward(hipStream_t s) override
+    {
+        const LrnApi* api = lrn_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const Blob* b = bottoms[0];
+        float* normalised = scratch_bytes ? net->arena.d : tops[0]->data;
+        const int rc = pooled && !scratch_bytes ? api->pool_forward(region, local_size, alpha, beta, bias, b->n, b->c, b->h, b->w, &q, tops[0]->data, b->data, s)
+                                                : api->forward(region, local_size, alpha, beta, bias, b->n, b->c, b->h, b->w, normalised, b->data, s);
+        if (rc) return failf(rc, "layer %s: %s", name.c_str(), api->last_error());
+        return scratch_bytes ? fhip_pooling(&q, b->n, tops[0]->data, normalised, s) : 0;
+    }
+    size_t arena_bytes() const override { return scratch_bytes; }
+    int Fuse(Layer* next, int level) override
+    {
+        if (level < 2 || pooled || next->type != "Pooling") return 0;
+        const fhip_pool_param& p = static_cast<PoolingLayer*>(next)->q;
+        if (p.global_pooling || p.kernel_h < 1 || p.kernel_w < 1 || p.stride_h < 1 || p.stride_w < 1) return 0;
+        if (p.pad_left < 0 || p.pad_right < 0 || p.pad_top < 0 || p.pad_bottom < 0) return 0;
+        q = p;
+        pooled = true;
+        return 1;
+    }
+    int algo() const override { return FHIP_NET_ROUTE_LRN; }
+};
+
 int ConvLayer::Fuse(Layer* next, int level)
 {
     if (pw) return pw->Fuse(next, level) == 1 ? 1 : 0; // behind the absorbed 1x1 convolution: its own fusions
@@ -2566,6 +2667,7 @@ static Layer* create_extended_layer(const std::string& type)
 {
     if (type == "Interp") return new InterpLayer;
     if (type == "HardSwish") return new HardSwishLayer;
+    if (type == "LRN") return new LRNLayer;
     return nullptr;
 }
 
@@ -2998,7 +3100,7 @@ static int prepare(Net& net)
                                                      l->type != "Split" && l->type != "Eltwise" && l->type != "Concat" && l->type != "Dropout" &&
                                                      l->type != "Sigmoid" && l->type != "TanH" && l->type != "Clip" && l->type != "ShuffleChannel" &&
                                                      l->type != "Slice" && l->type != "BinaryOp" && l->type != "Swish" && l->type != "HardSigmoid" &&
-                                                     l->type != "Interp" && l->type != "HardSwish" &&
+                                                     l->type != "Interp" && l->type != "HardSwish" && l->type != "LRN" &&
                                                      !(l->type == "Scale" && static_cast<ScaleLayer*>(l.get())->gated));
         if (needs) return failf(NET_E_IO, "weights have not been loaded");
     }

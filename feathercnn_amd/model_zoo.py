@@ -229,6 +229,11 @@ class GraphBuilder:
             params[6] = 1
         return self.layer("Interp", name, [bottom] + ([like] if like is not None else []), [name], params)
 
+    def lrn(self, name, bottom, local_size, alpha, beta, bias=1.0, region=0):
+        """ncnn's LRN: 0=region_type (0 across channels, 1 within channel), 1=local_size, 2=alpha, 3=beta, 4=bias.  A net that holds one
+        needs Net.SetExtendedLayers(True)."""
+        return self.layer("LRN", name, [bottom], [name], {0: int(region), 1: int(local_size), 2: f"{alpha:.8e}", 3: f"{beta:.8e}", 4: f"{bias:.8e}"})
+
     def conv_bn_swish(self, name, bottom, cin, cout, k, s=1, p=0, group=1, swish=True):
         x = self.conv_bn_relu(name, bottom, cin, cout, k, s, p, group, relu=False)
         return self.swish(name + "_swish", x) if swish else x
@@ -953,6 +958,107 @@ def fpn_resnet50(seed=1234, size=224, dry=False):
     return g.finish() + ("data", "fpn_p2")
 
 
+def tiny_lrn(seed=41, size=16, dry=False):
+    """A small net of LRN layers in every form the Net runtime has to get right (Net.SetExtendedLayers(True)): `norm1`, across 20 channels
+    (more than one chunk of 16) in front of a 3 x 3 / stride-2 max pooling whose last window hangs over the 16 x 16 plane (fusion level 2
+    makes the two one layer); `norm2`, within channel with beta 0.5, in front of a 2 x 2 average pooling (one layer too); `norm3`, beta 0.6
+    and bias 2, whose top is read by `pool3` and by `conv3` and must stay as written; `norm4` behind the pooling `pool4` (Pooling -> LRN is
+    not fused) and in front of a global pooling (not fused either); `norm5` on 3 channels, fewer than its local_size 5, in front of a padded
+    3 x 3 / stride-1 average pooling."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.relu("relu1", g.conv("conv1", x, 3, 20, 3, 1, 1))
+    x = g.pool("pool1", g.lrn("norm1", x, 5, 1.0, 0.75), 3, 2)                          # 16 x 16 -> 8 x 8, ceil mode
+    x = g.relu("relu2", g.conv("conv2", x, 20, 12, 3, 1, 1))
+    x = g.pool("pool2", g.lrn("norm2", x, 3, 2.0, 0.5, region=1), 2, 2, avg=True)       # 4 x 4
+    a, b, c = g.split("split1", x, 3)
+    n3 = g.lrn("norm3", a, 5, 0.5, 0.6, bias=2.0)                                       # read twice
+    head_a = g.pool("gap_a", g.pool("pool3", n3, 2, 2), 1, 1, avg=True, global_=True)
+    head_b = g.pool("gap_b", g.relu("relu3", g.conv("conv3", n3, 12, 8, 1)), 1, 1, avg=True, global_=True)
+    head_c = g.pool("gap_c", g.lrn("norm4", g.pool("pool4", b, 2, 2), 3, 1.0, 0.75), 1, 1, avg=True, global_=True)
+    n5 = g.lrn("norm5", g.conv("conv5", c, 12, 3, 1), 5, 1.0, 0.75)                     # 3 channels, local_size 5
+    head_d = g.pool("gap_d", g.pool("pool5", n5, 3, 1, 1, avg=True), 1, 1, avg=True, global_=True)
+    x = g.concat("heads", [head_a, head_b, head_c, head_d])
+    x = g.softmax("prob", g.fc("fc", x, 35, 10))
+    return g.finish() + ("data", "prob")
+
+
+def _pool3s2(v):
+    return -(-(v - 3) // 2) + 1  # 3 x 3 / stride 2, ceil mode
+
+
+def _alexnet(seed, classes, size, dry, norm_first):
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+
+    def stage(i, x, cin, cout, k, s, p, group):
+        x = g.relu(f"relu{i}", g.conv(f"conv{i}", x, cin, cout, k, s, p, group))
+        if norm_first:
+            return g.pool(f"pool{i}", g.lrn(f"norm{i}", x, 5, 1e-4, 0.75), 3, 2)
+        return g.lrn(f"norm{i}", g.pool(f"pool{i}", x, 3, 2), 5, 1e-4, 0.75)
+
+    x = stage(1, x, 3, 96, 11, 4, 0, 1)
+    x = stage(2, x, 96, 256, 5, 1, 2, 2)
+    x = g.relu("relu3", g.conv("conv3", x, 256, 384, 3, 1, 1))
+    x = g.relu("relu4", g.conv("conv4", x, 384, 384, 3, 1, 1, 2))
+    x = g.relu("relu5", g.conv("conv5", x, 384, 256, 3, 1, 1, 2))
+    x = g.pool("pool5", x, 3, 2)
+    feat = 256 * _pool3s2(_pool3s2(_pool3s2((size - 11) // 4 + 1))) ** 2
+    x = g.dropout("drop6", g.relu("relu6", g.fc("fc6", x, feat, 4096)))
+    x = g.dropout("drop7", g.relu("relu7", g.fc("fc7", x, 4096, 4096)))
+    x = g.softmax("prob", g.fc("fc8", x, 4096, classes))
+    return g.finish() + ("data", "prob")
+
+
+def alexnet(seed=1234, classes=1000, size=227, dry=False):
+    """BVLC AlexNet: 227 px, conv2 / conv4 / conv5 in two groups, norm1 / norm2 (LRN 5 / 1e-4 / 0.75) in front of pool1 / pool2.  The
+    smallest input is 67 px (pool5 then sees a 3 x 3 plane)."""
+    return _alexnet(seed, classes, size, dry, norm_first=True)
+
+
+def caffenet(seed=1234, classes=1000, size=227, dry=False):
+    """BVLC reference CaffeNet: AlexNet with pool1 / pool2 in front of norm1 / norm2."""
+    return _alexnet(seed, classes, size, dry, norm_first=False)
+
+
+def googlenet(seed=1234, classes=1000, size=224, dry=False):
+    """BVLC GoogLeNet (Inception v1) without the two auxiliary classifiers: pool1 -> norm1 and norm2 -> pool2 (LRN 5 / 1e-4 / 0.75), nine
+    inception modules, global average pooling.  Four ceil-mode 3 x 3 / stride-2 poolings behind a stride-2 convolution: the smallest input
+    that leaves every one of them a non-empty output is 31 px (16, 8, 4, 2 and 1 pixels a side)."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.relu("conv1/relu_7x7", g.conv("conv1/7x7_s2", x, 3, 64, 7, 2, 3))
+    x = g.lrn("pool1/norm1", g.pool("pool1/3x3_s2", x, 3, 2), 5, 1e-4, 0.75)
+    x = g.relu("conv2/relu_3x3_reduce", g.conv("conv2/3x3_reduce", x, 64, 64, 1))
+    x = g.relu("conv2/relu_3x3", g.conv("conv2/3x3", x, 64, 192, 3, 1, 1))
+    x = g.pool("pool2/3x3_s2", g.lrn("conv2/norm2", x, 5, 1e-4, 0.75), 3, 2)
+    cin = 192
+
+    def inception(tag, x, cin, n1, n3r, n3, n5r, n5, pp):
+        a, b, c, d = g.split(tag + "/split", x, 4)
+        a = g.relu(tag + "/relu_1x1", g.conv(tag + "/1x1", a, cin, n1, 1))
+        b = g.relu(tag + "/relu_3x3_reduce", g.conv(tag + "/3x3_reduce", b, cin, n3r, 1))
+        b = g.relu(tag + "/relu_3x3", g.conv(tag + "/3x3", b, n3r, n3, 3, 1, 1))
+        c = g.relu(tag + "/relu_5x5_reduce", g.conv(tag + "/5x5_reduce", c, cin, n5r, 1))
+        c = g.relu(tag + "/relu_5x5", g.conv(tag + "/5x5", c, n5r, n5, 5, 1, 2))
+        d = g.pool(tag + "/pool", d, 3, 1, 1)
+        d = g.relu(tag + "/relu_pool_proj", g.conv(tag + "/pool_proj", d, cin, pp, 1))
+        return g.concat(tag + "/output", [a, b, c, d]), n1 + n3 + n5 + pp
+
+    cfg = {"3a": (64, 96, 128, 16, 32, 32), "3b": (128, 128, 192, 32, 96, 64),
+           "4a": (192, 96, 208, 16, 48, 64), "4b": (160, 112, 224, 24, 64, 64), "4c": (128, 128, 256, 24, 64, 64),
+           "4d": (112, 144, 288, 32, 64, 64), "4e": (256, 160, 320, 32, 128, 128),
+           "5a": (256, 160, 320, 32, 128, 128), "5b": (384, 192, 384, 48, 128, 128)}
+    for tag, widths in cfg.items():
+        x, cin = inception("inception_" + tag, x, cin, *widths)
+        if tag in ("3b", "4e"):
+            x = g.pool(f"pool{tag[0]}/3x3_s2", x, 3, 2)
+    x = g.pool("pool5/7x7_s1", x, 7, 1, avg=True, global_=True)
+    x = g.dropout("pool5/drop_7x7_s1", x)
+    x = g.softmax("prob", g.fc("loss3/classifier", x, 1024, classes))
+    return g.finish() + ("data", "prob")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
@@ -963,7 +1069,8 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_dilated": tiny_dilated, "deeplab_largefov": deeplab_largefov, "deeplab_v2_aspp": deeplab_v2_aspp,
           "tiny_se": tiny_se, "se_resnet50": se_resnet50, "efficientnet_b0": efficientnet_b0,
           "tiny_resample": tiny_resample, "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small,
-          "deeplab_largefov_full": deeplab_largefov_full, "unet_bilinear": unet_bilinear, "fpn_resnet50": fpn_resnet50}
+          "deeplab_largefov_full": deeplab_largefov_full, "unet_bilinear": unet_bilinear, "fpn_resnet50": fpn_resnet50,
+          "tiny_lrn": tiny_lrn, "alexnet": alexnet, "caffenet": caffenet, "googlenet": googlenet}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -973,8 +1080,16 @@ DILATED_LAYERS = {"tiny_dilated": ("a1", "a2", "a3", "a_dw", "a_g", "a_far"),
                   "deeplab_v2_aspp": ("conv5_1", "conv5_2", "conv5_3", "fc6_1", "fc6_2", "fc6_3", "fc6_4"),
                   "deeplab_largefov_full": ("conv5_1", "conv5_2", "conv5_3", "fc6")}
 
-# nets that need Net.SetExtendedLayers(True) (Interp, HardSwish: libfeather_resample.so)
-EXTENDED_NETS = ("tiny_resample", "mobilenet_v3_large", "mobilenet_v3_small", "deeplab_largefov_full", "unet_bilinear", "fpn_resnet50")
+# nets that need Net.SetExtendedLayers(True) (Interp, HardSwish: libfeather_resample.so; LRN: libfeather_lrn.so)
+EXTENDED_NETS = ("tiny_resample", "mobilenet_v3_large", "mobilenet_v3_small", "deeplab_largefov_full", "unet_bilinear", "fpn_resnet50",
+                 "tiny_lrn", "alexnet", "caffenet", "googlenet")
+
+# the input size a builder's defaults describe, where it is not 224 px
+INPUT_SIZE = {"alexnet": 227, "caffenet": 227}
+
+# the LRN layers of each net that fusion level 2 makes one layer with the Pooling layer behind them, and those that must stay as written
+LRN_POOLS = {"tiny_lrn": (("norm1", "norm2", "norm5"), ("norm3", "norm4")), "alexnet": (("norm1", "norm2"), ()), "caffenet": ((), ("norm1", "norm2")),
+             "googlenet": (("conv2/norm2",), ("pool1/norm1",))}
 
 # the Interp layers of each net that fusion level 2 collapses with the Eltwise SUM (and ReLU) behind them, and those that must stay
 UPSAMPLE_ADDS = {"tiny_resample": (("up1",), ("up2", "shrink", "aligned", "to_ref", "down")),

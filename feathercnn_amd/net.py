@@ -27,6 +27,8 @@ ROUTE_GATE = 105  # FHIP_NET_ROUTE_GATE: a two-bottom BinaryOp mul / Scale -233,
 ROUTE_NAMES[ROUTE_GATE] = "GATE"
 ROUTE_RESAMPLE = 106  # FHIP_NET_ROUTE_RESAMPLE: an Interp or HardSwish layer, after SetExtendedLayers(True) (libfeather_resample.so)
 ROUTE_NAMES[ROUTE_RESAMPLE] = "RESAMPLE"
+ROUTE_LRN = 107  # FHIP_NET_ROUTE_LRN: an LRN layer, alone or with the Pooling layer behind it, after SetExtendedLayers(True) (libfeather_lrn.so)
+ROUTE_NAMES[ROUTE_LRN] = "LRN"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -57,7 +59,8 @@ class Net:
         _check(self._lib.fhip_net_set_dilated(self._h, int(bool(on))), "fhip_net_set_dilated")
 
     def SetExtendedLayers(self, on: bool = True):
-        """feather::Net::SetExtendedLayers: accept Interp and HardSwish layers (routed to libfeather_resample.so) instead of refusing them
+        """feather::Net::SetExtendedLayers: accept Interp and HardSwish layers (routed to libfeather_resample.so) and LRN layers
+        (libfeather_lrn.so) instead of refusing them
         at LoadParam.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_extended_layers(self._h, int(bool(on))), "fhip_net_set_extended_layers")
 

@@ -29,7 +29,8 @@
 //     InnerProduct / 1x1 Convolution layers, Sigmoid / HardSigmoid, BinaryOp mul or two-bottom Scale, the residual Eltwise and its ReLU)
 //     as one layer of libfeather_gate.so (FHIP_NET_ROUTE_GATE, feather_net.h);
 //   * layer types beyond the reference's factory are loaded too: see feather_net.h's route codes (BinaryOp mul, Scale 0=-233, Swish and
-//     HardSigmoid are the newest); Interp and HardSwish after SetExtendedLayers(true) (FHIP_NET_ROUTE_RESAMPLE).
+//     HardSigmoid are the newest); Interp and HardSwish (FHIP_NET_ROUTE_RESAMPLE) and LRN (FHIP_NET_ROUTE_LRN) after
+//     SetExtendedLayers(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -188,7 +189,8 @@ class Net
     int SetTunedSelection(bool on) { return fhip_net_set_tuned_selection(net_, on ? 1 : 0); }
     // accept Convolution layers with dilation > 1 (libfeather_atrous.so) instead of refusing them; before LoadParam (feather_net.h)
     int SetDilated(bool on) { return fhip_net_set_dilated(net_, on ? 1 : 0); }
-    // accept Interp and HardSwish layers (libfeather_resample.so) instead of refusing them; before LoadParam (feather_net.h)
+    // accept Interp and HardSwish layers (libfeather_resample.so) and LRN layers (libfeather_lrn.so) instead of refusing them; before
+    // LoadParam (feather_net.h)
     int SetExtendedLayers(bool on) { return fhip_net_set_extended_layers(net_, on ? 1 : 0); }
     int SetConcurrency(bool on) { return fhip_net_set_concurrency(net_, on ? 1 : 0); }
     int SetSubBatches(int replicas) { return fhip_net_set_sub_batches(net_, replicas); } // before LoadParam (feather_net.h)

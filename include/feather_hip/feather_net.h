@@ -245,7 +245,7 @@ FHIP_API int fhip_net_get_stream(fhip_net* net, void** stream);
  *      depthwise layer + the 1x1 convolution behind it as one layer (fhip_conv_forward_dw_pw where the pair qualifies), and two 1x1
  *      convolutions of the same input that follow each other as one GEMM (fhip_conv_forward_siblings; both blobs keep their storage);
  *      a squeeze-and-excitation block as one layer (FHIP_NET_ROUTE_GATE); Interp + Eltwise SUM (+ReLU) as one layer
- *      (FHIP_NET_ROUTE_RESAMPLE).
+ *      (FHIP_NET_ROUTE_RESAMPLE); LRN + the Pooling layer behind it as one layer (FHIP_NET_ROUTE_LRN).
  *   3: + runs of Winograd layers chained (fhip_conv_forward_chained): the blob between two chained layers has a shape but no storage;
  *      a first layer (3x3 / stride 1 / pad 1, 2 .. 4 input channels) in front of a Winograd layer is computed inside that layer's input
  *      transform (fhip_winograd_f63_input_from_first): its top has no storage either.
@@ -260,7 +260,9 @@ FHIP_API int fhip_net_set_tuned_selection(fhip_net* net, int on);
  * refusal (a dilated Deconvolution stays refused).  Call before LoadParam; later it is FHIP_E_BADARG. */
 FHIP_API int fhip_net_set_dilated(fhip_net* net, int on);
 /* 1: the layer types Interp (nearest / bilinear resize; one bottom, or two where the second gives the output size) and HardSwish are loaded
- * and run through libfeather_resample.so (feather_resample.h has their definitions; route code FHIP_NET_ROUTE_RESAMPLE); 0 (default):
+ * and run through libfeather_resample.so (feather_resample.h has their definitions; route code FHIP_NET_ROUTE_RESAMPLE), and LRN through
+ * libfeather_lrn.so (feather_lrn.h; FHIP_NET_ROUTE_LRN; an even or non-positive local_size, a region_type outside 0 / 1, alpha, beta or
+ * bias not finite, bias <= 0 or alpha < 0 are -100 at LoadParam); 0 (default):
  * LoadParam refuses them with -200, as tests/test_inorm_cpu.py and tests/test_gate_cpu.py pin for a default net.  Its only effect is
  * lifting that refusal: PixelShuffle stays -200 and a bicubic Interp -100.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to
  * sub-batch replicas. */
@@ -368,6 +370,14 @@ FHIP_API int fhip_net_layer_count(fhip_net* net);
  * stands where the chain's last layer stood; the up-sampled tensor is never written and the blobs inside the chain cannot be extracted.
  * No other fusion takes these layers.  Reported from LoadParam on. */
 #define FHIP_NET_ROUTE_RESAMPLE 106
+/* Route code of an LRN layer in a net with fhip_net_set_extended_layers: one launch of libfeather_lrn.so (feather_lrn.h), opened the same
+ * way the first time a net holds such a layer.  At fusion level 2 an LRN whose top has a sole consumer, a non-global Pooling layer with one
+ * bottom and one top, takes that layer over (AlexNet's and GoogLeNet's norm -> pool): one layer that keeps the LRN's type and name and equals
+ * the two layers bit for bit; the normalised tensor has no blob and cannot be extracted.  Up to 4 * 192 * 56 * 56 elements the layer is one launch
+ * (fhip_lrn_pool_forward) and that tensor is never written; above, where the one launch measured slower than the two, and where the pooling
+ * window covers the whole unpadded plane (fhip_pooling's plane-reduce route, whose order the one launch does not restate), it is
+ * fhip_lrn_forward into the net's scratch arena and fhip_pooling from there.  A Pooling layer in front of an LRN is not fused.  No other fusion takes the layer.  Reported from LoadParam on. */
+#define FHIP_NET_ROUTE_LRN 107
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
  * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);

@@ -1,5 +1,6 @@
 """Whole-net timing on the GPU: images/s and a per-layer-type breakdown (HIP events around every layer).
-usage: python tools/net_bench.py [net[:batch[:fusion]] ...]    e.g.  vgg16:32 resnet50:64:2 mobilenet_v1:256:2"""
+usage: python tools/net_bench.py [net[:batch[:fusion]] ...]    e.g.  vgg16:32 resnet50:64:2 mobilenet_v1:256:2 alexnet:256:2 googlenet:64:2
+The input is 224 px, or what model_zoo.INPUT_SIZE names for the net (alexnet, caffenet: 227)."""
 import os
 import sys
 import time
@@ -29,7 +30,8 @@ def run(name, batch, fusion, steps=10):
     net.LoadParam(p)
     net.LoadWeights(b)
     del b
-    x = torch.rand((batch, 3, 224, 224), device="cuda") * 2 - 1
+    size = model_zoo.INPUT_SIZE.get(name, 224)
+    x = torch.rand((batch, 3, size, size), device="cuda") * 2 - 1
     net.FeedInput(i, x)
     net.Forward()
     torch.cuda.synchronize()
