@@ -1,7 +1,7 @@
 """The life-cycle table of feather::Net: ONE handle walked through shapes and settings (tests/test_lifecycle_cpu.py,
 tests/test_lifecycle_gpu.py).  The invariant the walks test: a Net after any legal history equals a fresh Net in its final state, bit for bit.
 
-The model (`model()`, 3 input channels, at most 128 anywhere, seeded, built in memory) holds every plan kind of net.hip's re-plan path at once:
+The model (`model()`, 3 input channels, at most 128 anywhere, seeded, built in memory) holds every plan kind of the Net runtime's re-plan path (feathercnn_amd/csrc/net_plan.h) at once:
 
   data -> conv0 (3 -> 16, 3x3 p1) + ReLU               the RGB first layer, computed inside conv1's input transform (plan_chains: head / head_of)
        -> conv1 (16 -> 32) + ReLU -> conv2 (32 -> 32) + ReLU + 2x2 max pool -> conv3 (32 -> 32) + ReLU -> conv4 (32 -> 64) + ReLU

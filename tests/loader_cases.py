@@ -1,4 +1,4 @@
-"""Hostile-model cases for the .param / .bin readers (feathercnn_amd/csrc/net.hip): a deterministic table, no test code.
+"""Hostile-model cases for the .param / .bin readers (feathercnn_amd/csrc/net_model.h, net_layers.h, net.hip): a deterministic table, no test code.
 
 ``cases()`` returns a list of ``Case`` tuples ``(name, param, bin, expectation, code, dilated)``:
 
@@ -26,7 +26,7 @@ ACCEPT, REFUSE, EITHER = "accept", "refuse", "either"
 INT_VALUES = (0, -1, 2147483647, -2147483648)
 FLOAT_VALUES = ("nan", "inf", "1e39")
 
-# type -> (integer ids, float ids, array ids) its LoadParam reads; tests/test_loader_hostile_cpu.py holds this table against net.hip
+# type -> (integer ids, float ids, array ids) its LoadParam reads; tests/test_loader_hostile_cpu.py holds this table against the LoadParam bodies of net_layers.h
 _CONV = ((0, 1, 11, 2, 12, 3, 13, 4, 14, 5, 6, 7, 8), (), ())
 _DECONV = ((0, 1, 11, 2, 12, 3, 13, 4, 14, 15, 16, 18, 19, 20, 21, 5, 6, 7, 8, 9), (), ())
 PARAM_IDS = {

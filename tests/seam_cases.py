@@ -15,7 +15,7 @@ zeros, where the per-plane metric has nothing to normalise by: gap->relu draws i
 deviation 0.1, are then positive) and ip->relu gives its InnerProduct biases in (0.05, 0.15) (POSITIVE).
 `Input` cannot be a consumer (it has no bottom); every other type create_layer accepts is on both sides.
 
-`expect(case, level)` is the claim column, filled from the conditions of net.hip (ConvLayer::Fuse, DeconvLayer::Fuse, AffineLayer::Fuse,
+`expect(case, level)` is the claim column, filled from the conditions of the Net runtime (net_layers.h, net_plan.h: ConvLayer::Fuse, DeconvLayer::Fuse, AffineLayer::Fuse,
 InstanceNormLayer::Fuse, InnerProductLayer::Fuse, EltwiseLayer::Fuse, fuse_layers' residual rule, collapse_channel_maps,
 collapse_gate_blocks): (verdict, rule) with verdict "absorbed" (C's first layer is gone from the layer list), "kept" (it is there),
 "collapsed" (C is a squeeze-and-excitation block that became one layer) or None (no claim).

@@ -17,6 +17,7 @@ import pytest
 import atrous_cases as AC
 import atrous_ref as R
 import gconv_ref
+import helpers
 import kernel_instances as KI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -162,7 +163,7 @@ def test_other_libraries_keep_their_instantiations():
     import gconv_cases as GC
     assert len(KI.instances()) == 176
     assert set(KI.instances(GC.LIB)) == GC.targets() and set(KI.instances(DC.LIB)) == DC.targets()
-    assert "__global__" not in open(os.path.join(ROOT, "feathercnn_amd", "csrc", "net.hip")).read()  # net.hip only routes
+    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
 
 
 def test_refusals_come_before_any_device_call(lib):

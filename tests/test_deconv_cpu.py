@@ -16,6 +16,7 @@ import pytest
 
 import deconv_cases as DC
 import deconv_ref as R
+import helpers
 import kernel_instances as KI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -179,7 +180,7 @@ def test_other_libraries_keep_their_instantiations():
     assert len(KI.instances(os.path.join(ROOT, "feathercnn_amd", "libfeather_pixout.so"))) == 6
     assert set(KI.instances(GC.LIB)) == GC.targets()
     # no new __global__ under feathercnn_amd/csrc: net.hip only routes
-    assert "__global__" not in open(os.path.join(ROOT, "feathercnn_amd", "csrc", "net.hip")).read()
+    assert "__global__" not in helpers.net_runtime_source()
 
 
 def test_refusals_come_before_any_device_call(lib):

@@ -18,6 +18,7 @@ import pytest
 
 import gate_cases as GC
 import gate_ref as R
+import helpers
 import kernel_instances as KI
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,7 +137,7 @@ def test_other_libraries_keep_their_instantiations():
     assert set(KI.instances(IC.LIB)) == IC.targets()
     assert set(KI.instances(SC.LIB)) == SC.targets()
     assert set(KI.instances(AC.LIB)) == AC.targets()
-    assert "__global__" not in open(os.path.join(ROOT, "feathercnn_amd", "csrc", "net.hip")).read()  # net.hip only routes
+    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
 
 
 def test_refusals_come_before_any_device_call(lib):

@@ -19,6 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import helpers
 import inorm_cases as IC
 import inorm_ref as R
 import kernel_instances as KI
@@ -138,7 +139,7 @@ def test_other_libraries_keep_their_instantiations():
     assert len(KI.instances(os.path.join(ROOT, "feathercnn_amd", "libfeather_pixout.so"))) == 6
     assert set(KI.instances(GC.LIB)) == GC.targets()
     assert set(KI.instances(DC.LIB)) == DC.targets()
-    assert "__global__" not in open(os.path.join(ROOT, "feathercnn_amd", "csrc", "net.hip")).read()  # net.hip only routes
+    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
 
 
 def test_refusals_come_before_any_device_call(lib):

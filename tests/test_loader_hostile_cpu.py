@@ -1,4 +1,4 @@
-"""The model readers (LoadParam / LoadWeights of every layer type, feathercnn_amd/csrc/net.hip) on hostile files: the table of
+"""The model readers (LoadParam / LoadWeights of every layer type: feathercnn_amd/csrc/net_model.h, net_layers.h and the loaders of net.hip) on hostile files: the table of
 tests/loader_cases.py through the stand-alone driver tests/cpp/net_loader_hostile_main.cpp, once against the built library and once
 with the library's host side compiled under AddressSanitizer and UndefinedBehaviorSanitizer into the same executable.  Host side only:
 no feed, forward or extract call, no GPU, nothing loaded into python.
@@ -30,6 +30,7 @@ import time
 
 import pytest
 
+import helpers
 import loader_cases as L
 from oracle import netcheck
 
@@ -58,7 +59,7 @@ def case_dir(table, tmp_path_factory):
 
 
 def _net_hip():
-    return open(os.path.join(CSRC, "net.hip")).read()
+    return helpers.net_runtime_source()  # net.hip and the net_*.h it includes: the factories are in the first, the layer classes in the headers
 
 
 def _body(text, start):

@@ -20,6 +20,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import helpers
 import kernel_instances as KI
 import lrn_cases as LC
 import lrn_ref as R
@@ -204,7 +205,7 @@ def test_instantiations_and_route_names(lib):
     declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
     assert declared == {KI.base(n) for n in names} == KERNELS
     assert "atomic" not in src.split("#include", 1)[1] and "hipMalloc" not in src and "hipMemcpy" not in src and "getenv" not in src  # a forward only launches
-    assert "__global__" not in open(os.path.join(ROOT, "feathercnn_amd", "csrc", "net.hip")).read()  # net.hip only routes
+    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
     name = ctypes.create_string_buffer(96)
     v = ctypes.c_void_p
     seen = set()

@@ -19,6 +19,7 @@ import atrous_ref
 import deconv_ref
 import gate_ref
 import gconv_ref
+import helpers
 import inorm_ref
 import seam_cases as SC
 import seam_ref as R
@@ -135,7 +136,7 @@ def test_agrees_with_portnet_where_portnet_knows_the_layers(pname):
 
 
 def test_the_table_is_complete():
-    text = open(os.path.join(ROOT, "feathercnn_amd", "csrc", "net.hip")).read()
+    text = helpers.net_runtime_source()
     body = text[text.index("static Layer* create_layer("):]
     body = body[:body.index("\n}\n")]
     accepted = set(re.findall(r'type == "(\w+)"', body))

@@ -17,6 +17,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import helpers
 import kernel_instances as KI
 import shuffle_cases as SC
 import shuffle_ref as R
@@ -140,7 +141,7 @@ def test_other_libraries_keep_their_instantiations():
     assert set(KI.instances(GC.LIB)) == GC.targets()
     assert set(KI.instances(DC.LIB)) == DC.targets()
     assert set(KI.instances(IC.LIB)) == IC.targets()
-    assert "__global__" not in open(os.path.join(ROOT, "feathercnn_amd", "csrc", "net.hip")).read()  # net.hip only routes
+    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
 
 
 def test_slice_resolve_matches_the_restatement(lib):
