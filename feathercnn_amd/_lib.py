@@ -274,6 +274,17 @@ def _load(path, signatures):
     return lib
 
 
+def checker(load, last_error: str):
+    """The `_check(rc, what)` of one library: raises FeatherHipError with the text of the library's last-error symbol when a C-ABI call
+    returned non-zero.  `load` is the library's load_* function."""
+    def _check(rc: int, what: str):
+        if rc != 0:
+            from .booster import FeatherHipError  # booster imports this module
+            msg = getattr(load(), last_error)().decode(errors="replace")
+            raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+    return _check
+
+
 def lib_path() -> str:
     return os.environ.get("FEATHER_HIP_LIB", os.path.join(_HERE, "libfeather_hip.so"))
 

@@ -25,10 +25,7 @@ class FeatherHipError(RuntimeError):
     pass
 
 
-def _check(rc: int, what: str):
-    if rc != 0:
-        msg = _lib.load_library().fhip_last_error().decode(errors="replace")
-        raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+_check = _lib.checker(_lib.load_library, "fhip_last_error")
 
 
 @dataclass

@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
-from .booster import FeatherHipError, _check, _ptr, _stream
+from .booster import _check, _ptr, _stream
 
 ENTRY, INSIDE, EXIT = 1, 2, 3
 
@@ -24,9 +24,7 @@ def canvas_param(param, batch: int):
     return q if _lib.load_library().fhip_winograd_f63_canvas_param(ctypes.byref(c), int(batch), ctypes.byref(q)) == 0 else None
 
 
-def _check_canvas(rc, what):
-    if rc != 0:
-        raise FeatherHipError(f"{what} failed ({rc}): {_lib.load_canvas_library().fhip_canvas_last_error().decode()}")
+_check_canvas = _lib.checker(_lib.load_canvas_library, "fhip_canvas_last_error")
 
 
 def forward_chained_canvas(layers, x, pools, canvas, fill=None, keep=False):

@@ -27,30 +27,13 @@
 #include <string.h>
 
 #include <algorithm>
-#include <string>
 
 #include "feather_hip/feather_atrous.h"
+#include "direct_conv.h"
 #include "gemm_core.h"
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-// the two helpers ../csrc/common.h declares and gemm_core.h's includer must provide (hidden visibility: private to this library)
-int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-int fail_hip(hipError_t e, const char* what)
-{
-    g_error = std::string(what) + ": " + hipGetErrorString(e);
-    return FHIP_E_HIP;
-}
-
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4))); // a float4 that is only 4-byte aligned
 
 // out[e] = r[e + s] for 0 <= e + s < 4 (the other elements are masked by the caller)
 __device__ __forceinline__ float4 shift4(const f32x4u r, int s)
@@ -65,87 +48,20 @@ __device__ __forceinline__ float4 shift4(const f32x4u r, int s)
     return make_float4(o[0], o[1], o[2], o[3]);
 }
 
-// ---- the generic route ----------------------------------------------------------------------------------------------
-struct AtrousArgs
-{
-    const float* x;
-    const float* w; // generic: packed [group][chunk][C/group][kh * kw][KT], zero-padded past K/group; depthwise: [C][9]
-    const float* bias;
-    float* y;
-    int C, K, Cg, Kg, H, W, Ho, Wo, kh, kw, sh, sw, pt, pl, dh, dw;
-    int chunks; // generic: chunks of KT output channels per group
-    int strips; // depthwise: lanes per output row, ceil(Wo / 4)
-    int relu;
-    unsigned total; // lanes: generic batch * Ho * Wo; depthwise Ho * strips (of one plane)
-};
-
+// ---- the generic route: direct_conv.h's body under this library's kernel names (the names fhip_atrous_route and traces report) ----
 template <int KT>
-__global__ __launch_bounds__(256) void atrous_generic_kernel(const AtrousArgs a)
-{
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= a.total) return;
-    const int gc = blockIdx.y;
-    const int g = gc / a.chunks, chunk = gc - g * a.chunks;
-    const int ox = (int)(i % (unsigned)a.Wo);
-    const unsigned t = i / (unsigned)a.Wo;
-    const int oy = (int)(t % (unsigned)a.Ho), n = (int)(t / (unsigned)a.Ho);
-    const size_t plane = (size_t)a.H * a.W;
-    const float* xp = a.x + ((size_t)n * a.C + (size_t)g * a.Cg) * plane;
-    const float* __restrict__ wp = a.w + (size_t)gc * a.Cg * a.kh * a.kw * KT;
-    const int iy0 = oy * a.sh - a.pt, ix0 = ox * a.sw - a.pl;
+__global__ __launch_bounds__(256) void atrous_generic_kernel(const DirectConvArgs a) { direct_conv_body<KT, DilatedTaps>(a); }
 
-    float acc[KT];
-#pragma unroll
-    for (int k = 0; k < KT; ++k) acc[k] = 0.f;
-    for (int c = 0; c < a.Cg; ++c, xp += plane)
-        for (int r = 0; r < a.kh; ++r)
-        {
-            const int iy = iy0 + r * a.dh;
-            const bool row_in = iy >= 0 && iy < a.H;
-            const float* row = xp + (size_t)min(max(iy, 0), a.H - 1) * a.W; // always a row of the plane
-            for (int s = 0; s < a.kw; ++s, wp += KT)
-            {
-                const int ix = ix0 + s * a.dw;
-                float v = row[min(max(ix, 0), a.W - 1)];
-                if (!row_in || ix < 0 || ix >= a.W) v = 0.f;
-#pragma unroll
-                for (int k = 0; k < KT; ++k) acc[k] = fmaf(wp[k], v, acc[k]);
-            }
-        }
-
-    const int kk0 = chunk * KT;
-    const size_t oplane = (size_t)a.Ho * a.Wo;
-    float* yp = a.y + (((size_t)n * a.K + (size_t)g * a.Kg + kk0) * a.Ho + oy) * a.Wo + ox;
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-        if (kk0 + k < a.Kg)
-        {
-            float o = acc[k] + (a.bias ? a.bias[g * a.Kg + kk0 + k] : 0.f);
-            if (a.relu) o = fmaxf(o, 0.f);
-            yp[k * oplane] = o;
-        }
-}
-
-// kernel [K][Cg][taps] -> packed [group][chunk][Cg][taps][kt], zeros past Kg; one lane per packed word
 __global__ __launch_bounds__(256) void atrous_pack_generic_kernel(float* packed, const float* kernel, int Cg, int Kg, int taps, int kt, int chunks, unsigned total)
 {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= total) return;
-    const int k = (int)(i % (unsigned)kt);
-    unsigned t = i / (unsigned)kt;
-    const int tap = (int)(t % (unsigned)taps);
-    t /= (unsigned)taps;
-    const int c = (int)(t % (unsigned)Cg);
-    const int gc = (int)(t / (unsigned)Cg);
-    const int g = gc / chunks, kk = (gc - g * chunks) * kt + k;
-    packed[i] = kk < Kg ? kernel[(((size_t)g * Kg + kk) * Cg + c) * taps + tap] : 0.f;
+    direct_pack_body(packed, kernel, Cg, Kg, taps, kt, chunks, total);
 }
 
 // ---- the depthwise route --------------------------------------------------------------------------------------------
 // y[n][c][oy][4 * strip .. + 4) of a 3x3 depthwise layer with stride S in both directions, any dilation and pads.  blockIdx.x = n * C + c.
 // VEC: Wo % 4 == 0 (every strip is full: one 16-byte store) and, for S == 1, W >= 4 (a tap's four inputs are one 16-byte load from the row).
 template <int S, bool VEC>
-__global__ __launch_bounds__(256) void atrous_dw3x3_kernel(const AtrousArgs a)
+__global__ __launch_bounds__(256) void atrous_dw3x3_kernel(const DirectConvArgs a)
 {
     const unsigned i = blockIdx.y * 256u + threadIdx.x;
     if (i >= a.total) return;
@@ -482,9 +398,8 @@ static long long out_dim(int in, int pa, int pb, int k, int d, int s) { return (
 
 static int check_geometry(const fhip_atrous_param* p)
 {
-    if (!p) return fail(FHIP_E_BADARG, "null param");
-    if (p->input_channels < 1 || p->output_channels < 1 || p->input_h < 1 || p->input_w < 1) return fail(FHIP_E_BADARG, "channels and input size must be >= 1");
-    if (p->kernel_h < 1 || p->kernel_w < 1 || p->stride_h < 1 || p->stride_w < 1) return fail(FHIP_E_BADARG, "kernel size and stride must be >= 1");
+    const int rc = check_sizes(p);
+    if (rc) return rc;
     if (p->dilation_h < 1 || p->dilation_w < 1) return fail(FHIP_E_BADARG, "dilation must be >= 1");
     if (p->dilation_h == 1 && p->dilation_w == 1)
         return fail(FHIP_E_BADARG, "dilation 1 x 1 is not this library's: such a layer has tuned routes in libfeather_hip.so / libfeather_gconv.so");
@@ -498,7 +413,9 @@ static int check_geometry(const fhip_atrous_param* p)
     const long long oh = out_dim(p->input_h, p->pad_top, p->pad_bottom, p->kernel_h, p->dilation_h, p->stride_h);
     const long long ow = out_dim(p->input_w, p->pad_left, p->pad_right, p->kernel_w, p->dilation_w, p->stride_w);
     if (oh < 1 || ow < 1) return fail(FHIP_E_BADARG, "empty output");
-    if ((long long)p->input_channels * p->input_h * p->input_w > 0x7fffffffLL || (long long)p->output_channels * oh * ow > 0x7fffffffLL)
+    // factor by factor: the product of three numbers near 2^31 overflows 64 bits, and the refusal such a param met was the compiler's choice
+    const auto too_large = [](long long c, long long h, long long w) { return h > 0x7fffffffLL || w > 0x7fffffffLL || h * w > 0x7fffffffLL || c * (h * w) > 0x7fffffffLL; };
+    if (too_large(p->input_channels, p->input_h, p->input_w) || too_large(p->output_channels, oh, ow))
         return fail(FHIP_E_BADARG, "tensor too large: 2^31 elements or more");
     return FHIP_OK;
 }
@@ -600,22 +517,14 @@ static int route_by_name(const char* name)
     return -1;
 }
 
-constexpr int kGenericKT = 4;
-
 static size_t packed_floats(const fhip_atrous_param& p, int r)
 {
     const size_t taps = (size_t)p.kernel_h * p.kernel_w;
     if (is_dw(r)) return (size_t)p.input_channels * 9;
-    if (r == ROUTE_GENERIC)
-    {
-        const int Cg = p.input_channels / p.group, Kg = p.output_channels / p.group;
-        return (size_t)p.group * ((Kg + kGenericKT - 1) / kGenericKT) * Cg * taps * kGenericKT;
-    }
+    if (r == ROUTE_GENERIC) return generic_packed_floats(p, kGenericKT);
     const int bm = mfma_small(r) ? AtrousShapeSmallM::BM : AtrousShapeBig::BM;
     return (size_t)((p.output_channels + bm - 1) / bm) * bm * taps * p.input_channels;
 }
-
-static bool aligned(const void* q, uintptr_t to) { return ((uintptr_t)q & (to - 1)) == 0; }
 
 template <class Shape, bool ROW4, bool SKIP>
 static void launch_mfma(AtrousGemmParams& g, hipStream_t s)
@@ -659,11 +568,7 @@ static int do_init(const fhip_atrous_param* param, float* packed, const float* k
     if (is_dw(r))
         hipLaunchKernelGGL(atrous_pack_copy_kernel, grid, dim3(256), 0, (hipStream_t)stream, packed, kernel, (unsigned)total);
     else if (r == ROUTE_GENERIC)
-    {
-        const int Cg = p.input_channels / p.group, Kg = p.output_channels / p.group;
-        hipLaunchKernelGGL(atrous_pack_generic_kernel, grid, dim3(256), 0, (hipStream_t)stream, packed, kernel, Cg, Kg, taps, kGenericKT,
-                           (Kg + kGenericKT - 1) / kGenericKT, (unsigned)total);
-    }
+        launch_direct_pack(atrous_pack_generic_kernel, p, kGenericKT, total, packed, kernel, (hipStream_t)stream);
     else
         hipLaunchKernelGGL(atrous_pack_mfma_kernel, grid, dim3(256), 0, (hipStream_t)stream, packed, kernel, p.input_channels, p.output_channels, taps,
                            mfma_small(r) ? AtrousShapeSmallM::BM : AtrousShapeBig::BM, (unsigned)total);
@@ -675,54 +580,29 @@ static int do_forward(const fhip_atrous_param* param, int batch, float* out, con
                       const char* route)
 {
     int r;
-    const int rc = route_checks(param, route, r);
+    int rc = route_checks(param, route, r);
     if (rc) return rc;
-    if (batch < 1) return fail(FHIP_E_BADARG, "batch < 1");
-    if (!out || !in || !packed) return fail(FHIP_E_BADARG, "null out / in / packed");
     const fhip_atrous_param& p = *param;
-    if (p.bias_term && !bias) return fail(FHIP_E_BADARG, "bias_term is set and bias is NULL");
-    if (!aligned(out, 4) || !aligned(in, 4) || !aligned(packed, 16) || (p.bias_term && !aligned(bias, 4)))
-        return fail(FHIP_E_BADARG, "device pointers must be 4-byte aligned (packed: 16-byte)");
+    rc = check_forward_pointers(p, batch, out, in, packed, bias, 16, "device pointers must be 4-byte aligned (packed: 16-byte)");
+    if (rc) return rc;
     const unsigned long long in_count = (unsigned long long)batch * p.input_channels * p.input_h * p.input_w;
     const unsigned long long out_count = (unsigned long long)batch * p.output_channels * p.output_h * p.output_w;
     if (in_count > 0x7fffffffULL || out_count > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large: 2^31 elements or more");
     hipStream_t s = (hipStream_t)stream;
     if (!is_mfma(r))
     {
-        AtrousArgs a;
-        a.x = in;
-        a.w = packed;
-        a.bias = p.bias_term ? bias : nullptr;
-        a.y = out;
-        a.C = p.input_channels;
-        a.K = p.output_channels;
-        a.Cg = p.input_channels / p.group;
-        a.Kg = p.output_channels / p.group;
-        a.H = p.input_h;
-        a.W = p.input_w;
-        a.Ho = p.output_h;
-        a.Wo = p.output_w;
-        a.kh = p.kernel_h;
-        a.kw = p.kernel_w;
-        a.sh = p.stride_h;
-        a.sw = p.stride_w;
-        a.pt = p.pad_top;
-        a.pl = p.pad_left;
+        DirectConvArgs a = direct_conv_args(p, kGenericKT, out, in, packed, bias);
         a.dh = p.dilation_h;
         a.dw = p.dilation_w;
-        a.chunks = (a.Kg + kGenericKT - 1) / kGenericKT;
-        a.strips = (p.output_w + 3) / 4;
-        a.relu = p.activation == FHIP_ACT_RELU;
         if (r == ROUTE_GENERIC)
         {
-            const size_t total = (size_t)batch * p.output_h * p.output_w;
-            const size_t gy = (size_t)p.group * a.chunks;
-            if (gy > 65535) return fail(FHIP_E_BADARG, "more than 65535 chunks of 4 output channels");
-            a.total = (unsigned)total;
-            hipLaunchKernelGGL(atrous_generic_kernel<kGenericKT>, dim3((unsigned)((total + 255) / 256), (unsigned)gy), dim3(256), 0, s, a);
+            rc = launch_direct(atrous_generic_kernel<kGenericKT>, a, (size_t)batch * p.output_h * p.output_w, (size_t)p.group * a.chunks, s,
+                               "more than 65535 chunks of 4 output channels");
+            if (rc) return rc;
         }
         else
         {
+            a.strips = (p.output_w + 3) / 4;
             const size_t total = (size_t)p.output_h * a.strips;
             const size_t gy = (total + 255) / 256;
             if (gy > 65535) return fail(FHIP_E_BADARG, "output plane too large for the depthwise route: more than 65535 blocks of 256 lanes");
@@ -857,6 +737,6 @@ int fhip_atrous_forward_route(const fhip_atrous_param* param, int batch, float* 
     return do_forward(param, batch, out, in, packed, bias, stream, route);
 }
 
-const char* fhip_atrous_last_error(void) { return g_error.c_str(); }
+const char* fhip_atrous_last_error(void) { return last_error(); }
 
 } // extern "C"

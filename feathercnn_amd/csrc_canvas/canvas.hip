@@ -13,26 +13,12 @@
 #include <string>
 
 #include "feather_hip/feather_canvas.h"
+#include "side_error.h"
 #include "wino_butterfly.h"
 #include "wino_layout.h"
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-static int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-#define FHIP_CANVAS_CHECK_HIP(expr)                                                                               \
-    do                                                                                                            \
-    {                                                                                                             \
-        const hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return fail(FHIP_E_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 struct CanvasChain
 {
@@ -284,11 +270,11 @@ static int device_limits(int* cus, size_t* lds)
     static thread_local int dev_cached = -1, cus_cached = 0;
     static thread_local size_t lds_cached = 0;
     int dev = 0;
-    FHIP_CANVAS_CHECK_HIP(hipGetDevice(&dev));
+    FHIP_CHECK_HIP(hipGetDevice(&dev));
     if (dev != dev_cached)
     {
         hipDeviceProp_t prop;
-        FHIP_CANVAS_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
+        FHIP_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
         cus_cached = prop.multiProcessorCount;
         lds_cached = prop.maxSharedMemoryPerMultiProcessor;
         dev_cached = dev;
@@ -394,7 +380,7 @@ static int canvas_chain(int form, const fhip_conv_param& p, const fhip_conv_para
     else if (form == FHIP_CANVAS_INSIDE) FHIP_CANVAS_LAUNCH(FHIP_CANVAS_INSIDE, false);
     else FHIP_CANVAS_LAUNCH(FHIP_CANVAS_EXIT, false);
 #undef FHIP_CANVAS_LAUNCH
-    FHIP_CANVAS_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -430,7 +416,7 @@ static int canvas_output(const fhip_conv_param& p, int batch, const fhip_winogra
     if (pool) FHIP_CANVAS_OUT(true);
     else FHIP_CANVAS_OUT(false);
 #undef FHIP_CANVAS_OUT
-    FHIP_CANVAS_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -453,6 +439,6 @@ int fhip_canvas_output_transform(const fhip_conv_param* param, int batch, const 
     return fhip::canvas_output(*param, batch, *plan, output, m, bias, pool, (hipStream_t)stream);
 }
 
-const char* fhip_canvas_last_error(void) { return fhip::g_error.c_str(); }
+const char* fhip_canvas_last_error(void) { return fhip::last_error(); }
 
 } // extern "C"

@@ -29,109 +29,26 @@
 #include <string.h>
 
 #include <algorithm>
-#include <string>
 
 #include "feather_hip/feather_deconv.h"
+#include "direct_conv.h"
 #include "gemm_core.h"
 
 namespace fhip
 {
 
-static thread_local std::string g_error;
-
-// the two helpers ../csrc/common.h declares and gemm_core.h's includer must provide (hidden visibility: private to this library)
-int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-int fail_hip(hipError_t e, const char* what)
-{
-    g_error = std::string(what) + ": " + hipGetErrorString(e);
-    return FHIP_E_HIP;
-}
-
-// ---- the generic route ----------------------------------------------------------------------------------------------
-struct DeconvArgs
-{
-    const float* x;
-    const float* w; // packed [group][chunk][C/group][kh * kw][KT], zero-padded past K/group
-    const float* bias;
-    float* y;
-    int C, K, Cg, Kg, H, W, Ho, Wo, kh, kw, sh, sw, pt, pl;
-    int chunks; // chunks of KT output channels per group
-    int relu;
-    unsigned total; // lanes: batch * Ho * Wo
-};
-
+// ---- the generic route: direct_conv.h's body under this library's kernel names (the names fhip_deconv_route and traces report) ----
 template <int KT>
-__global__ __launch_bounds__(256) void deconv_generic_kernel(const DeconvArgs a)
-{
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= a.total) return;
-    const int gc = blockIdx.y;
-    const int g = gc / a.chunks, chunk = gc - g * a.chunks;
-    const int ox = (int)(i % (unsigned)a.Wo);
-    const unsigned t = i / (unsigned)a.Wo;
-    const int oy = (int)(t % (unsigned)a.Ho), n = (int)(t / (unsigned)a.Ho);
-    const int ty = oy + a.pt, tx = ox + a.pl;
-    const int qy = ty / a.sh, py = ty - qy * a.sh, qx = tx / a.sw, px = tx - qx * a.sw;
-    const int taps = a.kh * a.kw;
-    const size_t plane = (size_t)a.H * a.W;
-    const float* xp = a.x + ((size_t)n * a.C + (size_t)g * a.Cg) * plane;
-    const float* __restrict__ wp = a.w + (size_t)gc * a.Cg * taps * KT;
+__global__ __launch_bounds__(256) void deconv_generic_kernel(const DirectConvArgs a) { direct_conv_body<KT, PhaseTaps>(a); }
 
-    float acc[KT];
-#pragma unroll
-    for (int k = 0; k < KT; ++k) acc[k] = 0.f;
-    for (int c = 0; c < a.Cg; ++c, xp += plane, wp += taps * KT)
-        for (int r = py, iy = qy; r < a.kh; r += a.sh, --iy)
-        {
-            const bool row_in = iy >= 0 && iy < a.H;
-            const float* row = xp + (size_t)min(max(iy, 0), a.H - 1) * a.W; // always a row of the plane
-            for (int s = px, ix = qx; s < a.kw; s += a.sw, --ix)
-            {
-                float v = row[min(max(ix, 0), a.W - 1)];
-                if (!row_in || ix < 0 || ix >= a.W) v = 0.f;
-                const float* wq = wp + (r * a.kw + s) * KT;
-#pragma unroll
-                for (int k = 0; k < KT; ++k) acc[k] = fmaf(wq[k], v, acc[k]);
-            }
-        }
-
-    const int kk0 = chunk * KT;
-    const size_t oplane = (size_t)a.Ho * a.Wo;
-    float* yp = a.y + (((size_t)n * a.K + (size_t)g * a.Kg + kk0) * a.Ho + oy) * a.Wo + ox;
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-        if (kk0 + k < a.Kg)
-        {
-            float o = acc[k] + (a.bias ? a.bias[g * a.Kg + kk0 + k] : 0.f);
-            if (a.relu) o = fmaxf(o, 0.f);
-            yp[k * oplane] = o;
-        }
-}
-
-// kernel [K][Cg][taps] -> packed [group][chunk][Cg][taps][kt], zeros past Kg; one lane per packed word
 __global__ __launch_bounds__(256) void deconv_pack_generic_kernel(float* packed, const float* kernel, int Cg, int Kg, int taps, int kt, int chunks, unsigned total)
 {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= total) return;
-    const int k = (int)(i % (unsigned)kt);
-    unsigned t = i / (unsigned)kt;
-    const int tap = (int)(t % (unsigned)taps);
-    t /= (unsigned)taps;
-    const int c = (int)(t % (unsigned)Cg);
-    const int gc = (int)(t / (unsigned)Cg);
-    const int g = gc / chunks, kk = (gc - g * chunks) * kt + k;
-    packed[i] = kk < Kg ? kernel[(((size_t)g * Kg + kk) * Cg + c) * taps + tap] : 0.f;
+    direct_pack_body(packed, kernel, Cg, Kg, taps, kt, chunks, total);
 }
 
 // ---- the MFMA route: a policy of gemm_core.h ------------------------------------------------------------------------
 constexpr int kDeconvBK = 16;
 constexpr int kMaxPhases = 16;
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4))); // a float4 that is only 4-byte aligned
 
 struct DeconvGemmParams
 {
@@ -347,9 +264,8 @@ static int out_w(const fhip_deconv_param& p) { return (p.input_w - 1) * p.stride
 // Every refusal of a param except the output dims; 0 when the layer is one of this library's.
 static int check_geometry(const fhip_deconv_param* p)
 {
-    if (!p) return fail(FHIP_E_BADARG, "null param");
-    if (p->input_channels < 1 || p->output_channels < 1 || p->input_h < 1 || p->input_w < 1) return fail(FHIP_E_BADARG, "channels and input size must be >= 1");
-    if (p->kernel_h < 1 || p->kernel_w < 1 || p->stride_h < 1 || p->stride_w < 1) return fail(FHIP_E_BADARG, "kernel size and stride must be >= 1");
+    const int rc = check_sizes(p);
+    if (rc) return rc;
     if (p->pad_left < 0 || p->pad_right < 0 || p->pad_top < 0 || p->pad_bottom < 0) return fail(FHIP_E_BADARG, "negative padding");
     if (p->output_pad_right < 0 || p->output_pad_bottom < 0) return fail(FHIP_E_BADARG, "negative output padding");
     if (p->group < 1 || p->input_channels % p->group) return fail(FHIP_E_BADARG, "input_channels is not divisible by group");
@@ -405,23 +321,6 @@ static const char* route_name(RouteKind r)
     case ROUTE_MFMA_PAIR_SMALLM: return "fhip::gemm_mfma_kernel<fhip::GemmShape<64, 128, 16, 1, 4, 4>, fhip::DeconvGemmPolicy<true> >";
     default: return "fhip::deconv_generic_kernel<4>";
     }
-}
-
-constexpr int kGenericKT = 4;
-
-struct GenericPlan
-{
-    int Cg, Kg, chunks, taps;
-};
-
-static GenericPlan generic_plan(const fhip_deconv_param& p)
-{
-    GenericPlan pl;
-    pl.Cg = p.input_channels / p.group;
-    pl.Kg = p.output_channels / p.group;
-    pl.taps = p.kernel_h * p.kernel_w;
-    pl.chunks = (pl.Kg + kGenericKT - 1) / kGenericKT;
-    return pl;
 }
 
 // Everything of DeconvGemmParams that does not depend on the batch or the pointers; returns the packed floats.
@@ -482,16 +381,10 @@ static size_t mfma_plan(const fhip_deconv_param& p, RouteKind r, DeconvGemmParam
     return off;
 }
 
-static bool aligned(const void* q, uintptr_t to) { return ((uintptr_t)q & (to - 1)) == 0; }
-
 static size_t packed_floats(const fhip_deconv_param& p)
 {
     const RouteKind r = select(p);
-    if (r == ROUTE_GENERIC)
-    {
-        const GenericPlan pl = generic_plan(p);
-        return (size_t)p.group * pl.chunks * pl.Cg * pl.taps * kGenericKT;
-    }
+    if (r == ROUTE_GENERIC) return generic_packed_floats(p, kGenericKT);
     DeconvGemmParams g;
     return mfma_plan(p, r, g);
 }
@@ -548,11 +441,7 @@ int fhip_deconv_init(const fhip_deconv_param* param, float* packed, const float*
     if (total > 0x7fffffffULL) return fail(FHIP_E_BADARG, "filter tensor too large: 2^31 packed floats or more");
     const dim3 grid((unsigned)((total + 255) / 256));
     if (r == ROUTE_GENERIC)
-    {
-        const GenericPlan pl = generic_plan(p);
-        hipLaunchKernelGGL(deconv_pack_generic_kernel, grid, dim3(256), 0, (hipStream_t)stream, packed, kernel, pl.Cg, pl.Kg, pl.taps, kGenericKT, pl.chunks,
-                           (unsigned)total);
-    }
+        launch_direct_pack(deconv_pack_generic_kernel, p, kGenericKT, total, packed, kernel, (hipStream_t)stream);
     else
     {
         DeconvGemmParams g;
@@ -569,47 +458,21 @@ int fhip_deconv_init(const fhip_deconv_param* param, float* packed, const float*
 int fhip_deconv_forward(const fhip_deconv_param* param, int batch, float* out, const float* in, const float* packed, float* /*scratch*/,
                         const float* bias, void* stream)
 {
-    const int rc = check_param(param);
+    int rc = check_param(param);
     if (rc) return rc;
-    if (batch < 1) return fail(FHIP_E_BADARG, "batch < 1");
-    if (!out || !in || !packed) return fail(FHIP_E_BADARG, "null out / in / packed");
     const fhip_deconv_param& p = *param;
-    if (p.bias_term && !bias) return fail(FHIP_E_BADARG, "bias_term is set and bias is NULL");
-    if (!aligned(out, 4) || !aligned(in, 4) || !aligned(packed, 16) || (p.bias_term && !aligned(bias, 4)))
-        return fail(FHIP_E_BADARG, "device pointers must be 4-byte aligned (packed: 16-byte)");
+    rc = check_forward_pointers(p, batch, out, in, packed, bias, 16, "device pointers must be 4-byte aligned (packed: 16-byte)");
+    if (rc) return rc;
     const unsigned long long in_count = (unsigned long long)batch * p.input_channels * p.input_h * p.input_w;
     const unsigned long long out_count = (unsigned long long)batch * p.output_channels * p.output_h * p.output_w;
     if (in_count > 0x7fffffffULL || out_count > 0x7fffffffULL) return fail(FHIP_E_BADARG, "tensor too large: 2^31 elements or more");
     const RouteKind r = select(p);
     if (r == ROUTE_GENERIC)
     {
-        const GenericPlan pl = generic_plan(p);
-        DeconvArgs a;
-        a.x = in;
-        a.w = packed;
-        a.bias = p.bias_term ? bias : nullptr;
-        a.y = out;
-        a.C = p.input_channels;
-        a.K = p.output_channels;
-        a.Cg = pl.Cg;
-        a.Kg = pl.Kg;
-        a.H = p.input_h;
-        a.W = p.input_w;
-        a.Ho = p.output_h;
-        a.Wo = p.output_w;
-        a.kh = p.kernel_h;
-        a.kw = p.kernel_w;
-        a.sh = p.stride_h;
-        a.sw = p.stride_w;
-        a.pt = p.pad_top;
-        a.pl = p.pad_left;
-        a.chunks = pl.chunks;
-        a.relu = p.activation == FHIP_ACT_RELU;
-        const size_t total = (size_t)batch * p.output_h * p.output_w;
-        const size_t gy = (size_t)p.group * pl.chunks;
-        if (gy > 65535) return fail(FHIP_E_BADARG, "more than 65535 chunks of 4 output channels");
-        a.total = (unsigned)total;
-        hipLaunchKernelGGL(deconv_generic_kernel<kGenericKT>, dim3((unsigned)((total + 255) / 256), (unsigned)gy), dim3(256), 0, (hipStream_t)stream, a);
+        DirectConvArgs a = direct_conv_args(p, kGenericKT, out, in, packed, bias);
+        rc = launch_direct(deconv_generic_kernel<kGenericKT>, a, (size_t)batch * p.output_h * p.output_w, (size_t)p.group * a.chunks, (hipStream_t)stream,
+                           "more than 65535 chunks of 4 output channels");
+        if (rc) return rc;
     }
     else
     {
@@ -643,6 +506,6 @@ int fhip_deconv_route(const fhip_deconv_param* param, char* name, int len)
     return FHIP_OK;
 }
 
-const char* fhip_deconv_last_error(void) { return g_error.c_str(); }
+const char* fhip_deconv_last_error(void) { return last_error(); }
 
 } // extern "C"

@@ -27,24 +27,10 @@
 #include <string>
 
 #include "feather_hip/feather_gate.h"
+#include "side_error.h"
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-static int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-#define FHIP_GATE_CHECK_HIP(expr)                                                               \
-    do                                                                                          \
-    {                                                                                           \
-        const hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return fail(FHIP_E_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 constexpr int kGroupMaxHW = 4096;   // planes up to here: a group of lanes of one wave per plane
 constexpr int kChunk = 16384;       // floats one 256-thread block sums: a whole plane up to here, a chunk of a larger one
@@ -288,7 +274,7 @@ static int excite_launch(int slices, int n, int c, int r, float* gate, const flo
     if (slices < 1 || slices > 1024) return fail(FHIP_E_BADARG, "slices must be in 1 .. 1024");
     hipLaunchKernelGGL(excite_kernel, dim3(std::min(slices, c), n), dim3(kExciteThreads), 0, (hipStream_t)stream, gate, mean, w1, b1, w2, b2, c, r, mact, gact, alpha,
                        beta);
-    FHIP_GATE_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -312,7 +298,7 @@ int fhip_channel_gate_forward(int n, int c, int h, int w, float* out, const floa
         hipLaunchKernelGGL(gate_apply_kernel<true>, dim3(grid_for(total / 4)), dim3(256), 0, s, out, in, gate, residual, total / 4, hw, act);
     else
         hipLaunchKernelGGL(gate_apply_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, out, in, gate, residual, total, hw, act);
-    FHIP_GATE_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -364,7 +350,7 @@ int fhip_squeeze_forward(int n, int c, int h, int w, float* mean, const float* i
         break;
     }
     }
-    FHIP_GATE_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -398,7 +384,7 @@ int fhip_gate_activation_forward(int kind, float* out, const float* in, int n, i
         hipLaunchKernelGGL(gate_activation_kernel<true>, dim3(grid_for(total / 4)), dim3(256), 0, s, out, in, kind, total / 4, alpha, beta);
     else
         hipLaunchKernelGGL(gate_activation_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, out, in, kind, total, alpha, beta);
-    FHIP_GATE_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -425,6 +411,6 @@ int fhip_gate_route(int op, int n, int c, int h, int w, const float* out, const 
     return FHIP_OK;
 }
 
-const char* fhip_gate_last_error(void) { return g_error.c_str(); }
+const char* fhip_gate_last_error(void) { return last_error(); }
 
 } // extern "C"

@@ -19,53 +19,17 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <string>
-
 #include "feather_hip/feather_gconv.h"
+#include "direct_conv.h"
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-static int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-static int fail_hip(hipError_t e, const char* what)
-{
-    g_error = std::string(what) + ": " + hipGetErrorString(e);
-    return FHIP_E_HIP;
-}
-
-#define GCONV_CHECK_HIP(expr)                               \
-    do                                                      \
-    {                                                       \
-        hipError_t e__ = (expr);                            \
-        if (e__ != hipSuccess) return fail_hip(e__, #expr); \
-    } while (0)
-
-// What a kernel needs, by value (nothing to upload, so the call is stream-capturable).
-struct GconvArgs
-{
-    const float* x;
-    const float* w; // packed [group][chunk][C/group][kh * kw][KT], zero-padded past K/group
-    const float* bias;
-    float* y;
-    int C, K, Cg, Kg, H, W, Ho, Wo, kh, kw, sh, sw, pt, pl;
-    int chunks; // chunks of KT output channels per group
-    int strips; // lanes per output row: ceil(Wo / 4) (gconv3x3_kernel) or Wo (generic)
-    int relu;
-    unsigned total; // lanes: batch * Ho * strips
-};
 
 // y[n][g * Kg + chunk * KT .. + KT)[oy][ox .. ox + 4) for a 3x3 kernel with pad 1 and stride S in both directions.
 // VEC: W % (4 * S) == 0 (so Wo % 4 == 0, every strip is full and every 4 * S input columns behind ox * S are inside the row) and x, y
 // 16-byte aligned; else dword accesses, columns past the row neither loaded out of the plane nor stored.
 template <int KT, int S, bool VEC>
-__global__ __launch_bounds__(256) void gconv3x3_kernel(const GconvArgs a)
+__global__ __launch_bounds__(256) void gconv3x3_kernel(const DirectConvArgs a)
 {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= a.total) return;
@@ -164,67 +128,13 @@ __global__ __launch_bounds__(256) void gconv3x3_kernel(const GconvArgs a)
     }
 }
 
-// y[n][g * Kg + chunk * KT .. + KT)[oy][ox]: any kernel size, stride and padding; lane i of [batch][Ho][Wo].
+// Any kernel size, stride and padding: direct_conv.h's body under this library's kernel name (the name fhip_gconv_route reports).
 template <int KT>
-__global__ __launch_bounds__(256) void gconv_generic_kernel(const GconvArgs a)
-{
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= a.total) return;
-    const int gc = blockIdx.y;
-    const int g = gc / a.chunks, chunk = gc - g * a.chunks;
-    const int ox = (int)(i % (unsigned)a.Wo);
-    const unsigned t = i / (unsigned)a.Wo;
-    const int oy = (int)(t % (unsigned)a.Ho), n = (int)(t / (unsigned)a.Ho);
-    const size_t plane = (size_t)a.H * a.W;
-    const float* xp = a.x + ((size_t)n * a.C + (size_t)g * a.Cg) * plane;
-    const float* __restrict__ wp = a.w + (size_t)gc * a.Cg * a.kh * a.kw * KT;
-    const int iy0 = oy * a.sh - a.pt, ix0 = ox * a.sw - a.pl;
+__global__ __launch_bounds__(256) void gconv_generic_kernel(const DirectConvArgs a) { direct_conv_body<KT, UnitTaps>(a); }
 
-    float acc[KT];
-#pragma unroll
-    for (int k = 0; k < KT; ++k) acc[k] = 0.f;
-    for (int c = 0; c < a.Cg; ++c, xp += plane)
-        for (int r = 0; r < a.kh; ++r)
-        {
-            const int iy = iy0 + r;
-            const bool row_in = iy >= 0 && iy < a.H;
-            const float* row = xp + (size_t)min(max(iy, 0), a.H - 1) * a.W;
-            for (int s = 0; s < a.kw; ++s, wp += KT)
-            {
-                const int ix = ix0 + s;
-                float v = row[min(max(ix, 0), a.W - 1)];
-                if (!row_in || ix < 0 || ix >= a.W) v = 0.f;
-#pragma unroll
-                for (int k = 0; k < KT; ++k) acc[k] = fmaf(wp[k], v, acc[k]);
-            }
-        }
-
-    const int kk0 = chunk * KT;
-    const size_t oplane = (size_t)a.Ho * a.Wo;
-    float* yp = a.y + (((size_t)n * a.K + (size_t)g * a.Kg + kk0) * a.Ho + oy) * a.Wo + ox;
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-        if (kk0 + k < a.Kg)
-        {
-            float o = acc[k] + (a.bias ? a.bias[g * a.Kg + kk0 + k] : 0.f);
-            if (a.relu) o = fmaxf(o, 0.f);
-            yp[k * oplane] = o;
-        }
-}
-
-// kernel [K][Cg][taps] -> packed [group][chunk][Cg][taps][kt], zeros past Kg; one lane per packed word
 __global__ __launch_bounds__(256) void gconv_pack_kernel(float* packed, const float* kernel, int Cg, int Kg, int taps, int kt, int chunks, unsigned total)
 {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= total) return;
-    const int k = (int)(i % (unsigned)kt);
-    unsigned t = i / (unsigned)kt;
-    const int tap = (int)(t % (unsigned)taps);
-    t /= (unsigned)taps;
-    const int c = (int)(t % (unsigned)Cg);
-    const int gc = (int)(t / (unsigned)Cg);
-    const int g = gc / chunks, kk = (gc - g * chunks) * kt + k;
-    packed[i] = kk < Kg ? kernel[(((size_t)g * Kg + kk) * Cg + c) * taps + tap] : 0.f;
+    direct_pack_body(packed, kernel, Cg, Kg, taps, kt, chunks, total);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
@@ -232,18 +142,17 @@ __global__ __launch_bounds__(256) void gconv_pack_kernel(float* packed, const fl
 // Every refusal of a param; 0 when the layer is one of this library's.
 static int check_param(const fhip_conv_param* p)
 {
-    if (!p) return fail(FHIP_E_BADARG, "null param");
-    if (p->input_channels < 1 || p->output_channels < 1 || p->input_h < 1 || p->input_w < 1) return fail(FHIP_E_BADARG, "channels and input size must be >= 1");
-    if (p->kernel_h < 1 || p->kernel_w < 1 || p->stride_h < 1 || p->stride_w < 1) return fail(FHIP_E_BADARG, "kernel size and stride must be >= 1");
+    const int rc = check_sizes(p);
+    if (rc) return rc;
     if (p->pad_left < 0 || p->pad_right < 0 || p->pad_top < 0 || p->pad_bottom < 0) return fail(FHIP_E_BADARG, "negative padding");
     if (p->group <= 1) return fail(FHIP_E_BADARG, "group <= 1: a dense convolution runs through fhip_conv_forward (libfeather_hip.so)");
     if (p->group == p->input_channels) return fail(FHIP_E_BADARG, "group == input_channels: a depthwise convolution runs through fhip_conv_forward (libfeather_hip.so)");
     if (p->group > p->input_channels || p->input_channels % p->group) return fail(FHIP_E_BADARG, "input_channels is not divisible by group");
     if (p->output_channels % p->group) return fail(FHIP_E_BADARG, "output_channels (of the whole layer) is not divisible by group");
-    if (p->input_h + p->pad_top + p->pad_bottom < p->kernel_h || p->input_w + p->pad_left + p->pad_right < p->kernel_w)
-        return fail(FHIP_E_BADARG, "the kernel is larger than the padded input");
-    const int oh = (p->input_h + p->pad_top + p->pad_bottom - p->kernel_h) / p->stride_h + 1;
-    const int ow = (p->input_w + p->pad_left + p->pad_right - p->kernel_w) / p->stride_w + 1;
+    // 64-bit sums: pads near 2^31 overflowed the int form, and which refusal such a param met depended on how the compiler used that
+    const long long ph = (long long)p->input_h + p->pad_top + p->pad_bottom, pw = (long long)p->input_w + p->pad_left + p->pad_right;
+    if (ph < p->kernel_h || pw < p->kernel_w) return fail(FHIP_E_BADARG, "the kernel is larger than the padded input");
+    const long long oh = (ph - p->kernel_h) / p->stride_h + 1, ow = (pw - p->kernel_w) / p->stride_w + 1;
     if (p->output_h != oh || p->output_w != ow) return fail(FHIP_E_BADARG, "output_h / output_w are not what fhip_conv_assign_output_dim gives");
     if (p->activation != FHIP_ACT_NONE && p->activation != FHIP_ACT_RELU) return fail(FHIP_E_BADARG, "activation must be None or ReLU");
     return FHIP_OK;
@@ -251,7 +160,7 @@ static int check_param(const fhip_conv_param* p)
 
 struct Plan
 {
-    int Cg, Kg, kt, chunks, taps;
+    int kt;     // output channels per lane
     bool tuned; // gconv3x3_kernel
 };
 
@@ -259,27 +168,20 @@ static bool pow2_4_32(int v) { return v == 4 || v == 8 || v == 16 || v == 32; }
 
 static Plan plan_of(const fhip_conv_param& p)
 {
+    const int Cg = p.input_channels / p.group, Kg = p.output_channels / p.group;
     Plan pl;
-    pl.Cg = p.input_channels / p.group;
-    pl.Kg = p.output_channels / p.group;
-    pl.taps = p.kernel_h * p.kernel_w;
     pl.tuned = p.kernel_h == 3 && p.kernel_w == 3 && p.stride_h == p.stride_w && (p.stride_h == 1 || p.stride_h == 2) && p.pad_left == 1 &&
-               p.pad_right == 1 && p.pad_top == 1 && p.pad_bottom == 1 && pow2_4_32(pl.Cg) && pow2_4_32(pl.Kg);
-    pl.kt = pl.tuned ? (pl.Kg >= 16 ? 16 : pl.Kg) : 4;
-    pl.chunks = (pl.Kg + pl.kt - 1) / pl.kt;
+               p.pad_right == 1 && p.pad_top == 1 && p.pad_bottom == 1 && pow2_4_32(Cg) && pow2_4_32(Kg);
+    pl.kt = pl.tuned ? (Kg >= 16 ? 16 : Kg) : kGenericKT;
     return pl;
 }
-
-static size_t packed_floats(const fhip_conv_param& p, const Plan& pl) { return (size_t)p.group * pl.chunks * pl.Cg * pl.taps * pl.kt; }
-
-static bool aligned(const void* q, uintptr_t to) { return ((uintptr_t)q & (to - 1)) == 0; }
 
 static bool vec_ok(const fhip_conv_param& p, const float* out, const float* in)
 {
     return p.input_w % (4 * p.stride_w) == 0 && aligned(out, 16) && aligned(in, 16);
 }
 
-typedef void (*gconv_fn)(const GconvArgs);
+typedef void (*gconv_fn)(const DirectConvArgs);
 struct Route
 {
     gconv_fn fn;
@@ -307,24 +209,12 @@ static Route select(const fhip_conv_param& p, const Plan& pl, const float* out, 
     if (!pl.tuned)
     {
         Route r;
-        r.fn = gconv_generic_kernel<4>;
+        r.fn = gconv_generic_kernel<kGenericKT>;
         snprintf(r.name, sizeof(r.name), "fhip::gconv_generic_kernel<4>");
         return r;
     }
     const bool vec = vec_ok(p, out, in);
     return pl.kt == 16 ? route_k<16>(p.stride_h, vec) : pl.kt == 8 ? route_k<8>(p.stride_h, vec) : route_k<4>(p.stride_h, vec);
-}
-
-static int check_forward(const fhip_conv_param* p, int batch, const float* out, const float* in, const float* packed, const float* bias)
-{
-    const int rc = check_param(p);
-    if (rc) return rc;
-    if (batch < 1) return fail(FHIP_E_BADARG, "batch < 1");
-    if (!out || !in || !packed) return fail(FHIP_E_BADARG, "null out / in / packed");
-    if (p->bias_term && !bias) return fail(FHIP_E_BADARG, "bias_term is set and bias is NULL");
-    if (!aligned(out, 4) || !aligned(in, 4) || !aligned(packed, 4) || (p->bias_term && !aligned(bias, 4)))
-        return fail(FHIP_E_BADARG, "device pointers must be 4-byte aligned");
-    return FHIP_OK;
 }
 
 } // namespace fhip
@@ -342,7 +232,7 @@ int fhip_gconv_get_buffer_size(const fhip_conv_param* param, int batch, size_t* 
     if (rc) return rc;
     if (batch < 1 || !scratch_bytes || !packed_bytes) return fail(FHIP_E_BADARG, "batch < 1 or a null size pointer");
     *scratch_bytes = 0;
-    *packed_bytes = packed_floats(*param, plan_of(*param)) * sizeof(float);
+    *packed_bytes = generic_packed_floats(*param, plan_of(*param).kt) * sizeof(float);
     return FHIP_OK;
 }
 
@@ -352,51 +242,28 @@ int fhip_gconv_init(const fhip_conv_param* param, float* packed, const float* ke
     if (rc) return rc;
     if (!packed || !kernel) return fail(FHIP_E_BADARG, "null packed / kernel");
     if (!aligned(packed, 4) || !aligned(kernel, 4)) return fail(FHIP_E_BADARG, "device pointers must be 4-byte aligned");
-    const Plan pl = plan_of(*param);
-    const size_t total = packed_floats(*param, pl);
+    const int kt = plan_of(*param).kt;
+    const size_t total = generic_packed_floats(*param, kt);
     if (total > 0x7fffffffULL) return fail(FHIP_E_BADARG, "filter tensor too large: 2^31 packed floats or more");
-    hipLaunchKernelGGL(gconv_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, packed, kernel, pl.Cg, pl.Kg,
-                       pl.taps, pl.kt, pl.chunks, (unsigned)total);
-    GCONV_CHECK_HIP(hipGetLastError());
+    launch_direct_pack(gconv_pack_kernel, *param, kt, total, packed, kernel, (hipStream_t)stream);
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
 int fhip_gconv_forward(const fhip_conv_param* param, int batch, float* out, const float* in, const float* packed, float* /*scratch*/,
                        const float* bias, void* stream)
 {
-    const int rc = check_forward(param, batch, out, in, packed, bias);
+    int rc = check_param(param);
+    if (!rc) rc = check_forward_pointers(*param, batch, out, in, packed, bias, 4, "device pointers must be 4-byte aligned");
     if (rc) return rc;
     const fhip_conv_param& p = *param;
     const Plan pl = plan_of(p);
-    GconvArgs a;
-    a.x = in;
-    a.w = packed;
-    a.bias = p.bias_term ? bias : nullptr;
-    a.y = out;
-    a.C = p.input_channels;
-    a.K = p.output_channels;
-    a.Cg = pl.Cg;
-    a.Kg = pl.Kg;
-    a.H = p.input_h;
-    a.W = p.input_w;
-    a.Ho = p.output_h;
-    a.Wo = p.output_w;
-    a.kh = p.kernel_h;
-    a.kw = p.kernel_w;
-    a.sh = p.stride_h;
-    a.sw = p.stride_w;
-    a.pt = p.pad_top;
-    a.pl = p.pad_left;
-    a.chunks = pl.chunks;
-    a.strips = pl.tuned ? (p.output_w + 3) / 4 : p.output_w;
-    a.relu = p.activation == FHIP_ACT_RELU;
-    const size_t total = (size_t)batch * p.output_h * a.strips;
-    const size_t gy = (size_t)p.group * pl.chunks;
-    if (total > 0x7fffffffULL || gy > 65535) return fail(FHIP_E_BADARG, "tensor too large: 2^31 lanes or more, or more than 65535 channel chunks");
-    a.total = (unsigned)total;
-    const Route r = select(p, pl, out, in);
-    hipLaunchKernelGGL(r.fn, dim3((unsigned)((total + 255) / 256), (unsigned)gy), dim3(256), 0, (hipStream_t)stream, a);
-    GCONV_CHECK_HIP(hipGetLastError());
+    DirectConvArgs a = direct_conv_args(p, pl.kt, out, in, packed, bias);
+    if (pl.tuned) a.strips = (p.output_w + 3) / 4;
+    rc = launch_direct(select(p, pl, out, in).fn, a, (size_t)batch * p.output_h * a.strips, (size_t)p.group * a.chunks, (hipStream_t)stream,
+                       "tensor too large: 2^31 lanes or more, or more than 65535 channel chunks");
+    if (rc) return rc;
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -411,6 +278,6 @@ int fhip_gconv_route(const fhip_conv_param* param, const float* out, const float
     return FHIP_OK;
 }
 
-const char* fhip_gconv_last_error(void) { return g_error.c_str(); }
+const char* fhip_gconv_last_error(void) { return last_error(); }
 
 } // extern "C"

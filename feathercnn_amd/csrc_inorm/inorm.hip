@@ -25,24 +25,10 @@
 #include <string>
 
 #include "feather_hip/feather_inorm.h"
+#include "side_error.h"
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-static int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-#define FHIP_INORM_CHECK_HIP(expr)                                                              \
-    do                                                                                          \
-    {                                                                                           \
-        const hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return fail(FHIP_E_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 constexpr int PER = 16;            // floats of a plane (or chunk) one thread holds
 constexpr int CHUNK = 256 * PER;   // floats per block of the split-plane route
@@ -403,7 +389,7 @@ static int launch(Route route, int n, int c, int h, int w, float* out, const flo
         else
             hipLaunchKernelGGL((inorm_plane_kernel<1024, 1024, false>), grid, dim3(1024), 0, s, out, in, gamma, beta, planes, c, hw, eps, act, slope);
     }
-    FHIP_INORM_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -445,10 +431,10 @@ int fhip_activation_forward(int kind, float* out, const float* in, int n, int c,
         hipLaunchKernelGGL(activation_kernel<true>, dim3(blocks), dim3(256), 0, s, out, in, slopes, kind, units, c, hw, slope_or_min, max);
     else
         hipLaunchKernelGGL(activation_kernel<false>, dim3(blocks), dim3(256), 0, s, out, in, slopes, kind, units, c, hw, slope_or_min, max);
-    FHIP_INORM_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
-const char* fhip_inorm_last_error(void) { return g_error.c_str(); }
+const char* fhip_inorm_last_error(void) { return last_error(); }
 
 } // extern "C"

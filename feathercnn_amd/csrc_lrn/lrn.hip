@@ -25,24 +25,10 @@
 #include <string>
 
 #include "feather_hip/feather_lrn.h"
+#include "side_error.h"
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-static int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-#define FHIP_LRN_CHECK_HIP(expr)                                                                \
-    do                                                                                          \
-    {                                                                                           \
-        const hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return fail(FHIP_E_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 // A product and a sum that are each rounded to fp32: hipcc contracts a * b + c into one fma by default, and the pragma takes the
 // contraction off these operations wherever they are inlined (as in csrc_gate/gate.hip).
@@ -418,7 +404,7 @@ static int across_forward(const LrnArgs& g, int n, int c, int h, int w, int chun
         launch_across<4>(held(g.local_size), grid, (hipStream_t)stream, out, in, g, c, hw, bpi, chunk);
     else
         launch_across<1>(held(g.local_size), grid, (hipStream_t)stream, out, in, g, c, hw, bpi, chunk);
-    FHIP_LRN_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -474,7 +460,7 @@ int fhip_lrn_forward(int region, int local_size, float alpha, float beta, float 
     if ((rc = check_pointers(out, total, in, total))) return rc;
     if (region == FHIP_LRN_ACROSS_CHANNELS) return across_forward(g, n, c, h, w, -1, out, in, stream);
     hipLaunchKernelGGL(lrn_within_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, in, g, c, h, w, (unsigned)total);
-    FHIP_LRN_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -530,7 +516,7 @@ int fhip_lrn_pool_forward(int region, int local_size, float alpha, float beta, f
     }
     else
         hipLaunchKernelGGL(lrn_pool_direct_kernel, dim3((unsigned)((total_out + 255) / 256)), dim3(256), 0, s, out, in, g, q, region, c, (unsigned)total_out);
-    FHIP_LRN_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -552,6 +538,6 @@ int fhip_lrn_pool_route(int region, int local_size, int n, int c, int h, int w, 
     return FHIP_OK;
 }
 
-const char* fhip_lrn_last_error(void) { return g_error.c_str(); }
+const char* fhip_lrn_last_error(void) { return last_error(); }
 
 } // extern "C"

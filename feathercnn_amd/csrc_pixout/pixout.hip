@@ -14,31 +14,11 @@
 #include <string>
 
 #include "feather_hip/feather_pixout.h"
+#include "side_error.h"
 #include "pixel_resample.h"
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-static int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-static int fail_hip(hipError_t e, const char* what)
-{
-    g_error = std::string(what) + ": " + hipGetErrorString(e);
-    return FHIP_E_HIP;
-}
-
-#define PIXOUT_CHECK_HIP(expr)                              \
-    do                                                      \
-    {                                                       \
-        hipError_t e__ = (expr);                            \
-        if (e__ != hipSuccess) return fail_hip(e__, #expr); \
-    } while (0)
 
 // What the kernel needs, by value (nothing to upload, so the call is stream-capturable).
 struct PixelDst
@@ -252,7 +232,7 @@ static int launch(unsigned char* pixels, size_t pitch, const float* x, int batch
         launch_cn<3>(vec, grid, s, q, total);
     else
         launch_cn<4>(vec, grid, s, q, total);
-    PIXOUT_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -288,7 +268,7 @@ int fhip_float_to_pixels_host(unsigned char* pixels_host, size_t pitch, const fl
     if (rc) return rc;
     const size_t row = (size_t)target_w * cn, rows = (size_t)batch * target_h;
     unsigned char* staging = nullptr;
-    PIXOUT_CHECK_HIP(hipMalloc(&staging, rows * row));
+    FHIP_CHECK_HIP(hipMalloc(&staging, rows * row));
     rc = launch(staging, row, x, batch, type, cn, w, h, target_w, target_h, mean, norm, stream);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpy2DAsync(pixels_host, row_pitch, staging, row, row, rows, hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -299,6 +279,6 @@ int fhip_float_to_pixels_host(unsigned char* pixels_host, size_t pitch, const fl
     return FHIP_OK;
 }
 
-const char* fhip_pixout_last_error(void) { return g_error.c_str(); }
+const char* fhip_pixout_last_error(void) { return last_error(); }
 
 } // extern "C"

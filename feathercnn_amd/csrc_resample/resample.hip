@@ -27,24 +27,10 @@
 #include <string>
 
 #include "feather_hip/feather_resample.h"
+#include "side_error.h"
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-static int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-#define FHIP_RESAMPLE_CHECK_HIP(expr)                                                           \
-    do                                                                                          \
-    {                                                                                           \
-        const hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return fail(FHIP_E_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 constexpr unsigned kMaxGrid = 4096; // blocks of the grid-strided kernels (256 CUs x 16)
 
@@ -389,7 +375,7 @@ int fhip_interp_forward(int mode, int align_corner, int n, int c, int in_h, int 
             hipLaunchKernelGGL(interp_gather_kernel<FHIP_INTERP_BILINEAR>, dim3(grid_for(gather_units)), dim3(256), 0, s, out, in, residual, gather_units, ay, ax, relu);
         break;
     }
-    FHIP_RESAMPLE_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -426,7 +412,7 @@ int fhip_hardswish_forward(float* out, const float* in, int n, int c, int hw, fl
         hipLaunchKernelGGL(hardswish_kernel<true>, dim3(grid_for(total / 4)), dim3(256), 0, s, out, in, total / 4, alpha, beta, lower, upper);
     else
         hipLaunchKernelGGL(hardswish_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, out, in, total, alpha, beta, lower, upper);
-    FHIP_RESAMPLE_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return FHIP_OK;
 }
 
@@ -439,6 +425,6 @@ int fhip_hardswish_route(const float* out, const float* in, int n, int c, int hw
     return FHIP_OK;
 }
 
-const char* fhip_resample_last_error(void) { return g_error.c_str(); }
+const char* fhip_resample_last_error(void) { return last_error(); }
 
 } // extern "C"

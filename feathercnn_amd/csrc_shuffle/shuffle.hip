@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "feather_hip/feather_shuffle.h"
+#include "side_error.h"
 
 struct fhip_channel_map
 {
@@ -39,21 +40,6 @@ struct fhip_channel_map
 
 namespace fhip
 {
-
-static thread_local std::string g_error;
-
-static int fail(int code, const char* msg)
-{
-    g_error = msg;
-    return code;
-}
-
-#define FHIP_SHUFFLE_CHECK_HIP(expr)                                                            \
-    do                                                                                          \
-    {                                                                                           \
-        const hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) return fail(FHIP_E_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 constexpr int MAXB = FHIP_CHANNEL_MAP_MAX_BLOBS;
 constexpr int kBlock = 256;
@@ -152,8 +138,6 @@ __global__ __launch_bounds__(kBlock) void channel_map_kernel(const MapArgs a)
     }
 }
 
-static bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 static int check_shape(int n, int c, int h, int w)
 {
     if (n < 1 || c < 1 || h < 1 || w < 1) return fail(FHIP_E_BADARG, "every dimension must be at least 1");
@@ -201,7 +185,7 @@ static int launch(MapArgs& a, int n, int h, int w, bool vec, hipStream_t stream)
         hipLaunchKernelGGL((channel_map_kernel<KIND, true>), dim3(blocks), dim3(kBlock), 0, stream, a);
     else
         hipLaunchKernelGGL((channel_map_kernel<KIND, false>), dim3(blocks), dim3(kBlock), 0, stream, a);
-    FHIP_SHUFFLE_CHECK_HIP(hipGetLastError());
+    FHIP_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
@@ -370,6 +354,6 @@ int fhip_channel_map_route(int kind, int h, int w, const void* const* pointers, 
     return 0;
 }
 
-const char* fhip_shuffle_last_error(void) { return g_error.c_str(); }
+const char* fhip_shuffle_last_error(void) { return last_error(); }
 
 } // extern "C"

@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
-from .booster import FeatherHipError, _ptr, _stream
+from .booster import _ptr, _stream
 
 ACT_NONE, ACT_RELU = 0, 1
 SWISH, HARDSIGMOID = 0, 1
@@ -17,10 +17,7 @@ OP_APPLY, OP_SQUEEZE, OP_EXCITE, OP_ACTIVATION = range(4)
 OPS = {"apply": OP_APPLY, "squeeze": OP_SQUEEZE, "excite": OP_EXCITE, "activation": OP_ACTIVATION}
 
 
-def _check(rc: int, what: str):
-    if rc != 0:
-        msg = _lib.load_gate_library().fhip_gate_last_error().decode(errors="replace")
-        raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+_check = _lib.checker(_lib.load_gate_library, "fhip_gate_last_error")
 
 
 def _f32(t, what, dims=None):

@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
-from .booster import FeatherHipError, _ptr, _stream
+from .booster import _ptr, _stream
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 LEAKY_RELU, PRELU, SIGMOID, TANH, CLIP = range(5)
@@ -14,10 +14,7 @@ KINDS = {"leaky_relu": LEAKY_RELU, "prelu": PRELU, "sigmoid": SIGMOID, "tanh": T
 FLT_MAX = 3.4028234663852886e38
 
 
-def _check(rc: int, what: str):
-    if rc != 0:
-        msg = _lib.load_inorm_library().fhip_inorm_last_error().decode(errors="replace")
-        raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+_check = _lib.checker(_lib.load_inorm_library, "fhip_inorm_last_error")
 
 
 def _act(act, slope):

@@ -13,10 +13,7 @@ CHUNK = 16  # FHIP_LRN_CHUNK
 POOL_LDS_FLOATS = 8192  # FHIP_LRN_POOL_LDS_FLOATS
 
 
-def _check(rc: int, what: str):
-    if rc != 0:
-        msg = _lib.load_lrn_library().fhip_lrn_last_error().decode(errors="replace")
-        raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+_check = _lib.checker(_lib.load_lrn_library, "fhip_lrn_last_error")
 
 
 def _f32(t, what):

@@ -228,10 +228,7 @@ def output_channels(ptype: int) -> int:
     return _OUT_CHANNELS[ptype]
 
 
-def _check_pixout(rc: int, what: str):
-    if rc != 0:
-        msg = _lib.load_pixout_library().fhip_pixout_last_error().decode(errors="replace")
-        raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+_check_pixout = _lib.checker(_lib.load_pixout_library, "fhip_pixout_last_error")
 
 
 def float_to_pixels(x, ptype: int, target=None, mean=None, norm=None, out=None):

@@ -6,16 +6,13 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
-from .booster import FeatherHipError, _ptr, _stream
+from .booster import _ptr, _stream
 
 NEAREST, BILINEAR = 1, 2
 MODES = {"nearest": NEAREST, "bilinear": BILINEAR}
 
 
-def _check(rc: int, what: str):
-    if rc != 0:
-        msg = _lib.load_resample_library().fhip_resample_last_error().decode(errors="replace")
-        raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+_check = _lib.checker(_lib.load_resample_library, "fhip_resample_last_error")
 
 
 def _f32(t, what, dims=None):

@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
-from .booster import FeatherHipError, _ptr, _stream
+from .booster import _ptr, _stream
 
 MAX_BLOBS = 4  # FHIP_CHANNEL_MAP_MAX_BLOBS
 SHARE = -233   # FHIP_SLICE_SHARE
@@ -14,10 +14,7 @@ ROUTES = {"4b": 0, "16b": 1}
 KINDS = {"map": 0, "shuffle": 1, "slice": 2}
 
 
-def _check(rc: int, what: str):
-    if rc != 0:
-        msg = _lib.load_shuffle_library().fhip_shuffle_last_error().decode(errors="replace")
-        raise FeatherHipError(f"{what} failed with code {rc}: {msg}")
+_check = _lib.checker(_lib.load_shuffle_library, "fhip_shuffle_last_error")
 
 
 def _nchw(x, what):

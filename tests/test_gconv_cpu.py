@@ -71,7 +71,15 @@ def test_every_instantiation_has_a_case():
     src = "".join(open(p).read() for p in glob.glob(os.path.join(SOURCES, "*.hip")) + glob.glob(os.path.join(SOURCES, "*.h")))
     declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
     assert declared == {KI.base(n) for n in names}
-    assert not re.findall(r'#include\s+"(?!feather_hip/)', src)  # no helper header of feathercnn_amd/csrc: every kernel is in csrc_gconv
+    # no helper header of feathercnn_amd/csrc: every kernel is in csrc_gconv.  Beyond the public headers it includes only what the side
+    # libraries share (csrc_side), and those headers declare no kernel and take nothing of csrc but common.h (which holds none either)
+    kernel_decl = r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)"
+    quoted = r'#include\s+"(?!feather_hip/)([^"]*)'
+    side = os.path.join(ROOT, "feathercnn_amd", "csrc_side")
+    assert set(re.findall(quoted, src)) <= set(os.listdir(side))
+    shared = "".join(open(p).read() for p in glob.glob(os.path.join(side, "*.h")))
+    assert set(re.findall(quoted, shared)) <= set(os.listdir(side)) | {"common.h"}
+    assert not re.findall(kernel_decl, shared + open(os.path.join(ROOT, "feathercnn_amd", "csrc", "common.h")).read())
     assert len({c[0] for c in GC.CASES}) == len(GC.CASES)
     # every case is one the library takes, and the restated dispatch is the library's own
     from feathercnn_amd import _lib

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """tools/kernel_resources.py <file.hip> [name filter] [extra hipcc flags...] -- VGPRs / scratch / occupancy / LDS of every kernel of a
 translation unit (hipcc -Rpass-analysis=kernel-resource-usage; cross-compiles, no GPU needed).  <file.hip> may lie in any of the source
-directories (feathercnn_amd/csrc, csrc_pixout, csrc_gconv, csrc_deconv, csrc_inorm, csrc_shuffle, csrc_canvas, csrc_atrous, csrc_gate): headers of feathercnn_amd/csrc (gemm_core.h) are on the include path."""
+directories (feathercnn_amd/csrc and the side libraries' csrc_<x>): the headers of feathercnn_amd/csrc (gemm_core.h) and of
+feathercnn_amd/csrc_side (side_error.h, direct_conv.h) are on the include path."""
 import os
 import re
 import subprocess
@@ -14,7 +15,7 @@ def main():
     src = sys.argv[1]
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
     extra = sys.argv[3:]
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{R}/include", f"-I{R}/feathercnn_amd/csrc", f"-I{R}/tools",
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{R}/include", f"-I{R}/feathercnn_amd/csrc", f"-I{R}/feathercnn_amd/csrc_side", f"-I{R}/tools",
            f"-I{R}/tools/experiments", *extra, "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
     out = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = [], None
