@@ -102,6 +102,7 @@ SIGNATURES = {
     "fhip_net_set_graph": (_I, [_V, _I]),
     "fhip_net_set_tuned_selection": (_I, [_V, _I]),
     "fhip_net_set_dilated": (_I, [_V, _I]),
+    "fhip_net_set_quantized": (_I, [_V, _I]),
     "fhip_net_set_extended_layers": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
@@ -254,6 +255,29 @@ LRN_SIGNATURES = {
     "fhip_lrn_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_qconv.h -- libfeather_qconv.so, ncnn-style int8 convolution with fp32 input and output (a library of its own)
+class fhip_qconv_param(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("output_channels", "input_channels", "input_h", "input_w", "kernel_h", "kernel_w", "output_h", "output_w",
+                                            "stride_h", "stride_w", "pad_left", "pad_bottom", "pad_right", "pad_top", "group", "bias_term",
+                                            "activation", "dilation_h", "dilation_w", "int8_scale_term")]
+
+
+_QP = ctypes.POINTER(fhip_qconv_param)
+QCONV_SIGNATURES = {
+    "fhip_qconv_assign_output_dim": (_I, [_QP]),
+    "fhip_qconv_supported": (_I, [_QP]),
+    "fhip_qconv_get_buffer_size": (_I, [_QP, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "fhip_qconv_init": (_I, [_QP, _V, _V, _V]),
+    "fhip_qconv_dequant_scales": (_I, [_V, _V, _I, _FL]),
+    "fhip_qconv_forward": (_I, [_QP, _I, _V, _V, _V, _V, _V, _V, _FL, _V]),
+    "fhip_quantize_forward": (_I, [_V, _V, _SZ, _FL, _V]),
+    "fhip_qconv_route": (_I, [_QP, ctypes.c_char_p, _I]),
+    "fhip_qconv_get_buffer_size_route": (_I, [_QP, _I, ctypes.c_char_p, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "fhip_qconv_init_route": (_I, [_QP, _V, _V, _V, ctypes.c_char_p]),
+    "fhip_qconv_forward_route": (_I, [_QP, _I, _V, _V, _V, _V, _V, _V, _FL, _V, ctypes.c_char_p]),
+    "fhip_qconv_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -388,3 +412,13 @@ def load_lrn_library():
     """Load libfeather_lrn.so (fhip_lrn_forward, fhip_lrn_pool_forward).  Fails loudly like load_library: there is no fallback
     implementation."""
     return _load(lrn_path(), LRN_SIGNATURES)
+
+
+def qconv_path() -> str:
+    return os.path.join(_HERE, "libfeather_qconv.so")
+
+
+def load_qconv_library():
+    """Load libfeather_qconv.so (fhip_qconv_forward, fhip_quantize_forward).  Fails loudly like load_library: there is no fallback
+    implementation."""
+    return _load(qconv_path(), QCONV_SIGNATURES)

@@ -332,6 +332,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.tuned_selection = n->impl.tuned_selection;
         m->impl.dilated = n->impl.dilated;
         m->impl.extended = n->impl.extended;
+        m->impl.quantized = n->impl.quantized;
         m->impl.concurrency = n->impl.concurrency;
         n->more.push_back(std::move(m));
     }
@@ -388,6 +389,15 @@ int fhip_net_set_extended_layers(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the extended-layers switch before LoadParam");
     n->impl.extended = on != 0;
     for (auto& m : n->more) m->impl.extended = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_quantized(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the quantized-layers switch before LoadParam");
+    n->impl.quantized = on != 0;
+    for (auto& m : n->more) m->impl.quantized = on != 0;
     return FHIP_OK;
 }
 

@@ -174,6 +174,7 @@ struct Net
     bool tuned_selection = false; // fhip_conv_select_algo_tuned instead of the reference's SelectAlgo rule
     bool dilated = false;         // fhip_net_set_dilated: a Convolution with dilation > 1 is loaded (libfeather_atrous.so) instead of refused
     bool extended = false;        // fhip_net_set_extended_layers: Interp, HardSwish (libfeather_resample.so) and LRN (libfeather_lrn.so) are loaded instead of refused
+    bool quantized = false;       // fhip_net_set_quantized: Convolution / InnerProduct layers with int8 weights (8=int8_scale_term) are loaded (libfeather_qconv.so) instead of refused
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;
     // fusion level 3 (plan_chains): runs of Winograd layers hand their transformed input from one to the next; the arena then holds two V

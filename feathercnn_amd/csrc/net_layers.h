@@ -75,6 +75,95 @@ struct SideConv
     }
 };
 
+// The int8 side of a Convolution / ConvolutionDepthWise / InnerProduct layer of a net with fhip_net_set_quantized: it runs through
+// libfeather_qconv.so (qconv_api) with route code FHIP_NET_ROUTE_QCONV.  The library's calls do not fit SideConv (int8 weights, the
+// dequantisation scales and the input scale ride along), so its three calls stand here, once for both layer types.  The layer fills `q`
+// at Reshape; a BatchNorm / Scale fold goes into d[] and the bias as feather_qconv.h defines it, never into the weights.
+struct QuantRoute
+{
+    fhip_qconv_param q;
+    int scale_term = 0;
+    std::vector<signed char> w;
+    std::vector<float> s_w, b;
+    float s_in = 0.f;
+    DeviceVec packed, d, bias;
+    size_t packed_bytes = 0;
+    bool inited = false;
+
+    QuantRoute() { memset(&q, 0, sizeof(q)); }
+    // ncnn's param 8 of the layer, 0 where the file does not set it
+    int read_scale_term(const ParamDict& pd) { return scale_term = pd.get(8, 0); }
+    // the .bin of a quantised layer: int8-tagged weights, the bias, K weight scales, one input scale (the last three raw fp32)
+    int load(const Layer* l, ModelBin& mb, size_t wsize, int K, bool bias_term)
+    {
+        inited = false;
+        int rc = mb.load_int8(wsize, w);
+        if (rc) return rc;
+        if (bias_term && (rc = mb.load(K, 1, b))) return rc;
+        if ((rc = mb.load(K, 1, s_w))) return rc;
+        std::vector<float> one;
+        if ((rc = mb.load(1, 1, one))) return rc;
+        s_in = one[0];
+        if (!std::isfinite(s_in) || !(s_in > 0.f)) return failf(NET_E_SHAPE, "layer %s: the int8 input scale must be finite and > 0", l->name.c_str());
+        for (float v : s_w)
+            if (!std::isfinite(v) || v < 0.f) return failf(NET_E_SHAPE, "layer %s: an int8 weight scale is not finite or is negative", l->name.c_str());
+        return 0;
+    }
+    // the tail of Reshape, with the geometry and the input size in `q`
+    int reshape(Layer* l)
+    {
+        const QconvApi* api = qconv_api();
+        if (!api) return FHIP_E_UNSUPPORTED; // message set by side_api
+        const Blob* bt = l->bottoms[0];
+        int rc;
+        q.dilation_h = q.dilation_w = 1;
+        q.int8_scale_term = scale_term;
+        if ((rc = l->side(api, [&](const QconvApi* a) { return a->assign_output_dim(&q); }, NET_E_SHAPE))) return rc;
+        if ((rc = l->side(api, [&](const QconvApi* a) { return a->supported(&q) != 1; }, FHIP_E_UNSUPPORTED, "int8 convolution refused: "))) return rc;
+        if ((rc = l->tops[0]->reshape(bt->n, q.output_channels, q.output_h, q.output_w))) return rc;
+        size_t scratch = 0;
+        return l->side(api, [&](const QconvApi* a) { return a->get_buffer_size(&q, bt->n, &scratch, &packed_bytes); });
+    }
+    int init(Layer* l, const AffineFold& fold, hipStream_t s)
+    {
+        if (inited && packed.bytes == packed_bytes) return 0;
+        const QconvApi* api = qconv_api();
+        if (!api) return FHIP_E_UNSUPPORTED;
+        const int K = q.output_channels;
+        std::vector<float> dq(K), bq = b;
+        int rc = l->side(api, [&](const QconvApi* a) { return a->dequant_scales(dq.data(), s_w.data(), K, s_in); });
+        if (rc) return rc;
+        if (!fold.empty())
+        {
+            if (bq.empty()) bq.assign(K, 0.f);
+            for (int k = 0; k < K; ++k)
+            {
+                dq[k] = dq[k] * fold.mul[k];
+                const float scaled = bq[k] * fold.mul[k]; // rounded before the sum: no contraction
+                bq[k] = scaled + fold.add[k];
+            }
+            q.bias_term = 1;
+        }
+        DeviceVec raw;
+        if ((rc = raw.resize(w.size()))) return rc;
+        FHIP_CHECK_HIP(hipMemcpyAsync(raw.d, w.data(), w.size(), hipMemcpyHostToDevice, s));
+        if ((rc = packed.resize(packed_bytes))) return rc;
+        if ((rc = l->side(api, [&](const QconvApi* a) { return a->init(&q, packed.d, reinterpret_cast<const signed char*>(raw.d), s); }))) return rc;
+        if ((rc = d.upload(dq.data(), dq.size(), s))) return rc;
+        if (q.bias_term && (rc = bias.upload(bq.data(), bq.size(), s))) return rc;
+        FHIP_CHECK_HIP(hipStreamSynchronize(s)); // `raw` and the host copies go out of scope
+        inited = true;
+        return 0;
+    }
+    int forward(const Layer* l, hipStream_t s) const
+    {
+        return l->side(qconv_api(), [&](const QconvApi* a) {
+            return a->forward(&q, l->bottoms[0]->n, l->tops[0]->data, l->bottoms[0]->data, packed.d, nullptr, d.d, q.bias_term ? bias.d : nullptr, s_in, s);
+        });
+    }
+    size_t bytes() const { return packed.bytes + d.bytes + bias.bytes; }
+};
+
 // The same Init on the main library (a convolution on route `algo`, an InnerProduct on the implicit GEMM)
 static int init_packed(const fhip_conv_param& p, int algo, const std::vector<float>& w, const std::vector<float>& b, DeviceVec& packed, size_t packed_bytes,
                        DeviceVec& bias, hipStream_t s)
@@ -110,6 +199,11 @@ struct ConvLayer : Layer
     fhip_atrous_param dilated;
     typedef SideConv<GconvApi, fhip_conv_param> Grouped;
     typedef SideConv<AtrousApi, fhip_atrous_param> Dilated;
+    // 8=int8_scale_term in a net with fhip_net_set_quantized: the layer runs through libfeather_qconv.so (QuantRoute) with route code
+    // FHIP_NET_ROUTE_QCONV; group is 1 or depthwise.  p.output_channels holds the WHOLE layer's K here too.
+    // Fusions as on the grouped route: a following ReLU, at level 2 BatchNorm / Scale (into the dequantisation), nothing else.
+    bool quant = false;
+    QuantRoute qr;
     std::vector<float> w_host, b_host;
     AffineFold fold; // folded BatchNorm/Scale (fusion level 2)
     DeviceVec packed, bias;
@@ -176,7 +270,12 @@ struct ConvLayer : Layer
         if (atrous && !(net && net->dilated))
             return failf(NET_E_UNKNOWN_LAYER, "layer %s: dilated convolution is not supported (fhip_net_set_dilated lifts this)", name.c_str());
         if (dilation_w < 1 || dilation_h < 1) return failf(NET_E_SHAPE, "layer %s: dilation must be >= 1", name.c_str());
-        if (pd.get(8, 0)) return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8 convolution is not supported", name.c_str());
+        qr.scale_term = pd.get(8, 0);
+        quant = qr.scale_term != 0 && net && net->quantized;
+        if (qr.scale_term && !quant) return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8 convolution is not supported", name.c_str());
+        if (quant && (qr.scale_term < 0 || qr.scale_term > 100))
+            return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8_scale_term %d (requantised int8 output) is not supported", name.c_str(), qr.scale_term);
+        if (quant && atrous) return failf(NET_E_UNKNOWN_LAYER, "layer %s: a dilated int8 convolution is not supported", name.c_str());
         p.kernel_w = pd.get(1, 0);
         p.kernel_h = pd.get(11, p.kernel_w);
         p.stride_w = pd.get(3, 1);
@@ -201,8 +300,16 @@ struct ConvLayer : Layer
         if (weight_data_size < 0 || per_channel > INT_MAX || weight_data_size % per_channel)
             return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the convolution geometry", name.c_str());
         p.input_channels = (int)(weight_data_size / per_channel);
-        gconv = !atrous && p.group > 1 && p.group < p.input_channels;
-        if (gconv || atrous) p.output_channels *= p.group;
+        gconv = !atrous && !quant && p.group > 1 && p.group < p.input_channels;
+        if (gconv || atrous || quant) p.output_channels *= p.group;
+        if (quant)
+        {
+            if (p.pad_left < 0 || p.pad_top < 0) return failf(NET_E_UNKNOWN_LAYER, "layer %s: automatic padding is not supported", name.c_str());
+            if (p.input_channels < 1) return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the convolution geometry", name.c_str());
+            if (p.group != 1 && (p.group != p.input_channels || p.group != p.output_channels))
+                return failf(NET_E_UNKNOWN_LAYER, "layer %s: an int8 convolution with a partial group (1 < group < channels) is not supported", name.c_str());
+            algo_ = FHIP_NET_ROUTE_QCONV;
+        }
         if (atrous)
         {
             if (p.pad_left < 0 || p.pad_top < 0) return failf(NET_E_UNKNOWN_LAYER, "layer %s: automatic padding is not supported", name.c_str());
@@ -213,9 +320,10 @@ struct ConvLayer : Layer
     }
     int LoadWeights(ModelBin& mb) override
     {
-        const size_t wsize = (size_t)p.input_channels * p.output_channels * p.kernel_h * p.kernel_w / (gconv || atrous ? p.group : 1);
+        const size_t wsize = (size_t)p.input_channels * p.output_channels * p.kernel_h * p.kernel_w / (gconv || atrous || quant ? p.group : 1);
         inited_algo = -2; // new weights: every packed form is rebuilt at the next Init
         sib_packed_for = nullptr;
+        if (quant) return qr.load(this, mb, wsize, p.output_channels, p.bias_term != 0);
         int rc = mb.load(wsize, 0, w_host);
         if (rc) return rc;
         if (p.bias_term)
@@ -232,6 +340,18 @@ struct ConvLayer : Layer
         p.input_h = b->h;
         if (p.input_channels != b->c)
             return failf(NET_E_TOPOLOGY, "convolution layer %s has %d input channels while bottom blob has %d channels", name.c_str(), p.input_channels, b->c);
+        if (quant)
+        {
+            fhip_qconv_param& a = qr.q;
+            a.output_channels = p.output_channels, a.input_channels = p.input_channels, a.input_h = p.input_h, a.input_w = p.input_w;
+            a.kernel_h = p.kernel_h, a.kernel_w = p.kernel_w;
+            a.stride_h = p.stride_h, a.stride_w = p.stride_w, a.pad_left = p.pad_left, a.pad_bottom = p.pad_bottom, a.pad_right = p.pad_right, a.pad_top = p.pad_top;
+            a.group = p.group, a.bias_term = p.bias_term, a.activation = p.activation;
+            const int rc = qr.reshape(this);
+            p.output_h = a.output_h; // kept where conv_param() reports it
+            p.output_w = a.output_w;
+            return rc;
+        }
         if (atrous)
         {
             fhip_atrous_param& a = dilated;
@@ -342,6 +462,12 @@ struct ConvLayer : Layer
             const int rc = init_siblings(s);
             if (rc) return rc;
         }
+        if (quant)
+        {
+            const int rc = qr.init(this, fold, s);
+            if (!rc && !fold.empty()) p.bias_term = 1;
+            return rc;
+        }
         if (inited_algo == algo_ && packed.bytes == packed_bytes && inited_layout == layout) return 0;
         std::vector<float> w, b;
         folded(w, b);
@@ -358,6 +484,7 @@ struct ConvLayer : Layer
     }
     int Forward(hipStream_t s) override
     {
+        if (quant) return qr.forward(this, s);
         if (algo_ == FHIP_NET_ROUTE_ATROUS) return Dilated::forward(this, atrous_api(), dilated, packed, bias, s);
         if (algo_ == FHIP_NET_ROUTE_GCONV) return Grouped::forward(this, gconv_api(), p, packed, bias, s);
         const float* b = p.bias_term ? bias.d : nullptr;
@@ -463,14 +590,14 @@ struct ConvLayer : Layer
             bottoms.push_back(other); // dependency scans look at THIS layer
             return true;
         }
-        if (gconv || atrous || fuse_pool || residual || p.activation != FHIP_ACT_NONE) return false;
+        if (gconv || atrous || quant || fuse_pool || residual || p.activation != FHIP_ACT_NONE) return false;
         residual = other;
         bottoms.push_back(other); // so that dependency scans (fusion, branch concurrency) see the second input
         return true;
     }
     size_t weight_bytes() const override
     {
-        return packed.bytes + bias.bytes + pre_pool.bytes + mid.bytes + first_raw.bytes + sib_packed.bytes + sib_bias.bytes + (pw ? pw->weight_bytes() : 0);
+        return packed.bytes + bias.bytes + pre_pool.bytes + mid.bytes + first_raw.bytes + sib_packed.bytes + sib_bias.bytes + qr.bytes() + (pw ? pw->weight_bytes() : 0);
     }
     const fhip_conv_param* fused_pointwise(int* one_kernel) const override
     {
@@ -479,7 +606,7 @@ struct ConvLayer : Layer
     }
     size_t arena_bytes() const override { return std::max(buffer_bytes, chain_bytes); }
     const fhip_conv_param* conv_param() const override { return &p; }
-    int algo() const override { return atrous ? FHIP_NET_ROUTE_ATROUS : gconv ? FHIP_NET_ROUTE_GCONV : algo_; }
+    int algo() const override { return quant ? FHIP_NET_ROUTE_QCONV : atrous ? FHIP_NET_ROUTE_ATROUS : gconv ? FHIP_NET_ROUTE_GCONV : algo_; }
     int sibling_state() const override { return sib ? 1 : sib_of ? 2 : 0; }
     int residual_state() const override { return !residual ? 0 : res_fast ? 1 : 2; }
     void chain_state(int* v_from_previous, int* writes_next_v) const override
@@ -501,6 +628,10 @@ struct InnerProductLayer : Layer
     DeviceVec packed, bias;
     size_t buffer_bytes = 0, packed_bytes = 0;
     bool inited = false;
+    // 8=int8_scale_term in a net with fhip_net_set_quantized: the 1x1 convolution over a 1x1 image runs through libfeather_qconv.so
+    // (QuantRoute, route code FHIP_NET_ROUTE_QCONV) with the same ReLU fusion; the int8 weights stay int8 on the device
+    bool quant = false;
+    QuantRoute qr;
 
     InnerProductLayer() { memset(&p, 0, sizeof(p)); }
     bool needs_weights() const override { return true; }
@@ -517,10 +648,15 @@ struct InnerProductLayer : Layer
         p.output_channels = (int)output_size;
         p.input_h = p.input_w = p.kernel_h = p.kernel_w = p.stride_h = p.stride_w = p.group = 1;
         fhip_conv_assign_output_dim(&p);
+        // with the switch off nothing changes, not even a message: the weight reader refuses the int8 tag as it always has
+        quant = qr.read_scale_term(pd) != 0 && net && net->quantized;
+        if (quant && (qr.scale_term < 0 || qr.scale_term > 100))
+            return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8_scale_term %d (requantised int8 output) is not supported", name.c_str(), qr.scale_term);
         return 0;
     }
     int LoadWeights(ModelBin& mb) override
     {
+        if (quant) return qr.load(this, mb, weight_data_size, (int)output_size, p.bias_term != 0);
         int rc = mb.load(weight_data_size, 0, w_host);
         if (rc) return rc;
         if (p.bias_term) rc = mb.load(output_size, 1, b_host);
@@ -532,12 +668,21 @@ struct InnerProductLayer : Layer
         const size_t per_image = (size_t)b->c * b->h * b->w;
         if (input_size != per_image)
             return failf(NET_E_SHAPE, "In Layer %s: Bottom %s data size %zu is inconsistant with expected input size %zu.", name.c_str(), b->name.c_str(), per_image, input_size);
+        if (quant)
+        {
+            fhip_qconv_param& a = qr.q;
+            a.output_channels = p.output_channels, a.input_channels = p.input_channels;
+            a.input_h = a.input_w = a.kernel_h = a.kernel_w = a.stride_h = a.stride_w = a.group = 1;
+            a.bias_term = p.bias_term, a.activation = p.activation;
+            return qr.reshape(this);
+        }
         int rc = tops[0]->reshape(b->n, (int)output_size, 1, 1);
         if (rc) return rc;
         return fhip_conv_get_buffer_size(&p, FHIP_IM2COL, b->n, &buffer_bytes, &packed_bytes);
     }
     int Init(hipStream_t s) override
     {
+        if (quant) return qr.init(this, AffineFold(), s);
         if (inited) return 0;
         const int rc = init_packed(p, FHIP_IM2COL, w_host, b_host, packed, packed_bytes, bias, s);
         if (rc) return rc;
@@ -547,6 +692,7 @@ struct InnerProductLayer : Layer
     }
     int Forward(hipStream_t s) override
     {
+        if (quant) return qr.forward(this, s);
         return fhip_conv_forward(&p, FHIP_IM2COL, bottoms[0]->n, tops[0]->data, bottoms[0]->data, packed.d, (float*)net->arena.d,
                                  p.bias_term ? bias.d : nullptr, s);
     }
@@ -556,9 +702,9 @@ struct InnerProductLayer : Layer
         p.activation = FHIP_ACT_RELU;
         return 1;
     }
-    size_t weight_bytes() const override { return packed.bytes + bias.bytes; }
+    size_t weight_bytes() const override { return packed.bytes + bias.bytes + qr.bytes(); }
     size_t arena_bytes() const override { return buffer_bytes; }
-    int algo() const override { return FHIP_IM2COL; }
+    int algo() const override { return quant ? FHIP_NET_ROUTE_QCONV : FHIP_IM2COL; }
 };
 
 // ncnn's ReLU: 0=slope.  Slope 0 is the reference's layer (fhip_relu); a leaky one runs through libfeather_inorm.so.
@@ -1244,7 +1390,7 @@ int ConvLayer::Fuse(Layer* next, int level)
 {
     if (pw) return pw->Fuse(next, level) == 1 ? 1 : 0; // behind the absorbed 1x1 convolution: its own fusions
     if (fuse_pool) return 0; // nothing is absorbed behind the pooling
-    if ((gconv || atrous) && !is_plain_relu(next) && !next->as_affine()) return 0; // the grouped and dilated routes have these epilogues only
+    if ((gconv || atrous || quant) && !is_plain_relu(next) && !next->as_affine()) return 0; // the grouped, dilated and int8 routes have these epilogues only
     if (level >= 2 && !residual && next->type == "Convolution" && p.group == p.input_channels && p.group > 1 && p.group <= 256 && p.kernel_h == 3 &&
         p.kernel_w == 3 && p.stride_h == p.stride_w && (p.stride_h == 1 || p.stride_h == 2) && p.pad_left == 1 && p.pad_top == 1)
     {
@@ -1253,7 +1399,7 @@ int ConvLayer::Fuse(Layer* next, int level)
         // (a layer typed "Convolution" only, never "ConvolutionDepthWise": kept as found, the code gives no reason -- the group test below
         // would turn every real depthwise layer away anyway)
         const fhip_conv_param& q = next->as_conv()->p;
-        if (next->as_conv()->atrous) return 0;
+        if (next->as_conv()->atrous || next->as_conv()->quant) return 0;
         if (q.group != 1 || q.kernel_h != 1 || q.kernel_w != 1 || q.stride_h != 1 || q.stride_w != 1 || q.pad_left || q.pad_right || q.pad_top || q.pad_bottom)
             return 0;
         // fhip_conv_can_fuse_dw_pw's profitable range -- or the band-staged kernel's pair (32 channels, stride 1, a multiple of 64 output channels:
@@ -1281,7 +1427,7 @@ int ConvLayer::Fuse(Layer* next, int level)
     // level 2 (beyond the reference): fold a following BatchNorm / Scale into the weights and bias
     if (level >= 2 && p.activation == FHIP_ACT_NONE && next->as_affine())
     {
-        const int K = atrous ? p.output_channels : p.group == p.input_channels ? p.input_channels : p.output_channels;
+        const int K = atrous || quant ? p.output_channels : p.group == p.input_channels ? p.input_channels : p.output_channels;
         return fold.absorb(*next->as_affine(), K) ? 1 : 0;
     }
     return 0;

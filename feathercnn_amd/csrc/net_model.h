@@ -141,6 +141,23 @@ struct ModelBin
         p += bytes;
         return true;
     }
+    // The int8 weights of a quantised layer (tag 0x000D4B38, then w bytes padded to 4: modelbin.cpp:92-109 reads them so).  Weights under
+    // any other tag are refused: this runtime does not quantise at load.  load() below keeps refusing the tag for every fp32 caller.
+    int load_int8(size_t w, std::vector<signed char>& out)
+    {
+        out.clear();
+        unsigned char f[4];
+        if (!take(f, 4)) return failf(NET_E_SHAPE, "ModelBin read flag_struct failed");
+        uint32_t tag;
+        memcpy(&tag, f, 4);
+        if (tag != 0x000D4B38u) return failf(FHIP_E_UNSUPPORTED, "an int8 layer (int8_scale_term) needs int8 weights (tag 0x000D4B38), found tag 0x%08X: weights are not quantised at load", tag);
+        const size_t rest = (size_t)(end - p);
+        // the count is a product of file values: checked against the rest of the file before anything of that size is allocated
+        if (w > rest || (w + 3) / 4 * 4 > rest) return failf(NET_E_SHAPE, "ModelBin read int8_weights failed (file too short for %zu weights padded to 4 bytes)", w);
+        out.assign(reinterpret_cast<const signed char*>(p), reinterpret_cast<const signed char*>(p) + w);
+        p += (w + 3) / 4 * 4;
+        return 0;
+    }
     // type 0: 4-byte tag then payload (raw fp32 / fp16 / 256-entry table); type 1: raw fp32 (modelbin.cpp:52-189)
     int load(size_t w, int type, std::vector<float>& out)
     {

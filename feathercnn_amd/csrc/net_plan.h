@@ -135,14 +135,14 @@ static void collapse_gate_blocks(Net& net)
         if (l->type == "InnerProduct")
         {
             InnerProductLayer* ip = static_cast<InnerProductLayer*>(l);
-            if (ip->p.activation != FHIP_ACT_NONE || ip->w_host.size() != ip->input_size * ip->output_size) return false;
+            if (ip->quant || ip->p.activation != FHIP_ACT_NONE || ip->w_host.size() != ip->input_size * ip->output_size) return false;
             in = (int)ip->input_size, out = (int)ip->output_size, w = ip->w_host, b = ip->b_host, has_b = ip->p.bias_term != 0;
             return true;
         }
         if (l->type != "Convolution") return false; // not "ConvolutionDepthWise": kept as found (the group test below turns a real one away)
         ConvLayer* cv = l->as_conv();
         const fhip_conv_param& p = cv->p;
-        if (cv->gconv || cv->atrous || p.group != 1 || p.kernel_h != 1 || p.kernel_w != 1 || p.stride_h != 1 || p.stride_w != 1 || p.pad_left || p.pad_right ||
+        if (cv->gconv || cv->atrous || cv->quant || p.group != 1 || p.kernel_h != 1 || p.kernel_w != 1 || p.stride_h != 1 || p.stride_w != 1 || p.pad_left || p.pad_right ||
             p.pad_top || p.pad_bottom || p.activation != FHIP_ACT_NONE || !cv->fold.empty() || cv->w_host.size() != (size_t)p.input_channels * p.output_channels)
             return false;
         in = p.input_channels, out = p.output_channels, w = cv->w_host, b = cv->b_host, has_b = p.bias_term != 0;
@@ -412,7 +412,7 @@ static int plan_chains(Net& net)
     for (size_t i = 0; i + 1 < L; ++i)
     {
         ConvLayer *a = conv[i], *b = conv[i + 1];
-        if (!a || a->atrous || a->pw || a->residual || a->fuse_pool || a->chain_in || a->chain_next || a->tops.size() != 1 || a->bottoms.size() != 1) continue;
+        if (!a || a->atrous || a->quant || a->pw || a->residual || a->fuse_pool || a->chain_in || a->chain_next || a->tops.size() != 1 || a->bottoms.size() != 1) continue;
         if (!a->first_candidate() || !plain(b) || b->chain_in || b->bottoms[0] != a->tops[0]) continue;
         if (readers(net, a->tops[0], 0, true).count != 1) continue;
         if (!fhip_conv_can_fuse_first_winograd(&a->p, &b->p, b->algo_, a->bottoms[0]->n)) continue;

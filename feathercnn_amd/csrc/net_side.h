@@ -28,6 +28,7 @@
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
 #include "feather_hip/feather_lrn.h" // declarations only: the library is opened at run time (lrn_api)
 #include "feather_hip/feather_net.h"
+#include "feather_hip/feather_qconv.h" // declarations only: the library is opened at run time (qconv_api)
 #include "feather_hip/feather_resample.h" // declarations only: the library is opened at run time (resample_api)
 #include "feather_hip/feather_shuffle.h" // declarations only: the library is opened at run time (shuffle_api)
 
@@ -260,6 +261,26 @@ struct LrnApi
     }
 };
 static const LrnApi* lrn_api() { return side_api<LrnApi>(); }
+
+// libfeather_qconv.so, the route of the Convolution / InnerProduct layers with int8 weights of a net with fhip_net_set_quantized
+struct QconvApi
+{
+    decltype(&fhip_qconv_assign_output_dim) assign_output_dim = nullptr;
+    decltype(&fhip_qconv_supported) supported = nullptr;
+    decltype(&fhip_qconv_get_buffer_size) get_buffer_size = nullptr;
+    decltype(&fhip_qconv_init) init = nullptr;
+    decltype(&fhip_qconv_dequant_scales) dequant_scales = nullptr;
+    decltype(&fhip_qconv_forward) forward = nullptr;
+    decltype(&fhip_qconv_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_qconv.so", "an int8 convolution / InnerProduct layer", "feather_qconv.h",
+                {{&assign_output_dim, "fhip_qconv_assign_output_dim"}, {&supported, "fhip_qconv_supported"},
+                 {&get_buffer_size, "fhip_qconv_get_buffer_size"}, {&init, "fhip_qconv_init"}, {&dequant_scales, "fhip_qconv_dequant_scales"},
+                 {&forward, "fhip_qconv_forward"}, {&last_error, "fhip_qconv_last_error"}}};
+    }
+};
+static const QconvApi* qconv_api() { return side_api<QconvApi>(); }
 
 // libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases (plan_chains).  The canvas form is a
 // faster way to run the same run of layers, not a layer type: a net that qualifies and cannot find the library fails at plan_chains.

@@ -15,9 +15,34 @@ import struct
 import numpy as np
 
 
+INT8_TAG = 0x000D4B38           # ncnn's tag of int8 weights (modelbin.cpp)
+QUANT_DEFAULT_SCALE = 32.0      # input scale of a quantised layer that has no calibrated one: activations of order 1 use a quarter of the q range
+
+
+def _round_half_away(t):
+    a = np.abs(t)
+    f = np.floor(a)
+    return np.where(np.signbit(t), -1, 1) * np.where(a - f >= 0.5, f + 1, f)
+
+
+def quantize_weights(w, cout):
+    """fp32 weights [cout][...] -> (int8 weights, per-channel scales 127 / absmax(w[k]); 0 for an all-zero filter): ncnn's rule."""
+    w = np.asarray(w, np.float32).reshape(cout, -1)
+    amax = np.abs(w).max(axis=1)
+    with np.errstate(divide="ignore"):
+        s_w = np.where(amax == 0, np.float32(0), np.float32(127) / amax).astype(np.float32)
+    q = np.clip(_round_half_away(w * s_w[:, None]), -127, 127).astype(np.int8)
+    return q, s_w
+
+
 class GraphBuilder:
-    def __init__(self, seed: int = 1234, dry: bool = False):
-        """dry=True: build the .param only and count the .bin bytes (``nbytes``) without drawing any weights."""
+    def __init__(self, seed: int = 1234, dry: bool = False, quant=None):
+        """dry=True: build the .param only and count the .bin bytes (``nbytes``) without drawing any weights.
+        quant: None writes fp32 layers; a dict {layer name: input scale} makes conv() and fc() write int8 layers (param 8=1: int8-tagged
+        weights quantised per output channel, the bias, the weight scales, one input scale; a name the dict lacks gets QUANT_DEFAULT_SCALE).
+        The weights drawn are those of the fp32 build with the same seed.  A net that holds such a layer needs Net.SetQuantized(True)."""
+        self.quant = quant
+        self.trace = None  # a list: conv / fc / relu / bn / scale / pool record themselves for numpy_forward (input_scales)
         self.rng = np.random.default_rng(seed)
         self.lines: list[str] = []
         self.bin = bytearray()
@@ -45,6 +70,28 @@ class GraphBuilder:
             self.bin += np.ascontiguousarray(a, dtype="<f4").tobytes()
             self.nbytes += 4 * a.size
 
+    def _note(self, *op):
+        if self.trace is not None:
+            self.trace.append(op)
+
+    def _weights(self, name, w, cout, b):
+        """The .bin of a conv / fc layer: tagged fp32 weights and the raw bias, or the int8 form (see __init__)."""
+        if self.quant is None:
+            self._tagged(w)
+            if b is not None:
+                self._raw(b)
+            return
+        wsize = w if self.dry else w.size
+        self.nbytes += 4 + (wsize + 3) // 4 * 4
+        s_w = cout
+        if not self.dry:
+            q, s_w = quantize_weights(w, cout)
+            self.bin += struct.pack("<I", INT8_TAG) + q.tobytes() + bytes(-wsize % 4)
+        if b is not None:
+            self._raw(b)
+        self._raw(s_w)
+        self._raw(1 if self.dry else np.array([self.quant.get(name, QUANT_DEFAULT_SCALE)], np.float32))
+
     def _uniform(self, n, lo, hi, scale=None):
         if self.dry:
             return n
@@ -62,10 +109,14 @@ class GraphBuilder:
         params = {0: cout, 1: k, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group}
         if dilation != 1:  # ncnn's id 2 (written only when set); a net that holds one needs Net.SetDilated(True)
             params = {0: cout, 1: k, 2: dilation, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group}
+        if self.quant is not None:
+            params[8] = 1
         top = self.layer(type_, name, [bottom], [top or name], params)
-        self._tagged(self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in) * gain))
-        if bias:
-            self._raw(self._uniform(cout, -0.1, 0.1))
+        w = self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in) * gain)
+        b = self._uniform(cout, -0.1, 0.1) if bias else None
+        self._weights(name, w, cout, b)
+        if self.trace is not None:
+            self._note("conv", name, bottom, top, dict(w=w.reshape(cout, cin // group, k, k), b=b, s=s, p=p, group=group))
         return top
 
     def deconv(self, name, bottom, cin, cout, k, s=1, p=0, op=0, group=1, bias=True):
@@ -92,6 +143,7 @@ class GraphBuilder:
 
     def relu(self, name, bottom, slope=None):
         """slope: ncnn's leaky ReLU (param 0); None writes no params, the plain layer."""
+        self._note("relu", name, bottom, name, dict(slope=slope))
         return self.layer("ReLU", name, [bottom], [name], None if slope is None else {0: f"{slope:.6f}"})
 
     def instance_norm(self, name, bottom, c, eps=1e-3, affine=True):
@@ -127,28 +179,40 @@ class GraphBuilder:
         return self.relu(name + "_relu", x)
 
     def pool(self, name, bottom, k=2, s=2, p=0, avg=False, global_=False):
+        self._note("pool", name, bottom, name, dict(k=k, s=s, p=p, avg=avg, global_=global_))
         return self.layer("Pooling", name, [bottom], [name], {0: int(avg), 1: k, 2: s, 3: p, 4: int(global_)})
 
     def fc(self, name, bottom, cin, cout, bias=True, gain=1.0):
-        top = self.layer("InnerProduct", name, [bottom], [name], {0: cout, 1: int(bias), 2: cin * cout})
-        self._tagged(self._uniform(cin * cout, -1, 1, np.sqrt(6.0 / cin) * gain))
-        if bias:
-            self._raw(self._uniform(cout, -0.1, 0.1))
+        params = {0: cout, 1: int(bias), 2: cin * cout}
+        if self.quant is not None:
+            params[8] = 1
+        top = self.layer("InnerProduct", name, [bottom], [name], params)
+        w = self._uniform(cin * cout, -1, 1, np.sqrt(6.0 / cin) * gain)
+        b = self._uniform(cout, -0.1, 0.1) if bias else None
+        self._weights(name, w, cout, b)
+        if self.trace is not None:
+            self._note("fc", name, bottom, top, dict(w=w.reshape(cout, cin), b=b))
         return top
 
     def bn(self, name, bottom, c, eps=1e-5):
         top = self.layer("BatchNorm", name, [bottom], [name], {0: c, 1: f"{eps:.6e}"})
-        self._raw(self._uniform(c, 0.5, 1.5))    # slope
-        self._raw(self._uniform(c, -0.1, 0.1))   # mean
-        self._raw(self._uniform(c, 0.5, 1.5))    # var
-        self._raw(self._uniform(c, -0.1, 0.1))   # bias
+        slope, mean, var, bias = self._uniform(c, 0.5, 1.5), self._uniform(c, -0.1, 0.1), self._uniform(c, 0.5, 1.5), self._uniform(c, -0.1, 0.1)
+        for a in (slope, mean, var, bias):
+            self._raw(a)
+        if self.trace is not None:
+            root = np.sqrt(var + np.float32(eps))
+            self._note("affine", name, bottom, top, dict(mul=slope / root, add=bias - slope * mean / root))
         return top
 
     def scale(self, name, bottom, c, bias=True):
         top = self.layer("Scale", name, [bottom], [name], {0: c, 1: int(bias)})
-        self._raw(self._uniform(c, 0.5, 1.5))
+        mul = self._uniform(c, 0.5, 1.5)
+        self._raw(mul)
+        add = self._uniform(c, -0.1, 0.1) if bias else None
         if bias:
-            self._raw(self._uniform(c, -0.1, 0.1))
+            self._raw(add)
+        if self.trace is not None:
+            self._note("affine", name, bottom, top, dict(mul=mul, add=add if bias else np.zeros(c, np.float32)))
         return top
 
     def split(self, name, bottom, n=2):
@@ -258,8 +322,81 @@ class GraphBuilder:
         return text.encode(), (self.nbytes if self.dry else bytes(self.bin))  # dry: the .bin size instead of the .bin
 
 
-def vgg16(seed=1234, classes=1000, size=224, dry=False):
-    g = GraphBuilder(seed, dry)
+def numpy_forward(trace, input_name, x):
+    """A plain numpy forward (fp32 values, sums in float64) of the layers a GraphBuilder recorded in `trace` -- Convolution, InnerProduct,
+    plain ReLU, BatchNorm, Scale, Pooling -- from the input `x` [N][C][H][W]: every blob by name.  It exists to calibrate input scales."""
+    blobs = {input_name: np.asarray(x, np.float32)}
+    for kind, name, bottom, top, a in trace:
+        v = blobs[bottom]
+        if kind == "conv":
+            w, s, p, group = a["w"].astype(np.float64), a["s"], a["p"], a["group"]
+            k, cg, kh, kw = w.shape
+            n, c, h, wd = v.shape
+            ho, wo = (h + 2 * p - kh) // s + 1, (wd + 2 * p - kw) // s + 1
+            vp = np.zeros((n, c, h + 2 * p, wd + 2 * p))
+            vp[:, :, p:p + h, p:p + wd] = v
+            y = np.zeros((n, k, ho, wo))
+            kg = k // group
+            for g in range(group):
+                for i in range(kh):
+                    for j in range(kw):
+                        win = vp[:, g * cg:(g + 1) * cg, i:i + (ho - 1) * s + 1:s, j:j + (wo - 1) * s + 1:s]
+                        y[:, g * kg:(g + 1) * kg] += np.einsum("nchw,kc->nkhw", win, w[g * kg:(g + 1) * kg, :, i, j])
+            if a["b"] is not None:
+                y += a["b"].reshape(1, -1, 1, 1)
+        elif kind == "fc":
+            y = v.reshape(v.shape[0], -1).astype(np.float64) @ a["w"].astype(np.float64).T
+            if a["b"] is not None:
+                y += a["b"]
+            y = y.reshape(v.shape[0], -1, 1, 1)
+        elif kind == "relu" and a["slope"] is None:
+            y = np.maximum(v, 0)
+        elif kind == "affine":
+            y = v * a["mul"].reshape(1, -1, 1, 1) + a["add"].reshape(1, -1, 1, 1)
+        elif kind == "pool" and not a["global_"] and not a["p"] and not a["avg"] and v.shape[2] % a["s"] == 0 and a["k"] == a["s"]:
+            n, c, h, wd = v.shape
+            y = v.reshape(n, c, h // a["k"], a["k"], wd // a["k"], a["k"]).max(axis=(3, 5))
+        else:
+            raise ValueError(f"numpy_forward has no {kind} layer like {name}")
+        blobs[top] = y.astype(np.float32)
+    return blobs
+
+
+def input_scales(trace, input_name, x):
+    """{layer name: 127 / absmax(bottom)} for every Convolution and InnerProduct of `trace`, from one numpy_forward of `x`.  The absmax
+    is rounded up to a multiple of 1/64 first, so that the last bits of a sum (they may differ between numpy builds) do not reach the scale."""
+    blobs = numpy_forward(trace, input_name, x)
+    return {name: float(np.float32(127) / np.float32(max(np.ceil(float(np.abs(blobs[bottom]).max()) * 64), 1) / 64))
+            for kind, name, bottom, _, _ in trace if kind in ("conv", "fc")}
+
+
+def tiny_quant(seed=29, size=16, dry=False):
+    """A 16-px net whose Convolution and InnerProduct layers are all int8 (Net.SetQuantized(True)) and all exactly restatable: a 3 -> 16 first
+    layer (the generic route), 16 -> 32 at stride 1 and 32 -> 32 at stride 2 (the MFMA route) with a BatchNorm + Scale + ReLU tail, a
+    depthwise 3x3, a 1x1 to 24 channels (no multiple of 16) without a bias, ReLUs, a 2x2 max pooling and an InnerProduct.  The input
+    scales are calibrated: the fp32 net with the same seed runs once on a seeded input through numpy_forward (input_scales)."""
+    def build(quant, trace=False):
+        g = GraphBuilder(seed, dry, quant=quant)
+        g.trace = [] if trace else None
+        x = g.input("data", 3, size, size)
+        x = g.relu("relu1", g.conv("conv1", x, 3, 16, 3, 1, 1))
+        x = g.relu("relu2", g.conv("conv2", x, 16, 32, 3, 1, 1))
+        x = g.conv("conv3", x, 32, 32, 3, 2, 1)
+        x = g.relu("conv3_relu", g.scale("conv3_scale", g.bn("conv3_bn", x, 32), 32))
+        x = g.relu("relu_dw", g.conv("dw", x, 32, 32, 3, 1, 1, group=32))
+        x = g.relu("relu_pw", g.conv("pw", x, 32, 24, 1, bias=False))
+        x = g.pool("pool", x, 2, 2)
+        g.fc("fc", x, 24 * (size // 4) ** 2, 10)
+        return g
+    if dry:
+        return build({}).finish() + ("data", "fc")
+    calib = np.random.default_rng(seed + 1).uniform(-1, 1, (4, 3, size, size)).astype(np.float32)
+    scales = input_scales(build(None, trace=True).trace, "data", calib)
+    return build(scales).finish() + ("data", "fc")
+
+
+def vgg16(seed=1234, classes=1000, size=224, dry=False, quant=None):
+    g = GraphBuilder(seed, dry, quant)
     x = g.input("data", 3, size, size)
     cin = 3
     for stage, (n, c) in enumerate([(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)], 1):
@@ -274,9 +411,9 @@ def vgg16(seed=1234, classes=1000, size=224, dry=False):
     return g.finish() + ("data", "prob")
 
 
-def resnet50(seed=1234, classes=1000, size=224, dry=False):
+def resnet50(seed=1234, classes=1000, size=224, dry=False, quant=None):
     """Caffe ResNet-50: conv-BN-Scale-ReLU, stride on the first 1x1 of each stage, explicit Split for the shortcut."""
-    g = GraphBuilder(seed, dry)
+    g = GraphBuilder(seed, dry, quant)
     x = g.input("data", 3, size, size)
     x = g.conv_bn_relu("conv1", x, 3, 64, 7, 2, 3)
     x = g.pool("pool1", x, 3, 2)
@@ -298,8 +435,8 @@ def resnet50(seed=1234, classes=1000, size=224, dry=False):
     return g.finish() + ("data", "prob")
 
 
-def mobilenet_v1(seed=1234, classes=1000, size=224, dry=False):
-    g = GraphBuilder(seed, dry)
+def mobilenet_v1(seed=1234, classes=1000, size=224, dry=False, quant=None):
+    g = GraphBuilder(seed, dry, quant)
     x = g.input("data", 3, size, size)
     x = g.conv_bn_relu("conv1", x, 3, 32, 3, 2, 1)
     cfg = [(32, 64, 1), (64, 128, 2), (128, 128, 1), (128, 256, 2), (256, 256, 1), (256, 512, 2)] + [(512, 512, 1)] * 5 + \
@@ -310,6 +447,21 @@ def mobilenet_v1(seed=1234, classes=1000, size=224, dry=False):
     x = g.pool("pool6", x, 7, 1, avg=True, global_=True)
     x = g.softmax("prob", g.fc("fc7", x, 1024, classes))
     return g.finish() + ("data", "prob")
+
+
+def vgg16_int8(seed=1234, classes=1000, size=224, dry=False):
+    """vgg16 with every Convolution and InnerProduct int8 at the default input scale: a net for timing, not for accuracy (Net.SetQuantized(True))."""
+    return vgg16(seed, classes, size, dry, quant={})
+
+
+def resnet50_int8(seed=1234, classes=1000, size=224, dry=False):
+    """resnet50 with every Convolution and InnerProduct int8 at the default input scale (Net.SetQuantized(True)); see vgg16_int8."""
+    return resnet50(seed, classes, size, dry, quant={})
+
+
+def mobilenet_v1_int8(seed=1234, classes=1000, size=224, dry=False):
+    """mobilenet_v1 with every Convolution and InnerProduct int8 at the default input scale (Net.SetQuantized(True)); see vgg16_int8."""
+    return mobilenet_v1(seed, classes, size, dry, quant={})
 
 
 def squeezenet_v11(seed=1234, classes=1000, size=224, dry=False):
@@ -1070,7 +1222,8 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_se": tiny_se, "se_resnet50": se_resnet50, "efficientnet_b0": efficientnet_b0,
           "tiny_resample": tiny_resample, "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small,
           "deeplab_largefov_full": deeplab_largefov_full, "unet_bilinear": unet_bilinear, "fpn_resnet50": fpn_resnet50,
-          "tiny_lrn": tiny_lrn, "alexnet": alexnet, "caffenet": caffenet, "googlenet": googlenet}
+          "tiny_lrn": tiny_lrn, "alexnet": alexnet, "caffenet": caffenet, "googlenet": googlenet,
+          "tiny_quant": tiny_quant, "vgg16_int8": vgg16_int8, "resnet50_int8": resnet50_int8, "mobilenet_v1_int8": mobilenet_v1_int8}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -1083,6 +1236,10 @@ DILATED_LAYERS = {"tiny_dilated": ("a1", "a2", "a3", "a_dw", "a_g", "a_far"),
 # nets that need Net.SetExtendedLayers(True) (Interp, HardSwish: libfeather_resample.so; LRN: libfeather_lrn.so)
 EXTENDED_NETS = ("tiny_resample", "mobilenet_v3_large", "mobilenet_v3_small", "deeplab_largefov_full", "unet_bilinear", "fpn_resnet50",
                  "tiny_lrn", "alexnet", "caffenet", "googlenet")
+
+# nets that need Net.SetQuantized(True) (int8 Convolution / InnerProduct layers: libfeather_qconv.so), and the quantised layers of the small one
+QUANTIZED_NETS = ("tiny_quant", "vgg16_int8", "resnet50_int8", "mobilenet_v1_int8")
+QUANT_LAYERS = {"tiny_quant": ("conv1", "conv2", "conv3", "dw", "pw", "fc")}
 
 # the input size a builder's defaults describe, where it is not 224 px
 INPUT_SIZE = {"alexnet": 227, "caffenet": 227}

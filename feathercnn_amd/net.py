@@ -29,6 +29,8 @@ ROUTE_RESAMPLE = 106  # FHIP_NET_ROUTE_RESAMPLE: an Interp or HardSwish layer, a
 ROUTE_NAMES[ROUTE_RESAMPLE] = "RESAMPLE"
 ROUTE_LRN = 107  # FHIP_NET_ROUTE_LRN: an LRN layer, alone or with the Pooling layer behind it, after SetExtendedLayers(True) (libfeather_lrn.so)
 ROUTE_NAMES[ROUTE_LRN] = "LRN"
+ROUTE_QCONV = 108  # FHIP_NET_ROUTE_QCONV: a Convolution / InnerProduct layer with int8 weights, after SetQuantized(True) (libfeather_qconv.so)
+ROUTE_NAMES[ROUTE_QCONV] = "QCONV"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -57,6 +59,11 @@ class Net:
         """feather::Net::SetDilated: accept Convolution layers with dilation > 1 (routed to libfeather_atrous.so) instead of refusing them
         at LoadParam.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_dilated(self._h, int(bool(on))), "fhip_net_set_dilated")
+
+    def SetQuantized(self, on: bool = True):
+        """feather::Net::SetQuantized: accept Convolution, ConvolutionDepthWise and InnerProduct layers with int8 weights (ncnn's
+        int8_scale_term; routed to libfeather_qconv.so) instead of refusing them at LoadParam.  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_quantized(self._h, int(bool(on))), "fhip_net_set_quantized")
 
     def SetExtendedLayers(self, on: bool = True):
         """feather::Net::SetExtendedLayers: accept Interp and HardSwish layers (routed to libfeather_resample.so) and LRN layers

@@ -189,6 +189,8 @@ class Net
     int SetTunedSelection(bool on) { return fhip_net_set_tuned_selection(net_, on ? 1 : 0); }
     // accept Convolution layers with dilation > 1 (libfeather_atrous.so) instead of refusing them; before LoadParam (feather_net.h)
     int SetDilated(bool on) { return fhip_net_set_dilated(net_, on ? 1 : 0); }
+    // int8 Convolution / InnerProduct layers (ncnn's int8_scale_term) load and run through libfeather_qconv.so; before LoadParam
+    int SetQuantized(bool on) { return fhip_net_set_quantized(net_, on ? 1 : 0); }
     // accept Interp and HardSwish layers (libfeather_resample.so) and LRN layers (libfeather_lrn.so) instead of refusing them; before
     // LoadParam (feather_net.h)
     int SetExtendedLayers(bool on) { return fhip_net_set_extended_layers(net_, on ? 1 : 0); }

@@ -267,6 +267,14 @@ FHIP_API int fhip_net_set_dilated(fhip_net* net, int on);
  * lifting that refusal: PixelShuffle stays -200 and a bicubic Interp -100.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to
  * sub-batch replicas. */
 FHIP_API int fhip_net_set_extended_layers(fhip_net* net, int on);
+/* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
+ * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
+ * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
+ * param 8 with -200 and the weight reader refuses the int8 tag, as tests/loader_cases.py and the hostile-model tests pin for a default
+ * net.  Its only effect is lifting those refusals for the layers the library runs: int8_scale_term > 100 (requantised int8 output), a
+ * partial group, a dilation and automatic pads stay -200, and param 8 on weights with any other tag is refused when the weights are read
+ * (this runtime does not quantise at load).  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_quantized(fhip_net* net, int on);
 /* 1: independent branches run concurrently: a convolution that needs no scratch arena and whose output is only consumed
  * further down the layer list (ResNet's projection shortcut, SqueezeNet's expand1x1) is enqueued on a second stream owned by
  * the net while the main stream continues; fork and join are events (hipGraph-capturable).  0 (default): one stream. */
@@ -378,6 +386,11 @@ FHIP_API int fhip_net_layer_count(fhip_net* net);
  * window covers the whole unpadded plane (fhip_pooling's plane-reduce route, whose order the one launch does not restate), it is
  * fhip_lrn_forward into the net's scratch arena and fhip_pooling from there.  A Pooling layer in front of an LRN is not fused.  No other fusion takes the layer.  Reported from LoadParam on. */
 #define FHIP_NET_ROUTE_LRN 107
+/* Route code of a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights in a net with fhip_net_set_quantized: one
+ * launch of libfeather_qconv.so (feather_qconv.h), opened the same way the first time a net holds such a layer.  It fuses a following
+ * ReLU and, at fusion level 2, BatchNorm / Scale -- into the dequantisation scales and the bias, as feather_qconv.h defines it, never into
+ * the int8 weights; no other fusion takes it.  Reported from LoadParam on. */
+#define FHIP_NET_ROUTE_QCONV 108
 /* type / name are copied (truncated) into caller buffers of `len` bytes; algo = fhip_conv_algo for
  * convolutions after the first Forward (FHIP_NET_ROUTE_GCONV for a grouped one), else -1. */
 FHIP_API int fhip_net_layer_info(fhip_net* net, int index, char* type, char* name, int len, int* algo);

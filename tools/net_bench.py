@@ -15,11 +15,13 @@ from feathercnn_amd.net import Net  # noqa: E402
 
 
 def switches(net, name):
-    """The opt-in layer families a zoo net needs (Net.SetDilated, Net.SetExtendedLayers), set before LoadParam."""
+    """The opt-in layer families a zoo net needs (Net.SetDilated, Net.SetExtendedLayers, Net.SetQuantized), set before LoadParam."""
     if name in model_zoo.DILATED_LAYERS:
         net.SetDilated(True)
     if name in model_zoo.EXTENDED_NETS:
         net.SetExtendedLayers(True)
+    if name in model_zoo.QUANTIZED_NETS:
+        net.SetQuantized(True)
 
 
 def run(name, batch, fusion, steps=10):
