@@ -7,7 +7,8 @@
 // touch that buffer only after the barrier (RAW); a buffer is re-filled only after every wave waited lgkmcnt(0) for its reads
 // of it and passed the barrier (WAR).
 // No masks are needed: U is zero padded in both dimensions, V rows past C are clamped to row C-1 (finite data) and meet zero
-// rows of U; V columns past P only feed M columns nobody reads.
+// rows of U; V columns past P only feed M columns nobody reads.  A last column tile with at most 32 live columns computes only its first 32
+// (the narrow tile, prm.live_columns) and leaves the rest of M's padding unwritten.
 #pragma once
 
 #include "gemm_core.h"
@@ -49,12 +50,27 @@ __global__ __launch_bounds__(256, BK == 16 ? OCC : 3) void wino_gemm_glds_kernel
         vid = prm.tail_first + (grp / parts) * 8 + (e & 7);
         if (vid >= nwg) return; // (tail tiles) not a multiple of 8: the surplus blocks of the last group
     }
-    const int mt = vid % prm.m_tiles;
+    int mt = vid % prm.m_tiles;
     vid /= prm.m_tiles;
-    const int nt = vid % prm.n_tiles;
-    const int xi = vid / prm.n_tiles;
+    int nt = vid % prm.n_tiles;
+    int xi = vid / prm.n_tiles;
+    // a launch whose last column tile runs narrow (below) sends every XCD the full tiles of its frequency points first and their narrow tiles
+    // last: the half-length blocks fill the end of the launch (or, where all blocks are resident at once, every CU holds its share of them)
+    // instead of standing in groups of m_tiles between full ones.  Block b runs on XCD b % 8, which owns batches / 8 frequency points.
+    if (!SPLIT && prm.n_tiles > 1 && (prm.batches & 7) == 0 && prm.live_columns - (prm.n_tiles - 1) * BN <= 32)
+    {
+        const int local = blockIdx.x >> 3, per_xcd = prm.batches >> 3, full = per_xcd * prm.m_tiles * (prm.n_tiles - 1);
+        const int j = local < full ? local : local - full;
+        mt = j % prm.m_tiles;
+        nt = local < full ? j / prm.m_tiles % (prm.n_tiles - 1) : prm.n_tiles - 1;
+        xi = (blockIdx.x & 7) * per_xcd + (local < full ? j / (prm.m_tiles * (prm.n_tiles - 1)) : j / prm.m_tiles);
+    }
     const int m0 = mt * BM, n0 = nt * BN;
     const int k_tiles = prm.k_tiles;
+    // narrow tile: a whole-tile block of the last column tile whose live columns fit in 32 re-tiles its waves 4 x 1 -- wave w owns rows
+    // 32 w .. + 31 of columns n0 .. n0 + 31, one accumulator, half the MFMAs per k-tile -- and leaves columns n0 + 32 .. n0 + 63 of M unwritten
+    // (no reader goes past the live columns).  Same instruction, same k order, same zero start: every live M value is what the 2 x 2 tiling gives.
+    const bool narrow = whole && nt == prm.n_tiles - 1 && prm.live_columns - n0 <= 32;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -96,6 +112,54 @@ __global__ __launch_bounds__(256, BK == 16 ? OCC : 3) void wino_gemm_glds_kernel
     else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+
+    if (narrow)
+    {
+        // the main loop and the epilogue below for one accumulator: operand loads, waits and barriers as they are there
+        f32x16 c;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) c[r] = 0.f;
+        const int a_off = half * BM + wave * 32 + l31;
+        const int b_off = BK * BM + half * BN + l31;
+        int cur = 0;
+        for (int kt = 0; kt < k_tiles; ++kt)
+        {
+            const int ahead = kt + NBUF - 1;
+            int nb = cur + NBUF - 1;
+            if (nb >= NBUF) nb -= NBUF;
+            const bool more = ahead < k_tiles;
+            if (more) issue(ahead, nb);
+            const float* as = lds + cur * BUF_FLOATS + a_off;
+            const float* bs = lds + cur * BUF_FLOATS + b_off;
+#pragma unroll
+            for (int kp = 0; kp < BK / 2; ++kp) c = __builtin_amdgcn_mfma_f32_32x32x2f32(as[(2 * kp) * BM], bs[(2 * kp) * BN], c, 0, 0, 0);
+            if (NBUF == 3 && more)
+                asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
+            else
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            cur = cur + 1 == NBUF ? 0 : cur + 1;
+        }
+        float* const scr = lds + wave * (32 * EPI_LD);
+        const int e_row = lane >> 3, e_c4 = (lane & 7) * 4;
+        float* mbase = prm.M + (size_t)xi * prm.Lm.xis + prm.Lm.col(n0) + e_c4;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) scr[((r & 3) + 8 * (r >> 2) + 4 * half) * EPI_LD + l31] = c[r];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+        {
+            const float4 v = *reinterpret_cast<const float4*>(&scr[(q * 8 + e_row) * EPI_LD + e_c4]);
+            const int m = m0 + wave * 32 + e_row + q * 8;
+            if (m < prm.K)
+            {
+                if constexpr (NT & 2)
+                    stg4_nt(mbase + (size_t)m * prm.Lm.bp, v);
+                else
+                    *reinterpret_cast<float4*>(mbase + (size_t)m * prm.Lm.bp) = v;
+            }
+        }
+        return;
+    }
 
     // rows of this wave inside the 128-row tile: a whole tile gives wave (wm, wn) rows 64 wm .. + 63 (two accumulators); a half piece
     // (64 rows) gives it rows 64 part + 32 wm .. + 31, a quarter piece (32 rows) rows 32 part .. + 31 on the waves wm = 0 only (one accumulator)

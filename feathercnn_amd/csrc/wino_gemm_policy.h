@@ -21,6 +21,9 @@ struct WinoGemmParams
     // rows, one block each -- the remainder of the tile count over the CU count spread over all CUs instead of a whole tile more on some
     // (wino_gemm_row_split).  tail_parts = 1: every block is a whole tile.
     int tail_first = 0, tail_parts = 1;
+    // wino_gemm_glds_kernel only: the live column count P (<= Pp).  A whole-tile block of the last column tile with at most 32 live columns
+    // computes columns n0 .. n0 + 31 alone (wino_gemm_glds.h, narrow tile).  The default never narrows: every block is 64 columns wide.
+    int live_columns = 0x7fffffff;
 };
 
 // NT bit 0: V loads carry `nt` (every V element is read by exactly one block when the row tile covers all of K: m_tiles = 1);

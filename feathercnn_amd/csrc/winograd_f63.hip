@@ -1185,6 +1185,7 @@ static void wino_tile_gemm_launch(WinoGemmPolicy::Params& g, int columns, hipStr
         const int tiles = g.batches * g.m_tiles * g.n_tiles;
         g.tail_first = tiles;
         g.tail_parts = 1;
+        g.live_columns = columns; // at most 32 of them in the last column tile: its whole-tile blocks run narrow (wino_gemm_glds.h)
         // the row split takes launches of at most kWinoRowSplitMaxRounds (8) tiles per CU: 2048 tiles of 128 x 64 on 256 CUs, so K * Pp <=
         // 524288 -- below the 614400 of a big M (FHIP_M_NT_BYTES).  Only the FHIP_M_NT_SMALL form has a row-split instantiation.
         if constexpr (NT == FHIP_M_NT_SMALL)

@@ -1,6 +1,6 @@
 // tools/gemm_bench.hip -- measurement harness for the shared MFMA main loop (gemm_core.h) on Winograd tile-GEMM
 // shapes: times variants of tile shape / occupancy / ablations with HIP events. Not part of the product.
-//   usage: gemm_bench [reps]
+//   usage: gemm_bench [reps]      (GEMM_NARROW=1, GEMM_SPLIT=1, GEMM_TAIL=1, ... in the environment pick the comparison; see main)
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -46,6 +46,8 @@ static int g_ref_pp = 0;
 static int g_bp = 0; // column block of V / M (GEMM_BP)
 static int g_split_rounds = 0; // GEMM_SPLIT: wino_gemm_row_split's max_rounds for V0 == 3 (0 = whole tiles only)
 static int g_c64_blocks = 2; // persistent blocks per CU of wino_gemm_c64_kernel
+static bool g_narrow = false; // GEMM_NARROW: V0 == 3 passes the live column count, so the last column tile may run narrow (wino_gemm_glds.h)
+static bool g_bitwise = false; // GEMM_NARROW: the comparison with the first variant of the case is bit for bit
 static long long* g_prof = nullptr;
 
 template <class Shape, int ABLATE, int V0 = 0, int NT = 0>
@@ -76,6 +78,7 @@ double run(const char* name, const Case& cs, float* U, float* V, float* M, int r
     g.Lm = wino_layout(g.K, g.Pp, bp);
     const int tiles = g.batches * g.m_tiles * g.n_tiles;
     dim3 grid(tiles);
+    if (V0 == 3 && g_narrow) g.live_columns = cs.P;
     if (V0 == 3 && g_split_rounds)
     {
         wino_gemm_row_split(tiles, g_cus, g_split_rounds, g.tail_first, g.tail_parts);
@@ -133,7 +136,7 @@ double run(const char* name, const Case& cs, float* U, float* V, float* M, int r
             got[w].resize(plane);
             CK(hipMemcpy(got[w].data(), M + (size_t)(w ? g_batches - 1 : 0) * plane, plane * 4, hipMemcpyDeviceToHost));
         }
-        if (fresh && ABLATE == 0 && (V0 == 0 || (V0 == 3 && !g_split_rounds && getenv("GEMM_SPLIT"))) && !bp)
+        if (fresh && ABLATE == 0 && (V0 == 0 || (V0 == 3 && !g_split_rounds && getenv("GEMM_SPLIT")) || (V0 == 3 && g_bitwise && !g_narrow)) && !bp)
         {
             ref[0] = got[0];
             ref[1] = got[1];
@@ -143,6 +146,7 @@ double run(const char* name, const Case& cs, float* U, float* V, float* M, int r
         else if (!fresh && ABLATE == 0 && !bp)
         {
             double worst = 0, scale = 0;
+            size_t unequal = 0;
             for (int w = 0; w < 2; ++w)
                 for (int m = 0; m < cs.K; ++m)
                     for (int p = 0; p < cs.P; ++p)
@@ -150,7 +154,9 @@ double run(const char* name, const Case& cs, float* U, float* V, float* M, int r
                         const double a = got[w][(size_t)m * g.Pp + p], b = ref[w][(size_t)m * g_ref_pp + p];
                         worst = std::max(worst, std::abs(a - b));
                         scale = std::max(scale, std::abs(b));
+                        unequal += !(a == b);
                     }
+            if (g_bitwise) printf("    %s: %zu of the live M values (planes 0 and %d) differ from the full-tile launch\n", name, unequal, g_batches - 1);
             if (worst > 1e-5 * scale) printf("    !! %s differs from the product kernel: max |diff| %.3e (scale %.3e)\n", name, worst, scale);
         }
     }
@@ -168,9 +174,13 @@ int main(int argc, char** argv)
     // GEMM_TAIL: what a partial last round costs -- the LDS-DMA kernel on column counts that make whole rounds of 6 blocks per CU next to VGG-16's
     const Case tail[] = {{512, 512, 768}, {512, 512, 800}, {512, 512, 1152}, {256, 256, 3072}, {256, 256, 3200}, {256, 256, 4608}, {128, 128, 12288}, {128, 128, 11552}};
     // GEMM_SPLIT: the row split of the last tiles -- ResNet-50 b64's res5 (36 frequency points, set GEMM_BATCHES=36), res3, res4 on 64-column tiles, VGG-16's conv2_2
+    // GEMM_NARROW: the narrow last column tile -- conv5-class (4 column tiles: 8, 32 and 64 live columns in the last), conv4-class (13 tiles: 32
+    // and 64) and conv3-class (46 tiles: 8, 32 and 64) launches, the full-tile launch against the one that knows the live column count
+    const Case narrow[] = {{512, 512, 200}, {512, 512, 224}, {512, 512, 256}, {512, 512, 800}, {512, 512, 832}, {256, 256, 2888}, {256, 256, 2912}, {256, 256, 2944}};
     const Case split[] = {{512, 512, 256}, {128, 128, 1600}, {256, 256, 576}, {128, 128, 11552}, {512, 512, 256}, {128, 128, 1600}, {256, 256, 576}, {128, 128, 11552}};
     if (getenv("GEMM_BATCHES")) g_batches = atoi(getenv("GEMM_BATCHES"));
-    const Case* cases_p = getenv("GEMM_SPLIT") ? split : getenv("GEMM_TAIL") ? tail : getenv("GEMM_RESNET") ? resnet : vgg;
+    g_bitwise = getenv("GEMM_NARROW") != nullptr;
+    const Case* cases_p = g_bitwise ? narrow : getenv("GEMM_SPLIT") ? split : getenv("GEMM_TAIL") ? tail : getenv("GEMM_RESNET") ? resnet : vgg;
     Case cases[8];
     for (int i = 0; i < 8; ++i) cases[i] = cases_p[i];
     size_t maxU = 0, maxV = 0, maxM = 0;
@@ -223,6 +233,19 @@ int main(int argc, char** argv)
                 g_split_rounds = 0;
                 if (c.P <= 576) run<GemmShape<128, 64, 16, 2, 2, 4>, 0, 7>("128x96 glds", c, U, V, M, reps);
             }
+            continue;
+        }
+        if (g_bitwise)
+        {
+            // x = duration of a narrow block over a full one: with n column tiles, 1 - n * (1 - t_narrow / t_full) of a case's two lines
+            for (int round = 0; round < 3; ++round)
+            {
+                g_narrow = false;
+                run<GemmShape<128, 64, 16, 2, 2, 4>, 0, 3, 0>("128x64 glds full tiles", c, U, V, M, reps);
+                g_narrow = true;
+                run<GemmShape<128, 64, 16, 2, 2, 4>, 0, 3, 0>("128x64 glds narrow last tile", c, U, V, M, reps);
+            }
+            g_narrow = false;
             continue;
         }
         if (getenv("GEMM_TAIL"))
