@@ -16,11 +16,13 @@
 //   * optional hipGraph replay of the whole forward.
 //
 // One translation unit, read in this order (no header includes a later one): net_side.h -- errors, the side libraries; net_model.h --
-// ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_layers.h -- the layer classes; net_plan.h -- the
-// fusion and planning passes, prepare, forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
+// ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_conv.h -- the convolution layer, its side routes
+// and the weight staging it shares; net_layers.h -- the other layer classes; net_plan.h -- the fusion and planning passes, prepare,
+// forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
 #include "net_side.h"
 #include "net_model.h"
 #include "net_core.h"
+#include "net_conv.h"
 #include "net_layers.h"
 #include "net_plan.h"
 

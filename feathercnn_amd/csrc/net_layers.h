@@ -1,6 +1,6 @@
-// net_layers.h -- the layer classes of the Net runtime, and the one life cycle of the side-library convolutions (SideConv).
+// net_layers.h -- the layer classes of the Net runtime but the convolution's (net_conv.h), and the two definitions of net_conv.h that need them.
 #pragma once
-#include "net_core.h"
+#include "net_conv.h"
 
 namespace fhip::net
 {
@@ -9,612 +9,6 @@ struct InputLayer : Layer
 {
     int Reshape() override { return 0; } // shape comes from FeedInput (input_layer.h:33-46)
     int Forward(hipStream_t) override { return 0; }
-};
-
-// A BatchNorm / Scale folded into the convolution or deconvolution before it (fusion level 2): y = y * mul[k] + add[k] per output
-// channel k, applied to the filters and the bias at Init.  K is the caller's business: the layers count their channels differently.
-struct AffineFold
-{
-    std::vector<float> mul, add;
-    bool empty() const { return mul.empty(); }
-    // composes nx behind what is folded already; false, with nothing changed, if nx is no plain affine map over K channels
-    bool absorb(const AffineLayer& nx, int K);
-    // w = [K][...] filters, b = K biases or none (then a zero bias is created); does nothing while no layer was absorbed
-    void apply(std::vector<float>& w, std::vector<float>& b, int K) const
-    {
-        if (mul.empty()) return;
-        const size_t per = w.size() / K;
-        if (b.empty()) b.assign(K, 0.f);
-        for (int k = 0; k < K; ++k)
-        {
-            for (size_t i = 0; i < per; ++i) w[k * per + i] *= mul[k];
-            b[k] = b[k] * mul[k] + add[k];
-        }
-    }
-};
-
-// The life cycle of a convolution that runs through a side library -- grouped (GconvApi on fhip_conv_param), dilated (AtrousApi on
-// fhip_atrous_param), transposed (DeconvApi on fhip_deconv_param) -- once.  The layer decides that it takes the route and keeps the
-// library's param `p`; its own checks (the bottom's channels, an empty output) stay in front of these calls.
-template <class Api, class Param>
-struct SideConv
-{
-    // the tail of Reshape, with the input size in `p`: the library's output size where it has its own rule (else the caller has set it),
-    // its verdict on the geometry, the top, the scratch and packed sizes
-    template <bool Assign>
-    static int reshape(Layer* l, const Api* api, Param& p, const char* refusal, size_t* buffer_bytes, size_t* packed_bytes)
-    {
-        if (!api) return FHIP_E_UNSUPPORTED; // message set by side_api
-        const Blob* b = l->bottoms[0];
-        int rc;
-        if constexpr (Assign)
-            if ((rc = l->side(api, [&](const Api* a) { return a->assign_output_dim(&p); }, NET_E_SHAPE))) return rc;
-        if ((rc = l->side(api, [&](const Api* a) { return a->supported(&p) != 1; }, FHIP_E_UNSUPPORTED, refusal))) return rc;
-        if ((rc = l->tops[0]->reshape(b->n, p.output_channels, p.output_h, p.output_w))) return rc;
-        return l->side(api, [&](const Api* a) { return a->get_buffer_size(&p, b->n, buffer_bytes, packed_bytes); });
-    }
-    // Init: filters `w` and bias `b` with the layer's fold applied -> the library's packed form and the bias on the device
-    static int init(Layer* l, const Api* api, const Param& p, const std::vector<float>& w, const std::vector<float>& b, DeviceVec& packed,
-                    size_t packed_bytes, DeviceVec& bias, hipStream_t s)
-    {
-        if (!api) return FHIP_E_UNSUPPORTED;
-        DeviceVec raw;
-        int rc = raw.upload(w.data(), w.size(), s);
-        if (rc) return rc;
-        if ((rc = packed.resize(packed_bytes))) return rc;
-        if ((rc = l->side(api, [&](const Api* a) { return a->init(&p, packed.d, raw.d, s); }))) return rc;
-        if (p.bias_term && (rc = bias.upload(b.data(), b.size(), s))) return rc;
-        FHIP_CHECK_HIP(hipStreamSynchronize(s)); // `raw` and the host copies go out of scope
-        return 0;
-    }
-    static int forward(const Layer* l, const Api* api, const Param& p, const DeviceVec& packed, const DeviceVec& bias, hipStream_t s)
-    {
-        return l->side(api, [&](const Api* a) {
-            return a->forward(&p, l->bottoms[0]->n, l->tops[0]->data, l->bottoms[0]->data, packed.d, nullptr, p.bias_term ? bias.d : nullptr, s);
-        });
-    }
-};
-
-// The int8 side of a Convolution / ConvolutionDepthWise / InnerProduct layer of a net with fhip_net_set_quantized: it runs through
-// libfeather_qconv.so (qconv_api) with route code FHIP_NET_ROUTE_QCONV.  The library's calls do not fit SideConv (int8 weights, the
-// dequantisation scales and the input scale ride along), so its three calls stand here, once for both layer types.  The layer fills `q`
-// at Reshape; a BatchNorm / Scale fold goes into d[] and the bias as feather_qconv.h defines it, never into the weights.
-struct QuantRoute
-{
-    fhip_qconv_param q;
-    int scale_term = 0;
-    std::vector<signed char> w;
-    std::vector<float> s_w, b;
-    float s_in = 0.f;
-    DeviceVec packed, d, bias;
-    size_t packed_bytes = 0;
-    bool inited = false;
-
-    QuantRoute() { memset(&q, 0, sizeof(q)); }
-    // ncnn's param 8 of the layer, 0 where the file does not set it
-    int read_scale_term(const ParamDict& pd) { return scale_term = pd.get(8, 0); }
-    // the .bin of a quantised layer: int8-tagged weights, the bias, K weight scales, one input scale (the last three raw fp32)
-    int load(const Layer* l, ModelBin& mb, size_t wsize, int K, bool bias_term)
-    {
-        inited = false;
-        int rc = mb.load_int8(wsize, w);
-        if (rc) return rc;
-        if (bias_term && (rc = mb.load(K, 1, b))) return rc;
-        if ((rc = mb.load(K, 1, s_w))) return rc;
-        std::vector<float> one;
-        if ((rc = mb.load(1, 1, one))) return rc;
-        s_in = one[0];
-        if (!std::isfinite(s_in) || !(s_in > 0.f)) return failf(NET_E_SHAPE, "layer %s: the int8 input scale must be finite and > 0", l->name.c_str());
-        for (float v : s_w)
-            if (!std::isfinite(v) || v < 0.f) return failf(NET_E_SHAPE, "layer %s: an int8 weight scale is not finite or is negative", l->name.c_str());
-        return 0;
-    }
-    // the tail of Reshape, with the geometry and the input size in `q`
-    int reshape(Layer* l)
-    {
-        const QconvApi* api = qconv_api();
-        if (!api) return FHIP_E_UNSUPPORTED; // message set by side_api
-        const Blob* bt = l->bottoms[0];
-        int rc;
-        q.dilation_h = q.dilation_w = 1;
-        q.int8_scale_term = scale_term;
-        if ((rc = l->side(api, [&](const QconvApi* a) { return a->assign_output_dim(&q); }, NET_E_SHAPE))) return rc;
-        if ((rc = l->side(api, [&](const QconvApi* a) { return a->supported(&q) != 1; }, FHIP_E_UNSUPPORTED, "int8 convolution refused: "))) return rc;
-        if ((rc = l->tops[0]->reshape(bt->n, q.output_channels, q.output_h, q.output_w))) return rc;
-        size_t scratch = 0;
-        return l->side(api, [&](const QconvApi* a) { return a->get_buffer_size(&q, bt->n, &scratch, &packed_bytes); });
-    }
-    int init(Layer* l, const AffineFold& fold, hipStream_t s)
-    {
-        if (inited && packed.bytes == packed_bytes) return 0;
-        const QconvApi* api = qconv_api();
-        if (!api) return FHIP_E_UNSUPPORTED;
-        const int K = q.output_channels;
-        std::vector<float> dq(K), bq = b;
-        int rc = l->side(api, [&](const QconvApi* a) { return a->dequant_scales(dq.data(), s_w.data(), K, s_in); });
-        if (rc) return rc;
-        if (!fold.empty())
-        {
-            if (bq.empty()) bq.assign(K, 0.f);
-            for (int k = 0; k < K; ++k)
-            {
-                dq[k] = dq[k] * fold.mul[k];
-                const float scaled = bq[k] * fold.mul[k]; // rounded before the sum: no contraction
-                bq[k] = scaled + fold.add[k];
-            }
-            q.bias_term = 1;
-        }
-        DeviceVec raw;
-        if ((rc = raw.resize(w.size()))) return rc;
-        FHIP_CHECK_HIP(hipMemcpyAsync(raw.d, w.data(), w.size(), hipMemcpyHostToDevice, s));
-        if ((rc = packed.resize(packed_bytes))) return rc;
-        if ((rc = l->side(api, [&](const QconvApi* a) { return a->init(&q, packed.d, reinterpret_cast<const signed char*>(raw.d), s); }))) return rc;
-        if ((rc = d.upload(dq.data(), dq.size(), s))) return rc;
-        if (q.bias_term && (rc = bias.upload(bq.data(), bq.size(), s))) return rc;
-        FHIP_CHECK_HIP(hipStreamSynchronize(s)); // `raw` and the host copies go out of scope
-        inited = true;
-        return 0;
-    }
-    int forward(const Layer* l, hipStream_t s) const
-    {
-        return l->side(qconv_api(), [&](const QconvApi* a) {
-            return a->forward(&q, l->bottoms[0]->n, l->tops[0]->data, l->bottoms[0]->data, packed.d, nullptr, d.d, q.bias_term ? bias.d : nullptr, s_in, s);
-        });
-    }
-    size_t bytes() const { return packed.bytes + d.bytes + bias.bytes; }
-};
-
-// The same Init on the main library (a convolution on route `algo`, an InnerProduct on the implicit GEMM)
-static int init_packed(const fhip_conv_param& p, int algo, const std::vector<float>& w, const std::vector<float>& b, DeviceVec& packed, size_t packed_bytes,
-                       DeviceVec& bias, hipStream_t s)
-{
-    DeviceVec raw;
-    int rc = raw.upload(w.data(), w.size(), s);
-    if (rc) return rc;
-    if ((rc = packed.resize(packed_bytes))) return rc;
-    if ((rc = fhip_conv_init(&p, algo, packed.d, raw.d, s))) return rc;
-    if (p.bias_term && (rc = bias.upload(b.data(), b.size(), s))) return rc;
-    FHIP_CHECK_HIP(hipStreamSynchronize(s)); // `raw` and the host copies go out of scope
-    return 0;
-}
-
-// feather::ConvLayer, layers/conv_layer.h:26-193 (also registered as ConvolutionDepthWise, layer_factory.cpp)
-struct ConvLayer : Layer
-{
-    fhip_conv_param p;
-    int algo_ = -1, inited_algo = -2;
-    // what the packed weights' content depends on besides the route and the byte count (fhip_conv_packed_layout): a new input size packs
-    // again when it changes -- a 1x1 layer's streamed image and its InnerProduct image have the same size
-    int layout = 0, inited_layout = -1;
-    // 1 < group < input_channels: the layer runs through libfeather_gconv.so (gconv_api) with route code FHIP_NET_ROUTE_GCONV.
-    // p.output_channels then holds the WHOLE layer's K (the library's convention), not K / group as conv_layer.h:69-75 leaves it.
-    // Such a layer fuses a following ReLU and, at level 2, BatchNorm / Scale; every other fusion declines it.
-    bool gconv = false;
-    // dilation > 1 in a net with fhip_net_set_dilated: the layer runs through libfeather_atrous.so (atrous_api) with route code
-    // FHIP_NET_ROUTE_ATROUS, whatever its group.  p.output_channels holds the WHOLE layer's K here too; `dilated` is the library's param,
-    // filled from p at every Reshape (Init adds the bias a fold created).
-    // Fusions as on the grouped route: a following ReLU, at level 2 BatchNorm / Scale, nothing else.
-    bool atrous = false;
-    int dilation_h = 1, dilation_w = 1;
-    fhip_atrous_param dilated;
-    typedef SideConv<GconvApi, fhip_conv_param> Grouped;
-    typedef SideConv<AtrousApi, fhip_atrous_param> Dilated;
-    // 8=int8_scale_term in a net with fhip_net_set_quantized: the layer runs through libfeather_qconv.so (QuantRoute) with route code
-    // FHIP_NET_ROUTE_QCONV; group is 1 or depthwise.  p.output_channels holds the WHOLE layer's K here too.
-    // Fusions as on the grouped route: a following ReLU, at level 2 BatchNorm / Scale (into the dequantisation), nothing else.
-    bool quant = false;
-    QuantRoute qr;
-    std::vector<float> w_host, b_host;
-    AffineFold fold; // folded BatchNorm/Scale (fusion level 2)
-    DeviceVec packed, bias;
-    size_t buffer_bytes = 0, packed_bytes = 0;
-    // fusion level 2: a following 2x2 / stride-2 max pooling is absorbed (fhip_conv_forward_maxpool2 when the route can,
-    // else this layer runs conv -> pre_pool -> fhip_pooling itself)
-    bool fuse_pool = false, pool_fast = false;
-    fhip_pool_param poolq;
-    DeviceVec pre_pool;
-    // fusion level 2: a following Eltwise SUM (+ReLU) with an earlier blob is absorbed: top = act(conv + bias + residual)
-    Blob* residual = nullptr;
-    bool res_fast = false;
-    // fusion level 2: this is a 3x3 depthwise layer and the 1x1 convolution that is its only consumer was absorbed (`pw` owns its
-    // parameters, weights and further fusions); when the pair qualifies at the current shape the two run as ONE kernel
-    // (fhip_conv_forward_dw_pw) and the depthwise output never exists, else dw -> `mid` -> pw one after the other
-    std::unique_ptr<ConvLayer> pw;
-    bool pair_fast = false;
-    DeviceVec mid;
-    // fusion level 3 (plan_chains, after Reshape): this Winograd layer's input arrives already transformed (chain_in) and / or its
-    // output leaves as the next layer's transformed input (chain_next); chain_pos = position in the run (picks the V slot)
-    ConvLayer* chain_next = nullptr;
-    bool chain_in = false;
-    int chain_pos = 0;
-    size_t chain_bytes = 0; // arena the run needs (reported instead of buffer_bytes)
-    // fusion level 3 (plan_chains): this chained layer's V and M hold 2x2 image canvases (feather_canvas.h): its tile GEMM runs on
-    // canvas_p -- the layer as one (2H + 2)-pixel image -- at a quarter of the batch, its boundaries through libfeather_canvas.so
-    bool canvas = false;
-    fhip_conv_param canvas_p;
-    fhip_winograd_plan run_plan; // the plan this chained layer runs with (plain or canvas), set by plan_chains
-    // fusion level 3 (plan_chains): a first layer (3x3 / s1 / p1, 2 .. 4 input channels) whose only consumer is a Winograd layer is computed
-    // inside that layer's input transform (fhip_winograd_f63_input_from_first): `head_of` = the consumer (this layer then launches nothing,
-    // its top has no storage), `head` = the absorbed first layer (on the consumer); first_raw = this layer's filters as loaded
-    ConvLayer* head_of = nullptr;
-    ConvLayer* head = nullptr;
-    DeviceVec first_raw;
-    // fusion level 2 (plan_siblings, after Reshape): this 1x1 layer and the NEXT layer of the list -- a 1x1 layer on the same bottom with
-    // the same stride: ResNet's projection shortcut and the first layer of the main branch -- run as ONE GEMM over the stacked filters
-    // (fhip_conv_forward_siblings).  `sib` (on the first layer) = the second; `sib_of` (on the second, which launches nothing) = the first.
-    ConvLayer* sib = nullptr;
-    ConvLayer* sib_of = nullptr;
-    ConvLayer* sib_packed_for = nullptr; // the partner sib_packed / sib_bias were built with
-    DeviceVec sib_packed, sib_bias;
-    bool sib_has_bias = false;
-    bool first_candidate() const
-    {
-        return p.kernel_h == 3 && p.kernel_w == 3 && p.stride_h == 1 && p.stride_w == 1 && p.group == 1 && p.input_channels >= 2 && p.input_channels <= 4 && p.pad_left == 1 &&
-               p.pad_right == 1 && p.pad_top == 1 && p.pad_bottom == 1;
-    }
-
-    ConvLayer()
-    {
-        memset(&p, 0, sizeof(p));
-        memset(&poolq, 0, sizeof(poolq));
-        memset(&dilated, 0, sizeof(dilated));
-    }
-    bool needs_weights() const override { return true; }
-    ConvLayer* as_conv() override { return this; }
-
-    int LoadParam(const ParamDict& pd) override
-    {
-        dilation_w = pd.get(2, 1);
-        dilation_h = pd.get(12, dilation_w);
-        atrous = dilation_w > 1 || dilation_h > 1;
-        if (atrous && !(net && net->dilated))
-            return failf(NET_E_UNKNOWN_LAYER, "layer %s: dilated convolution is not supported (fhip_net_set_dilated lifts this)", name.c_str());
-        if (dilation_w < 1 || dilation_h < 1) return failf(NET_E_SHAPE, "layer %s: dilation must be >= 1", name.c_str());
-        qr.scale_term = pd.get(8, 0);
-        quant = qr.scale_term != 0 && net && net->quantized;
-        if (qr.scale_term && !quant) return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8 convolution is not supported", name.c_str());
-        if (quant && (qr.scale_term < 0 || qr.scale_term > 100))
-            return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8_scale_term %d (requantised int8 output) is not supported", name.c_str(), qr.scale_term);
-        if (quant && atrous) return failf(NET_E_UNKNOWN_LAYER, "layer %s: a dilated int8 convolution is not supported", name.c_str());
-        p.kernel_w = pd.get(1, 0);
-        p.kernel_h = pd.get(11, p.kernel_w);
-        p.stride_w = pd.get(3, 1);
-        p.stride_h = pd.get(13, p.stride_w);
-        p.pad_left = pd.get(4, 0);
-        p.pad_bottom = pd.get(14, p.pad_left);
-        p.pad_right = pd.get(4, 0);
-        p.pad_top = pd.get(14, p.pad_left);
-        p.group = pd.get(7, 1);
-        p.output_channels = pd.get(0, 0);
-        p.bias_term = pd.get(5, 0);
-        p.activation = FHIP_ACT_NONE;
-        const int weight_data_size = pd.get(6, 0);
-        // conv_layer.h:69-75: output_channels is divided by group (AssignOutputDim restores it for depthwise)
-        if (p.group < 1 || p.output_channels % p.group) return failf(NET_E_SHAPE, "layer %s: output_channels is not divisible by its group", name.c_str());
-        p.output_channels /= p.group;
-        if (p.output_channels <= 0 || p.kernel_h <= 0 || p.kernel_w <= 0) return failf(NET_E_SHAPE, "layer %s: bad convolution geometry", name.c_str());
-        // the reference truncates here (conv_layer.h:75); a size that is no whole number of input channels would leave the weight stream
-        // out of step with the file for every later layer
-        long long per_channel = (long long)p.output_channels * p.kernel_h; // three ints: the product is taken in two steps, each below 2^62
-        if (per_channel <= INT_MAX) per_channel *= p.kernel_w;
-        if (weight_data_size < 0 || per_channel > INT_MAX || weight_data_size % per_channel)
-            return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the convolution geometry", name.c_str());
-        p.input_channels = (int)(weight_data_size / per_channel);
-        gconv = !atrous && !quant && p.group > 1 && p.group < p.input_channels;
-        if (gconv || atrous || quant) p.output_channels *= p.group;
-        if (quant)
-        {
-            if (p.pad_left < 0 || p.pad_top < 0) return failf(NET_E_UNKNOWN_LAYER, "layer %s: automatic padding is not supported", name.c_str());
-            if (p.input_channels < 1) return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the convolution geometry", name.c_str());
-            if (p.group != 1 && (p.group != p.input_channels || p.group != p.output_channels))
-                return failf(NET_E_UNKNOWN_LAYER, "layer %s: an int8 convolution with a partial group (1 < group < channels) is not supported", name.c_str());
-            algo_ = FHIP_NET_ROUTE_QCONV;
-        }
-        if (atrous)
-        {
-            if (p.pad_left < 0 || p.pad_top < 0) return failf(NET_E_UNKNOWN_LAYER, "layer %s: automatic padding is not supported", name.c_str());
-            if (p.input_channels < 1 || p.input_channels % p.group) return failf(NET_E_SHAPE, "layer %s: weight_data_size does not fit the convolution geometry", name.c_str());
-            algo_ = FHIP_NET_ROUTE_ATROUS;
-        }
-        return 0;
-    }
-    int LoadWeights(ModelBin& mb) override
-    {
-        const size_t wsize = (size_t)p.input_channels * p.output_channels * p.kernel_h * p.kernel_w / (gconv || atrous || quant ? p.group : 1);
-        inited_algo = -2; // new weights: every packed form is rebuilt at the next Init
-        sib_packed_for = nullptr;
-        if (quant) return qr.load(this, mb, wsize, p.output_channels, p.bias_term != 0);
-        int rc = mb.load(wsize, 0, w_host);
-        if (rc) return rc;
-        if (p.bias_term)
-        {
-            const int k = atrous ? p.output_channels : p.group == p.input_channels ? p.input_channels : p.output_channels;
-            rc = mb.load(k, 1, b_host);
-        }
-        return rc;
-    }
-    int Reshape() override
-    {
-        const Blob* b = bottoms[0];
-        p.input_w = b->w;
-        p.input_h = b->h;
-        if (p.input_channels != b->c)
-            return failf(NET_E_TOPOLOGY, "convolution layer %s has %d input channels while bottom blob has %d channels", name.c_str(), p.input_channels, b->c);
-        if (quant)
-        {
-            fhip_qconv_param& a = qr.q;
-            a.output_channels = p.output_channels, a.input_channels = p.input_channels, a.input_h = p.input_h, a.input_w = p.input_w;
-            a.kernel_h = p.kernel_h, a.kernel_w = p.kernel_w;
-            a.stride_h = p.stride_h, a.stride_w = p.stride_w, a.pad_left = p.pad_left, a.pad_bottom = p.pad_bottom, a.pad_right = p.pad_right, a.pad_top = p.pad_top;
-            a.group = p.group, a.bias_term = p.bias_term, a.activation = p.activation;
-            const int rc = qr.reshape(this);
-            p.output_h = a.output_h; // kept where conv_param() reports it
-            p.output_w = a.output_w;
-            return rc;
-        }
-        if (atrous)
-        {
-            fhip_atrous_param& a = dilated;
-            a.output_channels = p.output_channels, a.input_channels = p.input_channels, a.input_h = p.input_h, a.input_w = p.input_w;
-            a.kernel_h = p.kernel_h, a.kernel_w = p.kernel_w, a.output_h = p.output_h, a.output_w = p.output_w;
-            a.stride_h = p.stride_h, a.stride_w = p.stride_w, a.pad_left = p.pad_left, a.pad_bottom = p.pad_bottom, a.pad_right = p.pad_right, a.pad_top = p.pad_top;
-            a.group = p.group, a.bias_term = p.bias_term, a.activation = p.activation, a.dilation_h = dilation_h, a.dilation_w = dilation_w;
-            const int rc = Dilated::reshape<true>(this, atrous_api(), a, "dilated convolution refused: ", &buffer_bytes, &packed_bytes);
-            p.output_h = a.output_h; // the library's rule for the output size, kept where conv_param() reports it
-            p.output_w = a.output_w;
-            return rc;
-        }
-        fhip_conv_assign_output_dim(&p);
-        if (p.output_h < 1 || p.output_w < 1) return failf(NET_E_SHAPE, "layer %s: empty output", name.c_str());
-        if (gconv)
-        {
-            algo_ = FHIP_NET_ROUTE_GCONV;
-            return Grouped::reshape<false>(this, gconv_api(), p, "grouped convolution refused: ", &buffer_bytes, &packed_bytes);
-        }
-        int rc = net->tuned_selection ? fhip_conv_select_algo_tuned(&p, &algo_) : fhip_conv_select_algo(&p, &algo_);
-        if (rc) return rc;
-        if (pw)
-        {
-            // the absorbed 1x1 convolution reshapes against a stand-in for the depthwise output, then takes over this layer's top
-            Blob dwout;
-            dwout.n = b->n;
-            dwout.c = p.output_channels;
-            dwout.h = p.output_h;
-            dwout.w = p.output_w;
-            pw->bottoms.assign(1, &dwout);
-            pw->tops = tops;
-            pw->net = net;
-            rc = pw->Reshape();
-            pw->bottoms.clear();
-            if (rc) return rc;
-            pair_fast = fhip_conv_can_fuse_dw_pw(&p, &pw->p, b->n) != 0 && !pw->fuse_pool && !pw->residual && pw->algo_ == FHIP_IM2COL;
-            if (!pair_fast && (rc = mid.resize((size_t)b->n * p.output_channels * p.output_h * p.output_w * sizeof(float)))) return rc;
-            size_t bb = 0;
-            if ((rc = fhip_conv_get_buffer_size(&p, algo_, b->n, &bb, &packed_bytes))) return rc;
-            buffer_bytes = std::max(bb, pw->buffer_bytes);
-            return fhip_conv_packed_layout(&p, algo_, &layout);
-        }
-        res_fast = residual && fhip_conv_can_fuse_residual(&p, algo_) != 0;
-        if (residual && (residual->n != b->n || residual->c != p.output_channels || residual->h != p.output_h || residual->w != p.output_w))
-            return failf(NET_E_SHAPE, "Shape mismatch among bottoms of layer %s.", name.c_str());
-        if (fuse_pool)
-        {
-            poolq.channels = p.output_channels;
-            poolq.input_h = p.output_h;
-            poolq.input_w = p.output_w;
-            int ph, pw;
-            if ((rc = fhip_pooling_output_dim(&poolq, &ph, &pw))) return rc;
-            pool_fast = fhip_conv_can_fuse_maxpool2(&p, algo_) != 0;
-            if (!pool_fast && (rc = pre_pool.resize((size_t)b->n * p.output_channels * p.output_h * p.output_w * sizeof(float)))) return rc;
-            rc = tops[0]->reshape(b->n, p.output_channels, ph, pw);
-        }
-        else
-            rc = tops[0]->reshape(b->n, p.output_channels, p.output_h, p.output_w);
-        if (rc) return rc;
-        if ((rc = fhip_conv_get_buffer_size(&p, algo_, b->n, &buffer_bytes, &packed_bytes))) return rc;
-        return fhip_conv_packed_layout(&p, algo_, &layout);
-    }
-    // filters and bias with the folded BatchNorm / Scale (fusion level 2) applied
-    void folded(std::vector<float>& w, std::vector<float>& b) const
-    {
-        w = w_host;
-        b = b_host;
-        fold.apply(w, b, p.output_channels);
-    }
-    int init_siblings(hipStream_t s)
-    {
-        std::vector<float> wa, ba, wb, bb;
-        folded(wa, ba);
-        sib->folded(wb, bb);
-        fhip_conv_param pa = p, pb = sib->p, both;
-        pa.bias_term = ba.empty() ? 0 : 1;
-        pb.bias_term = bb.empty() ? 0 : 1;
-        int rc = fhip_conv_siblings_geometry(&pa, &pb, &both);
-        if (rc) return rc;
-        wa.insert(wa.end(), wb.begin(), wb.end());
-        sib_has_bias = both.bias_term != 0;
-        if (sib_has_bias)
-        {
-            if (ba.empty()) ba.assign(p.output_channels, 0.f);
-            if (bb.empty()) bb.assign(sib->p.output_channels, 0.f);
-            ba.insert(ba.end(), bb.begin(), bb.end());
-            if ((rc = sib_bias.upload(ba.data(), ba.size(), s))) return rc;
-        }
-        size_t bytes = 0, pk = 0;
-        if ((rc = fhip_conv_get_buffer_size(&both, FHIP_IM2COL, bottoms[0]->n, &bytes, &pk))) return rc;
-        DeviceVec raw;
-        if ((rc = raw.upload(wa.data(), wa.size(), s))) return rc;
-        if ((rc = sib_packed.resize(pk))) return rc;
-        if ((rc = fhip_conv_init(&both, FHIP_IM2COL, sib_packed.d, raw.d, s))) return rc;
-        FHIP_CHECK_HIP(hipStreamSynchronize(s)); // `raw` goes out of scope
-        sib_packed_for = sib;
-        return 0;
-    }
-    int Init(hipStream_t s) override
-    {
-        if (pw)
-        {
-            const int rc = pw->Init(s);
-            if (rc) return rc;
-        }
-        if (sib && sib_packed_for != sib)
-        {
-            const int rc = init_siblings(s);
-            if (rc) return rc;
-        }
-        if (quant)
-        {
-            const int rc = qr.init(this, fold, s);
-            if (!rc && !fold.empty()) p.bias_term = 1;
-            return rc;
-        }
-        if (inited_algo == algo_ && packed.bytes == packed_bytes && inited_layout == layout) return 0;
-        std::vector<float> w, b;
-        folded(w, b);
-        if (!fold.empty()) p.bias_term = dilated.bias_term = 1;
-        int rc;
-        if (first_candidate() && (rc = first_raw.upload(w.data(), w.size(), s))) return rc; // 27 floats per output channel
-        if ((rc = algo_ == FHIP_NET_ROUTE_ATROUS  ? Dilated::init(this, atrous_api(), dilated, w, b, packed, packed_bytes, bias, s)
-                  : algo_ == FHIP_NET_ROUTE_GCONV ? Grouped::init(this, gconv_api(), p, w, b, packed, packed_bytes, bias, s)
-                                                  : init_packed(p, algo_, w, b, packed, packed_bytes, bias, s)))
-            return rc;
-        inited_algo = algo_;
-        inited_layout = layout;
-        return 0;
-    }
-    int Forward(hipStream_t s) override
-    {
-        if (quant) return qr.forward(this, s);
-        if (algo_ == FHIP_NET_ROUTE_ATROUS) return Dilated::forward(this, atrous_api(), dilated, packed, bias, s);
-        if (algo_ == FHIP_NET_ROUTE_GCONV) return Grouped::forward(this, gconv_api(), p, packed, bias, s);
-        const float* b = p.bias_term ? bias.d : nullptr;
-        if (head_of) return 0; // computed inside head_of's input transform
-        if (sib_of) return 0;  // computed by the layer before, in the same GEMM
-        if (sib)
-            return fhip_conv_forward_siblings(&p, &sib->p, bottoms[0]->n, tops[0]->data, sib->tops[0]->data, bottoms[0]->data, sib_packed.d,
-                                              sib_has_bias ? sib_bias.d : nullptr, s);
-        if (pw)
-        {
-            const float* pb = pw->p.bias_term ? pw->bias.d : nullptr;
-            if (pair_fast)
-                return fhip_conv_forward_dw_pw(&p, &pw->p, bottoms[0]->n, tops[0]->data, bottoms[0]->data, packed.d, b, pw->packed.d, pb, s);
-            int rc = fhip_conv_forward(&p, algo_, bottoms[0]->n, mid.d, bottoms[0]->data, packed.d, (float*)net->arena.d, b, s);
-            if (rc) return rc;
-            Blob dwout; // stand-in for the depthwise output the pair no longer has a blob for
-            dwout.n = bottoms[0]->n;
-            dwout.c = p.output_channels;
-            dwout.h = p.output_h;
-            dwout.w = p.output_w;
-            dwout.data = mid.d;
-            pw->bottoms.assign(1, &dwout);
-            pw->tops = tops;
-            rc = pw->Forward(s);
-            pw->bottoms.clear();
-            dwout.data = nullptr;
-            return rc;
-        }
-        if (chain_in || chain_next || head)
-        {
-            char* base = reinterpret_cast<char*>(net->arena.d);
-            float* v = reinterpret_cast<float*>(base + net->chain_slot[chain_pos & 1]);
-            float* vn = reinterpret_cast<float*>(base + net->chain_slot[(chain_pos + 1) & 1]);
-            float* m = reinterpret_cast<float*>(base + net->chain_m);
-            const float* in = chain_in || head ? nullptr : bottoms[0]->data;
-            const int n = bottoms[0]->n;
-            if (head)
-            {
-                const int rc = fhip_winograd_f63_input_from_first(&head->p, &p, n, v, head->bottoms[0]->data, head->first_raw.d,
-                                                                  head->p.bias_term ? head->bias.d : nullptr, s);
-                if (rc) return rc;
-            }
-            if (canvas || (chain_next && chain_next->canvas)) return forward_canvas(n, in, v, m, vn, b, s);
-            if (chain_next) return fhip_conv_forward_chained(&p, n, nullptr, in, packed.d, v, m, b, &chain_next->p, vn, fuse_pool ? 1 : 0, s);
-            if (!fuse_pool || pool_fast) return fhip_conv_forward_chained(&p, n, tops[0]->data, in, packed.d, v, m, b, nullptr, nullptr, fuse_pool ? 1 : 0, s);
-            const int rc = fhip_conv_forward_chained(&p, n, pre_pool.d, in, packed.d, v, m, b, nullptr, nullptr, 0, s);
-            if (rc) return rc;
-            return fhip_pooling(&poolq, n, tops[0]->data, pre_pool.d, s);
-        }
-        if (residual)
-        {
-            if (residual->alias) residual->data = residual->alias->data;
-            if (res_fast)
-                return fhip_conv_forward_residual(&p, algo_, bottoms[0]->n, tops[0]->data, bottoms[0]->data, packed.d, (float*)net->arena.d, b,
-                                                  residual->data, s);
-            fhip_conv_param q = p; // route without the fused epilogue: conv, then the add (+ReLU) in place on the top
-            q.activation = FHIP_ACT_NONE;
-            const int rc = fhip_conv_forward(&q, algo_, bottoms[0]->n, tops[0]->data, bottoms[0]->data, packed.d, (float*)net->arena.d, b, s);
-            if (rc) return rc;
-            return fhip_add(tops[0]->data, tops[0]->data, residual->data, tops[0]->count(), p.activation == FHIP_ACT_RELU, s);
-        }
-        if (!fuse_pool) return fhip_conv_forward(&p, algo_, bottoms[0]->n, tops[0]->data, bottoms[0]->data, packed.d, (float*)net->arena.d, b, s);
-        if (pool_fast)
-            return fhip_conv_forward_maxpool2(&p, algo_, bottoms[0]->n, tops[0]->data, bottoms[0]->data, packed.d, (float*)net->arena.d, b, s);
-        const int rc = fhip_conv_forward(&p, algo_, bottoms[0]->n, pre_pool.d, bottoms[0]->data, packed.d, (float*)net->arena.d, b, s);
-        if (rc) return rc;
-        return fhip_pooling(&poolq, bottoms[0]->n, tops[0]->data, pre_pool.d, s);
-    }
-    // One layer of a chained run that is, or is followed by, a canvas layer: input transform (a plain first layer only) -> tile GEMM on the
-    // geometry the layer runs with -> the boundary's form of the chained transform, or the canvas output transform at the end of the run.
-    int forward_canvas(int n, const float* in, float* v, float* m, float* vn, const float* b, hipStream_t s)
-    {
-        const CanvasApi* api = canvas_api();
-        if (!api) return FHIP_E_UNSUPPORTED; // message set by canvas_api
-        int rc;
-        if (in)
-        {
-            // plan_chains enters a canvas stretch through a chained boundary only: a layer that transforms its own input is plain
-            if (canvas) return failf(FHIP_E_UNSUPPORTED, "layer %s: a canvas layer takes its input from the chained transform before it", name.c_str());
-            if ((rc = fhip_winograd_f63_input_transform(&p, n, v, in, s))) return rc;
-        }
-        rc = canvas ? fhip_winograd_f63_tile_gemm(&canvas_p, n / 4, m, packed.d, v, s) : fhip_winograd_f63_tile_gemm(&p, n, m, packed.d, v, s);
-        if (rc) return rc;
-        if (chain_next)
-        {
-            const int form = !canvas ? FHIP_CANVAS_ENTRY : chain_next->canvas ? FHIP_CANVAS_INSIDE : FHIP_CANVAS_EXIT;
-            rc = api->chain(form, &p, &chain_next->p, n, &run_plan, &chain_next->run_plan, vn, m, b, s);
-        }
-        else
-            rc = api->output(&p, n, &run_plan, tops[0]->data, m, b, fuse_pool ? 1 : 0, s);
-        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
-    }
-    int Fuse(Layer* next, int level) override;
-    // absorb `elt` = Eltwise SUM of this layer's top and `other` (a blob produced earlier in the layer list)
-    bool FuseResidual(Blob* other)
-    {
-        if (pw)
-        {
-            // behind an absorbed 1x1 convolution (MobileNet-V2 style dw -> pw(linear) -> add): the add goes into the POINTWISE layer's
-            // epilogue; the pair then runs its two kernels one after the other (Reshape: pair_fast needs a pointwise layer without residual)
-            if (fuse_pool || residual || !pw->FuseResidual(other)) return false;
-            pw->bottoms.pop_back();   // the pointwise layer's bottoms are set per call (a stand-in for the depthwise output)
-            bottoms.push_back(other); // dependency scans look at THIS layer
-            return true;
-        }
-        if (gconv || atrous || quant || fuse_pool || residual || p.activation != FHIP_ACT_NONE) return false;
-        residual = other;
-        bottoms.push_back(other); // so that dependency scans (fusion, branch concurrency) see the second input
-        return true;
-    }
-    size_t weight_bytes() const override
-    {
-        return packed.bytes + bias.bytes + pre_pool.bytes + mid.bytes + first_raw.bytes + sib_packed.bytes + sib_bias.bytes + qr.bytes() + (pw ? pw->weight_bytes() : 0);
-    }
-    const fhip_conv_param* fused_pointwise(int* one_kernel) const override
-    {
-        if (one_kernel) *one_kernel = pair_fast ? 1 : 0;
-        return pw ? &pw->p : nullptr;
-    }
-    size_t arena_bytes() const override { return std::max(buffer_bytes, chain_bytes); }
-    const fhip_conv_param* conv_param() const override { return &p; }
-    int algo() const override { return quant ? FHIP_NET_ROUTE_QCONV : atrous ? FHIP_NET_ROUTE_ATROUS : gconv ? FHIP_NET_ROUTE_GCONV : algo_; }
-    int sibling_state() const override { return sib ? 1 : sib_of ? 2 : 0; }
-    int residual_state() const override { return !residual ? 0 : res_fast ? 1 : 2; }
-    void chain_state(int* v_from_previous, int* writes_next_v) const override
-    {
-        *v_from_previous = head ? 2 : chain_in ? 1 : 0;
-        *writes_next_v = head_of ? 2 : chain_next ? 1 : 0;
-    }
-    int canvas_state() const override { return canvas ? 1 : 0; }
 };
 
 // feather::InnerProductLayer, layers/inner_product_layer.h:28-171: y = W x + b, W [out][in].  On the device it is a
@@ -627,7 +21,7 @@ struct InnerProductLayer : Layer
     std::vector<float> w_host, b_host;
     DeviceVec packed, bias;
     size_t buffer_bytes = 0, packed_bytes = 0;
-    bool inited = false;
+    BuiltFor built; // never built again once done: the packed copy is shape independent
     // 8=int8_scale_term in a net with fhip_net_set_quantized: the 1x1 convolution over a 1x1 image runs through libfeather_qconv.so
     // (QuantRoute, route code FHIP_NET_ROUTE_QCONV) with the same ReLU fusion; the int8 weights stay int8 on the device
     bool quant = false;
@@ -670,10 +64,7 @@ struct InnerProductLayer : Layer
             return failf(NET_E_SHAPE, "In Layer %s: Bottom %s data size %zu is inconsistant with expected input size %zu.", name.c_str(), b->name.c_str(), per_image, input_size);
         if (quant)
         {
-            fhip_qconv_param& a = qr.q;
-            a.output_channels = p.output_channels, a.input_channels = p.input_channels;
-            a.input_h = a.input_w = a.kernel_h = a.kernel_w = a.stride_h = a.stride_w = a.group = 1;
-            a.bias_term = p.bias_term, a.activation = p.activation;
+            copy_geometry(qr.q, p); // a 1x1 convolution over a 1x1 image without padding, as LoadParam left p
             return qr.reshape(this);
         }
         int rc = tops[0]->reshape(b->n, (int)output_size, 1, 1);
@@ -683,11 +74,11 @@ struct InnerProductLayer : Layer
     int Init(hipStream_t s) override
     {
         if (quant) return qr.init(this, AffineFold(), s);
-        if (inited) return 0;
-        const int rc = init_packed(p, FHIP_IM2COL, w_host, b_host, packed, packed_bytes, bias, s);
+        if (built.done()) return 0;
+        const int rc = init_main(p, FHIP_IM2COL, w_host, b_host, packed, packed_bytes, bias, s);
         if (rc) return rc;
-        std::vector<float>().swap(w_host); // the packed copy is shape independent: the raw weights are not needed again
-        inited = true;
+        std::vector<float>().swap(w_host); // the raw weights are not needed again
+        built = BuiltFor{FHIP_IM2COL, 0, packed_bytes};
         return 0;
     }
     int Forward(hipStream_t s) override
@@ -983,6 +374,49 @@ bool AffineFold::absorb(const AffineLayer& nx, int K)
         add[k] = add[k] * nx.mul[k] + (nx.has_add ? nx.add[k] : 0.f);
     }
     return true;
+}
+
+int ConvLayer::Fuse(Layer* next, int level)
+{
+    if (ep.pw) return ep.pw->Fuse(next, level) == 1 ? 1 : 0; // behind the absorbed 1x1 convolution: its own fusions
+    if (ep.fuse_pool) return 0; // nothing is absorbed behind the pooling
+    if (side_epilogues_only() && !is_plain_relu(next) && !next->as_affine()) return 0;
+    if (level >= 2 && unclaimed() && next->type == "Convolution" && p.group == p.input_channels && p.group > 1 && p.group <= 256 && p.kernel_h == 3 &&
+        p.kernel_w == 3 && p.stride_h == p.stride_w && (p.stride_h == 1 || p.stride_h == 2) && p.pad_left == 1 && p.pad_top == 1)
+    {
+        // depthwise 3x3 (at most 256 channels: fhip_conv_can_fuse_dw_pw's structural conditions) -> 1x1 convolution: the pair becomes one
+        // layer -- one kernel where the shapes qualify too, else the two kernels one after the other inside this layer
+        // (a layer typed "Convolution" only, never "ConvolutionDepthWise": kept as found, the code gives no reason -- the group test below
+        // would turn every real depthwise layer away anyway)
+        const fhip_conv_param& q = next->as_conv()->p;
+        if (next->as_conv()->route != ROUTE_MAIN) return 0; // (a grouped one would fail the group test below anyway)
+        if (q.group != 1 || q.kernel_h != 1 || q.kernel_w != 1 || q.stride_h != 1 || q.stride_w != 1 || q.pad_left || q.pad_right || q.pad_top || q.pad_bottom)
+            return 0;
+        // fhip_conv_can_fuse_dw_pw's profitable range -- or the band-staged kernel's pair (32 channels, stride 1, a multiple of 64 output channels:
+        // MobileNet's first pair); the row width is only known at Reshape, where the pair falls back to its two kernels if it does not qualify
+        const bool band_pair = p.input_channels == 32 && p.stride_h == 1 && q.output_channels % 64 == 0 && q.output_channels <= 128; // = dwpw_band_applicable's bound
+        if (!band_pair && (q.output_channels <= 64 || q.output_channels >= (p.stride_h == 1 ? 160 : 400))) return 0;
+        return 2; // the pass hands `next` over (fuse_layers)
+    }
+    if (ep.residual && !is_plain_relu(next)) return 0; // behind the residual add only its ReLU
+    if (level >= 2 && next->as_pooling())
+    {
+        const fhip_pool_param& q = next->as_pooling()->q;
+        if (q.pooling_type != 0 || q.global_pooling || q.kernel_h != 2 || q.kernel_w != 2 || q.stride_h != 2 || q.stride_w != 2 || q.pad_left ||
+            q.pad_right || q.pad_top || q.pad_bottom)
+            return 0;
+        ep.poolq = q;
+        ep.fuse_pool = true;
+        return 1;
+    }
+    if (is_plain_relu(next))
+    {
+        p.activation = FHIP_ACT_RELU;
+        return 1;
+    }
+    // level 2 (beyond the reference): fold a following BatchNorm / Scale into the weights and bias
+    if (level >= 2 && p.activation == FHIP_ACT_NONE && next->as_affine()) return fold.absorb(*next->as_affine(), bias_channels()) ? 1 : 0;
+    return 0;
 }
 
 struct BatchNormLayer : AffineLayer
@@ -1386,53 +820,6 @@ struct LRNLayer : Layer
     int algo() const override { return FHIP_NET_ROUTE_LRN; }
 };
 
-int ConvLayer::Fuse(Layer* next, int level)
-{
-    if (pw) return pw->Fuse(next, level) == 1 ? 1 : 0; // behind the absorbed 1x1 convolution: its own fusions
-    if (fuse_pool) return 0; // nothing is absorbed behind the pooling
-    if ((gconv || atrous || quant) && !is_plain_relu(next) && !next->as_affine()) return 0; // the grouped, dilated and int8 routes have these epilogues only
-    if (level >= 2 && !residual && next->type == "Convolution" && p.group == p.input_channels && p.group > 1 && p.group <= 256 && p.kernel_h == 3 &&
-        p.kernel_w == 3 && p.stride_h == p.stride_w && (p.stride_h == 1 || p.stride_h == 2) && p.pad_left == 1 && p.pad_top == 1)
-    {
-        // depthwise 3x3 (at most 256 channels: fhip_conv_can_fuse_dw_pw's structural conditions) -> 1x1 convolution: the pair becomes one
-        // layer -- one kernel where the shapes qualify too, else the two kernels one after the other inside this layer
-        // (a layer typed "Convolution" only, never "ConvolutionDepthWise": kept as found, the code gives no reason -- the group test below
-        // would turn every real depthwise layer away anyway)
-        const fhip_conv_param& q = next->as_conv()->p;
-        if (next->as_conv()->atrous || next->as_conv()->quant) return 0;
-        if (q.group != 1 || q.kernel_h != 1 || q.kernel_w != 1 || q.stride_h != 1 || q.stride_w != 1 || q.pad_left || q.pad_right || q.pad_top || q.pad_bottom)
-            return 0;
-        // fhip_conv_can_fuse_dw_pw's profitable range -- or the band-staged kernel's pair (32 channels, stride 1, a multiple of 64 output channels:
-        // MobileNet's first pair); the row width is only known at Reshape, where the pair falls back to its two kernels if it does not qualify
-        const bool band_pair = p.input_channels == 32 && p.stride_h == 1 && q.output_channels % 64 == 0 && q.output_channels <= 128; // = dwpw_band_applicable's bound
-        if (!band_pair && (q.output_channels <= 64 || q.output_channels >= (p.stride_h == 1 ? 160 : 400))) return 0;
-        return 2; // the pass hands `next` over (fuse_layers)
-    }
-    if (residual && !is_plain_relu(next)) return 0; // behind the residual add only its ReLU
-    if (level >= 2 && next->as_pooling())
-    {
-        const fhip_pool_param& q = next->as_pooling()->q;
-        if (q.pooling_type != 0 || q.global_pooling || q.kernel_h != 2 || q.kernel_w != 2 || q.stride_h != 2 || q.stride_w != 2 || q.pad_left ||
-            q.pad_right || q.pad_top || q.pad_bottom)
-            return 0;
-        poolq = q;
-        fuse_pool = true;
-        return 1;
-    }
-    if (is_plain_relu(next))
-    {
-        p.activation = FHIP_ACT_RELU;
-        return 1;
-    }
-    // level 2 (beyond the reference): fold a following BatchNorm / Scale into the weights and bias
-    if (level >= 2 && p.activation == FHIP_ACT_NONE && next->as_affine())
-    {
-        const int K = atrous || quant ? p.output_channels : p.group == p.input_channels ? p.input_channels : p.output_channels;
-        return fold.absorb(*next->as_affine(), K) ? 1 : 0;
-    }
-    return 0;
-}
-
 // ncnn's Deconvolution / DeconvolutionDepthWise (no reference counterpart; the definition is include/feather_hip/feather_deconv.h).
 // Runs through libfeather_deconv.so (deconv_api) with route code FHIP_NET_ROUTE_DECONV.  Fuses a following ReLU and, at level 2,
 // BatchNorm / Scale (weights are [K][C/group][kh][kw], so the fold is the convolution's); it is no "Convolution" to any other fusion
@@ -1446,7 +833,7 @@ struct DeconvLayer : Layer
     AffineFold fold; // folded BatchNorm/Scale (fusion level 2)
     DeviceVec packed, bias;
     size_t buffer_bytes = 0, packed_bytes = 0;
-    bool inited = false;
+    BuiltFor built;
 
     DeconvLayer() { memset(&p, 0, sizeof(p)); }
 
@@ -1492,7 +879,7 @@ struct DeconvLayer : Layer
     }
     int LoadWeights(ModelBin& mb) override
     {
-        inited = false; // new weights: the packed form is rebuilt at the next Init
+        built = BuiltFor(); // new weights: the packed form is rebuilt at the next Init
         int rc = mb.load((size_t)weight_data_size, 0, w_host);
         if (rc) return rc;
         if (p.bias_term) rc = mb.load(p.output_channels, 1, b_host);
@@ -1509,12 +896,13 @@ struct DeconvLayer : Layer
     }
     int Init(hipStream_t s) override
     {
-        if (inited && packed.bytes == packed_bytes) return 0;
+        const BuiltFor want{FHIP_NET_ROUTE_DECONV, 0, packed_bytes};
+        if (built == want) return 0;
         std::vector<float> w = w_host, b = b_host;
         fold.apply(w, b, p.output_channels);
         if (!fold.empty()) p.bias_term = 1;
         const int rc = Route::init(this, deconv_api(), p, w, b, packed, packed_bytes, bias, s);
-        inited = inited || !rc;
+        if (!rc) built = want;
         return rc;
     }
     int Forward(hipStream_t s) override { return Route::forward(this, deconv_api(), p, packed, bias, s); }

@@ -142,7 +142,7 @@ static void collapse_gate_blocks(Net& net)
         if (l->type != "Convolution") return false; // not "ConvolutionDepthWise": kept as found (the group test below turns a real one away)
         ConvLayer* cv = l->as_conv();
         const fhip_conv_param& p = cv->p;
-        if (cv->gconv || cv->atrous || cv->quant || p.group != 1 || p.kernel_h != 1 || p.kernel_w != 1 || p.stride_h != 1 || p.stride_w != 1 || p.pad_left || p.pad_right ||
+        if (cv->route != ROUTE_MAIN || p.group != 1 || p.kernel_h != 1 || p.kernel_w != 1 || p.stride_h != 1 || p.stride_w != 1 || p.pad_left || p.pad_right ||
             p.pad_top || p.pad_bottom || p.activation != FHIP_ACT_NONE || !cv->fold.empty() || cv->w_host.size() != (size_t)p.input_channels * p.output_channels)
             return false;
         in = p.input_channels, out = p.output_channels, w = cv->w_host, b = cv->b_host, has_b = p.bias_term != 0;
@@ -296,7 +296,7 @@ static void fuse_layers(Net& net)
             if (nx->bottoms.size() != 1 || nx->tops.size() != 1) break;
             const int fr = cur->Fuse(nx, net.fusion);
             if (fr != 1 && fr != 2) break;
-            if (fr == 2) cur->as_conv()->pw.reset(net.layers[consumer].release()->as_conv()); // adopted, not dropped
+            if (fr == 2) cur->as_conv()->ep.pw.reset(net.layers[consumer].release()->as_conv()); // adopted, not dropped
             top->fused_away = true;
             cur->tops[0] = nx->tops[0];
             net.layers.erase(net.layers.begin() + consumer);
@@ -346,30 +346,30 @@ static int plan_chains(Net& net)
     const size_t L = net.layers.size();
     std::vector<ConvLayer*> conv(L, nullptr);
     for (size_t i = 0; i < L; ++i)
-        if ((conv[i] = net.layers[i]->as_conv()))
-        {
-            conv[i]->chain_next = conv[i]->head = conv[i]->head_of = nullptr;
-            conv[i]->chain_in = conv[i]->canvas = false;
-            conv[i]->chain_pos = 0;
-            conv[i]->chain_bytes = 0;
-        }
+        if ((conv[i] = net.layers[i]->as_conv())) conv[i]->chain.reset();
     for (auto& kv : net.blobs) kv.second->chained = false;
     for (auto& b : net.shadowed) b->chained = false; // blobs whose name a later top re-used (in-place style .param files) re-plan too
     net.chain_slot[0] = net.chain_slot[1] = net.chain_m = 0;
     if (net.fusion < 3) return 0;
-    auto plain = [](const ConvLayer* c) { return c && !c->pw && !c->residual && c->algo_ == FHIP_WINOGRADF63 && c->tops.size() == 1 && c->bottoms.size() == 1; };
+    // A layer of a run, or the consumer of a first layer.  Of the claims only the pair and the residual turn a layer away: a pooled boundary
+    // may be chained, the chain and head marks are this pass's own and being written (the scans below test the ones they mean), and the
+    // sibling plan is still the previous shape's -- plan_siblings runs behind this pass.
+    auto plain = [](const ConvLayer* c) {
+        return c && c->unclaimed(CLAIM_POOL | CLAIM_CHAIN | CLAIM_HEAD | CLAIM_SIBLING) && c->algo_ == FHIP_WINOGRADF63 && c->tops.size() == 1 && c->bottoms.size() == 1;
+    };
+    auto chain_away = [](Blob* b) {
+        b->chained = true;
+        b->drop_storage();
+    };
     for (size_t i = 0; i + 1 < L; ++i)
     {
         ConvLayer *a = conv[i], *b = conv[i + 1];
         if (!plain(a) || !plain(b) || b->bottoms[0] != a->tops[0]) continue;
-        if (a->fuse_pool && !a->pool_fast) continue;
+        if (a->ep.fuse_pool && !a->ep.pool_fast) continue;
         if (readers(net, a->tops[0], 0, true).count != 1) continue;
-        if (!fhip_conv_can_chain_winograd(&a->p, a->algo_, &b->p, b->algo_, a->fuse_pool ? 1 : 0)) continue;
-        a->chain_next = b;
-        b->chain_in = true;
-        b->chain_pos = a->chain_pos + 1;
-        a->tops[0]->chained = true;
-        a->tops[0]->drop_storage();
+        if (!fhip_conv_can_chain_winograd(&a->p, a->algo_, &b->p, b->algo_, a->ep.fuse_pool ? 1 : 0)) continue;
+        ChainPlan::link(a, b);
+        chain_away(a->tops[0]);
     }
     // 2x2 image canvases (feather_canvas.h): a maximal sub-run of chained layers on one plane size, entered through a pooled boundary, whose
     // planes are whole tiles as canvases (14 and 56 pixels: 0.69 x and 0.90 x the tiles) runs with four images of a channel per "image".
@@ -377,11 +377,11 @@ static int plan_chains(Net& net)
     for (size_t i = 0; i < L; ++i)
     {
         ConvLayer* c = conv[i];
-        if (!c || !c->chain_in || c->canvas) continue;
+        if (!c || !c->chain.in || c->chain.canvas) continue;
         ConvLayer* prev = nullptr;
         for (size_t j = 0; j < i; ++j)
-            if (conv[j] && conv[j]->chain_next == c) prev = conv[j];
-        if (!prev || prev->canvas || !prev->fuse_pool || prev->head) continue; // a sub-run starts behind a plain layer's pooled boundary
+            if (conv[j] && conv[j]->chain.next == c) prev = conv[j];
+        if (!prev || prev->chain.canvas || !prev->ep.fuse_pool || prev->chain.head) continue; // a sub-run starts behind a plain layer's pooled boundary
         const int n = c->bottoms[0]->n;
         fhip_conv_param q;
         if (fhip_winograd_f63_canvas_param(&prev->p, n, &q) == FHIP_OK) continue; // (never: a pooled consumer of a canvas plane is not one)
@@ -389,37 +389,33 @@ static int plan_chains(Net& net)
             prev->p.output_h != prev->p.output_w || prev->p.output_h != prev->p.input_h)
             continue;
         std::vector<ConvLayer*> run;
-        for (ConvLayer* x = c; x; x = x->chain_next)
+        for (ConvLayer* x = c; x; x = x->chain.next)
         {
             if (x->p.input_h != c->p.input_h || x->p.input_w != c->p.input_w || fhip_winograd_f63_canvas_param(&x->p, n, &q) != FHIP_OK) break;
             if (x->p.activation != FHIP_ACT_NONE && x->p.activation != FHIP_ACT_RELU) break;
             run.push_back(x);
-            if (x->fuse_pool) break; // the plane size changes behind it
+            if (x->ep.fuse_pool) break; // the plane size changes behind it
         }
         if (run.empty()) continue;
         ConvLayer* last = run.back();
         // the sub-run must be the whole stretch on this plane size, and leave through a form that exists: EXIT (pooled), or the end of the run
-        if (last->chain_next && !last->fuse_pool) continue;
-        if (!last->chain_next && last->fuse_pool && !last->pool_fast) continue;
+        if (last->chain.next && !last->ep.fuse_pool) continue;
+        if (!last->chain.next && last->ep.fuse_pool && !last->ep.pool_fast) continue;
         if (!canvas_api()) return FHIP_E_UNSUPPORTED; // message set by canvas_api
-        for (ConvLayer* x : run)
-        {
-            x->canvas = true;
-            (void)fhip_winograd_f63_canvas_param(&x->p, n, &x->canvas_p);
-        }
+        for (ConvLayer* x : run) x->chain.to_canvas(x->p, n);
     }
     // a first layer in front of a Winograd layer (VGG-16: conv1_1 -> conv1_2) is computed inside that layer's input transform
     for (size_t i = 0; i + 1 < L; ++i)
     {
         ConvLayer *a = conv[i], *b = conv[i + 1];
-        if (!a || a->atrous || a->quant || a->pw || a->residual || a->fuse_pool || a->chain_in || a->chain_next || a->tops.size() != 1 || a->bottoms.size() != 1) continue;
-        if (!a->first_candidate() || !plain(b) || b->chain_in || b->bottoms[0] != a->tops[0]) continue;
+        // on the main library (a grouped layer is no first_candidate) and unclaimed -- but for the head marks, which this scan never looked
+        // at, and the sibling plan, which is the previous shape's here
+        if (!a || a->route != ROUTE_MAIN || !a->unclaimed(CLAIM_HEAD | CLAIM_SIBLING) || a->tops.size() != 1 || a->bottoms.size() != 1) continue;
+        if (!a->first_candidate() || !plain(b) || b->chain.in || b->bottoms[0] != a->tops[0]) continue;
         if (readers(net, a->tops[0], 0, true).count != 1) continue;
         if (!fhip_conv_can_fuse_first_winograd(&a->p, &b->p, b->algo_, a->bottoms[0]->n)) continue;
-        a->head_of = b;
-        b->head = a;
-        a->tops[0]->chained = true;
-        a->tops[0]->drop_storage();
+        ChainPlan::absorb_first(a, b);
+        chain_away(a->tops[0]);
     }
     // blobs the previous plan had chained and this one did not: Reshape left them without storage
     auto restore = [](Blob* b) -> int {
@@ -434,22 +430,19 @@ static int plan_chains(Net& net)
         if (const int rc = restore(b.get())) return rc;
     auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     size_t slot[2] = {0, 0}, msz = 0;
-    for (size_t i = 0; i < L; ++i)
+    for (ConvLayer* c : conv)
     {
-        ConvLayer* c = conv[i];
-        if (!c || (!c->chain_in && !c->chain_next && !c->head)) continue;
-        fhip_winograd_plan pl;
-        const int rc = fhip_winograd_f63_plan_canvas(&c->p, c->bottoms[0]->n, c->canvas ? 2 : 1, &pl);
+        if (!c || !c->chain.runs()) continue;
+        const int rc = c->chain.plan_run(c->p, c->bottoms[0]->n);
         if (rc) return rc;
-        c->run_plan = pl;
-        slot[c->chain_pos & 1] = std::max(slot[c->chain_pos & 1], up(pl.v_bytes));
-        msz = std::max(msz, up(pl.m_bytes));
+        slot[c->chain.pos & 1] = std::max(slot[c->chain.pos & 1], up(c->chain.run_plan.v_bytes));
+        msz = std::max(msz, up(c->chain.run_plan.m_bytes));
     }
     net.chain_slot[0] = 0;
     net.chain_slot[1] = slot[0];
     net.chain_m = slot[0] + slot[1];
-    for (size_t i = 0; i < L; ++i)
-        if (conv[i] && (conv[i]->chain_in || conv[i]->chain_next || conv[i]->head)) conv[i]->chain_bytes = slot[0] + slot[1] + msz;
+    for (ConvLayer* c : conv)
+        if (c && c->chain.runs()) c->chain.arena(slot[0] + slot[1] + msz);
     return 0;
 }
 
@@ -462,33 +455,25 @@ static int plan_siblings(Net& net)
     // layers typed "Convolution" only: a "ConvolutionDepthWise" layer never becomes a sibling.  Kept as found -- the code gives no reason
     // (fhip_conv_can_fuse_siblings has its own tests of the geometry)
     for (size_t i = 0; i < L; ++i)
-        if (net.layers[i]->type != "ConvolutionDepthWise" && (conv[i] = net.layers[i]->as_conv())) conv[i]->sib = conv[i]->sib_of = nullptr;
+        if (net.layers[i]->type != "ConvolutionDepthWise" && (conv[i] = net.layers[i]->as_conv())) conv[i]->sibs.reset();
     if (net.fusion < 2) return 0;
     auto root = [](const Blob* b) { return b->alias ? b->alias : b; };
-    auto plain = [](const ConvLayer* c) {
-        return c && !c->pw && !c->residual && !c->fuse_pool && !c->chain_in && !c->chain_next && !c->head && !c->head_of && !c->sib && !c->sib_of &&
-               c->algo_ == FHIP_IM2COL && c->tops.size() == 1 && c->bottoms.size() == 1;
-    };
-    for (size_t i = 0; i + 1 < L; ++i)
-    {
-        ConvLayer *a = conv[i], *b = conv[i + 1];
-        if (!plain(a) || !plain(b) || root(a->bottoms[0]) != root(b->bottoms[0]) || a->tops[0] == b->tops[0]) continue;
+    auto plain = [](const ConvLayer* c) { return c && c->unclaimed() && c->algo_ == FHIP_IM2COL && c->tops.size() == 1 && c->bottoms.size() == 1; };
+    auto pairs = [&](const ConvLayer* a, const ConvLayer* b) {
+        if (!plain(a) || !plain(b) || root(a->bottoms[0]) != root(b->bottoms[0]) || a->tops[0] == b->tops[0]) return false;
         // both layers on the 128-row tile when alone (a 64-row layer -- ResNet's res2a_branch2a -- is faster on its own 64 x 128 tile:
         // tools/sibling_bench.py 116 vs 126 us for the pair)
-        if (a->p.output_channels <= 64 || b->p.output_channels <= 64) continue;
-        if (!fhip_conv_can_fuse_siblings(&a->p, a->algo_, &b->p, b->algo_, a->bottoms[0]->n)) continue;
-        a->sib = b;
-        b->sib_of = a;
-    }
-    // a pair that a new shape un-planned keeps no stacked copy of its filters (the layers' own packed weights stay -- they are what
-    // the pair falls back to, and what Extract-driven level changes run)
+        if (a->p.output_channels <= 64 || b->p.output_channels <= 64) return false;
+        return fhip_conv_can_fuse_siblings(&a->p, a->algo_, &b->p, b->algo_, a->bottoms[0]->n) != 0;
+    };
+    // a layer's partner is the next one or none, so layer i's part of the plan is settled once this loop has looked at (i, i + 1)
     for (size_t i = 0; i < L; ++i)
-        if (conv[i] && !conv[i]->sib && conv[i]->sib_packed.bytes)
-        {
-            conv[i]->sib_packed.release();
-            conv[i]->sib_bias.release();
-            conv[i]->sib_packed_for = nullptr;
-        }
+    {
+        if (i + 1 < L && pairs(conv[i], conv[i + 1]))
+            SiblingPlan::pair(conv[i], conv[i + 1]);
+        else if (conv[i])
+            conv[i]->sibs.unpaired();
+    }
     return 0;
 }
 
