@@ -40,7 +40,9 @@ class GraphBuilder:
         """dry=True: build the .param only and count the .bin bytes (``nbytes``) without drawing any weights.
         quant: None writes fp32 layers; a dict {layer name: input scale} makes conv() and fc() write int8 layers (param 8=1: int8-tagged
         weights quantised per output channel, the bias, the weight scales, one input scale; a name the dict lacks gets QUANT_DEFAULT_SCALE).
-        The weights drawn are those of the fp32 build with the same seed.  A net that holds such a layer needs Net.SetQuantized(True)."""
+        The weights drawn are those of the fp32 build with the same seed.  A net that holds such a layer needs Net.SetQuantized(True).
+        conv(), fc() and se_block() take a `quant=` of their own for ONE layer of an otherwise fp32 (or int8) net: None keeps the build's
+        setting, False writes fp32, True int8 at QUANT_DEFAULT_SCALE, a number int8 at that input scale."""
         self.quant = quant
         self.trace = None  # a list: conv / fc / relu / bn / scale / pool record themselves for numpy_forward (input_scales)
         self.rng = np.random.default_rng(seed)
@@ -74,9 +76,17 @@ class GraphBuilder:
         if self.trace is not None:
             self.trace.append(op)
 
-    def _weights(self, name, w, cout, b):
-        """The .bin of a conv / fc layer: tagged fp32 weights and the raw bias, or the int8 form (see __init__)."""
-        if self.quant is None:
+    def _scale_of(self, name, quant):
+        """The int8 input scale of layer `name`, or None for a fp32 layer: the layer's own `quant=` where it gives one, else the build's."""
+        if quant is None:
+            return None if self.quant is None else self.quant.get(name, QUANT_DEFAULT_SCALE)
+        if quant is False:
+            return None
+        return QUANT_DEFAULT_SCALE if quant is True else float(quant)
+
+    def _weights(self, name, w, cout, b, s_in=None):
+        """The .bin of a conv / fc layer: tagged fp32 weights and the raw bias, or (with an input scale `s_in`) the int8 form (see __init__)."""
+        if s_in is None:
             self._tagged(w)
             if b is not None:
                 self._raw(b)
@@ -90,7 +100,7 @@ class GraphBuilder:
         if b is not None:
             self._raw(b)
         self._raw(s_w)
-        self._raw(1 if self.dry else np.array([self.quant.get(name, QUANT_DEFAULT_SCALE)], np.float32))
+        self._raw(1 if self.dry else np.array([s_in], np.float32))
 
     def _uniform(self, n, lo, hi, scale=None):
         if self.dry:
@@ -102,19 +112,20 @@ class GraphBuilder:
     def input(self, name, c, h, w):
         return self.layer("Input", name, [], [name], {0: w, 1: h, 2: c})
 
-    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None, dilation=1, gain=1.0):
+    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None, dilation=1, gain=1.0, quant=None):
         fan_in = cin // group * k * k
         wsize = cout * (cin // group) * k * k
         type_ = type_ or ("ConvolutionDepthWise" if group > 1 else "Convolution")  # what ncnn's converter writes; both load alike
         params = {0: cout, 1: k, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group}
         if dilation != 1:  # ncnn's id 2 (written only when set); a net that holds one needs Net.SetDilated(True)
             params = {0: cout, 1: k, 2: dilation, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group}
-        if self.quant is not None:
+        s_in = self._scale_of(name, quant)
+        if s_in is not None:
             params[8] = 1
         top = self.layer(type_, name, [bottom], [top or name], params)
         w = self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in) * gain)
         b = self._uniform(cout, -0.1, 0.1) if bias else None
-        self._weights(name, w, cout, b)
+        self._weights(name, w, cout, b, s_in)
         if self.trace is not None:
             self._note("conv", name, bottom, top, dict(w=w.reshape(cout, cin // group, k, k), b=b, s=s, p=p, group=group))
         return top
@@ -182,14 +193,15 @@ class GraphBuilder:
         self._note("pool", name, bottom, name, dict(k=k, s=s, p=p, avg=avg, global_=global_))
         return self.layer("Pooling", name, [bottom], [name], {0: int(avg), 1: k, 2: s, 3: p, 4: int(global_)})
 
-    def fc(self, name, bottom, cin, cout, bias=True, gain=1.0):
+    def fc(self, name, bottom, cin, cout, bias=True, gain=1.0, quant=None):
         params = {0: cout, 1: int(bias), 2: cin * cout}
-        if self.quant is not None:
+        s_in = self._scale_of(name, quant)
+        if s_in is not None:
             params[8] = 1
         top = self.layer("InnerProduct", name, [bottom], [name], params)
         w = self._uniform(cin * cout, -1, 1, np.sqrt(6.0 / cin) * gain)
         b = self._uniform(cout, -0.1, 0.1) if bias else None
-        self._weights(name, w, cout, b)
+        self._weights(name, w, cout, b, s_in)
         if self.trace is not None:
             self._note("fc", name, bottom, top, dict(w=w.reshape(cout, cin), b=b))
         return top
@@ -252,23 +264,24 @@ class GraphBuilder:
         """ncnn's Scale 0=-233 with two bottoms: the scale comes from the second one (Caffe's two-bottom Scale, SENet's multiply)."""
         return self.layer("Scale", name, [bottom, gate], [name], {0: -233})
 
-    def se_block(self, name, bottom, c, r, spelling="caffe", mact="relu", gact="sigmoid", alpha=0.2, beta=0.5, gate_first=False, gain=1.0):
+    def se_block(self, name, bottom, c, r, spelling="caffe", mact="relu", gact="sigmoid", alpha=0.2, beta=0.5, gate_first=False, gain=1.0, quant=(None, None)):
         """A squeeze-and-excitation block on `bottom` ([c] channels, reduction to r): Split, global average Pooling, two dense layers with
         `mact` ("relu", "swish" or None) between them, `gact` ("sigmoid" or "hard_sigmoid"), and the multiply.  spelling "caffe":
         InnerProduct layers and Scale 0=-233 (SENet as published); "converter": 1x1 Convolution layers and BinaryOp mul (what ncnn's
         converters write for EfficientNet and RegNetY).  gate_first puts the gate first among BinaryOp's bottoms.  `gain` scales the first dense layer's
         weights: the gate's logits scale with the squeezed activations, and a net whose activations grow with depth passes the inverse of
-        that growth, so that the logits stay of order one as in a trained net and the gate does not saturate.  Returns the gated top."""
+        that growth, so that the logits stay of order one as in a trained net and the gate does not saturate.  `quant` = the `quant=` of the
+        first and of the second dense layer (see __init__).  Returns the gated top."""
         keep, sq = self.split(name + "_split", bottom)
         g = self.pool(name + "_gap", sq, 1, 1, avg=True, global_=True)
-        dense = (lambda nm, x, i, o, gain=1.0: self.fc(nm, x, i, o, gain=gain)) if spelling == "caffe" else \
-                (lambda nm, x, i, o, gain=1.0: self.conv(nm, x, i, o, 1, type_="Convolution", gain=gain))
-        g = dense(name + ("_fc1" if spelling == "caffe" else "_conv1"), g, c, r, gain)
+        dense = (lambda nm, x, i, o, gain=1.0, quant=None: self.fc(nm, x, i, o, gain=gain, quant=quant)) if spelling == "caffe" else \
+                (lambda nm, x, i, o, gain=1.0, quant=None: self.conv(nm, x, i, o, 1, type_="Convolution", gain=gain, quant=quant))
+        g = dense(name + ("_fc1" if spelling == "caffe" else "_conv1"), g, c, r, gain, quant[0])
         if mact == "relu":
             g = self.relu(name + "_relu", g)
         elif mact == "swish":
             g = self.swish(name + "_swish", g)
-        g = dense(name + ("_fc2" if spelling == "caffe" else "_conv2"), g, r, c)
+        g = dense(name + ("_fc2" if spelling == "caffe" else "_conv2"), g, r, c, quant=quant[1])
         g = self.sigmoid(name + "_sigmoid", g) if gact == "sigmoid" else self.hard_sigmoid(name + "_hsigmoid", g, alpha, beta)
         if spelling == "caffe":
             return self.scale_by(name + "_scale", keep, g)

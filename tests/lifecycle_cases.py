@@ -182,7 +182,7 @@ def deep_model():
 
 
 def shape_of(key):
-    return SHAPES[key] if key in SHAPES else DEEP_SHAPES[key]
+    return SHAPES[key] if key in SHAPES else DEEP_SHAPES[key] if key in DEEP_SHAPES else MIXED_SHAPES[key]
 
 
 def input(key, variant=0):
@@ -270,6 +270,80 @@ WALK_DEEP = [
 ]
 
 WALKS = {"cycle": WALK_CYCLE, "routes": WALK_ROUTES, "setters": WALK_SETTERS, "graph": WALK_GRAPH, "replicas": WALK_REPLICAS, "deep": WALK_DEEP}
+
+
+# ---- a third model: int8 layers among fp32 ones ---------------------------------------------------------------------------------------
+# (3 input channels, at most 128 anywhere; Net.SetQuantized)  What is checked after every Forward is the fresh-net invariant above, bit for bit,
+# and every int8 layer against its restatement from the device's own bottom blob (tests/qseam_ref.py); the fp32 layers against float64
+# from there.
+#
+#   data -> conv0 (3 -> 16, 3x3 p1, fp32) + ReLU                            a fp32 first layer in front of an int8 layer: never absorbed
+#        -> q1 (16 -> 32) + ReLU -> q2 (32 -> 32) + ReLU + 2x2 max pool     an int8 3x3 run; the pooling stays a layer
+#        -> qdw (depthwise 3x3, 32) + ReLU -> qpw (32 -> 72, 1x1) + ReLU    an int8 depthwise + 1x1 pair (72: inside the fp32 pair's range)
+#        -> qbn (72 -> 64, 3x3 p1) + BatchNorm + Scale + ReLU                the level-2 fold into d[] and the bias
+#        -> Split -> qa (64 -> 64, 1x1, int8)
+#                 -> fb (64 -> 64, 3x3 p1, fp32) + Eltwise with qa + ReLU    the fp32 branch takes the add with the int8 branch's top
+#        -> global average pooling -> out (InnerProduct 64 -> 10, int8)
+MIXED_SHAPES = {
+    "m16b4": (4, 3, 16, 16), "m16b5": (5, 3, 16, 16), "m16b1": (1, 3, 16, 16), "m12b4": (4, 3, 12, 12), "modd4": (4, 3, 13, 21),
+    "m16b7": (7, 3, 16, 16), "m16b2": (2, 3, 16, 16), "m12b1": (1, 3, 12, 12), "m12b7": (7, 3, 12, 12),
+}
+MIXED_INT8 = ("q1", "q2", "qdw", "qpw", "qbn", "qa", "out")
+MIXED_OUTPUTS = ("out", "sum_relu")
+MIXED_SHIFT = 3.0
+MIXED_FP32 = ("conv0", "relu0", "fb", "sum", "sum_relu")  # the convolution planes float64 is the yardstick of: they keep PLANE_FLOOR
+
+
+def mixed_model():
+    """-> (param, weights, input name, outputs)."""
+    if "x" not in _MODEL:
+        g = model_zoo.GraphBuilder(SEED + 2)
+        x = g.input("data", 3, 16, 16)
+        x = g.relu("relu0", g.conv("conv0", x, 3, 16, 3, 1, 1))
+        x = g.relu("relu1", g.conv("q1", x, 16, 32, 3, 1, 1, quant=True))
+        x = g.relu("relu2", g.conv("q2", x, 32, 32, 3, 1, 1, quant=True))
+        x = g.pool("pool2", x, 2, 2)
+        x = g.relu("qdw_relu", g.conv("qdw", x, 32, 32, 3, 1, 1, group=32, quant=True))
+        x = g.relu("qpw_relu", g.conv("qpw", x, 32, 72, 1, quant=True))
+        x = g.conv("qbn", x, 72, 64, 3, 1, 1, quant=True)
+        x = g.relu("qbn_relu", g.scale("qbn_scale", g.bn("qbn_bn", x, 64), 64))
+        ta, tb = g.split("trunk", x)
+        a = g.conv("qa", ta, 64, 64, 1, quant=True)
+        fb = g.conv("fb", tb, 64, 64, 3, 1, 1)
+        # no plane behind the sum's ReLU may die (see the module docstring): the fp32 branch's biases, the last 64 floats written, lift every
+        # channel of the sum by MIXED_SHIFT, one and a half of its standard deviations (the global average behind it sums values >= 0)
+        g.bin[-4 * 64:] = (np.frombuffer(bytes(g.bin[-4 * 64:]), "<f4") + np.float32(MIXED_SHIFT)).astype("<f4").tobytes()
+        x = g.relu("sum_relu", g.eltwise("sum", fb, a))
+        x = g.pool("gap", x, 1, 1, avg=True, global_=True)
+        g.fc("out", x, 64, 10, quant=True)
+        _MODEL["x"] = g.finish() + ("data", MIXED_OUTPUTS)
+    return _MODEL["x"]
+
+
+# batches 4 -> 5 -> 1 -> 4; planes 16 -> 12 -> 13 x 21 and back; the three setters flipped between Forwards; graph on with a feed of a new
+# shape; use_current_stream
+WALK_MIXED = [
+    ("feed", "m16b4"), ("forward", 1), ("feed", "m16b5"), ("forward", 1), ("feed", "m16b1"), ("forward", 1), ("feed", "m16b4", 1), ("forward", 1),
+    ("feed", "m12b4"), ("forward", 1), ("feed", "modd4"), ("forward", 1), ("feed", "m16b4"), ("forward", 1),
+    ("set_tuned", True), ("forward", 1), ("set_concurrency", True), ("forward", 1), ("set_graph", True), ("forward", 2),
+    ("feed", "m12b4", 1), ("forward", 2), ("feed", "modd4", 1), ("forward", 1),
+    ("set_graph", False), ("set_tuned", False), ("set_concurrency", False), ("forward", 1),
+    ("stream",), ("forward", 2), ("feed", "m16b5", 1), ("forward", 1),
+]
+# sub_batches = 3 at batches 7, 2 and 1 (one replica, then two, get no image), a new size while they sit out, and all back
+WALK_MIXED_REPLICAS = [
+    ("feed", "m16b7"), ("forward", 1), ("feed", "m16b2"), ("forward", 1), ("feed", "m16b1"), ("forward", 1),
+    ("feed", "m12b1"), ("forward", 1), ("feed", "m12b7"), ("forward", 1), ("feed", "m16b7", 1), ("forward", 2),
+]
+MIXED_WALKS = {"mixed": WALK_MIXED, "mixed_replicas": WALK_MIXED_REPLICAS}
+
+
+def mixed_table():
+    """[(walk name, fusion level, Net keywords)]: the mixed walk at the five settings of LEVELS; the replica walk at levels 2 and 3 + tuned,
+    with and without graph."""
+    rows = [("mixed", lv, dict(kw)) for lv, kw in LEVELS]
+    rows += [("mixed_replicas", lv, dict(kw, sub_batches=3, **g)) for lv, kw in ((2, {}), (3, {"tuned": True})) for g in ({}, {"graph": True})]
+    return rows
 
 
 def setting_id(level, kw):

@@ -1,7 +1,8 @@
 """The table of two-layer seams: every net `Input -> P -> C` with P from PRODUCERS and C from CONSUMERS, and what feather::Net's planner
 must do at that seam (tests/test_seams_cpu.py, tests/test_seams_gpu.py).
 
-Shapes: 12 channels (divisible by 2, 3 and 4; slices as 5 + 7), the planes 11 x 9 (odd, W % 4 != 0) and 12 x 8 (W % 4 == 0), batch 3, then
+Shapes: 12 channels (divisible by 2, 3 and 4; slices as 5 + 7; `Build(c0=...)` builds the same nets on another count for
+tests/qseam_cases.py), the planes 11 x 9 (odd, W % 4 != 0) and 12 x 8 (W % 4 == 0), batch 3, then
 batch 1 through the same handle.  Inputs are normal(0, 1); weights are GraphBuilder's (He-uniform times `gain`), biases non-zero.
 
 A layer with two bottoms takes its other operand from the input through a 1x1 convolution (`branch`), written BEFORE P in the layer list
@@ -58,8 +59,9 @@ class Build:
     """One pass over a case.  The first pass is dry: it counts the taps of the input and notes the branches C asks for, whose shapes follow
     from P's top; the second writes Input, the Split of the input, the branches, P and C in that order."""
 
-    def __init__(self, plane, seed, plan=None):
+    def __init__(self, plane, seed, plan=None, c0=C0):
         self.h0, self.w0 = plane
+        self.c0 = c0  # the channel count of the input and of every full-width layer (tests/qseam_cases.py builds the same nets on 16)
         self.plan = plan
         self.g = model_zoo.GraphBuilder(seed, dry=plan is None)
         self.taps, self.requests, self.made = 0, [], {}
@@ -79,7 +81,7 @@ class Build:
         self.p_scale = 1.0  # the magnitude of P's top where it is far from one (Softmax): a Concat's other operand is scaled to match
 
     def start(self):
-        data = self.g.input("data", C0, self.h0, self.w0)
+        data = self.g.input("data", self.c0, self.h0, self.w0)
         if self.plan is None:
             return
         self.tap_tops = [data] if self.plan.taps <= 1 else list(self.g.split("tap", data, self.plan.taps))
@@ -94,10 +96,10 @@ class Build:
         kind, c, h, w, gain = spec
         x = self.tap()
         if kind == "gate":  # [n][c][1][1] in (0, 1)
-            y = self.g.conv(f"br{i}", x, C0, c, 1)
+            y = self.g.conv(f"br{i}", x, self.c0, c, 1)
             return self.g.sigmoid(f"br{i}_sig", self.g.pool(f"br{i}_gap", y, 1, 1, avg=True, global_=True))
         s = 1 if (h, w) == (self.h0, self.w0) else 2
-        return self.g.conv(f"br{i}", x, C0, c, 1, s, gain=gain)
+        return self.g.conv(f"br{i}", x, self.c0, c, 1, s, gain=gain)
 
     def branch(self, kind, c, h=1, w=1, gain=1.0):
         """The other operand of a two-bottom consumer: a blob of shape (c, h, w) ("conv") or a gate (c, 1, 1) ("gate") from the input."""
@@ -112,9 +114,10 @@ class Build:
 
 
 # ---- layers with one bottom, usable on both sides: fn(b, name, x, (c, h, w)) -> (top, (c, h, w)) ----------------------------------------
-def _conv(k, s, p, group=None, dilation=1, cout=C0):
-    def fn(b, n, x, shp):
+def _conv(k, s, p, group=None, dilation=1, cout=None):
+    def fn(b, n, x, shp, cout=cout):
         c, h, w = shp
+        cout = cout or b.c0
         grp = {None: 1, "dw": c}.get(group, group)
         _need(group == "dw" or (c % grp == 0 and cout % grp == 0))
         ko = c if group == "dw" else cout
@@ -127,7 +130,7 @@ def _conv(k, s, p, group=None, dilation=1, cout=C0):
 def _deconv(dw):
     def fn(b, n, x, shp):
         c, h, w = shp
-        return b.g.deconv(n, x, c, c if dw else C0, 4, 2, 1, group=c if dw else 1), (c if dw else C0, 2 * h, 2 * w)
+        return b.g.deconv(n, x, c, c if dw else b.c0, 4, 2, 1, group=c if dw else 1), (c if dw else b.c0, 2 * h, 2 * w)
     return fn
 
 
@@ -149,7 +152,7 @@ def _same(make):
 def _slice2(b, n, x, shp):
     c, h, w = shp
     _need(c >= 2)
-    first = 5 if c == 12 else c // 2
+    first = 5 if c == b.c0 else c // 2
     return b.g.slice(n, x, [first, c - first])[1], (c - first, h, w)  # the second piece: a non-zero channel offset
 
 
@@ -171,11 +174,11 @@ def _ip(b, n, x, shp):
     # of large float32 partial sums.  A plane here is ONE value and plane_nerr its relative error: at gain 1 a value at the floor of
     # 1e-3 of the maximum carries the rounding of a 1188-term float32 sum a thousand times enlarged, beyond 1e-4 whatever the kernel.
     # A wrong weight still moves the value by several per cent.  It also keeps |y| below 2.5, where a HardSigmoid behind it clamps.
-    top = b.g.fc(n, x, c * h * w, C0, gain=0.01)
-    if b.positive_bias and n == "p" and not b.g.dry:  # the biases are the last C0 floats written: U(-0.1, 0.1) -> 0.05 + |U|
-        bias = np.frombuffer(bytes(b.g.bin[-4 * C0:]), "<f4")
-        b.g.bin[-4 * C0:] = (np.abs(bias) + np.float32(0.05)).astype("<f4").tobytes()
-    return top, (C0, 1, 1)
+    top = b.g.fc(n, x, c * h * w, b.c0, gain=0.01)
+    if b.positive_bias and n == "p" and not b.g.dry:  # the biases are the last c0 floats written: U(-0.1, 0.1) -> 0.05 + |U|
+        bias = np.frombuffer(bytes(b.g.bin[-4 * b.c0:]), "<f4")
+        b.g.bin[-4 * b.c0:] = (np.abs(bias) + np.float32(0.05)).astype("<f4").tobytes()
+    return top, (b.c0, 1, 1)
 
 
 def _softmax(b, n, x, shp):
@@ -205,24 +208,24 @@ CONVS = ("conv3x3", "conv1x1", "conv3x3s2", "conv5x5", "dw3x3", "gconv3", "dil3x
 
 # ---- producers: fn(b) -> (top, shape) ------------------------------------------------------------------------------------------------------
 def _p_unary(op):
-    return lambda b: UNARY[op](b, "p", b.tap(), (C0, b.h0, b.w0))
+    return lambda b: UNARY[op](b, "p", b.tap(), (b.c0, b.h0, b.w0))
 
 
 def _p_input(b):
-    return b.tap(), (C0, b.h0, b.w0)
+    return b.tap(), (b.c0, b.h0, b.w0)
 
 
 def _p_eltsum(b):
     # the operand written last is no convolution: one would take the add into its epilogue at level 2 and P would be no Eltwise layer
-    a = b.g.conv("p_a", b.tap(), C0, C0, 1)
+    a = b.g.conv("p_a", b.tap(), b.c0, b.c0, 1)
     c = b.g.tanh("p_b", b.tap())
-    return b.g.eltwise("p", a, c), (C0, b.h0, b.w0)
+    return b.g.eltwise("p", a, c), (b.c0, b.h0, b.w0)
 
 
 def _p_concat(b):
-    a = b.g.conv("p_a", b.tap(), C0, 5, 1)
-    c = b.g.conv("p_b", b.tap(), C0, 7, 1)
-    return b.g.concat("p", [a, c]), (C0, b.h0, b.w0)
+    a = b.g.conv("p_a", b.tap(), b.c0, 5, 1)
+    c = b.g.conv("p_b", b.tap(), b.c0, b.c0 - 5, 1)
+    return b.g.concat("p", [a, c]), (b.c0, b.h0, b.w0)
 
 
 PRODUCERS = {"input": _p_input, "eltsum": _p_eltsum, "concat": _p_concat}

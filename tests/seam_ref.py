@@ -24,6 +24,11 @@ mathematics of its own -- and rounds every blob to float32 as they do.  Where tw
 
 The .bin is read by gate_ref.Net (inorm_ref.Net's reader, with a two-bottom Scale reading nothing); the .param by
 shuffle_ref.parse_param (oracle.netcheck.parse_param plus ncnn's array params).
+
+An int8 layer (8=int8_scale_term: tests/qseam_ref.py) is no float64 operation.  The reader steps over it -- the int8 tag, the bytes padded
+to 4, then the bias, K weight scales and one input scale, as qconv_ref._Bin reads them -- and keeps what it read in `Net.q`; `run` takes
+such a layer's top from `given` (a dict of blobs; a layer ALL of whose tops are given is skipped, whatever its type) and refuses to run
+without it.  Without `given` and without int8 layers everything is as it was.
 """
 from __future__ import annotations
 
@@ -52,19 +57,61 @@ def _gated(type_, bottoms, pd):
     return type_ == "Scale" and pd.get(0, 0) == -233 and len(bottoms) == 2
 
 
+QUANT_TYPES = ("Convolution", "ConvolutionDepthWise", "InnerProduct")
+
+
+def is_int8(layer):
+    return layer[0] in QUANT_TYPES and layer[4].get(8, 0) != 0
+
+
 class Net:
     def __init__(self, param: bytes, weights: bytes):
         self.layers = shuffle_ref.parse_param(param)
-        reader = gate_ref.Net(param, weights)
-        self.w, self.read = reader.w, reader.read
+        self.q = {}
+        if not any(is_int8(layer) for layer in self.layers):
+            reader = gate_ref.Net(param, weights)
+            self.w, self.read = reader.w, reader.read
+            return
+        # layer by layer: gate_ref.Net reads the fp32 layers (one one-layer net each, from where the last one stopped), this one the int8 ones
+        import qconv_ref
+        rows = param.decode().splitlines()[2:]
+        assert len(rows) == len(self.layers)
+        self.w, self.read = {}, 0
+        for row, layer in zip(rows, self.layers):
+            type_, name, _, _, pd = layer
+            if not is_int8(layer):
+                reader = gate_ref.Net(f"7767517\n1 1\n{row}\n".encode(), memoryview(weights)[self.read:])
+                self.w.update(reader.w)
+                self.read += reader.read
+                continue
+            rd = qconv_ref._Bin(weights)
+            rd.at = self.read
+            if type_ == "InnerProduct":
+                k, bias_term, kh, kw, group = pd.get(0, 0), pd.get(1, 0), 1, 1, 1
+                cg = pd.get(2, 0) // k
+            else:
+                k, kw, bias_term, group = pd.get(0, 0), pd.get(1, 0), pd.get(5, 0), pd.get(7, 1)
+                kh = pd.get(11, kw)
+                cg = pd.get(6, 0) // (k * kh * kw)
+            wq = rd.int8(k * cg * kh * kw).reshape(k, cg, kh, kw)
+            b = rd.raw(k) if bias_term else None
+            self.q[name] = dict(wq=wq, b=b, s_w=rd.raw(k), s_in=rd.raw(1)[0], group=group)
+            self.read = rd.at
 
-    def run(self, input_name: str, x: np.ndarray, output_name: str = None, keep: bool = False):
+    def run(self, input_name: str, x: np.ndarray, output_name: str = None, keep: bool = False, given: dict = None):
         from oracle.netcheck import PortNet
         blobs = {input_name: np.ascontiguousarray(x, np.float32)}
+        given = given or {}
         for layer in self.layers:
             type_, name, bottoms, tops, pd = layer
             if type_ == "Input":
                 continue
+            if tops and all(t in given for t in tops):
+                for t in tops:
+                    blobs[t] = given[t]
+                continue
+            if is_int8(layer):
+                raise RuntimeError(f"int8 layer {name} is not restated in float64: its top must be given")
             a = blobs[bottoms[0]]
             if type_ == "Split":
                 for t in tops:

@@ -176,3 +176,59 @@ def test_packed_layout_tells_apart_what_the_byte_count_does_not():
     assert len({query(64, 128, 1, 0, s, s, IM2COL) for s in (14, 8, 6, 3)}) == 1
     assert query(32, 32, 3, 1, 14, 14, WINOGRADF63)[1] == 64 and query(32, 32, 3, 1, 8, 8, WINOGRADF63)[1] == 36
     assert lib.fhip_conv_packed_layout(None, IM2COL, None) != 0
+
+
+# ---- the model with int8 layers among fp32 ones ---------------------------------------------------------------------------------------
+def test_mixed_model_and_its_walks():
+    """LC.mixed_model(): 3 input channels, at most 128 anywhere, the seven int8 layers of its docstring among fp32 ones; its walks are
+    well-formed and cover what they claim; on every fed input the evaluation fed its own blobs (tests/qseam_ref.py) is finite and the
+    planes float64 is the yardstick of keep PLANE_FLOOR."""
+    import qseam_ref as QR
+    param, weights, name, outputs = LC.mixed_model()
+    net = R.Net(param, weights)
+    assert net.read == len(weights) and sorted(net.q) == sorted(LC.MIXED_INT8)
+    by_name = {n: (t, pd) for t, n, _, _, pd in net.layers}
+    assert by_name["conv0"][1][6] == 16 * 3 * 9 and not by_name["conv0"][1].get(8) and not by_name["fb"][1].get(8)
+    assert max(pd[0] for t, pd in by_name.values() if t in ("Convolution", "ConvolutionDepthWise")) <= 128
+    assert by_name["qdw"][0] == "ConvolutionDepthWise" and by_name["qdw"][1][7] == 32 and by_name["qpw"][1][1] == 1 and 64 < by_name["qpw"][1][0] < 160
+    assert by_name["out"][0] == "InnerProduct" and by_name["out"][1][8] == 1
+    order = [n for _, n, *_ in net.layers]
+    assert order.index("qbn") + 3 == order.index("qbn_relu") and order.index("pool2") == order.index("q2") + 2  # BatchNorm, Scale, ReLU; ReLU, pooling
+    # the walks
+    for wname, walk in LC.MIXED_WALKS.items():
+        fed = False
+        for step in walk:
+            assert step[0] in LC.STEP_KINDS and step[0] != "extract", (wname, step)
+            if step[0] == "feed":
+                assert step[1] in LC.MIXED_SHAPES, (wname, step)
+                fed = True
+            elif step[0] == "forward":
+                assert fed and step[1] >= 1
+        assert walk[-1][0] == "forward"
+    feeds = [LC.MIXED_SHAPES[s[1]] for s in LC.WALK_MIXED if s[0] == "feed"]
+    assert [f[0] for f in feeds[:4]] == [4, 5, 1, 4] and [f[2:] for f in feeds[3:7]] == [(16, 16), (12, 12), (13, 21), (16, 16)]
+    kinds = [s[0] for s in LC.WALK_MIXED]
+    assert {"set_tuned", "set_concurrency", "set_graph", "stream"} <= set(kinds)
+    on = kinds.index("set_graph")
+    assert LC.WALK_MIXED[on][1] is True and "feed" in kinds[on:kinds.index("set_graph", on + 1)]  # a new shape while the graph is on
+    assert [LC.MIXED_SHAPES[s[1]][0] for s in LC.WALK_MIXED_REPLICAS if s[0] == "feed"][:3] == [7, 2, 1]
+    rows = LC.mixed_table()
+    ids = [LC.row_id(r) for r in rows]
+    assert len(ids) == len(set(ids)) == 9 and not set(ids) & {LC.row_id(r) for r in LC.table()}
+    assert all(r[2].get("sub_batches") == 3 for r in rows if r[0] == "mixed_replicas")
+    # the evaluation
+    floor = (1.0, None)
+    for key, variant in sorted({f for w in LC.MIXED_WALKS.values() for f in _fed(w)}):
+        x = LC.input(key, variant)
+        for level in (0, 2):
+            blobs = QR.own(net, x, level)
+            assert all(o in blobs for o in outputs)
+            for n, v in blobs.items():
+                assert np.isfinite(v).all() and v.shape[0] == x.shape[0], (key, n)
+            for n in LC.MIXED_FP32:
+                if n in blobs:
+                    m = np.abs(blobs[n]).max(axis=(2, 3))
+                    floor = min(floor, (float(m.min() / m.max()), n, key, variant))
+                    assert m.min() >= LC.PLANE_FLOOR * m.max(), (key, variant, n, float(m.min() / m.max()))
+            assert float(blobs["gap"].min()) > 0.0  # a mean of values >= 0: no cancellation in the one-value planes
+    print(f"mixed model: smallest plane maximum relative to its tensor's: {floor}")

@@ -42,7 +42,7 @@ class Walked:
         self.sub_batches = kw.get("sub_batches", 1)
         self.start = {k: bool(kw.get(k)) for k in ("tuned", "concurrency", "graph")}
         self.cur = dict(self.start)
-        self.param, self.weights, self.input_name, _ = LC.deep_model() if self.walk_name == "deep" else LC.model()
+        self.param, self.weights, self.input_name, _ = self.model()
         self.net = self.make()
         self.fed = None
         self.side = None  # the torch stream of a "stream" step: it must outlive the net's use of it
@@ -51,12 +51,19 @@ class Walked:
         self.seen = {k: set() for k in ("algo3x3", "chains", "canvases", "siblings", "residuals", "one_kernel", "points")}
         self.forwards = 0
 
+    def model(self):
+        return LC.deep_model() if self.walk_name == "deep" else LC.model()
+
     def make(self):
         from feathercnn_amd.net import Net
         net = Net(fusion=self.level, sub_batches=self.sub_batches, **self.cur)
+        self.configure(net)
         net.LoadParam(self.param)
         net.LoadWeights(self.weights)
         return net
+
+    def configure(self, net):
+        pass
 
     def read(self, net, names):
         from feathercnn_amd import FeatherHipError
@@ -184,10 +191,68 @@ class Walked:
             raise AssertionError(step)
 
 
-def _walk(row):
+class WalkedMixed(Walked):
+    """The model with int8 layers among fp32 ones (LC.mixed_model): after every Forward the fresh-net invariant on every blob and plan,
+    every int8 layer against its restatement from the walked net's own bottom blob (np.array_equal; qseam_ref.int8_layers, which first
+    asserts what each int8 layer absorbed), and the fp32 layers against float64 from the device's int8 outputs (plane_nerr <= TOL)."""
+
+    def model(self):
+        return LC.mixed_model()
+
+    def configure(self, net):
+        net.SetQuantized(True)
+
+    def check(self):
+        import qseam_ref as QR
+        self.forwards += 1
+        if not hasattr(self, "ref"):
+            self.ref = R.Net(self.param, self.weights)
+            self.names = [t for layer in self.ref.layers for t in layer[3]]
+        x = LC.input(*self.fed)
+        fresh = self.make()
+        try:
+            fresh.FeedInput(self.input_name, x)
+            for _ in range(2 if self.cur["graph"] else 1):
+                fresh.Forward()
+            mine, theirs = self.plan(self.net), self.plan(fresh)
+            for k in mine:
+                if mine[k] != theirs[k]:
+                    self.note(f"{k} differs from the fresh net's", (mine[k], theirs[k]))
+            got, want = self.read(self.net, self.names), self.read(fresh, self.names)
+        finally:
+            fresh.close()
+        for name in self.names:
+            a, b = got[name], want[name]
+            if isinstance(a, str) or isinstance(b, str):
+                if not (isinstance(a, str) and isinstance(b, str) and a == b):
+                    self.note(f"Extract({name}): {a if isinstance(a, str) else 'ok'} here, {b if isinstance(b, str) else 'ok'} in the fresh net")
+            elif a.shape != b.shape or not np.array_equal(a.view(np.int32), b.view(np.int32)):
+                self.note(f"{name} is not the fresh net's bit for bit", R.plane_nerr(a, b) if a.shape == b.shape else None)
+        if any(v == "chained" for v in got.values() if isinstance(v, str)) or mine["chains"] or mine["fused_pointwise"] or mine["siblings"]:
+            self.note("a chain, a pair or a sibling plan in a net whose neighbours are int8", (mine["chains"], mine["fused_pointwise"], mine["siblings"]))
+        try:
+            given = QR.int8_layers(self.ref, x, self.net, self.level)
+        except AssertionError as err:
+            self.note("an int8 layer against its restatement", str(err)[:400])
+            return
+        if sum(v is not None for v in given.values()) != len(LC.MIXED_INT8):
+            self.note("not every int8 layer was compared", sorted(given))
+        blobs = self.ref.run(self.input_name, x, keep=True, given=given)
+        for name, a in got.items():
+            if isinstance(a, str) or blobs.get(name) is None:
+                continue
+            e = R.plane_nerr(a, blobs[name]) if a.shape == blobs[name].shape else float("inf")
+            if self.worst[1] is None or e > self.worst[0]:
+                self.worst = (e, f"{name}@{self.fed[0]}")
+            if not e <= TOL:
+                self.note(f"{name} against float64", e)
+        self.seen["residuals"].add(tuple(sorted(mine["residuals"].items())))
+
+
+def _walk(row, cls=Walked, walks=None):
     t0 = time.perf_counter()
-    w = Walked(row)
-    walk = LC.WALKS[row[0]]
+    w = cls(row)
+    walk = (walks or LC.WALKS)[row[0]]
     memory = []
     try:
         for at, step in enumerate(walk):
@@ -226,3 +291,11 @@ def test_walked_net_equals_a_fresh_one(cuda, row):
         for kind in ("chains", "canvases"):
             assert len(w.seen[kind]) >= (2 if level >= 3 else 1), (kind, w.seen[kind])
         assert (36 in w.seen["points"]) == tuned and 64 in w.seen["points"], w.seen["points"]
+
+
+@pytest.mark.parametrize("row", LC.mixed_table(), ids=LC.row_id)
+def test_walked_mixed_int8_net_equals_a_fresh_one_and_its_restatement(cuda, row):
+    w, _ = _walk(row, WalkedMixed, LC.MIXED_WALKS)
+    assert w.forwards == sum(s[1] for s in LC.MIXED_WALKS[row[0]] if s[0] == "forward")
+    # the fp32 branch takes the add with the int8 branch's top from level 2 on: the one plan of this net
+    assert all(bool(r) == (row[1] >= 2) for r in w.seen["residuals"]), w.seen["residuals"]
