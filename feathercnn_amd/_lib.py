@@ -1,7 +1,9 @@
 """ctypes binding of the C-ABI in include/feather_hip/feather_hip.h (one declaration per exported symbol)."""
 from __future__ import annotations
 
+import collections
 import ctypes
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -309,116 +311,58 @@ def checker(load, last_error: str):
     return _check
 
 
+Library = collections.namedtuple("Library", "file headers macro signatures last_error structs route")
+
+# One row per run-time library, in the order of csrc/Makefile (the main library, then SIDE): the file next to this module, the public headers
+# under include/feather_hip/, the export macro of those headers, the signature table, the last-error symbol, the ctypes mirrors of the structs
+# the headers define, and the name of the ROUTE_* constant of feathercnn_amd/net.py where the Net runtime routes layers to the library.
+# tests/test_side_contract_cpu.py holds every row to the contract the libraries share; a new library adds a row here.
+LIBRARIES = {
+    "hip": Library("libfeather_hip.so", ("feather_hip.h", "feather_net.h"), "FHIP_API", SIGNATURES, "fhip_last_error",
+                   (fhip_conv_param, fhip_winograd_plan, fhip_pool_param, fhip_pixel_image), None),
+    "pixout": Library("libfeather_pixout.so", ("feather_pixout.h",), "FHIP_PIXOUT_API", PIXOUT_SIGNATURES, "fhip_pixout_last_error", (), None),
+    "gconv": Library("libfeather_gconv.so", ("feather_gconv.h",), "FHIP_GCONV_API", GCONV_SIGNATURES, "fhip_gconv_last_error", (), "ROUTE_GCONV"),
+    "deconv": Library("libfeather_deconv.so", ("feather_deconv.h",), "FHIP_DECONV_API", DECONV_SIGNATURES, "fhip_deconv_last_error",
+                      (fhip_deconv_param,), "ROUTE_DECONV"),
+    "inorm": Library("libfeather_inorm.so", ("feather_inorm.h",), "FHIP_INORM_API", INORM_SIGNATURES, "fhip_inorm_last_error", (), "ROUTE_INORM"),
+    "shuffle": Library("libfeather_shuffle.so", ("feather_shuffle.h",), "FHIP_SHUFFLE_API", SHUFFLE_SIGNATURES, "fhip_shuffle_last_error", (),
+                       "ROUTE_SHUFFLE"),
+    "canvas": Library("libfeather_canvas.so", ("feather_canvas.h",), "FHIP_CANVAS_API", CANVAS_SIGNATURES, "fhip_canvas_last_error", (), None),
+    "atrous": Library("libfeather_atrous.so", ("feather_atrous.h",), "FHIP_ATROUS_API", ATROUS_SIGNATURES, "fhip_atrous_last_error",
+                      (fhip_atrous_param,), "ROUTE_ATROUS"),
+    "gate": Library("libfeather_gate.so", ("feather_gate.h",), "FHIP_GATE_API", GATE_SIGNATURES, "fhip_gate_last_error", (), "ROUTE_GATE"),
+    "resample": Library("libfeather_resample.so", ("feather_resample.h",), "FHIP_RESAMPLE_API", RESAMPLE_SIGNATURES, "fhip_resample_last_error", (),
+                        "ROUTE_RESAMPLE"),
+    "lrn": Library("libfeather_lrn.so", ("feather_lrn.h",), "FHIP_LRN_API", LRN_SIGNATURES, "fhip_lrn_last_error", (), "ROUTE_LRN"),
+    "qconv": Library("libfeather_qconv.so", ("feather_qconv.h",), "FHIP_QCONV_API", QCONV_SIGNATURES, "fhip_qconv_last_error",
+                     (fhip_qconv_param,), "ROUTE_QCONV"),
+}
+MAIN = "hip"
+
+
+def path(name: str) -> str:
+    """Where the library `name` of LIBRARIES lies: next to this module; FEATHER_HIP_LIB names another main library."""
+    default = os.path.join(_HERE, LIBRARIES[name].file)
+    return os.environ.get("FEATHER_HIP_LIB", default) if name == MAIN else default
+
+
+def load(name: str):
+    """Load the library `name` of LIBRARIES and type every symbol of its table.  Fails loudly: there is no fallback implementation."""
+    return _load(path(name), LIBRARIES[name].signatures)
+
+
 def lib_path() -> str:
-    return os.environ.get("FEATHER_HIP_LIB", os.path.join(_HERE, "libfeather_hip.so"))
+    return path(MAIN)
 
 
 def load_library():
     """Load libfeather_hip.so.  Fails loudly: there is no fallback implementation."""
-    return _load(lib_path(), SIGNATURES)
+    return load(MAIN)
 
 
-def pixout_path() -> str:
-    return os.path.join(_HERE, "libfeather_pixout.so")
-
-
-def load_pixout_library():
-    """Load libfeather_pixout.so (fhip_float_to_pixels).  Fails loudly like load_library: there is no fallback implementation."""
-    return _load(pixout_path(), PIXOUT_SIGNATURES)
-
-
-def gconv_path() -> str:
-    return os.path.join(_HERE, "libfeather_gconv.so")
-
-
-def load_gconv_library():
-    """Load libfeather_gconv.so (fhip_gconv_forward).  Fails loudly like load_library: there is no fallback implementation."""
-    return _load(gconv_path(), GCONV_SIGNATURES)
-
-
-def deconv_path() -> str:
-    return os.path.join(_HERE, "libfeather_deconv.so")
-
-
-def load_deconv_library():
-    """Load libfeather_deconv.so (fhip_deconv_forward).  Fails loudly like load_library: there is no fallback implementation."""
-    return _load(deconv_path(), DECONV_SIGNATURES)
-
-
-def inorm_path() -> str:
-    return os.path.join(_HERE, "libfeather_inorm.so")
-
-
-def load_inorm_library():
-    """Load libfeather_inorm.so (fhip_instance_norm_forward, fhip_activation_forward).  Fails loudly like load_library: there is no fallback
-    implementation."""
-    return _load(inorm_path(), INORM_SIGNATURES)
-
-
-def shuffle_path() -> str:
-    return os.path.join(_HERE, "libfeather_shuffle.so")
-
-
-def load_shuffle_library():
-    """Load libfeather_shuffle.so (fhip_channel_shuffle_forward, fhip_channel_slice_forward, fhip_channel_map_forward).  Fails loudly like
-    load_library: there is no fallback implementation."""
-    return _load(shuffle_path(), SHUFFLE_SIGNATURES)
-
-
-def canvas_path() -> str:
-    return os.path.join(_HERE, "libfeather_canvas.so")
-
-
-def load_canvas_library():
-    """Load libfeather_canvas.so (fhip_canvas_output_to_next_input, fhip_canvas_output_transform).  Fails loudly like load_library: there is
-    no fallback implementation."""
-    return _load(canvas_path(), CANVAS_SIGNATURES)
-
-
-def atrous_path() -> str:
-    return os.path.join(_HERE, "libfeather_atrous.so")
-
-
-def load_atrous_library():
-    """Load libfeather_atrous.so (fhip_atrous_forward).  Fails loudly like load_library: there is no fallback implementation."""
-    return _load(atrous_path(), ATROUS_SIGNATURES)
-
-
-def gate_path() -> str:
-    return os.path.join(_HERE, "libfeather_gate.so")
-
-
-def load_gate_library():
-    """Load libfeather_gate.so (fhip_channel_gate_forward, fhip_squeeze_forward, fhip_excite_forward, fhip_gate_activation_forward).  Fails
-    loudly like load_library: there is no fallback implementation."""
-    return _load(gate_path(), GATE_SIGNATURES)
-
-
-def resample_path() -> str:
-    return os.path.join(_HERE, "libfeather_resample.so")
-
-
-def load_resample_library():
-    """Load libfeather_resample.so (fhip_interp_forward, fhip_hardswish_forward).  Fails loudly like load_library: there is no fallback
-    implementation."""
-    return _load(resample_path(), RESAMPLE_SIGNATURES)
-
-
-def lrn_path() -> str:
-    return os.path.join(_HERE, "libfeather_lrn.so")
-
-
-def load_lrn_library():
-    """Load libfeather_lrn.so (fhip_lrn_forward, fhip_lrn_pool_forward).  Fails loudly like load_library: there is no fallback
-    implementation."""
-    return _load(lrn_path(), LRN_SIGNATURES)
-
-
-def qconv_path() -> str:
-    return os.path.join(_HERE, "libfeather_qconv.so")
-
-
-def load_qconv_library():
-    """Load libfeather_qconv.so (fhip_qconv_forward, fhip_quantize_forward).  Fails loudly like load_library: there is no fallback
-    implementation."""
-    return _load(qconv_path(), QCONV_SIGNATURES)
+# the names the wrappers, tools/ and the tests call: <x>_path() and load_<x>_library() of every side library
+for _name in LIBRARIES:
+    if _name != MAIN:
+        globals()[f"{_name}_path"] = functools.partial(path, _name)
+        globals()[f"load_{_name}_library"] = functools.partial(load, _name)
+del _name

@@ -30,6 +30,7 @@ def main():
                         dilation_h=dh, dilation_w=dw, batch=2)
         q.AssignOutputDim()
         print("ROUTE", AtrousConv().Route(q))
+    print("child ok")
 
 
 if __name__ == "__main__":

@@ -18,3 +18,4 @@ for _ in range(2):
     net.Forward()
 assert len(net.canvases()) == 6, net.canvases()
 assert np.isfinite(net.Extract(o)).all()
+print("child ok")

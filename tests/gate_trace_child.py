@@ -1,7 +1,6 @@
 """Child process of tests/test_gate_gpu.py's kernel-trace test: one Forward of a residual squeeze-and-excitation block (Caffe spelling, 64
 channels on 14 x 14, Eltwise + ReLU) between two Input blobs at fusion level 2, bracketed by two fhip_relu launches so that the trace can be
 cut at them.  Prints the three kernel names fhip_gate_route reports for the block's shapes ("route <name>") and checks the result."""
-import ctypes
 import os
 import sys
 
@@ -23,8 +22,8 @@ def model():
 
 def main():
     import gate_ref as R
+    import ktrace
     import torch
-    from feathercnn_amd import _lib
     from feathercnn_amd.gate import gate_route
     from feathercnn_amd.net import Net
     rng = np.random.default_rng(1)
@@ -37,16 +36,9 @@ def main():
     net.FeedInput("short", short)
     net.Forward()  # the first Forward reshapes and uploads the weights; the traced one only launches
     assert [(t, nm, a) for t, nm, a in net.layers()][-1] == ("Pooling", "se_gap", "GATE"), net.layers()
-    mark = torch.zeros(256, device="cuda")
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    relu = _lib.load_library().fhip_relu
-    torch.cuda.synchronize()
-    assert relu(ctypes.c_void_p(mark.data_ptr()), ctypes.c_void_p(mark.data_ptr()), 256, stream) == 0
-    torch.cuda.synchronize()
+    ktrace.marker()
     net.Forward()
-    torch.cuda.synchronize()
-    assert relu(ctypes.c_void_p(mark.data_ptr()), ctypes.c_void_p(mark.data_ptr()), 256, stream) == 0
-    torch.cuda.synchronize()
+    ktrace.marker()
     got = net.Extract("out")
     net.close()
     xt = torch.from_numpy(x).cuda()

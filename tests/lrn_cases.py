@@ -23,6 +23,14 @@ import numpy as np
 CHUNK = 16               # FHIP_LRN_CHUNK
 CHUNKS = (4, 8, 16)      # the channels of a block: 16, halved to 8 and to 4 while the grid stays below 2048 blocks (every row here gets 4)
 POOL_LDS_FLOATS = 8192   # FHIP_LRN_POOL_LDS_FLOATS
+KERNELS = {"lrn_across_kernel", "lrn_within_kernel", "lrn_pool_lds_kernel", "lrn_pool_direct_kernel"}
+
+
+def targets():
+    """Every instantiation the library holds, as rocprofv3, fhip_lrn_route and fhip_lrn_pool_route name it."""
+    return ({f"fhip::lrn_across_kernel<{v}, {l}>" for v in (1, 4) for l in (0, 3, 5)} | {"fhip::lrn_within_kernel", "fhip::lrn_pool_direct_kernel"} |
+            {f"fhip::lrn_pool_lds_kernel<{l}>" for l in (0, 3, 5)})
+
 
 E_REF = 2.2926e-07
 T = E_REF + 16 * 2.0 ** -24

@@ -2,7 +2,6 @@
 96 channels of 27 x 27, local_size 5) with a 3 x 3 / stride-2 max pooling behind it, which level 2 makes one layer, and `plain`, the same
 LRN alone -- separated by three fhip_relu launches so that the trace can be cut at them.  Prints the kernel names fhip_lrn_pool_route and
 fhip_lrn_route report for the shapes ("route <name>", in that order) and checks both results against the library called directly."""
-import ctypes
 import os
 import sys
 
@@ -25,8 +24,9 @@ def models():
 
 
 def main():
+    import ktrace
     import torch
-    from feathercnn_amd import _lib, lrn, lrn_pool, lrn_pool_route, lrn_route
+    from feathercnn_amd import lrn, lrn_pool, lrn_pool_route, lrn_route
     from feathercnn_amd.net import Net
     x = np.random.default_rng(1).normal(0, 1, SHAPE).astype(np.float32)
     nets = []
@@ -39,20 +39,11 @@ def main():
         net.Forward()  # the first Forward reshapes; the traced one only launches
         assert net.layers() == want, net.layers()
         nets.append(net)
-    mark = torch.zeros(256, device="cuda")
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    relu = _lib.load_library().fhip_relu
-
-    def marker():
-        torch.cuda.synchronize()
-        assert relu(ctypes.c_void_p(mark.data_ptr()), ctypes.c_void_p(mark.data_ptr()), 256, stream) == 0
-        torch.cuda.synchronize()
-
-    marker()
+    ktrace.marker()
     nets[0].Forward()
-    marker()
+    ktrace.marker()
     nets[1].Forward()
-    marker()
+    ktrace.marker()
     fused, plain = nets[0].Extract("pool"), nets[1].Extract("norm")
     for net in nets:
         net.close()

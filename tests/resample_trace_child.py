@@ -2,7 +2,6 @@
 Eltwise SUM with `lat`, a ReLU; 32 channels, 14 x 14 -> 28 x 28) between two Input blobs at fusion level 2, bracketed by two fhip_relu
 launches so that the trace can be cut at them.  Prints the kernel name fhip_interp_route reports for the shapes ("route <name>") and
 checks the result against the float32 restatement, bit for bit."""
-import ctypes
 import os
 import sys
 
@@ -22,9 +21,9 @@ def model():
 
 
 def main():
+    import ktrace
     import resample_ref as R
     import torch
-    from feathercnn_amd import _lib
     from feathercnn_amd.net import Net
     from feathercnn_amd.resample import interp_route
     rng = np.random.default_rng(1)
@@ -39,16 +38,9 @@ def main():
     net.FeedInput("lat", lat)
     net.Forward()  # the first Forward reshapes; the traced one only launches
     assert [(t, nm, a) for t, nm, a in net.layers()][-1] == ("Interp", "up", "RESAMPLE") and len(net.layers()) == 3, net.layers()
-    mark = torch.zeros(256, device="cuda")
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    relu = _lib.load_library().fhip_relu
-    torch.cuda.synchronize()
-    assert relu(ctypes.c_void_p(mark.data_ptr()), ctypes.c_void_p(mark.data_ptr()), 256, stream) == 0
-    torch.cuda.synchronize()
+    ktrace.marker()
     net.Forward()
-    torch.cuda.synchronize()
-    assert relu(ctypes.c_void_p(mark.data_ptr()), ctypes.c_void_p(mark.data_ptr()), 256, stream) == 0
-    torch.cuda.synchronize()
+    ktrace.marker()
     got = net.Extract("out")
     net.close()
     print("route", interp_route(torch.from_numpy(x).cuda(), "nearest", scale=2.0))

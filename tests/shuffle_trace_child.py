@@ -1,7 +1,6 @@
 """Child process of tests/test_shuffle_gpu.py's kernel-trace test: one Forward of Concat -> ShuffleChannel(2) -> Slice(2) between two Input
 blobs at the fusion level given on the command line, bracketed by two fhip_relu launches so that the trace can be cut at them (the feeds
 and the extraction copy too)."""
-import ctypes
 import os
 import sys
 
@@ -26,18 +25,10 @@ def main():
     net.FeedInput("a", a)
     net.FeedInput("b", b)
     net.Forward()  # the first Forward reshapes and builds the table; the traced one only launches
-    import torch
-    from feathercnn_amd import _lib
-    mark = torch.zeros(256, device="cuda")
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    relu = _lib.load_library().fhip_relu
-    torch.cuda.synchronize()
-    assert relu(ctypes.c_void_p(mark.data_ptr()), ctypes.c_void_p(mark.data_ptr()), 256, stream) == 0
-    torch.cuda.synchronize()
+    import ktrace
+    ktrace.marker()
     net.Forward()
-    torch.cuda.synchronize()
-    assert relu(ctypes.c_void_p(mark.data_ptr()), ctypes.c_void_p(mark.data_ptr()), 256, stream) == 0
-    torch.cuda.synchronize()
+    ktrace.marker()
     keep, work = net.Extract("keep"), net.Extract("work")
     net.close()
     want = R.channel_slice(R.channel_shuffle(np.concatenate([a, b], 1), 2), [-233, -233])

@@ -1,15 +1,13 @@
 """The dilated-convolution route without a GPU: the fp64 definition the GPU tests compare against (tests/atrous_ref.py) equals torch's CPU
 conv2d(dilation=) in float64 on every sweep geometry, equals the plain convolution with the zero-stuffed kernel, and equals the reference's
-recorded results with that kernel (tests/golden/atrous_golden.npz); libfeather_atrous.so (include/feather_hip/feather_atrous.h) exports
-what its header and the Python binding declare; every kernel instantiation it holds has a case in the sweep table (tests/atrous_cases.py);
+recorded results with that kernel (tests/golden/atrous_golden.npz); every case of the sweep table (tests/atrous_cases.py) is one
+libfeather_atrous.so (include/feather_hip/feather_atrous.h) takes and routes as the table says;
 bad arguments are refused on the host with a message by every entry point; feather::Net refuses a dilated Convolution by default and loads
-it after SetDilated, reports the route code and keeps refusing a dilated Deconvolution; the zoo nets parse; and a reference-style C++
-application compiles and links."""
+it after SetDilated, reports the route and keeps refusing a dilated Deconvolution; the zoo nets parse.
+What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py."""
 import ctypes
-import glob
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,22 +15,13 @@ import pytest
 import atrous_cases as AC
 import atrous_ref as R
 import gconv_ref
-import helpers
-import kernel_instances as KI
+import side_contract
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_atrous.h")
-SOURCES = os.path.join(ROOT, "feathercnn_amd", "csrc_atrous")
 BADARG, UNSUPPORTED = -2, -1
-ROUTE_ATROUS = 104  # FHIP_NET_ROUTE_ATROUS
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(AC.LIB):
-        pytest.fail(f"{AC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_atrous_library()
+lib = side_contract.fixture("atrous")
 
 
 def _param(c=16, k=64, group=1, h=9, w=8, kh=3, kw=3, s=1, pads=(2, 2, 2, 2), dil=(2, 2), bias=1, act=1, **over):
@@ -116,30 +105,7 @@ def test_restatement_equals_the_recorded_reference():
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------------
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_ATROUS_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", AC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.ATROUS_SIGNATURES)
-    others = set(_lib.SIGNATURES) | set(_lib.PIXOUT_SIGNATURES) | set(_lib.GCONV_SIGNATURES) | set(_lib.DECONV_SIGNATURES)
-    assert not set(declared) & others  # an application may load them all
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_atrous" not in needed  # the main library reaches this one at run time only
-    # the C struct and its ctypes mirror have the same fields in the same order: fhip_conv_param's, then the two dilations
-    body = re.search(r"typedef struct fhip_atrous_param\s*\{(.*?)\}", open(HEADER).read(), re.S).group(1)
-    fields = re.findall(r"int\s+(\w+);", body)
-    assert fields == [f[0] for f in _lib.fhip_atrous_param._fields_]
-    assert fields[:-2] == [f[0] for f in _lib.fhip_conv_param._fields_] and fields[-2:] == ["dilation_h", "dilation_w"]
-
-
 def test_every_instantiation_has_a_case(lib):
-    names = KI.instances(AC.LIB)
-    assert names, "the dilated-convolution library holds no kernel"
-    assert set(names) == AC.targets(), f"library {names} / sweep table {sorted(AC.targets())}"
-    src = "".join(open(p).read() for p in glob.glob(os.path.join(SOURCES, "*.hip")) + glob.glob(os.path.join(SOURCES, "*.h")))
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared | {"gemm_mfma_kernel"} == {KI.base(n) for n in names}  # gemm_mfma_kernel: the shared main loop of csrc/gemm_core.h
     assert len({c[0] for c in AC.CASES}) == len(AC.CASES)
     for case in AC.CASES:
         _, c, k, group, h, w, kh, kw, s, pads, dil, offset = case
@@ -156,14 +122,6 @@ def test_every_instantiation_has_a_case(lib):
         assert lib.fhip_atrous_assign_output_dim(ctypes.byref(q)) == 0 and (q.output_h, q.output_w) == AC.out_dims(case)
         for route in AC.accepted_routes(case):  # the named-route calls accept what the table says, on the host
             assert lib.fhip_atrous_get_buffer_size_route(ctypes.byref(p), 1, route.encode(), ctypes.byref(sb), ctypes.byref(pk)) == 0, (case[0], route)
-
-
-def test_other_libraries_keep_their_instantiations():
-    import deconv_cases as DC
-    import gconv_cases as GC
-    assert len(KI.instances()) == 176
-    assert set(KI.instances(GC.LIB)) == GC.targets() and set(KI.instances(DC.LIB)) == DC.targets()
-    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
 
 
 def test_refusals_come_before_any_device_call(lib):
@@ -315,31 +273,3 @@ def test_restatement_runs_tiny_dilated():
     shapes = {k: v.shape for k, v in blobs.items()}
     assert shapes["a1"] == (2, 64, 16, 16) and shapes["a3"] == (2, 96, 8, 8) and shapes["a_far"] == (2, 48, 8, 8) and shapes[o] == (2, 8, 4, 4)
     assert all(np.abs(blobs[nm]).max() > 1e-3 for nm in model_zoo.DILATED_LAYERS["tiny_dilated"])  # no layer of the net is dead
-
-
-def test_route_code_is_named_in_the_header():
-    text = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    m = re.search(r"#define\s+FHIP_NET_ROUTE_ATROUS\s+(\d+)", text)
-    assert m and int(m.group(1)) == ROUTE_ATROUS
-    assert "fhip_net_set_dilated" in text
-    from feathercnn_amd import net
-    assert net.ROUTE_ATROUS == ROUTE_ATROUS and len({net.ROUTE_GCONV, net.ROUTE_DECONV, net.ROUTE_INORM, net.ROUTE_SHUFFLE, net.ROUTE_ATROUS}) == 5
-
-
-def build_app(tmp_path) -> str:
-    from feathercnn_amd import _lib
-    libdir = os.path.dirname(_lib.atrous_path())
-    inc = os.path.join(ROOT, "include")
-    exe = str(tmp_path / "atrous_app_main")
-    subprocess.run(["g++", "-std=c++11", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + os.path.join(inc, "feather"),
-                    "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "atrous_app_main.cpp"), "-o", exe, "-L" + libdir, "-lfeather_hip",
-                    "-lfeather_atrous", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True,
-                   capture_output=True, text=True)
-    return exe
-
-
-def test_reference_style_application_compiles(lib, tmp_path):
-    """booster::AtrousConv (include/booster/atrous.h) next to feather::Net::SetDilated: compiles with plain g++ -std=c++11 -Wall against
-    include/ and links against the product libraries."""
-    exe = build_app(tmp_path)
-    assert os.path.exists(exe)

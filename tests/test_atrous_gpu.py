@@ -10,21 +10,22 @@
 * the reference's recorded results with the zero-stuffed kernel (tests/golden/atrous_golden.npz);
 * run-to-run bit identity, idempotent init and capture into a hipGraph;
 * feather::Net with dilated layers (Net.SetDilated): tiny_dilated at fusion levels 0 - 3, with sub-batches, concurrency and the graph,
-  Extract of a dilated layer's top; deeplab_largefov and deeplab_v2_aspp at 65 pixels, batch 2; a missing library is an error message at
-  the first Reshape, not a crash; a kernel trace of tiny_dilated in a process of its own; a reference-style C++ application.
+  Extract of a dilated layer's top; deeplab_largefov and deeplab_v2_aspp at 65 pixels, batch 2 (the missing library:
+  tests/test_side_contract_gpu.py); a kernel trace of tiny_dilated in a process of its own; a reference-style C++ application.
 Bound everywhere: max|y - ref| / max|ref| <= 1e-4; fusion levels among themselves 1e-5.  Each test prints its own
 figures; the measured worst cases are recorded in DESIGN.md 3.17."""
 import ctypes
 import os
-import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import atrous_cases as AC
 import atrous_ref as R
+import kernel_instances as KI
+import ktrace
+import side_contract
 from guarded import Guarded, describe
 
 pytestmark = pytest.mark.gpu
@@ -41,10 +42,7 @@ def _family(inst):
     return "generic" if inst == AC.GENERIC else "depthwise" if "dw3x3" in inst else "MFMA"
 
 
-@pytest.fixture(scope="module")
-def lib(cuda):
-    from feathercnn_amd import _lib
-    return _lib.load_atrous_library()
+lib = side_contract.fixture("atrous", gpu=True)
 
 
 def _param(case, bias, act, batch):
@@ -58,9 +56,7 @@ def _param(case, bias, act, batch):
     return p
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 def _want(case, x, wt, b, act):
@@ -124,7 +120,6 @@ def test_sweep_between_guards(lib, case):
 
 
 def test_sweep_reaches_every_instantiation():
-    import kernel_instances as KI
     assert set(KI.instances(AC.LIB)) == AC.targets()
 
 
@@ -297,50 +292,13 @@ def test_deeplab_nets_65px_batch2(cuda, name):
         assert e <= TOL, (kw, e)
 
 
-def test_missing_library_is_an_error_at_reshape(cuda, tmp_path):
-    """libfeather_hip.so alone in a directory: nets without dilated layers run, one with a dilated Convolution fails at its first Reshape
-    with FHIP_E_UNSUPPORTED and a message that names the missing library."""
-    from feathercnn_amd import _lib
-    shutil.copy(_lib.lib_path(), tmp_path / "libfeather_hip.so")
-    code = (
-        "import numpy as np\n"
-        "from feathercnn_amd import model_zoo, FeatherHipError\n"
-        "from feathercnn_amd.net import Net\n"
-        "for name, size in (('tiny_allsorts', 20), ('tiny_dilated', 16)):\n"
-        "    p, b, i, o = model_zoo.MODELS[name]()\n"
-        "    net = Net(); net.SetDilated(True); net.LoadParam(p); net.LoadWeights(b)\n"
-        "    try:\n"
-        "        net.FeedInput(i, np.zeros((1, 3, size, size), np.float32)); net.Forward(); net.Extract(o); print(name, 'ran')\n"
-        "    except FeatherHipError as e:\n"
-        "        print(name, 'refused:', e)\n")
-    env = dict(os.environ, FEATHER_HIP_LIB=str(tmp_path / "libfeather_hip.so"), PYTHONPATH=ROOT)
-    r = subprocess.run(["timeout", "-k", "10", "240", sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "tiny_allsorts ran" in r.stdout
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("tiny_dilated")][0]
-    assert "refused" in line and "libfeather_atrous.so" in line and "code -1" in line, r.stdout
-
-
 def test_kernel_trace_of_tiny_dilated(cuda, tmp_path):
     """One child under rocprofv3 --kernel-trace (tests/atrous_trace_child.py, a run of its own): tiny_dilated launches the kernels the routes
     of its dilated layers report -- MFMA instantiations on both tiles, the depthwise and the generic kernel."""
-    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(prof):
-        pytest.fail("rocprofv3 is not installed")
-    out = tmp_path / "trace"
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.path.join(ROOT, "tests"))
-    r = subprocess.run(["timeout", "-k", "10", "240", prof, "--kernel-trace", "--output-format", "csv", "-d", str(out), "--", sys.executable,
-                        os.path.join(ROOT, "tests", "atrous_trace_child.py")], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
-    want = [ln.split(" ", 1)[1] for ln in r.stdout.splitlines() if ln.startswith("ROUTE ")]
-    assert len(want) == 6, r.stdout
-    import csv
-    import glob
-    import kernel_instances as KI
-    launched = set()
-    for path in glob.glob(str(out / "**" / "*kernel_trace.csv"), recursive=True):
-        with open(path) as f:
-            launched |= {KI.normalise(row["Kernel_Name"]) for row in csv.DictReader(f)}
+    text, rows, _ = ktrace.trace("atrous_trace_child.py", [], tmp_path, 240)
+    want = [ln.split(" ", 1)[1] for ln in text.splitlines() if ln.startswith("ROUTE ")]
+    assert len(want) == 6, text
+    launched = {KI.normalise(name) for _, name, *_ in rows}
     assert launched, "the trace holds no kernel"
     missing = [w for w in want if w not in launched]
     assert not missing, (missing, sorted(n for n in launched if "trous" in n))
@@ -354,8 +312,7 @@ def test_reference_style_application_runs(lib, tmp_path):
     """tests/cpp/atrous_app_main.cpp executed: feather::Net::SetDilated + tiny_dilated, and booster::AtrousConv Init / Forward on one layer,
     both against the fp64 restatement."""
     from feathercnn_amd import model_zoo
-    from test_atrous_cpu import build_app
-    exe = build_app(tmp_path)
+    exe = side_contract.build_app("atrous", tmp_path)
     p, b, i, o = model_zoo.tiny_dilated()
     x = np.random.default_rng(9).uniform(-1, 1, (2, 3, 16, 16)).astype(np.float32)
     lx, lw, lb = R.synth(32, 64, 5, 8, 3, 3, 1, 2, seed=10)

@@ -5,16 +5,12 @@ stage kernels run on them as ordinary images of that size (fhip_winograd_f63_inp
 zeroed between layers.  The canvas run's V, its M and its final activation must equal that EXACTLY: same butterflies, same values, same order.
 V, M and the output are filled with NaN before every canvas run, so an unmasked seam or a column nobody wrote shows up in the result.
 Then the compiled reference per image, the net-level choice on VGG-16, and the GEMM grids in a kernel trace."""
-import csv
-import glob
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import ktrace
 from oracle import conv_geom, nerr
 
 pytestmark = pytest.mark.gpu
@@ -275,23 +271,8 @@ def test_a_batch_that_is_not_a_multiple_of_4_takes_the_plain_path(cuda, batch):
 
 def test_kernel_trace_shows_the_canvas_gemm_grids(cuda, tmp_path):
     """Once, under rocprofv3 --kernel-trace (no counters): VGG-16 b32's conv3_x tile GEMMs run on 2888 columns and conv5_x's on 200."""
-    prof = shutil.which("rocprofv3")
-    assert prof, "rocprofv3 not found: the trace cannot be taken (a failure, not a skip)"
-    child = os.path.join(HERE, "canvas_trace_child.py")
-    log = tmp_path / "trace.log"
-    cmd = ["timeout", "-k", "10", "300", prof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", str(tmp_path / "trace"), "-o", "trace", "--",
-           sys.executable, child]
-    with open(log, "w") as fh:
-        rc = subprocess.run(cmd, stdout=fh, stderr=subprocess.STDOUT, cwd=os.path.dirname(HERE)).returncode
-    assert rc == 0, "".join(open(log).readlines()[-30:])
-    files = glob.glob(os.path.join(str(tmp_path / "trace"), "**", "*kernel_trace.csv"), recursive=True)
-    assert files
-    launches = []  # (kernel name, blocks) per launch
-    for f in files:
-        with open(f, newline="") as fh:
-            for r in csv.DictReader(fh):
-                gx, wx = int(r.get("Grid_Size_X") or r["Grid_Size"]), int(r.get("Workgroup_Size_X") or r["Workgroup_Size"])
-                launches.append((r["Kernel_Name"], gx, wx))
+    _, rows, _ = ktrace.trace("canvas_trace_child.py", [], tmp_path, 300, stats=True)
+    launches = [(name, gx, wx) for _, name, gx, wx in rows]  # (kernel name, grid, workgroup) per launch
 
     def count(target):
         # GEMM launches of `target` blocks.  The tool reports work-items (target * workgroup) or blocks; a tile-GEMM grid is a multiple of 64

@@ -1,37 +1,25 @@
 """The transposed-convolution route without a GPU: the fp64 definition the GPU tests compare against (tests/deconv_ref.py) equals torch's
 CPU conv_transpose2d in float64 on every sweep geometry, satisfies the adjoint identity against the project's convolution checker, and
 equals the reference's recorded results on the zero-stuffed input with the flipped kernel (tests/golden/deconv_golden.npz);
-libfeather_deconv.so (include/feather_hip/feather_deconv.h) exports what its header and the Python binding declare; every kernel
-instantiation it holds has a case in the sweep table (tests/deconv_cases.py) while the other three libraries keep their counts; bad
-arguments are refused on the host with a message; feather::Net loads the three zoo nets that hold deconvolution layers, reports the route
-code for them and refuses what the definition leaves out; and a reference-style C++ application compiles and links."""
+every case of the sweep table (tests/deconv_cases.py) is one libfeather_deconv.so takes and routes as the table says; bad arguments are
+refused on the host with a message; feather::Net loads the three zoo nets that hold deconvolution layers, reports the route for them and
+refuses what the definition leaves out.  What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py."""
 import ctypes
-import glob
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import deconv_cases as DC
 import deconv_ref as R
-import helpers
-import kernel_instances as KI
+import side_contract
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_deconv.h")
-SOURCES = os.path.join(ROOT, "feathercnn_amd", "csrc_deconv")
 BADARG = -2
-ROUTE_DECONV = 101  # FHIP_NET_ROUTE_DECONV
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(DC.LIB):
-        pytest.fail(f"{DC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_deconv_library()
+lib = side_contract.fixture("deconv")
 
 
 def _param(c=32, k=64, group=1, h=8, w=8, kh=4, kw=4, s=2, pads=(1, 1, 1, 1), out_pads=(0, 0), bias=1, act=1, **over):
@@ -137,28 +125,7 @@ def test_restatement_equals_the_recorded_reference():
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------------
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_DECONV_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", DC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.DECONV_SIGNATURES)
-    others = set(_lib.SIGNATURES) | set(_lib.PIXOUT_SIGNATURES) | set(_lib.GCONV_SIGNATURES)
-    assert not set(declared) & others  # an application may load all four
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_deconv" not in needed  # the main library reaches this one at run time only
-    # the C struct and its ctypes mirror have the same fields in the same order
-    body = re.search(r"typedef struct fhip_deconv_param\s*\{(.*?)\}", open(HEADER).read(), re.S).group(1)
-    assert re.findall(r"int\s+(\w+);", body) == [f[0] for f in _lib.fhip_deconv_param._fields_]
-
-
 def test_every_instantiation_has_a_case(lib):
-    names = KI.instances(DC.LIB)
-    assert names, "the deconvolution library holds no kernel"
-    assert set(names) == DC.targets(), f"library {names} / sweep table {sorted(DC.targets())}"
-    src = "".join(open(p).read() for p in glob.glob(os.path.join(SOURCES, "*.hip")) + glob.glob(os.path.join(SOURCES, "*.h")))
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared | {"gemm_mfma_kernel"} == {KI.base(n) for n in names}  # gemm_mfma_kernel: the shared main loop of csrc/gemm_core.h
     assert len({c[0] for c in DC.CASES}) == len(DC.CASES)
     for case in DC.CASES:
         _, c, k, group, h, w, kh, kw, s, pads, out_pads, offset = case
@@ -172,15 +139,6 @@ def test_every_instantiation_has_a_case(lib):
         assert sb.value == 0 and pk.value >= 4 * k * (c // group) * kh * kw, case[0]
         q = _param(c, k, group, h, w, kh, kw, s, pads, out_pads, output_h=0, output_w=0)
         assert lib.fhip_deconv_assign_output_dim(ctypes.byref(q)) == 0 and (q.output_h, q.output_w) == DC.out_dims(case)
-
-
-def test_other_libraries_keep_their_instantiations():
-    import gconv_cases as GC
-    assert len(KI.instances()) == 176
-    assert len(KI.instances(os.path.join(ROOT, "feathercnn_amd", "libfeather_pixout.so"))) == 6
-    assert set(KI.instances(GC.LIB)) == GC.targets()
-    # no new __global__ under feathercnn_amd/csrc: net.hip only routes
-    assert "__global__" not in helpers.net_runtime_source()
 
 
 def test_refusals_come_before_any_device_call(lib):
@@ -268,30 +226,3 @@ def test_load_param_refuses_what_the_definition_leaves_out(extra, code):
     dw = Net()
     dw.LoadParam(_one_layer("7=16", "DeconvolutionDepthWise", wsize=16 * 16, base="0=16 1=4 3=2 4=1 5=0"))
     assert dw.layers()[1][2] == "DECONV"
-
-
-def test_route_code_is_named_in_the_header():
-    text = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    m = re.search(r"#define\s+FHIP_NET_ROUTE_DECONV\s+(\d+)", text)
-    assert m and int(m.group(1)) == ROUTE_DECONV and ROUTE_DECONV not in range(7)
-    from feathercnn_amd import net
-    assert net.ROUTE_DECONV == ROUTE_DECONV and net.ROUTE_DECONV != net.ROUTE_GCONV
-
-
-def build_app(tmp_path) -> str:
-    from feathercnn_amd import _lib
-    libdir = os.path.dirname(_lib.deconv_path())
-    inc = os.path.join(ROOT, "include")
-    exe = str(tmp_path / "deconv_app_main")
-    subprocess.run(["g++", "-std=c++11", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + os.path.join(inc, "feather"),
-                    "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "deconv_app_main.cpp"), "-o", exe, "-L" + libdir, "-lfeather_hip",
-                    "-lfeather_deconv", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True,
-                   capture_output=True, text=True)
-    return exe
-
-
-def test_reference_style_application_compiles(lib, tmp_path):
-    """booster::Deconv (include/booster/deconv.h) next to feather::Net: compiles with plain g++ -std=c++11 -Wall against include/ and links
-    against the product libraries (tests/test_deconv_gpu.py runs it)."""
-    exe = build_app(tmp_path)
-    assert os.path.exists(exe)

@@ -7,22 +7,21 @@
 * the reference's recorded results on the zero-stuffed input with the flipped kernel (tests/golden/deconv_golden.npz);
 * run-to-run bit identity, idempotent init and capture into a hipGraph;
 * feather::Net with deconvolution layers: tiny_deconv at fusion levels 0 - 3, with sub-batches, concurrency and the graph, Extract of a
-  deconvolution's top; style_transfer and unet_k4 at batch 4; FeedPixels -> style_transfer -> ExtractPixels; a missing library is an error
-  message at the first Reshape, not a crash; a reference-style C++ application.
+  deconvolution's top; style_transfer and unet_k4 at batch 4; FeedPixels -> style_transfer -> ExtractPixels (the missing library:
+  tests/test_side_contract_gpu.py); a reference-style C++ application.
 Bound everywhere: max|y - ref| / max|ref| <= 1e-4.  Measured on the MI355X: MFMA sweep 5.7e-7, generic sweep 3.4e-7, fixtures
 5.3e-6 against the recorded reference and 3.5e-7 against fp64, tiny_deconv 5.0e-7, unet_k4 b4 8.2e-7, style_transfer b4 1.1e-5
 (DESIGN.md 3.13); each test prints its own figures."""
 import ctypes
 import os
-import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import deconv_cases as DC
 import deconv_ref as R
+import side_contract
 from guarded import Guarded, describe
 
 pytestmark = pytest.mark.gpu
@@ -35,10 +34,7 @@ def _note(family, e):
     WORST[family] = max(WORST.get(family, 0.0), e)
 
 
-@pytest.fixture(scope="module")
-def lib(cuda):
-    from feathercnn_amd import _lib
-    return _lib.load_deconv_library()
+lib = side_contract.fixture("deconv", gpu=True)
 
 
 def _param(case, bias, act, batch):
@@ -52,9 +48,7 @@ def _param(case, bias, act, batch):
     return p
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 @pytest.mark.parametrize("case", DC.CASES, ids=[c[0] for c in DC.CASES])
@@ -281,34 +275,9 @@ def test_pixels_through_style_transfer_to_pixels(cuda):
         assert expect.min() == 0 and expect.max() == 255
 
 
-def test_missing_library_is_an_error_at_reshape(cuda, tmp_path):
-    """libfeather_hip.so alone in a directory: nets without deconvolution layers run, one with a Deconvolution fails at its first Reshape
-    with FHIP_E_UNSUPPORTED and a message that names the missing library."""
-    from feathercnn_amd import _lib
-    shutil.copy(_lib.lib_path(), tmp_path / "libfeather_hip.so")
-    code = (
-        "import numpy as np\n"
-        "from feathercnn_amd import model_zoo, FeatherHipError\n"
-        "from feathercnn_amd.net import Net\n"
-        "for name, size in (('tiny_allsorts', 20), ('tiny_deconv', 16)):\n"
-        "    p, b, i, o = model_zoo.MODELS[name]()\n"
-        "    net = Net(); net.LoadParam(p); net.LoadWeights(b)\n"
-        "    try:\n"
-        "        net.FeedInput(i, np.zeros((1, 3, size, size), np.float32)); net.Forward(); net.Extract(o); print(name, 'ran')\n"
-        "    except FeatherHipError as e:\n"
-        "        print(name, 'refused:', e)\n")
-    env = dict(os.environ, FEATHER_HIP_LIB=str(tmp_path / "libfeather_hip.so"), PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "tiny_allsorts ran" in r.stdout
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("tiny_deconv")][0]
-    assert "refused" in line and "libfeather_deconv.so" in line and "code -1" in line, r.stdout
-
-
 def test_reference_style_application_runs(lib, tmp_path):
     from feathercnn_amd import model_zoo
-    from test_deconv_cpu import build_app
-    exe = build_app(tmp_path)
+    exe = side_contract.build_app("deconv", tmp_path)
     p, b, i, o = model_zoo.tiny_deconv()
     x = np.random.default_rng(9).uniform(-1, 1, (2, 3, 16, 16)).astype(np.float32)
     lx, lw, lb = R.synth(32, 40, 5, 7, 4, 4, 1, 2, seed=10, sh=2, sw=2)

@@ -3,38 +3,29 @@
 Checks of the yardstick, which need no library: the fp64 restatement the GPU tests compare against (tests/gate_ref.py) equals what torch
 computes on the CPU (tests/golden/se_golden.npz, written by tests/golden/make_se_golden.py), and it runs tiny_se.
 
-Checks of the feature (they fail on the parent commit, where BinaryOp answers -200 and the library does not exist): the library exports
-what its header and the Python binding declare and holds the kernels tests/gate_cases.py names; bad arguments are refused on the host
+Checks of the feature (they fail on the parent commit, where BinaryOp answers -200 and the library does not exist): fhip_gate_route names
+the kernels tests/gate_cases.py states; bad arguments are refused on the host
 with their word; feather::Net loads every new line with route GATE and refuses what the definition leaves out; fusion level 2 collapses
 the blocks of tiny_se that match and leaves the one that does not; the zoo nets load at every level and the restatement reads every
-weight byte; the C++ application compiles."""
+weight byte.  What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import gate_cases as GC
 import gate_ref as R
-import helpers
-import kernel_instances as KI
+import side_contract
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_gate.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "se_golden.npz")
 BADARG = -2
-ROUTE_GATE = 105  # FHIP_NET_ROUTE_GATE
 NEW_MODELS = ["tiny_se", "se_resnet50", "efficientnet_b0"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(GC.LIB):
-        pytest.fail(f"{GC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_gate_library()
+lib = side_contract.fixture("gate")
 
 
 # ---- the definition ------------------------------------------------------------------------------------------------------------------
@@ -79,28 +70,7 @@ def test_restatement_runs_tiny_se():
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------------
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_GATE_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", GC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.GATE_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.PIXOUT_SIGNATURES) | set(_lib.GCONV_SIGNATURES) | set(_lib.DECONV_SIGNATURES) | set(_lib.INORM_SIGNATURES) |
-              set(_lib.SHUFFLE_SIGNATURES) | set(_lib.CANVAS_SIGNATURES) | set(_lib.ATROUS_SIGNATURES))
-    assert not set(declared) & others  # an application may load all nine
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_gate" not in needed  # the main library reaches this one at run time only
-    import feathercnn_amd
-    assert all(callable(getattr(feathercnn_amd, f)) for f in ("channel_gate", "squeeze", "excite", "gate_activation"))
-
-
 def test_instantiations_and_route_names(lib):
-    names = KI.instances(GC.LIB)
-    assert set(names) == GC.targets(), names
-    src = open(os.path.join(ROOT, "feathercnn_amd", "csrc_gate", "gate.hip")).read()
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared == {KI.base(n) for n in names} == GC.KERNELS
-    assert "atomic" not in src.split("#include", 1)[1]  # fixed-order sums only
     name = ctypes.create_string_buffer(96)
     v = ctypes.c_void_p
     seen = set()
@@ -127,17 +97,6 @@ def test_instantiations_and_route_names(lib):
         seen.add(name.value.decode())
     assert seen | {"fhip::squeeze_merge_kernel"} == GC.targets()  # the tables' shapes reach every instantiation
     assert lib.fhip_gate_route(4, 2, 3, 7, 7, None, None, None, name, 96) == BADARG and "unknown" in lib.fhip_gate_last_error().decode()
-
-
-def test_other_libraries_keep_their_instantiations():
-    import atrous_cases as AC
-    import inorm_cases as IC
-    import shuffle_cases as SC
-    assert len(KI.instances()) == 176
-    assert set(KI.instances(IC.LIB)) == IC.targets()
-    assert set(KI.instances(SC.LIB)) == SC.targets()
-    assert set(KI.instances(AC.LIB)) == AC.targets()
-    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
 
 
 def test_refusals_come_before_any_device_call(lib):
@@ -215,15 +174,6 @@ def test_load_param_refuses_what_the_definition_leaves_out(line, code, word):
     with pytest.raises(FeatherHipError) as e:
         net.LoadParam(_two(line))
     assert f"code {code}" in str(e.value) and word in str(e.value), str(e.value)
-
-
-def test_route_code_is_named_in_the_header():
-    text = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    m = re.search(r"#define\s+FHIP_NET_ROUTE_GATE\s+(\d+)", text)
-    assert m and int(m.group(1)) == ROUTE_GATE
-    from feathercnn_amd import net
-    assert net.ROUTE_GATE == ROUTE_GATE and net.ROUTE_NAMES[ROUTE_GATE] == "GATE"
-    assert len({net.ROUTE_GCONV, net.ROUTE_DECONV, net.ROUTE_INORM, net.ROUTE_SHUFFLE, net.ROUTE_ATROUS, net.ROUTE_GATE}) == 6
 
 
 def _fused_layers(param, weights, level):
@@ -332,22 +282,3 @@ def test_a_grouped_or_strided_excite_convolution_is_no_block():
     got = _fused_layers(p, w, 2)
     assert [(t, nm) for t, nm, _ in got] == [("Input", "data"), ("Convolution", "conv"), ("Split", "se_split"), ("Pooling", "se_gap")]
     assert got[3][2] == "GATE"
-
-
-def build_app(tmp_path) -> str:
-    from feathercnn_amd import _lib
-    libdir = os.path.dirname(_lib.gate_path())
-    inc = os.path.join(ROOT, "include")
-    exe = str(tmp_path / "gate_app_main")
-    subprocess.run(["g++", "-std=c++11", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + os.path.join(inc, "feather"),
-                    "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "gate_app_main.cpp"), "-o", exe, "-L" + libdir, "-lfeather_hip",
-                    "-lfeather_gate", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True,
-                   capture_output=True, text=True)
-    return exe
-
-
-def test_reference_style_application_compiles(lib, tmp_path):
-    """tests/cpp/gate_app_main.cpp -- feather::Net on tiny_se next to the C-ABI of feather_gate.h -- compiles with plain g++ -std=c++11
-    -Wall against include/ and links against the product libraries."""
-    exe = build_app(tmp_path)
-    assert os.path.exists(exe)

@@ -12,8 +12,6 @@
   refusals; a second input size; se_resnet50 and efficientnet_b0 at 64 px; a net without these layers never opens the library; the launches
   of one collapsed residual block by kernel trace.
 Each test prints its own figures."""
-import csv
-import glob
 import os
 import shutil
 import subprocess
@@ -24,11 +22,11 @@ import pytest
 
 import gate_cases as GC
 import gate_ref as R
+import ktrace
 from guarded import CANARY, POISON
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
 TOL = 1e-4
 GUARD = 1 << 14  # floats on each side
 TRACE_TIMEOUT = 240
@@ -428,25 +426,10 @@ def test_one_collapsed_residual_block_is_three_launches_by_kernel_trace(cuda, tm
     """One residual SE block (Caffe spelling, 64 channels on 14 x 14, Eltwise + ReLU) at fusion level 2, one Forward in a fresh child process
     under rocprofv3 (kernel trace only), cut at the two marker launches around the Forward: squeeze, excite and apply, under the names
     fhip_gate_route reports, and nothing else."""
-    prof = shutil.which("rocprofv3")
-    assert prof, "rocprofv3 not found: the trace cannot be taken (a failure, not a skip)"
-    d, log = tmp_path / "trace", tmp_path / "trace.log"
-    cmd = ["timeout", "-k", "10", str(TRACE_TIMEOUT), prof, "--kernel-trace", "--output-format", "csv", "-d", str(d), "-o", "trace",
-           "--", sys.executable, os.path.join(HERE, "gate_trace_child.py")]
-    with open(log, "w") as fh:
-        rc = subprocess.run(cmd, stdout=fh, stderr=subprocess.STDOUT, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT)).returncode
-    text = open(log).read()
-    assert rc == 0 and "child ok" in text, text[-3000:]
+    text, rows, _ = ktrace.trace("gate_trace_child.py", [], tmp_path, TRACE_TIMEOUT)
     routes = [ln.split(" ", 1)[1] for ln in text.splitlines() if ln.startswith("route ")]
     assert len(routes) == 3, text[-3000:]
-    kernels = []
-    for f in glob.glob(os.path.join(str(d), "**", "*kernel_trace.csv"), recursive=True):
-        with open(f, newline="") as fh:
-            kernels += [(int(r["Start_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(fh)]
-    kernels.sort()
-    marks = [t for t, k in kernels if "relu_kernel" in k]
-    assert len(marks) == 2, kernels  # the child brackets its Forward with two fhip_relu launches
-    window = [k for t, k in kernels if marks[0] < t < marks[1]]
+    window, = ktrace.between(rows, 2)  # the child brackets its Forward with two fhip_relu launches
     print("kernels of the collapsed block:", window)
     assert len(window) <= 3 and len(window) == len(routes), window
     for got, want in zip(window, routes):

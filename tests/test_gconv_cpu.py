@@ -1,36 +1,29 @@
-"""The grouped-convolution route (1 < group < C) without a GPU: libfeather_gconv.so (include/feather_hip/feather_gconv.h) exports what its
-header and the Python binding declare and nothing the other two libraries export; every kernel instantiation it holds has a case in the
-GPU sweep's table (tests/gconv_cases.py) and the kernels named in its sources are the ones it holds, while the main library keeps its 176
-and the output library its 6; bad arguments are refused on the host with a message; fhip_conv_select_algo still answers -1 for a partial
-group; the buffer sizes are pure; feather::Net loads the two zoo nets that hold grouped layers and reports the route code for them; the
+"""The grouped-convolution route (1 < group < C) without a GPU: every case of the GPU sweep's table
+(tests/gconv_cases.py) is one libfeather_gconv.so (include/feather_hip/feather_gconv.h) takes and routes as the table says, and its
+sources include only what the side libraries share; bad arguments are refused on the host with a message; fhip_conv_select_algo still answers -1 for a partial
+group; the buffer sizes are pure; feather::Net loads the two zoo nets that hold grouped layers and reports the route for them; the
 fp64 restatement the GPU tests compare against (tests/gconv_ref.py) equals the reference's recorded results on slices
-(tests/golden/gconv_golden.npz); and a reference-style C++ application compiles and links."""
+(tests/golden/gconv_golden.npz).  What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py."""
 import ctypes
 import glob
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import gconv_cases as GC
 import gconv_ref as R
-import kernel_instances as KI
+import side_contract
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_gconv.h")
 SOURCES = os.path.join(ROOT, "feathercnn_amd", "csrc_gconv")
 BADARG, UNSUPPORTED = -2, -1
-ROUTE_GCONV = 100  # FHIP_NET_ROUTE_GCONV
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(GC.LIB):
-        pytest.fail(f"{GC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_gconv_library()
+lib = side_contract.fixture("gconv")
 
 
 def _param(c=16, k=16, group=4, h=8, w=8, kh=3, kw=3, s=1, pads=(1, 1, 1, 1), bias=1, act=1, **over):
@@ -51,26 +44,8 @@ def _forward(lib, p, batch=1, out=0x1000, x=0x2000, packed=0x3000, bias=0x4000):
     return lib.fhip_gconv_forward(ctypes.byref(p), batch, v(out), v(x), v(packed), None, v(bias), None)
 
 
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_GCONV_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", GC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.GCONV_SIGNATURES)
-    # the three libraries export different names: an application may load all of them
-    assert not set(declared) & set(_lib.SIGNATURES) and not set(declared) & set(_lib.PIXOUT_SIGNATURES)
-    # and the main library reaches this one at run time only: no link-time dependency
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_gconv" not in needed
-
-
 def test_every_instantiation_has_a_case():
-    names = KI.instances(GC.LIB)
-    assert names, "the grouped-convolution library holds no kernel"
-    assert set(names) == GC.targets(), f"library {names} / sweep table {sorted(GC.targets())}"
     src = "".join(open(p).read() for p in glob.glob(os.path.join(SOURCES, "*.hip")) + glob.glob(os.path.join(SOURCES, "*.h")))
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared == {KI.base(n) for n in names}
     # no helper header of feathercnn_amd/csrc: every kernel is in csrc_gconv.  Beyond the public headers it includes only what the side
     # libraries share (csrc_side), and those headers declare no kernel and take nothing of csrc but common.h (which holds none either)
     kernel_decl = r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)"
@@ -95,11 +70,6 @@ def test_every_instantiation_has_a_case():
         sb, pk = ctypes.c_size_t(1), ctypes.c_size_t()
         assert lib.fhip_gconv_get_buffer_size(ctypes.byref(p), 3, ctypes.byref(sb), ctypes.byref(pk)) == 0
         assert sb.value == 0 and pk.value == 4 * GC.packed_floats(c, k, group, kh, kw, s, pads), case[0]
-
-
-def test_other_libraries_keep_their_instantiations():
-    assert len(KI.instances()) == 176
-    assert len(KI.instances(os.path.join(ROOT, "feathercnn_amd", "libfeather_pixout.so"))) == 6
 
 
 def test_refusals_come_before_any_device_call(lib):
@@ -199,14 +169,6 @@ def test_net_loads_the_grouped_nets(name):
         net.LoadWeights(b[:-4])
 
 
-def test_route_code_is_named_in_the_header():
-    text = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    m = re.search(r"#define\s+FHIP_NET_ROUTE_GCONV\s+(\d+)", text)
-    assert m and int(m.group(1)) == ROUTE_GCONV and ROUTE_GCONV not in range(7)  # none of the reference's ConvAlgo values
-    from feathercnn_amd import net
-    assert net.ROUTE_GCONV == ROUTE_GCONV
-
-
 def test_restatement_equals_the_recorded_reference():
     """The reference on slices (tests/golden/make_gconv_golden.py) against the fp64 definition, <= 1e-4 normalised."""
     g = np.load(os.path.join(ROOT, "tests", "golden", "gconv_golden.npz"))
@@ -240,22 +202,3 @@ def test_restatement_against_an_independent_convolution():
         t = torch.nn.functional.conv2d(xt, torch.from_numpy(wt).double(), torch.from_numpy(b).double(), stride=GC.strides(s), groups=group)
         assert y.shape[2:] == GC.out_dims(case)
         assert np.abs(y - t.relu().numpy()).max() < 1e-12, case[0]
-
-
-def test_reference_style_application_compiles(lib, tmp_path):
-    """booster::GroupedConv (include/booster/gconv.h) next to feather::Net on a net with grouped layers: compiles against include/ and
-    links against the product libraries (tests/test_gconv_gpu.py runs it)."""
-    exe = build_app(tmp_path)
-    assert os.path.exists(exe)
-
-
-def build_app(tmp_path) -> str:
-    from feathercnn_amd import _lib
-    libdir = os.path.dirname(_lib.gconv_path())
-    inc = os.path.join(ROOT, "include")
-    exe = str(tmp_path / "gconv_app_main")
-    subprocess.run(["g++", "-std=c++11", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + os.path.join(inc, "feather"),
-                    "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "gconv_app_main.cpp"), "-o", exe, "-L" + libdir, "-lfeather_hip",
-                    "-lfeather_gconv", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True,
-                   capture_output=True, text=True)
-    return exe

@@ -7,20 +7,19 @@
 * the reference's recorded results on slices (tests/golden/gconv_golden.npz);
 * run-to-run bit identity and capture into a hipGraph;
 * feather::Net with grouped layers: tiny_grouped at fusion levels 0 - 3, with sub-batches, with the graph; ResNeXt-50 (32x4d) at batch 8;
-  Extract of a grouped layer's top; a missing library is an error message at the first Reshape, not a crash.
+  Extract of a grouped layer's top (the missing library: tests/test_side_contract_gpu.py).
 Bound everywhere: max|y - ref| / max|ref| <= 1e-4.  Measured on the MI355X: tuned sweep 7.9e-7, generic sweep 2.9e-7, fixtures
 3.9e-6 against the recorded reference, ResNeXt-50 logits 3.5e-7; each test prints its own figures."""
 import ctypes
 import os
-import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import gconv_cases as GC
 import gconv_ref as R
+import side_contract
 from guarded import Guarded, describe
 
 pytestmark = pytest.mark.gpu
@@ -33,10 +32,7 @@ def _note(family, e):
     WORST[family] = max(WORST.get(family, 0.0), e)
 
 
-@pytest.fixture(scope="module")
-def lib(cuda):
-    from feathercnn_amd import _lib
-    return _lib.load_gconv_library()
+lib = side_contract.fixture("gconv", gpu=True)
 
 
 def _param(case, bias, act, batch):
@@ -49,9 +45,7 @@ def _param(case, bias, act, batch):
     return p
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 @pytest.mark.parametrize("case", GC.CASES, ids=[c[0] for c in GC.CASES])
@@ -228,34 +222,9 @@ def test_resnext50_batch8(cuda):
         assert (y.reshape(8, -1).argmax(1) == want["fc1000"].reshape(8, -1).argmax(1)).all()
 
 
-def test_missing_library_is_an_error_at_reshape(cuda, tmp_path):
-    """libfeather_hip.so alone in a directory: nets without grouped layers run, one with a partial group fails at its first Reshape with
-    FHIP_E_UNSUPPORTED and a message that names the missing library."""
-    from feathercnn_amd import _lib
-    shutil.copy(_lib.lib_path(), tmp_path / "libfeather_hip.so")
-    code = (
-        "import numpy as np\n"
-        "from feathercnn_amd import model_zoo, FeatherHipError\n"
-        "from feathercnn_amd.net import Net\n"
-        "for name, size in (('tiny_allsorts', 20), ('tiny_grouped', 21)):\n"
-        "    p, b, i, o = model_zoo.MODELS[name]()\n"
-        "    net = Net(); net.LoadParam(p); net.LoadWeights(b)\n"
-        "    try:\n"
-        "        net.FeedInput(i, np.zeros((1, 3, size, size), np.float32)); net.Forward(); net.Extract(o); print(name, 'ran')\n"
-        "    except FeatherHipError as e:\n"
-        "        print(name, 'refused:', e)\n")
-    env = dict(os.environ, FEATHER_HIP_LIB=str(tmp_path / "libfeather_hip.so"), PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "tiny_allsorts ran" in r.stdout
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("tiny_grouped")][0]
-    assert "refused" in line and "libfeather_gconv.so" in line and "code -1" in line, r.stdout
-
-
 def test_reference_style_application_runs(lib, tmp_path):
     from feathercnn_amd import model_zoo
-    from test_gconv_cpu import build_app
-    exe = build_app(tmp_path)
+    exe = side_contract.build_app("gconv", tmp_path)
     p, b, i, o = model_zoo.tiny_grouped()
     x = np.random.default_rng(9).uniform(-1, 1, (2, 3, 21, 21)).astype(np.float32)
     lx, lw, lb = R.synth(16, 16, 9, 13, 3, 3, 4, 2, seed=10)

@@ -6,38 +6,23 @@ test_relu_with_a_slope_loads_and_is_restated_as_leaky): the fp64 definition the 
 torch's CPU instance_norm / activations in float64; in float32 the two-pass form meets the project's bound on offset planes where
 E[x^2] - E[x]^2 misses it.  That a slope is no longer dropped on the device is checked in tests/test_inorm_gpu.py, not here.
 
-Checks of the feature: the library exports what its header and the Python binding declare; every kernel
-instantiation it holds has a case in tests/inorm_cases.py and fhip_instance_norm_route names it, while the other four libraries keep their
-sets; bad arguments are refused on the host; feather::Net loads the three zoo nets that hold the new layers, consuming every weight byte,
-and refuses what the definition leaves out; a ReLU with a slope loads as a ReLU and is restated as the leaky one."""
+Checks of the feature: fhip_instance_norm_route names the instantiation tests/inorm_cases.py states for every case; bad arguments are refused on the host; feather::Net loads the three zoo nets that hold the new layers, consuming every weight byte,
+and refuses what the definition leaves out; a ReLU with a slope loads as a ReLU and is restated as the leaky one.  What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py."""
 import ctypes
-import glob
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers
 import inorm_cases as IC
 import inorm_ref as R
-import kernel_instances as KI
+import side_contract
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_inorm.h")
-SOURCES = os.path.join(ROOT, "feathercnn_amd", "csrc_inorm")
 BADARG = -2
-ROUTE_INORM = 102  # FHIP_NET_ROUTE_INORM
 NEW_MODELS = ["tiny_generative", "style_transfer_in", "pix2pix_unet"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(IC.LIB):
-        pytest.fail(f"{IC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_inorm_library()
+lib = side_contract.fixture("inorm")
 
 
 # ---- the definition ------------------------------------------------------------------------------------------------------------------
@@ -92,20 +77,6 @@ def test_offset_planes_tell_the_two_variance_forms_apart():
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------------
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_INORM_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", IC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.INORM_SIGNATURES)
-    others = set(_lib.SIGNATURES) | set(_lib.PIXOUT_SIGNATURES) | set(_lib.GCONV_SIGNATURES) | set(_lib.DECONV_SIGNATURES)
-    assert not set(declared) & others  # an application may load all five
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_inorm" not in needed  # the main library reaches this one at run time only
-    import feathercnn_amd
-    assert callable(feathercnn_amd.instance_norm) and callable(feathercnn_amd.activation)
-
-
 def _route(lib, case):
     _, n, c, h, w, offset = case
     name = ctypes.create_string_buffer(96)
@@ -115,12 +86,6 @@ def _route(lib, case):
 
 
 def test_every_instantiation_has_a_case(lib):
-    names = KI.instances(IC.LIB)
-    assert names, "the library holds no kernel"
-    assert set(names) == IC.targets(), f"library {names} / case table {sorted(IC.targets())}"
-    src = "".join(open(p).read() for p in glob.glob(os.path.join(SOURCES, "*.hip")) + glob.glob(os.path.join(SOURCES, "*.h")))
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared == {KI.base(n) for n in names}
     assert len({c[0] for c in IC.CASES}) == len(IC.CASES) and len({c[0] for c in IC.ACT_CASES}) == len(IC.ACT_CASES)
     for case in IC.CASES:
         _, n, c, h, w, _ = case
@@ -130,16 +95,6 @@ def test_every_instantiation_has_a_case(lib):
         assert sb.value == IC.scratch_bytes(case), case[0]
     assert {IC.route(c) for c in IC.CASES} == {"wave", "block256", "block1024", "split"}
     assert any(n % 2 and n > 1 for _, n, *_ in IC.CASES)  # batch sizes that are not powers of two
-
-
-def test_other_libraries_keep_their_instantiations():
-    import deconv_cases as DC
-    import gconv_cases as GC
-    assert len(KI.instances()) == 176
-    assert len(KI.instances(os.path.join(ROOT, "feathercnn_amd", "libfeather_pixout.so"))) == 6
-    assert set(KI.instances(GC.LIB)) == GC.targets()
-    assert set(KI.instances(DC.LIB)) == DC.targets()
-    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
 
 
 def test_refusals_come_before_any_device_call(lib):
@@ -259,15 +214,6 @@ def test_relu_with_a_slope_loads_and_is_restated_as_leaky():
     assert (y[x < 0] < 0).all()
     plain = R.Net(_one("ReLU r 1 1 data r"), b"").run("data", x, "r")
     assert np.array_equal(plain, np.maximum(x, 0))
-
-
-def test_route_code_is_named_in_the_header():
-    text = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    m = re.search(r"#define\s+FHIP_NET_ROUTE_INORM\s+(\d+)", text)
-    assert m and int(m.group(1)) == ROUTE_INORM
-    from feathercnn_amd import net
-    assert net.ROUTE_INORM == ROUTE_INORM and net.ROUTE_NAMES[ROUTE_INORM] == "INORM"
-    assert len({net.ROUTE_INORM, net.ROUTE_DECONV, net.ROUTE_GCONV}) == 3
 
 
 def test_pixel_round_trip_under_the_parity_bound():

@@ -7,36 +7,27 @@
 * run-to-run bit identity of every case and capture into a hipGraph (an allocation in Forward would fail the capture);
 * the activations over [-20, 20], +-0 and +-88; a ReLU without a slope through the Net is fhip_relu bit for bit;
 * feather::Net: tiny_generative at fusion levels 0 - 3 with the expected layer lists, style_transfer_in and pix2pix_unet at batch 4,
-  FeedPixels -> style_transfer_in -> ExtractPixels, refusals at Reshape, a missing library.
+  FeedPixels -> style_transfer_in -> ExtractPixels, refusals at Reshape (the missing library: tests/test_side_contract_gpu.py).
 Bound everywhere: max|y - ref| / max|ref| <= 1e-4, per plane for the layer itself.  Each test prints its own figures."""
 import ctypes
-import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import inorm_cases as IC
 import inorm_ref as R
+import side_contract
 from guarded import Guarded, describe
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-4
 ACT_CODE = {None: 0, "relu": 1, "leaky_relu": 2}
 
 
-@pytest.fixture(scope="module")
-def lib(cuda):
-    from feathercnn_amd import _lib
-    return _lib.load_inorm_library()
+lib = side_contract.fixture("inorm", gpu=True)
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 def _synth(case, seed):
@@ -376,29 +367,3 @@ def test_pixels_through_style_transfer_in_to_pixels(cuda):
         print(f"style_transfer_in pixels {kw}: blob error {e:.2e}; {100 * share:.3f} % of {diff.size} bytes differ, by at most {int(diff.max())}")
         assert e <= TOL
         assert diff.max() <= 1 and share <= R.PIXEL_CAP
-
-
-def test_missing_library_is_an_error_at_reshape(cuda, tmp_path):
-    """libfeather_hip.so alone in a directory: a net without the new layers runs, one with an InstanceNorm fails at its first Reshape with
-    FHIP_E_UNSUPPORTED and a message that names the missing library."""
-    from feathercnn_amd import _lib
-    shutil.copy(_lib.lib_path(), tmp_path / "libfeather_hip.so")
-    code = (
-        "import numpy as np\n"
-        "from feathercnn_amd import FeatherHipError\n"
-        "from feathercnn_amd.net import Net\n"
-        "head = '7767517\\n2 2\\nInput data 0 1 data 0=8 1=8 2=8\\n'\n"
-        "for name, line, w in (('plain', 'ReLU r 1 1 data r', b''), ('inorm', 'InstanceNorm r 1 1 data r 0=8 2=0', b''), ('leaky', 'ReLU r 1 1 data r 0=0.2', b''),\n"
-        "                      ('tanh', 'TanH r 1 1 data r', b'')):\n"
-        "    net = Net(); net.LoadParam((head + line + '\\n').encode()); net.LoadWeights(w)\n"
-        "    try:\n"
-        "        net.FeedInput('data', np.zeros((1, 8, 8, 8), np.float32)); net.Forward(); net.Extract('r'); print(name, 'ran')\n"
-        "    except FeatherHipError as e:\n"
-        "        print(name, 'refused:', e)\n")
-    env = dict(os.environ, FEATHER_HIP_LIB=str(tmp_path / "libfeather_hip.so"), PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "plain ran" in r.stdout
-    for name in ("inorm", "leaky", "tanh"):
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith(name)][0]
-        assert "refused" in line and "libfeather_inorm.so" in line and "code -1" in line, r.stdout

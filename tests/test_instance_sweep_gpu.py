@@ -7,21 +7,15 @@ windows together every instantiation of the library but the EXCLUDED ones.
 """
 from __future__ import annotations
 
-import csv
-import glob
-import os
-import shutil
-import subprocess
-import sys
 
 import pytest
 
 import instance_sweep as S
+import ktrace
 from instance_cases import CASES, EXCLUDED
 from kernel_instances import base, instances, normalise
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 TRACE_TIMEOUT = 600
 
 
@@ -45,16 +39,9 @@ def _windows(rows, ncases):
     return wins
 
 
-def _read_trace(d):
-    files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-    assert files, f"no *kernel_trace.csv under {d}: {os.listdir(d)}"
-    rows = []
-    for f in files:
-        with open(f, newline="") as fh:
-            for r in csv.DictReader(fh):
-                gx, wx = int(r.get("Grid_Size_X") or r["Grid_Size"]), int(r.get("Workgroup_Size_X") or r["Workgroup_Size"])
-                rows.append((int(r["Start_Timestamp"]), normalise(r["Kernel_Name"]), gx, wx))
-    rows.sort()
+def _blocks(rows):
+    """ktrace's rows with normalised names and the grid in blocks: (start, name, blocks)."""
+    rows = [(t, normalise(n), gx, wx) for t, n, gx, wx in rows]
     # the grid is reported in work-items: blocks = grid / workgroup (the first separator, one block, tells which unit the trace uses)
     first_sep = next(r for r in rows if base(r[1]) == "relu_kernel")
     per_item = first_sep[2] == first_sep[3] and first_sep[3] > 1
@@ -62,16 +49,8 @@ def _read_trace(d):
 
 
 def test_sweep_trace(cuda, tmp_path):
-    prof = shutil.which("rocprofv3")
-    assert prof, "rocprofv3 not found: the sweep trace cannot be taken (a failure, not a skip)"
-    log = tmp_path / "sweep.log"
-    cmd = ["timeout", "-k", "10", str(TRACE_TIMEOUT), prof, "--kernel-trace", "--output-format", "csv", "-d", str(tmp_path / "trace"), "-o", "trace",
-           "--", sys.executable, os.path.join(HERE, "instance_sweep.py")]
-    with open(log, "w") as fh:
-        rc = subprocess.run(cmd, stdout=fh, stderr=subprocess.STDOUT, cwd=os.path.dirname(HERE)).returncode
-    tail = "".join(open(log).readlines()[-40:])
-    assert rc == 0, f"the traced sweep exited with {rc}:\n{tail}"
-    wins = _windows(_read_trace(str(tmp_path / "trace")), len(CASES))
+    _, rows, _ = ktrace.trace("instance_sweep.py", [], tmp_path, TRACE_TIMEOUT, ok=None)  # the sweep ends with a JSON line of its own
+    wins = _windows(_blocks(rows), len(CASES))
     import torch
     cus256 = torch.cuda.get_device_properties(0).multi_processor_count == 256
     missing = [f"{c.name}: {sorted(set(c.targets) - wins[i])} (ran {sorted(n for n in wins[i] if n.startswith('fhip::'))})"

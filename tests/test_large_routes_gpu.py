@@ -35,6 +35,7 @@ import gc
 import pytest
 
 import large_ref as R
+import side_contract
 
 pytestmark = pytest.mark.gpu
 TOL, MAG_TOL = 1e-4, 1e-6
@@ -59,9 +60,7 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 def _main():

@@ -6,41 +6,29 @@ header step by step) stays within E_REF of it on the whole table; dropping one t
 chunk boundary -- moves the result by at least 100 x the tolerance on every across-channel row, so the GPU sweep can see such a mistake;
 the restatement runs tiny_lrn.
 
-Checks of the feature (every one fails on the parent commit, where there is no library and LRN is refused with the switch on): the library
-exports what its header and the Python binding declare and holds the kernels tests/lrn_cases.py names; the route functions select the
+Checks of the feature (every one fails on the parent commit, where there is no library and LRN is refused with the switch on): the header
+states the chunk, the LDS budget and the size limit the tests use; the route functions select the
 instantiation the header states; bad arguments are refused on the host with their word; feather::Net refuses LRN by default and names the
 switch, loads it with route LRN after SetExtendedLayers, and answers every hostile param line with its code and a message; fusion level 2
 makes LRN -> Pooling one layer and leaves an LRN with two readers, a Pooling -> LRN and an LRN -> global Pooling as written; the zoo nets
-are the published ones and load at every level."""
+are the published ones and load at every level.  What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers
-import kernel_instances as KI
 import lrn_cases as LC
 import lrn_ref as R
+import side_contract
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_lrn.h")
-LIB = os.path.join(ROOT, "feathercnn_amd", "libfeather_lrn.so")
 BADARG = -2
-ROUTE_LRN = 107  # FHIP_NET_ROUTE_LRN
-KERNELS = {"lrn_across_kernel", "lrn_within_kernel", "lrn_pool_lds_kernel", "lrn_pool_direct_kernel"}
-TARGETS = ({f"fhip::lrn_across_kernel<{v}, {l}>" for v in (1, 4) for l in (0, 3, 5)} | {"fhip::lrn_within_kernel", "fhip::lrn_pool_direct_kernel"} |
-           {f"fhip::lrn_pool_lds_kernel<{l}>" for l in (0, 3, 5)})
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(LIB):
-        pytest.fail(f"{LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_lrn_library()
+lib = side_contract.fixture("lrn")
 
 
 def _both(r, **kw):
@@ -162,24 +150,7 @@ def test_pooling_restatement_and_tiny_lrn():
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------------
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_LRN_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.LRN_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.PIXOUT_SIGNATURES) | set(_lib.GCONV_SIGNATURES) | set(_lib.DECONV_SIGNATURES) | set(_lib.INORM_SIGNATURES) |
-              set(_lib.SHUFFLE_SIGNATURES) | set(_lib.CANVAS_SIGNATURES) | set(_lib.ATROUS_SIGNATURES) | set(_lib.GATE_SIGNATURES) | set(_lib.RESAMPLE_SIGNATURES))
-    assert not set(declared) & others  # an application may load all eleven
-    assert _lib.lrn_path() == LIB
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_lrn" not in needed  # the main library reaches this one at run time only
-    needed = subprocess.run(["readelf", "-d", LIB], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_hip" not in needed  # and this one stands alone
-    import feathercnn_amd
-    assert all(callable(getattr(feathercnn_amd, f)) for f in ("lrn", "lrn_pool", "lrn_route", "lrn_pool_route"))
-    mk = open(os.path.join(ROOT, "feathercnn_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^SIDE\s*:=.*\blrn\b", mk, re.M)  # built by the one mechanism
+def test_header_states_the_chunk_the_lds_budget_and_the_size_limit():
     text = open(HEADER).read()
     assert f"#define FHIP_LRN_CHUNK {LC.CHUNK}\n" in text and f"#define FHIP_LRN_POOL_LDS_FLOATS {LC.POOL_LDS_FLOATS}\n" in text
     import importlib
@@ -199,13 +170,6 @@ def _pool_param(p):
 
 
 def test_instantiations_and_route_names(lib):
-    names = KI.instances(LIB)
-    assert set(names) == TARGETS, names
-    src = open(os.path.join(ROOT, "feathercnn_amd", "csrc_lrn", "lrn.hip")).read()
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared == {KI.base(n) for n in names} == KERNELS
-    assert "atomic" not in src.split("#include", 1)[1] and "hipMalloc" not in src and "hipMemcpy" not in src and "getenv" not in src  # a forward only launches
-    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
     name = ctypes.create_string_buffer(96)
     v = ctypes.c_void_p
     seen = set()
@@ -228,7 +192,7 @@ def test_instantiations_and_route_names(lib):
         # the header's rule: 16 channels of kernel_h rows in 8192 floats of LDS, across channels only
         assert (p.route != "fhip::lrn_pool_direct_kernel") == (r.region == 0 and LC.CHUNK * p.kernel * r.w <= LC.POOL_LDS_FLOATS)
         seen.add(p.route)
-    assert seen == TARGETS  # the tables reach every instantiation the library holds
+    assert seen == LC.targets()  # the tables reach every instantiation the library holds
     # a 16-byte path only where plane and pointers allow
     assert {(r.h * r.w % 4 == 0) for r in LC.ACROSS_ROWS} == {True, False}
     assert lib.fhip_lrn_route(2, 5, 1, 1, 4, 4, None, None, name, 96) == BADARG and "region_type 2" in lib.fhip_lrn_last_error().decode()
@@ -330,18 +294,6 @@ def test_load_param_accepts_lrn():
         assert net.layers()[2] == ("LRN", "n", "LRN"), line
         net.LoadWeights(b"")  # the layer has no weights
     assert _load("HardSwish m 1 1 data m").layers()[2] == ("HardSwish", "m", "RESAMPLE")  # the other extended types load as before
-
-
-def test_route_code_is_named_in_the_header():
-    text = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    m = re.search(r"#define\s+FHIP_NET_ROUTE_LRN\s+(\d+)", text)
-    assert m and int(m.group(1)) == ROUTE_LRN
-    codes = [int(c) for c in re.findall(r"#define\s+FHIP_NET_ROUTE_\w+\s+(\d+)", text)]
-    assert len(codes) == len(set(codes)) >= 8
-    from feathercnn_amd import net
-    assert net.ROUTE_LRN == ROUTE_LRN and net.ROUTE_NAMES[ROUTE_LRN] == "LRN"
-    assert len({net.ROUTE_GCONV, net.ROUTE_DECONV, net.ROUTE_INORM, net.ROUTE_SHUFFLE, net.ROUTE_ATROUS, net.ROUTE_GATE, net.ROUTE_RESAMPLE, net.ROUTE_LRN}) == 8
-    assert list(net.ROUTE_NAMES.values()).count("LRN") == 1
 
 
 # A param value is stored as ncnn stores it: a token with '.', 'e' or 'E' is a float, any other token goes through atoi ("nan" and "inf" are

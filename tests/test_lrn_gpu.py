@@ -11,27 +11,22 @@
 * feather::Net: tiny_lrn at fusion levels 0 .. 3, with sub-batches, the graph and concurrency, against lrn_ref.Net at the project's 1e-4
   normalised, levels >= 2 within 1e-5 of level 0, and the blobs on both sides of a fused LRN -> Pooling at level 2 bit-identical to level
   1's; a fused layer above the size up to which one launch pays runs the two kernels through the scratch arena, same bits; alexnet, caffenet
-  and googlenet at batch 4 at their smallest inputs; a missing library is an error at Reshape; one launch per fused LRN -> Pooling and one
+  and googlenet at batch 4 at their smallest inputs; one launch per fused LRN -> Pooling and one
   per plain LRN by kernel trace.
 Each test prints its own figures."""
-import csv
-import glob
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import kernel_instances as KI
+import ktrace
 import lrn_cases as LC
 import lrn_ref as R
 from guarded import CANARY, POISON
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(ROOT, "feathercnn_amd", "libfeather_lrn.so")
 TOL = 1e-4
 GUARD = 1 << 14  # floats on each side
@@ -390,65 +385,14 @@ def test_zoo_nets_batch4_against_the_restatement(cuda, name, size):
         assert R.nerr(outs[level], outs[0]) <= 1e-5, (level, R.nerr(outs[level], outs[0]))
 
 
-def test_missing_library_is_an_error_at_reshape(cuda, tmp_path):
-    """The tree's libraries in a directory without libfeather_lrn.so: a net without LRN runs and never looks for it, one with an LRN -- plain
-    or with a pooling behind it -- fails at its first Reshape with FHIP_E_UNSUPPORTED and a message that names the missing library."""
-    from feathercnn_amd import _lib
-    libs = glob.glob(os.path.join(os.path.dirname(_lib.lib_path()), "libfeather_*.so"))
-    assert len(libs) >= 11 and LIB in libs
-    for f in libs:
-        if f != LIB:
-            shutil.copy(f, tmp_path / os.path.basename(f))
-    code = (
-        "import numpy as np\n"
-        "from feathercnn_amd import FeatherHipError\n"
-        "from feathercnn_amd.net import Net\n"
-        "head = '7767517\\n3 3\\nInput data 0 1 data 0=8 1=8 2=8\\n'\n"
-        "mapped = lambda: 'libfeather_lrn' in open('/proc/self/maps').read()\n"
-        "for name, lines in (('plain', 'ReLU r 1 1 data r\\nHardSwish p 1 1 r p\\n'), ('lrn', 'ReLU r 1 1 data r\\nLRN p 1 1 r p\\n'),\n"
-        "                    ('lrnpool', 'LRN r 1 1 data r 1=3\\nPooling p 1 1 r p 0=0 1=3 2=2\\n')):\n"
-        "    net = Net(fusion=2); net.SetExtendedLayers(True); net.LoadParam((head + lines).encode()); net.LoadWeights(b'')\n"
-        "    try:\n"
-        "        net.FeedInput('data', np.ones((1, 8, 8, 8), np.float32)); net.Forward(); net.Extract('p'); print(name, 'ran', 'mapped' if mapped() else 'unmapped')\n"
-        "    except FeatherHipError as e:\n"
-        "        print(name, 'refused:', e, 'mapped' if mapped() else 'unmapped')\n")
-    for lib_dir, expect in ((tmp_path, "refused"), (None, "ran")):
-        env = dict(os.environ, PYTHONPATH=ROOT)
-        if lib_dir:
-            env["FEATHER_HIP_LIB"] = str(tmp_path / "libfeather_hip.so")
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        lines = {ln.split()[0]: ln for ln in r.stdout.splitlines() if ln.split() and ln.split()[0] in ("plain", "lrn", "lrnpool")}
-        assert "plain ran unmapped" in lines["plain"], r.stdout  # the switch alone opens nothing
-        for name in ("lrn", "lrnpool"):
-            if expect == "refused":
-                assert "refused" in lines[name] and "libfeather_lrn.so" in lines[name] and "code -1" in lines[name] and "unmapped" in lines[name], r.stdout
-            else:
-                assert lines[name] == f"{name} ran mapped", r.stdout
-
-
 def test_one_launch_per_layer_by_kernel_trace(cuda, tmp_path):
     """An LRN -> Pooling at fusion level 2, then a plain LRN, one Forward each in a fresh child process under rocprofv3 (kernel trace only),
     cut at the three marker launches around them: exactly one kernel each, under the names the route functions report."""
-    prof = shutil.which("rocprofv3")
-    assert prof, "rocprofv3 not found: the trace cannot be taken (a failure, not a skip)"
-    d, log = tmp_path / "trace", tmp_path / "trace.log"
-    cmd = ["timeout", "-k", "10", str(TRACE_TIMEOUT), prof, "--kernel-trace", "--output-format", "csv", "-d", str(d), "-o", "trace",
-           "--", sys.executable, os.path.join(HERE, "lrn_trace_child.py")]
-    with open(log, "w") as fh:
-        rc = subprocess.run(cmd, stdout=fh, stderr=subprocess.STDOUT, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT)).returncode
-    text = open(log).read()
-    assert rc == 0 and "child ok" in text, text[-3000:]
+    text, rows, _ = ktrace.trace("lrn_trace_child.py", [], tmp_path, TRACE_TIMEOUT)
     routes = [ln.split(" ", 1)[1] for ln in text.splitlines() if ln.startswith("route ")]
     assert routes == ["fhip::lrn_pool_lds_kernel<5>", "fhip::lrn_across_kernel<1, 5>"], text[-3000:]
-    kernels = []
-    for f in glob.glob(os.path.join(str(d), "**", "*kernel_trace.csv"), recursive=True):
-        with open(f, newline="") as fh:
-            kernels += [(int(r["Start_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(fh)]
-    kernels.sort()
-    marks = [t for t, k in kernels if "relu_kernel" in k]
-    assert len(marks) == 3, kernels  # the child separates its two Forwards with three fhip_relu launches
+    windows = ktrace.between(rows, 3)  # the child separates its two Forwards with three fhip_relu launches
     for which, route in enumerate(routes):
-        window = [k for t, k in kernels if marks[which] < t < marks[which + 1]]
+        window = windows[which]
         print(f"kernels of {'the fused LRN -> Pooling' if which == 0 else 'the plain LRN'}:", window)
         assert len(window) == 1 and route.replace(" ", "") in window[0].replace(" ", "").replace("void", ""), window

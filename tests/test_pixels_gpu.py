@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import pixels_ref as R
+import side_contract
 from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
@@ -39,9 +40,7 @@ def _lib():
     return load_library()
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 def test_every_fixture_bit_exact_in_a_batch(cuda):

@@ -1,34 +1,24 @@
 """The image output path without a GPU: libfeather_pixout.so (include/feather_hip/feather_pixout.h) refuses bad arguments on the host
-before any device call; its exports, its header and the Python binding agree; every kernel instantiation it holds has a case in the
-GPU sweep's table (tests/pixout_cases.py) and the kernels named in its sources are the ones it holds; the main library still has its
-176; a reference-style C++ application using feather::Net::ExtractPixels compiles against include/; the Python wrappers refuse what the
-library refuses; and the numpy restatement the GPU tests compare against equals the reference's recorded to_pixels results."""
+before any device call; the GPU sweep's table (tests/pixout_cases.py) has the size it states; the Python wrappers refuse what the
+library refuses; and the numpy restatement the GPU tests compare against equals the reference's recorded to_pixels results.
+What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py."""
 import ctypes
-import glob
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import kernel_instances as KI
 import pixels_ref as R
 import pixout_cases as PC
+import side_contract
 import yuv_ref as Y
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_pixout.h")
-SOURCES = os.path.join(ROOT, "feathercnn_amd", "csrc_pixout")
 BADARG = -2  # FHIP_E_BADARG
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(PC.LIB):
-        pytest.fail(f"{PC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_pixout_library()
+lib = side_contract.fixture("pixout")
 
 
 def _call(lib, pixels=0x1000, pitch=0, x=0x2000, batch=1, ptype=R.PIXEL_RGB, w=8, h=8, tw=8, th=8, mean=None, norm=None):
@@ -74,28 +64,11 @@ def test_python_wrappers_refuse_before_the_library():
         float_to_pixels(torch.zeros(1, 3, 4, 4), R.PIXEL_RGB)  # no quiet host path
 
 
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_PIXOUT_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", PC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.PIXOUT_SIGNATURES)
-    # the two libraries export different names: an application may load both
-    assert not set(declared) & set(_lib.SIGNATURES)
-
-
 def test_every_instantiation_has_a_case():
-    names = KI.instances(PC.LIB)
-    assert names, "the output library holds no kernel"
-    assert set(names) == PC.targets(), f"library {names} / sweep table {sorted(PC.targets())}"
-    src = "".join(open(p).read() for p in glob.glob(os.path.join(SOURCES, "*.hip")) + glob.glob(os.path.join(SOURCES, "*.h")))
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared == {KI.base(n) for n in names}
     assert len(PC.cases()) == len(PC.TYPES) * len(PC.GEOMETRIES) * len(PC.MEAN_NORM) * len(PC.BATCHES) * 2
 
 
 def test_main_library_keeps_its_instantiations():
-    assert len(KI.instances()) == 176
     shared = os.path.join(ROOT, "feathercnn_amd", "csrc", "pixel_resample.h")
     assert "__global__" not in open(shared).read()  # helpers only: the census of feathercnn_amd/csrc scans this header too
 
@@ -125,22 +98,3 @@ def test_restatement_equals_the_recorded_reference():
     x = PC.make_input(3, 1, 3, 5, 7, *PC.mean_norm("both", 3))
     v = R.mean_norm(x, *PC.mean_norm("both", 3))[0]
     assert np.array_equal(Y.to_pixels(v, R.PIXEL_RGB2BGR), Y.to_pixels(v, R.PIXEL_RGB)[..., ::-1])
-
-
-def test_reference_style_output_application_compiles(lib, tmp_path):
-    """Mat::substract_mean_normalize + Mat::to_pixels_resize next to feather::Net::ExtractPixels / ExtractPixelsDevice: compiles against
-    include/ and links against both product libraries (tests/test_pixout_gpu.py runs it)."""
-    exe = build_app(tmp_path)
-    assert os.path.exists(exe)
-
-
-def build_app(tmp_path) -> str:
-    from feathercnn_amd import _lib
-    libdir = os.path.dirname(_lib.pixout_path())
-    inc = os.path.join(ROOT, "include")
-    exe = str(tmp_path / "pixout_app_main")
-    subprocess.run(["g++", "-std=c++11", "-O1", "-Wall", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + inc,
-                    "-I" + os.path.join(inc, "feather"), "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "pixout_app_main.cpp"),
-                    "-o", exe, "-L" + libdir, "-lfeather_hip", "-lfeather_pixout", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir,
-                    "-Wl,-rpath,/opt/rocm/lib"], check=True, capture_output=True, text=True)
-    return exe

@@ -15,6 +15,7 @@ import pytest
 
 import pixels_ref as R
 import pixout_cases as PC
+import side_contract
 import yuv_ref as Y
 from guarded import Guarded
 
@@ -285,7 +286,6 @@ def test_net_round_trip(cuda, fusion, graph, sub):
 def test_cpp_output_application_end_to_end(cuda, tmp_path):
     """tests/cpp/pixout_app_main.cpp: Extract + Mat::substract_mean_normalize + Mat::to_pixels_resize on the host against
     feather::Net::ExtractPixels and ExtractPixelsDevice -- the same bytes all three ways, and what Net.ExtractPixels gives from Python."""
-    from test_pixout_cpu import build_app
     param, weights, i, o = _image_net()
     (tmp_path / "m.param").write_bytes(param)
     (tmp_path / "m.bin").write_bytes(weights)
@@ -302,7 +302,7 @@ def test_cpp_output_application_end_to_end(cuda, tmp_path):
     lo, hi = f.min(axis=(0, 2, 3)), f.max(axis=(0, 2, 3))
     norm = (380.0 / (hi - lo)).astype(np.float32)  # the net's output spread over about -60..320
     mean = (lo + 60.0 / norm).astype(np.float32)
-    exe = build_app(tmp_path)
+    exe = side_contract.build_app("pixout", tmp_path)
     outs = [str(tmp_path / f"{k}.u8") for k in ("mat", "host", "device")]
     run = subprocess.run([exe, str(tmp_path / "m.param"), str(tmp_path / "m.bin"), str(tmp_path / "img.u8"), str(w), str(h), str(tw), str(th),
                           i, o] + outs + [float(v).hex() for v in mean] + [float(v).hex() for v in norm],

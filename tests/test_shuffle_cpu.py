@@ -3,38 +3,26 @@
 Checks of the yardstick, which need no library and pass on any tree: tests/shuffle_ref.py equals torch's channel_shuffle / split on the CPU,
 `reverse` is the exact inverse, a composed table equals the three steps applied one by one, the restatement runs tiny_shuffle end to end.
 
-Checks of the feature: the library exports what its header and the Python binding declare and holds the six instantiations of the case
-table while the other five libraries keep theirs; bad arguments are refused on the host with the documented codes; feather::Net loads
+Checks of the feature: fhip_channel_map_route names the instantiation of the case table for every kind, plane and offset; bad arguments are refused on the host with the documented codes; feather::Net loads
 ShuffleChannel and Slice (the factory answered -200 before), reports route 103 from LoadParam on, refuses what the definition leaves out,
 and at fusion level 2 reports the Concat / ShuffleChannel / Slice runs of tiny_shuffle and of a ShuffleNet v2 unit as one layer each.
 Shapes: the runtime resolves a Slice through fhip_channel_slice_resolve, which is checked here against the restatement; the blob shapes
-after Reshape need device memory and are checked in tests/test_shuffle_gpu.py."""
+after Reshape need device memory and are checked in tests/test_shuffle_gpu.py.  What the library shares with the other run-time libraries -- its exports, the instantiations it holds, its route code, the build
+of its application, its last-error state -- is in tests/test_side_contract_cpu.py."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers
-import kernel_instances as KI
 import shuffle_cases as SC
 import shuffle_ref as R
+import side_contract
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "feather_hip", "feather_shuffle.h")
 BADARG = -2
-ROUTE_SHUFFLE = 103  # FHIP_NET_ROUTE_SHUFFLE
 NEW_MODELS = ["tiny_shuffle", "shufflenet_v2_x1_0", "shufflenet_v1_g3"]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(SC.LIB):
-        pytest.fail(f"{SC.LIB} is missing: run build() first")
-    from feathercnn_amd import _lib
-    return _lib.load_shuffle_library()
+lib = side_contract.fixture("shuffle")
 
 
 # ---- the definition ------------------------------------------------------------------------------------------------------------------
@@ -98,28 +86,7 @@ def test_composed_table_equals_the_steps_one_by_one():
 
 
 # ---- the library ---------------------------------------------------------------------------------------------------------------------
-def test_exports_header_and_binding_agree(lib):
-    from feathercnn_amd import _lib
-    declared = sorted(set(re.findall(r"FHIP_SHUFFLE_API\s+[\w\s\*]+?\b(fhip_\w+)\s*\(", open(HEADER).read())))
-    out = subprocess.run(["nm", "-D", "--defined-only", SC.LIB], capture_output=True, text=True, check=True).stdout
-    exported = sorted(s for s in re.findall(r"\s[TDB]\s+(\w+)$", out, re.M) if s.startswith("fhip_"))
-    assert declared and declared == exported == sorted(_lib.SHUFFLE_SIGNATURES)
-    for name in declared:
-        assert getattr(lib, name).argtypes is not None  # load_shuffle_library resolved and typed every one
-    others = set(_lib.SIGNATURES) | set(_lib.PIXOUT_SIGNATURES) | set(_lib.GCONV_SIGNATURES) | set(_lib.DECONV_SIGNATURES) | set(_lib.INORM_SIGNATURES)
-    assert not set(declared) & others  # an application may load all six
-    needed = subprocess.run(["readelf", "-d", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
-    assert "libfeather_shuffle" not in needed  # the main library reaches this one at run time only
-    import feathercnn_amd
-    assert callable(feathercnn_amd.channel_shuffle) and callable(feathercnn_amd.channel_slice) and callable(feathercnn_amd.channel_map)
-
-
 def test_instantiations_and_route_names(lib):
-    names = KI.instances(SC.LIB)
-    assert set(names) == SC.targets(), names
-    src = open(os.path.join(ROOT, "feathercnn_amd", "csrc_shuffle", "shuffle.hip")).read()
-    declared = set(re.findall(r"__global__\s+(?:__launch_bounds__\((?:[^()]|\([^()]*\))*\)\s+)?void\s+(\w+)", src))
-    assert declared == {KI.base(n) for n in names} == {"channel_map_kernel"}
     name = ctypes.create_string_buffer(96)
     for kind in (0, 1, 2):
         for h, w in SC.PLANES:
@@ -130,18 +97,6 @@ def test_instantiations_and_route_names(lib):
     seen = {SC.instance(k, h, w, [o]) for k in (0, 1, 2) for h, w in SC.PLANES for o in SC.OFFSETS}
     assert seen == SC.targets()  # the GPU sweep's shapes reach every instantiation
     assert lib.fhip_channel_map_route(3, 7, 7, None, 0, name, 96) == BADARG
-
-
-def test_other_libraries_keep_their_instantiations():
-    import deconv_cases as DC
-    import gconv_cases as GC
-    import inorm_cases as IC
-    assert len(KI.instances()) == 176
-    assert len(KI.instances(os.path.join(ROOT, "feathercnn_amd", "libfeather_pixout.so"))) == 6
-    assert set(KI.instances(GC.LIB)) == GC.targets()
-    assert set(KI.instances(DC.LIB)) == DC.targets()
-    assert set(KI.instances(IC.LIB)) == IC.targets()
-    assert "__global__" not in helpers.net_runtime_source()  # net.hip only routes
 
 
 def test_slice_resolve_matches_the_restatement(lib):
@@ -215,15 +170,6 @@ def test_load_param_refuses_what_the_definition_leaves_out(line, code):
     with pytest.raises(FeatherHipError) as e:
         net.LoadParam(_one(line, blobs=6))
     assert f"code {code}" in str(e.value), str(e.value)
-
-
-def test_route_code_is_named_in_the_header():
-    text = open(os.path.join(ROOT, "include", "feather_hip", "feather_net.h")).read()
-    m = re.search(r"#define\s+FHIP_NET_ROUTE_SHUFFLE\s+(\d+)", text)
-    assert m and int(m.group(1)) == ROUTE_SHUFFLE
-    from feathercnn_amd import net
-    assert net.ROUTE_SHUFFLE == ROUTE_SHUFFLE and net.ROUTE_NAMES[ROUTE_SHUFFLE] == "SHUFFLE"
-    assert len({net.ROUTE_SHUFFLE, net.ROUTE_INORM, net.ROUTE_DECONV, net.ROUTE_GCONV}) == 4
 
 
 def _fused_layers(param, weights, level):

@@ -11,8 +11,6 @@ The kernels only copy, so every comparison of a layer is bit for bit (int32 view
   of shufflenet_v2_x1_0); a net without these layers never opens the library.
 Each test prints its own figures."""
 import ctypes
-import csv
-import glob
 import os
 import shutil
 import subprocess
@@ -21,13 +19,14 @@ import sys
 import numpy as np
 import pytest
 
+import ktrace
 import shuffle_cases as SC
 import shuffle_ref as R
+import side_contract
 from guarded import CANARY, POISON
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
 TOL = 1e-4
 GUARD = 1 << 16  # floats on each side
 TRACE_TIMEOUT = 240
@@ -61,15 +60,10 @@ class Region:
         return self.raw[self.lo:self.lo + self.n].cpu().numpy().reshape(self.shape)
 
 
-@pytest.fixture(scope="module")
-def lib(cuda):
-    from feathercnn_amd import _lib
-    return _lib.load_shuffle_library()
+lib = side_contract.fixture("shuffle", gpu=True)
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 def _values(rng, shape):
@@ -372,27 +366,9 @@ def test_collapsed_run_equals_the_three_layers_bit_for_bit(cuda):
 
 
 def _trace(tmp_path, level):
-    prof = shutil.which("rocprofv3")
-    assert prof, "rocprofv3 not found: the trace cannot be taken (a failure, not a skip)"
-    d = tmp_path / f"trace{level}"
-    log = tmp_path / f"trace{level}.log"
-    cmd = ["timeout", "-k", "10", str(TRACE_TIMEOUT), prof, "--kernel-trace", "--memory-copy-trace", "--output-format", "csv", "-d", str(d), "-o", "trace",
-           "--", sys.executable, os.path.join(HERE, "shuffle_trace_child.py"), str(level)]
-    with open(log, "w") as fh:
-        rc = subprocess.run(cmd, stdout=fh, stderr=subprocess.STDOUT, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT)).returncode
-    text = open(log).read()
-    assert rc == 0 and "child ok" in text, text[-3000:]
-    kernels, copies = [], []
-    for f in glob.glob(os.path.join(str(d), "**", "*kernel_trace.csv"), recursive=True):
-        with open(f, newline="") as fh:
-            kernels += [(int(r["Start_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(fh)]
-    for f in glob.glob(os.path.join(str(d), "**", "*memory_copy_trace.csv"), recursive=True):
-        with open(f, newline="") as fh:
-            copies += [int(r["Start_Timestamp"]) for r in csv.DictReader(fh) if "DEVICE_TO_DEVICE" in (r.get("Direction") or "").upper()]
-    kernels.sort()
-    marks = [t for t, k in kernels if "relu_kernel" in k]
-    assert len(marks) == 2, kernels  # the child brackets its Forward with two fhip_relu launches
-    return [k for t, k in kernels if marks[0] < t < marks[1]], sum(marks[0] < t < marks[1] for t in copies)
+    _, rows, copies = ktrace.trace("shuffle_trace_child.py", [level], tmp_path, TRACE_TIMEOUT, copies=True)
+    (kernels,), (copied,) = ktrace.between(rows, 2, copies)  # the child brackets its Forward with two fhip_relu launches
+    return kernels, copied
 
 
 def test_launch_counts_of_one_v2_unit_by_kernel_trace(cuda, tmp_path):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import pixels_ref as R
+import side_contract
 import yuv_ref as Y
 from guarded import Guarded
 
@@ -44,9 +45,7 @@ def _frames(rng, n, w, h):
     return rng.integers(0, 256, (n, h * 3 // 2, w), dtype=np.uint8)
 
 
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = side_contract.stream
 
 
 def test_every_fixture_bit_exact_in_a_batch(cuda):
