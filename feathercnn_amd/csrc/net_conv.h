@@ -113,20 +113,27 @@ struct SideConv
 // libfeather_qconv.so (qconv_api) with route code FHIP_NET_ROUTE_QCONV.  Init and Forward do not fit SideConv (int8 weights, the
 // dequantisation scales and the input scale ride along), so those calls stand here, once for both layer types.  The layer fills `q`
 // at Reshape; a BatchNorm / Scale fold goes into d[] and the bias as feather_qconv.h defines it, never into the weights.
+// A layer whose input or output is a q8 blob (Blob::q8; the output of a layer with int8_scale_term 101 .. 200 in a net with
+// fhip_net_set_requantized is one) makes the same calls on libfeather_q8.so (q8_api) with `q8`, which is `q` plus the two forms; the route
+// code stays FHIP_NET_ROUTE_QCONV.
 struct QuantRoute
 {
     fhip_qconv_param q = {};
+    fhip_q8_param q8 = {};
+    bool on_q8 = false; // this shape runs on libfeather_q8.so (Reshape)
     int scale_term = 0;
     std::vector<signed char> w;
     std::vector<float> s_w, b;
-    float s_in = 0.f;
+    float s_in = 0.f, s_out = 0.f;
     DeviceVec packed, d, bias;
     size_t packed_bytes = 0;
     BuiltFor built;
 
     // ncnn's param 8 of the layer, 0 where the file does not set it
     int read_scale_term(const ParamDict& pd) { return scale_term = pd.get(8, 0); }
-    // the .bin of a quantised layer: int8-tagged weights, the bias, K weight scales, one input scale (the last three raw fp32)
+    bool requant() const { return scale_term > 100; } // the output is a q8 blob
+    // the .bin of a quantised layer: int8-tagged weights, the bias, K weight scales, one input scale (the last three raw fp32); behind them
+    // the output scale of a requantised layer
     int load(const Layer* l, ModelBin& mb, size_t wsize, int K, bool bias_term)
     {
         built = BuiltFor();
@@ -140,6 +147,10 @@ struct QuantRoute
         if (!std::isfinite(s_in) || !(s_in > 0.f)) return failf(NET_E_SHAPE, "layer %s: the int8 input scale must be finite and > 0", l->name.c_str());
         for (float v : s_w)
             if (!std::isfinite(v) || v < 0.f) return failf(NET_E_SHAPE, "layer %s: an int8 weight scale is not finite or is negative", l->name.c_str());
+        if (!requant()) return 0;
+        if ((rc = mb.load(1, 1, one))) return rc;
+        s_out = one[0];
+        if (!std::isfinite(s_out) || !(s_out > 0.f)) return failf(NET_E_SHAPE, "layer %s: the int8 output scale must be finite and > 0", l->name.c_str());
         return 0;
     }
     // the tail of Reshape, with the geometry and the input size in `q`: SideConv's, on the library's own rule for the output size
@@ -148,17 +159,29 @@ struct QuantRoute
         q.dilation_h = q.dilation_w = 1;
         q.int8_scale_term = scale_term;
         size_t scratch = 0;
-        return SideConv<QconvApi, fhip_qconv_param>::reshape<true>(l, qconv_api(), q, "int8 convolution refused: ", &scratch, &packed_bytes);
+        on_q8 = requant() || l->bottoms[0]->q8;
+        if (!on_q8) return SideConv<QconvApi, fhip_qconv_param>::reshape<true>(l, qconv_api(), q, "int8 convolution refused: ", &scratch, &packed_bytes);
+        static_assert(sizeof(fhip_q8_param) == sizeof(fhip_qconv_param) + 2 * sizeof(int), "fhip_q8_param is fhip_qconv_param and the two forms");
+        memcpy(&q8, &q, sizeof(q));
+        q8.input_int8 = l->bottoms[0]->q8 ? 1 : 0;
+        q8.output_int8 = requant() ? 1 : 0;
+        const int rc = SideConv<Q8Api, fhip_q8_param>::reshape<true>(l, q8_api(), q8, "int8 convolution refused: ", &scratch, &packed_bytes);
+        q.output_h = q8.output_h, q.output_w = q8.output_w;
+        return rc;
     }
+    // what the packed weights were built for: the library and the forms pick the layout
+    int layout() const { return on_q8 ? 1 + q8.input_int8 + 2 * q8.output_int8 : 0; }
     int init(Layer* l, const AffineFold& fold, hipStream_t s)
     {
-        const BuiltFor want{FHIP_NET_ROUTE_QCONV, 0, packed_bytes};
+        const BuiltFor want{FHIP_NET_ROUTE_QCONV, layout(), packed_bytes};
         if (built == want) return 0;
-        const QconvApi* api = qconv_api();
-        if (!api) return FHIP_E_UNSUPPORTED;
+        const QconvApi* api = on_q8 ? nullptr : qconv_api();
+        const Q8Api* api8 = on_q8 ? q8_api() : nullptr;
+        if (!api && !api8) return FHIP_E_UNSUPPORTED;
         const int K = q.output_channels;
         std::vector<float> dq(K), bq = b;
-        int rc = l->side(api, [&](const QconvApi* a) { return a->dequant_scales(dq.data(), s_w.data(), K, s_in); });
+        int rc = on_q8 ? l->side(api8, [&](const Q8Api* a) { return a->dequant_scales(dq.data(), s_w.data(), K, s_in); })
+                       : l->side(api, [&](const QconvApi* a) { return a->dequant_scales(dq.data(), s_w.data(), K, s_in); });
         if (rc) return rc;
         if (!fold.empty())
         {
@@ -169,11 +192,12 @@ struct QuantRoute
                 const float scaled = bq[k] * fold.mul[k]; // rounded before the sum: no contraction
                 bq[k] = scaled + fold.add[k];
             }
-            q.bias_term = 1;
+            q.bias_term = q8.bias_term = 1;
         }
         // the raw copy is int8; d[] goes up behind the pack call, in front of the bias
         rc = stage_weights(w, packed, packed_bytes, q.bias_term ? &bq : nullptr, bias, s, [&](const signed char* raw) {
-            const int e = l->side(api, [&](const QconvApi* a) { return a->init(&q, packed.d, raw, s); });
+            const int e = on_q8 ? l->side(api8, [&](const Q8Api* a) { return a->init(&q8, packed.d, raw, s); })
+                                : l->side(api, [&](const QconvApi* a) { return a->init(&q, packed.d, raw, s); });
             return e ? e : d.upload(dq.data(), dq.size(), s);
         });
         if (!rc) built = want;
@@ -181,6 +205,10 @@ struct QuantRoute
     }
     int forward(const Layer* l, hipStream_t s) const
     {
+        if (on_q8)
+            return l->side(q8_api(), [&](const Q8Api* a) {
+                return a->forward(&q8, l->bottoms[0]->n, l->tops[0]->data, l->bottoms[0]->data, packed.d, nullptr, d.d, q8.bias_term ? bias.d : nullptr, s_in, s_out, s);
+            });
         return l->side(qconv_api(), [&](const QconvApi* a) {
             return a->forward(&q, l->bottoms[0]->n, l->tops[0]->data, l->bottoms[0]->data, packed.d, nullptr, d.d, q.bias_term ? bias.d : nullptr, s_in, s);
         });
@@ -277,6 +305,8 @@ struct ConvLayer : Layer
 
     bool needs_weights() const override { return true; }
     ConvLayer* as_conv() override { return this; }
+    bool reads_q8() const override { return route == ROUTE_INT8; }
+    bool writes_q8() const override { return route == ROUTE_INT8 && qr.requant(); }
     bool first_candidate() const
     {
         return p.kernel_h == 3 && p.kernel_w == 3 && p.stride_h == 1 && p.stride_w == 1 && p.group == 1 && p.input_channels >= 2 && p.input_channels <= 4 && p.pad_left == 1 &&
@@ -307,8 +337,9 @@ struct ConvLayer : Layer
         qr.scale_term = pd.get(8, 0);
         const bool quant = qr.scale_term != 0 && net && net->quantized;
         if (qr.scale_term && !quant) return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8 convolution is not supported", name.c_str());
-        if (quant && (qr.scale_term < 0 || qr.scale_term > 100))
+        if (quant && (qr.scale_term < 0 || (qr.scale_term > 100 && !net->requantized)))
             return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8_scale_term %d (requantised int8 output) is not supported", name.c_str(), qr.scale_term);
+        if (quant && qr.scale_term > 200) return failf(NET_E_UNKNOWN_LAYER, "layer %s: int8_scale_term %d is not one of 0 .. 200", name.c_str(), qr.scale_term);
         if (quant && atrous) return failf(NET_E_UNKNOWN_LAYER, "layer %s: a dilated int8 convolution is not supported", name.c_str());
         p.kernel_w = pd.get(1, 0);
         p.kernel_h = pd.get(11, p.kernel_w);

@@ -15,8 +15,11 @@ struct Blob
     Blob* alias = nullptr; // data is another blob's
     bool fused_away = false;
     bool chained = false; // fusion level 3: lives only as the next layer's Winograd-domain input (plan_chains); shape kept, no storage
+    bool q8 = false;      // a q8 tensor (feather_q8.h: signed char [n][ceil(c / 16)][h][w][16]) instead of fp32 NCHW; reshape_all sets it before the producer's Reshape
 
     size_t count() const { return (size_t)n * c * h * w; }
+    size_t q8_bytes() const { return (size_t)n * ((c + 15) / 16) * h * w * 16; }
+    size_t floats() const { return q8 ? q8_bytes() / 4 : count(); } // the storage, in floats
     int reshape(int n_, int c_, int h_, int w_)
     {
         n = n_;
@@ -27,13 +30,13 @@ struct Blob
         // a blob the previous plan chained away has no storage and, as a rule, will have none after this Reshape either: plan_chains
         // allocates it afterwards if the new shapes un-chain it (no device malloc + free per chained blob and shape change)
         if (chained && !data) return 0;
-        if (count() > capacity)
+        if (floats() > capacity)
         {
             if (data && capacity) (void)hipFree(data);
             data = nullptr;
             capacity = 0;
-            FHIP_CHECK_HIP(hipMalloc((void**)&data, count() * sizeof(float)));
-            capacity = count();
+            FHIP_CHECK_HIP(hipMalloc((void**)&data, floats() * sizeof(float)));
+            capacity = floats();
         }
         return 0;
     }
@@ -119,6 +122,10 @@ struct Layer
     virtual EltwiseLayer* as_eltwise() { return nullptr; }   // Eltwise
     virtual InterpLayer* as_interp() { return nullptr; }     // Interp
     virtual const float* relu_slope() const { return nullptr; } // ReLU: its slope
+    // q8 blobs (Blob::q8, the int8 activation between two int8 layers): a layer that can read one says so, every other layer that meets
+    // one is refused by reshape_all; writes_q8() is asked there too, after the layer's bottoms are settled and before its Reshape
+    virtual bool reads_q8() const { return false; }
+    virtual bool writes_q8() const { return false; }
     // The one form of a call into a side library: FHIP_E_UNSUPPORTED where the library is missing (side_api has set the message), else
     // the call's code -- `code` in its place, for an entry point that only says yes or no -- with the library's message behind the
     // layer's name and `prefix`.
@@ -175,6 +182,7 @@ struct Net
     bool dilated = false;         // fhip_net_set_dilated: a Convolution with dilation > 1 is loaded (libfeather_atrous.so) instead of refused
     bool extended = false;        // fhip_net_set_extended_layers: Interp, HardSwish (libfeather_resample.so) and LRN (libfeather_lrn.so) are loaded instead of refused
     bool quantized = false;       // fhip_net_set_quantized: Convolution / InnerProduct layers with int8 weights (8=int8_scale_term) are loaded (libfeather_qconv.so) instead of refused
+    bool requantized = false;     // fhip_net_set_requantized: an int8 Convolution with int8_scale_term 101 .. 200 (requantised int8 output) is loaded (libfeather_q8.so) instead of refused
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;
     // fusion level 3 (plan_chains): runs of Winograd layers hand their transformed input from one to the next; the arena then holds two V

@@ -107,9 +107,25 @@ struct ReluLayer : Layer
         slope = pd.get(0, 0.f);
         return 0;
     }
-    int Reshape() override { return slope == 0.f ? Layer::Reshape() : reshape_with(inorm_api()); }
+    // a plain ReLU on a q8 blob is max(q, 0) on its bytes (libfeather_q8.so): quantise commutes with it
+    bool reads_q8() const override { return slope == 0.f; }
+    bool writes_q8() const override { return bottoms[0]->q8; }
+    int Reshape() override
+    {
+        if (slope != 0.f) return reshape_with(inorm_api());
+        if (!bottoms[0]->q8) return Layer::Reshape();
+        if (!q8_api()) return FHIP_E_UNSUPPORTED; // (message set by side_api)
+        // in place where this layer alone reads the blob and the blob owns its bytes (a Split top's are its siblings' too): the top shares
+        // them and no second q8 blob exists; else a top of its own
+        Blob* b = bottoms[0];
+        if (tops.size() != 1 || bottoms.size() != 1) return failf(NET_E_BASE_RESHAPE, "layer %s: base Reshape needs 1 bottom and 1 top", name.c_str());
+        if (b->alias || readers(*net, b).count != 1) return Layer::Reshape(); // (exact readers: what shares b reads it as a Split does, by name)
+        tops[0]->share(b);
+        return 0;
+    }
     int Forward(hipStream_t s) override
     {
+        if (bottoms[0]->q8) return side(q8_api(), [&](const Q8Api* api) { return api->relu(tops[0]->data, bottoms[0]->data, bottoms[0]->q8_bytes(), s); });
         if (slope == 0.f) return fhip_relu(tops[0]->data, bottoms[0]->data, bottoms[0]->count(), s);
         const Blob* b = bottoms[0];
         return side(inorm_api(), [&](const InormApi* api) {
@@ -257,6 +273,9 @@ struct PoolingLayer : Layer
     fhip_pool_param q;
     PoolingLayer() { memset(&q, 0, sizeof(q)); }
     PoolingLayer* as_pooling() override { return this; }
+    // a max pooling on a q8 blob is the byte-wise max (libfeather_q8.so): quantise commutes with it; its top is q8
+    bool reads_q8() const override { return q.pooling_type == 0; }
+    bool writes_q8() const override { return bottoms[0]->q8; }
     int LoadParam(const ParamDict& pd) override // pooling_layer.h:90-107
     {
         q.pooling_type = pd.get(0, 0);
@@ -281,9 +300,14 @@ struct PoolingLayer : Layer
         int rc = fhip_pooling_output_dim(&q, &oh, &ow);
         if (rc) return rc;
         if (oh < 1 || ow < 1) return failf(NET_E_SHAPE, "layer %s: empty pooling output", name.c_str());
+        if (b->q8 && !q8_api()) return FHIP_E_UNSUPPORTED; // (message set by side_api)
         return tops[0]->reshape(b->n, b->c, oh, ow);
     }
-    int Forward(hipStream_t s) override { return fhip_pooling(&q, bottoms[0]->n, tops[0]->data, bottoms[0]->data, s); }
+    int Forward(hipStream_t s) override
+    {
+        if (bottoms[0]->q8) return side(q8_api(), [&](const Q8Api* api) { return api->max_pool(&q, bottoms[0]->n, tops[0]->data, bottoms[0]->data, s); });
+        return fhip_pooling(&q, bottoms[0]->n, tops[0]->data, bottoms[0]->data, s);
+    }
 };
 
 struct SoftmaxLayer : Layer
@@ -1147,6 +1171,8 @@ struct ChannelMapLayer : Layer
 
 struct SplitLayer : Layer
 {
+    bool reads_q8() const override { return true; } // the tops share the blob, whatever it holds
+    bool writes_q8() const override { return bottoms[0]->q8; }
     int Reshape() override
     {
         for (Blob* t : tops) t->share(bottoms[0]);

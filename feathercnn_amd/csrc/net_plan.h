@@ -477,12 +477,40 @@ static int plan_siblings(Net& net)
     return 0;
 }
 
+// The layer a q8 blob's bytes come from: the requantised convolution above the ReLU, max Pooling and Split layers that pass them on.
+static const Layer* q8_producer(Net& net, const Blob* b)
+{
+    Layer* found = nullptr;
+    for (size_t hops = 0; hops <= net.layers.size(); ++hops)
+    {
+        Layer* writer = nullptr;
+        for (auto& l : net.layers)
+            for (const Blob* t : l->tops)
+                if (t == b) writer = l.get();
+        if (!writer) break;
+        found = writer;
+        if (writer->bottoms.empty() || !writer->bottoms[0]->q8 || writer->as_conv()) break;
+        b = writer->bottoms[0];
+    }
+    return found;
+}
+
 static int reshape_all(Net& net)
 {
     net.drop_graph();
     size_t need = 0;
     for (auto& l : net.layers)
     {
+        // q8 blobs: a layer that cannot read one is refused; whether the layer's tops are q8 is settled before its Reshape sizes them
+        for (const Blob* b : l->bottoms)
+            if (b->q8 && !l->reads_q8())
+            {
+                const Layer* from = q8_producer(net, b);
+                return failf(NET_E_TOPOLOGY, "blob %s holds the int8 output of layer %s, which %s layer %s cannot read", b->name.c_str(),
+                             from ? from->name.c_str() : "?", l->type.c_str(), l->name.c_str());
+            }
+        const bool q8 = !l->bottoms.empty() && l->writes_q8();
+        for (Blob* t : l->tops) t->q8 = q8;
         const int rc = l->Reshape();
         if (rc) return rc;
     }

@@ -28,6 +28,7 @@
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
 #include "feather_hip/feather_lrn.h" // declarations only: the library is opened at run time (lrn_api)
 #include "feather_hip/feather_net.h"
+#include "feather_hip/feather_q8.h" // declarations only: the library is opened at run time (q8_api)
 #include "feather_hip/feather_qconv.h" // declarations only: the library is opened at run time (qconv_api)
 #include "feather_hip/feather_resample.h" // declarations only: the library is opened at run time (resample_api)
 #include "feather_hip/feather_shuffle.h" // declarations only: the library is opened at run time (shuffle_api)
@@ -281,6 +282,29 @@ struct QconvApi
     }
 };
 static const QconvApi* qconv_api() { return side_api<QconvApi>(); }
+
+// libfeather_q8.so, the int8 layers of a net with fhip_net_set_requantized whose input, output or both are q8 blobs, and the ReLU and max
+// Pooling layers between them
+struct Q8Api
+{
+    decltype(&fhip_q8_assign_output_dim) assign_output_dim = nullptr;
+    decltype(&fhip_q8_supported) supported = nullptr;
+    decltype(&fhip_q8_get_buffer_size) get_buffer_size = nullptr;
+    decltype(&fhip_q8_init) init = nullptr;
+    decltype(&fhip_q8_dequant_scales) dequant_scales = nullptr;
+    decltype(&fhip_q8_forward) forward = nullptr;
+    decltype(&fhip_q8_relu_forward) relu = nullptr;
+    decltype(&fhip_q8_max_pool_forward) max_pool = nullptr;
+    decltype(&fhip_q8_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_q8.so", "an int8 layer with int8 input or output", "feather_q8.h",
+                {{&assign_output_dim, "fhip_q8_assign_output_dim"}, {&supported, "fhip_q8_supported"}, {&get_buffer_size, "fhip_q8_get_buffer_size"},
+                 {&init, "fhip_q8_init"}, {&dequant_scales, "fhip_q8_dequant_scales"}, {&forward, "fhip_q8_forward"}, {&relu, "fhip_q8_relu_forward"},
+                 {&max_pool, "fhip_q8_max_pool_forward"}, {&last_error, "fhip_q8_last_error"}}};
+    }
+};
+static const Q8Api* q8_api() { return side_api<Q8Api>(); }
 
 // libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases (plan_chains).  The canvas form is a
 // faster way to run the same run of layers, not a layer type: a net that qualifies and cannot find the library fails at plan_chains.

@@ -29,27 +29,12 @@
 
 #include "feather_hip/feather_qconv.h"
 #include "direct_conv.h"
+#include "int8_rules.h"
 
 namespace fhip
 {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// feather_qconv.h "Quantise an input value"
-__device__ __forceinline__ int quantise(float x, float s_in)
-{
-    const float t = __fmul_rn(x, s_in);
-    const float r = fminf(fmaxf(roundf(t), -127.f), 127.f);
-    return t != t ? 0 : (int)r;
-}
-
-// feather_qconv.h "Dequantise"
-__device__ __forceinline__ float dequantise(int acc, float d, const float* bias, int k, int relu)
-{
-    float y = __fmul_rn((float)acc, d); // v_cvt_f32_i32 rounds to nearest even
-    if (bias) y = __fadd_rn(y, bias[k]);
-    return relu ? fmaxf(y, 0.f) : y;
-}
 
 __global__ __launch_bounds__(256) void quantize_kernel(signed char* out, const float* in, unsigned count, float s_in)
 {
@@ -72,8 +57,6 @@ struct QDirectArgs
     int relu;
     unsigned total; // lanes: batch * Ho * Wo (depthwise: batch * C * Ho * strips)
 };
-
-__device__ __forceinline__ int byte_of(int w, int k) { return (int)(signed char)((unsigned)w >> (8 * k)); }
 
 // ---- the generic route: y[n][g * Kg + chunk * KT .. + KT)[oy][ox]; lane i of [batch][Ho][Wo], blockIdx.y = (group, chunk) ------------
 template <int KT>
@@ -356,8 +339,6 @@ __global__ __launch_bounds__(256) void qconv_pack_mfma_kernel(int* packed, const
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static bool good_input_scale(float s) { return std::isfinite(s) && s > 0.f; }
-
 static int check_geometry(const fhip_qconv_param* p)
 {
     const int rc = check_sizes(p);
@@ -612,19 +593,7 @@ int fhip_qconv_get_buffer_size(const fhip_qconv_param* param, int batch, size_t*
 
 int fhip_qconv_init(const fhip_qconv_param* param, void* packed, const signed char* kernel, void* stream) { return do_init(param, packed, kernel, stream, nullptr); }
 
-int fhip_qconv_dequant_scales(float* d, const float* s_w, int K, float s_in)
-{
-    if (!d || !s_w || K < 1) return fail(FHIP_E_BADARG, "null d / s_w or K < 1");
-    if (!good_input_scale(s_in)) return fail(FHIP_E_BADARG, "s_in must be finite and > 0");
-    for (int k = 0; k < K; ++k)
-        if (!std::isfinite(s_w[k]) || s_w[k] < 0.f) return fail(FHIP_E_BADARG, "a weight scale is not finite or is negative");
-    for (int k = 0; k < K; ++k)
-    {
-        const float prod = s_in * s_w[k]; // rounded to fp32 before the reciprocal
-        d[k] = s_w[k] == 0.f ? 0.f : 1.0f / prod;
-    }
-    return FHIP_OK;
-}
+int fhip_qconv_dequant_scales(float* d, const float* s_w, int K, float s_in) { return int8_dequant_scales(d, s_w, K, s_in); }
 
 int fhip_qconv_forward(const fhip_qconv_param* param, int batch, float* out, const float* in, const void* packed, float* /*scratch*/, const float* d,
                        const float* bias, float s_in, void* stream)

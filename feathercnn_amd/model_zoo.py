@@ -36,7 +36,7 @@ def quantize_weights(w, cout):
 
 
 class GraphBuilder:
-    def __init__(self, seed: int = 1234, dry: bool = False, quant=None):
+    def __init__(self, seed: int = 1234, dry: bool = False, quant=None, requant=None):
         """dry=True: build the .param only and count the .bin bytes (``nbytes``) without drawing any weights.
         quant: None writes fp32 layers; a dict {layer name: input scale} makes conv() and fc() write int8 layers (param 8=1: int8-tagged
         weights quantised per output channel, the bias, the weight scales, one input scale; a name the dict lacks gets QUANT_DEFAULT_SCALE).
@@ -44,6 +44,7 @@ class GraphBuilder:
         conv(), fc() and se_block() take a `quant=` of their own for ONE layer of an otherwise fp32 (or int8) net: None keeps the build's
         setting, False writes fp32, True int8 at QUANT_DEFAULT_SCALE, a number int8 at that input scale."""
         self.quant = quant
+        self.requant = requant  # {layer name: output scale}: conv() writes those layers of an int8 build with a requantised int8 output
         self.trace = None  # a list: conv / fc / relu / bn / scale / pool record themselves for numpy_forward (input_scales)
         self.rng = np.random.default_rng(seed)
         self.lines: list[str] = []
@@ -84,8 +85,9 @@ class GraphBuilder:
             return None
         return QUANT_DEFAULT_SCALE if quant is True else float(quant)
 
-    def _weights(self, name, w, cout, b, s_in=None):
-        """The .bin of a conv / fc layer: tagged fp32 weights and the raw bias, or (with an input scale `s_in`) the int8 form (see __init__)."""
+    def _weights(self, name, w, cout, b, s_in=None, s_out=None):
+        """The .bin of a conv / fc layer: tagged fp32 weights and the raw bias, or (with an input scale `s_in`) the int8 form (see __init__);
+        with `s_out` one more raw fp32 behind it, the output scale of a requantised layer."""
         if s_in is None:
             self._tagged(w)
             if b is not None:
@@ -101,6 +103,8 @@ class GraphBuilder:
             self._raw(b)
         self._raw(s_w)
         self._raw(1 if self.dry else np.array([s_in], np.float32))
+        if s_out is not None:
+            self._raw(1 if self.dry else np.array([s_out], np.float32))
 
     def _uniform(self, n, lo, hi, scale=None):
         if self.dry:
@@ -112,7 +116,11 @@ class GraphBuilder:
     def input(self, name, c, h, w):
         return self.layer("Input", name, [], [name], {0: w, 1: h, 2: c})
 
-    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None, dilation=1, gain=1.0, quant=None):
+    def conv(self, name, bottom, cin, cout, k, s=1, p=0, group=1, bias=True, top=None, type_=None, dilation=1, gain=1.0, quant=None, requant=None):
+        """requant=<scale>: an int8 layer whose output is requantised to int8 at that scale (param 8=101 and one more scale in the .bin, what
+        ncnn2int8's fuse_requantize writes); a net that holds one needs Net.SetQuantized(True) and Net.SetRequantized(True)."""
+        if requant is None and self.requant:
+            requant = self.requant.get(name)
         fan_in = cin // group * k * k
         wsize = cout * (cin // group) * k * k
         type_ = type_ or ("ConvolutionDepthWise" if group > 1 else "Convolution")  # what ncnn's converter writes; both load alike
@@ -121,11 +129,13 @@ class GraphBuilder:
             params = {0: cout, 1: k, 2: dilation, 3: s, 4: p, 5: int(bias), 6: wsize, 7: group}
         s_in = self._scale_of(name, quant)
         if s_in is not None:
-            params[8] = 1
+            params[8] = 1 if requant is None else 101
+        elif requant is not None:
+            raise ValueError(f"layer {name}: only an int8 layer has a requantised output")
         top = self.layer(type_, name, [bottom], [top or name], params)
         w = self._uniform(wsize, -1, 1, np.sqrt(6.0 / fan_in) * gain)
         b = self._uniform(cout, -0.1, 0.1) if bias else None
-        self._weights(name, w, cout, b, s_in)
+        self._weights(name, w, cout, b, s_in, None if requant is None else float(requant))
         if self.trace is not None:
             self._note("conv", name, bottom, top, dict(w=w.reshape(cout, cin // group, k, k), b=b, s=s, p=p, group=group))
         return top
@@ -408,8 +418,80 @@ def tiny_quant(seed=29, size=16, dry=False):
     return build(scales).finish() + ("data", "fc")
 
 
-def vgg16(seed=1234, classes=1000, size=224, dry=False, quant=None):
-    g = GraphBuilder(seed, dry, quant)
+# The _int8 nets with their chains of int8 convolutions requantised (Net.SetQuantized(True) and Net.SetRequantized(True)), up to the last
+# int8 convolution in front of an fp32 reader, every output scale the default input scale of its readers (what fuse_requantize writes): nets
+# for timing.  Each equals its _int8 build bit for bit.  Those with a BatchNorm behind the requantised layers need fusion level >= 2.
+def _requant(names):
+    return dict.fromkeys(names, QUANT_DEFAULT_SCALE)
+
+
+def vgg16_int8_rq(seed=1234, classes=1000, size=224, dry=False):
+    """Every convolution but conv5_3, whose reader (through pool5) is the InnerProduct fc6."""
+    names = [f"conv{s}_{i}" for s, n in enumerate((2, 2, 3, 3, 3), 1) for i in range(1, n + 1)]
+    return vgg16(seed, classes, size, dry, quant={}, requant=_requant(names[:-1]))
+
+
+def resnet50_int8_rq(seed=1234, classes=1000, size=224, dry=False):
+    """conv1 (read through pool1 and res2a's Split by two int8 convolutions) and branch2a / branch2b of every block; branch2c and branch1
+    stay fp32-out for the Eltwise.  Fusion level >= 2."""
+    tags = [f"res{si + 2}{chr(ord('a') + b)}" for si, blocks in enumerate((3, 4, 6, 3)) for b in range(blocks)]
+    return resnet50(seed, classes, size, dry, quant={}, requant=_requant(["conv1"] + [t + br for t in tags for br in ("_branch2a", "_branch2b")]))
+
+
+def mobilenet_v1_int8_rq(seed=1234, classes=1000, size=224, dry=False):
+    """Every convolution but conv14_pw, whose reader is the average pooling.  Fusion level >= 2."""
+    names = ["conv1"] + [f"conv{i}_{k}" for i in range(2, 15) for k in ("dw", "pw")]
+    return mobilenet_v1(seed, classes, size, dry, quant={}, requant=_requant(names[:-1]))
+
+
+def tiny_requant(seed=31, size=16, dry=False, twin=False, mismatch=None, bn=True, fc=True):
+    """tiny_quant's layers with the activations between the int8 convolutions kept int8 (Net.SetQuantized(True) and
+    Net.SetRequantized(True)): conv1, conv2, conv3 (BatchNorm + Scale + ReLU tail) and dw have a requantised output (8=101), at the input
+    scale of their readers as ncnn2int8's fuse_requantize writes it.  The readers are reached through a ReLU (conv2, pw), through a 2x2 max
+    pooling (conv3) and through a Split with two int8 readers (dw and the 1x1 `side`); pw and side write fp32 for the Eltwise, the pooling
+    and the InnerProduct behind them.  The BatchNorm behind conv3 exists only folded: the net needs fusion level >= 2.
+    twin=True: the same model with 100 subtracted from those terms and the extra scales removed (SetQuantized alone): every fp32 blob of
+    the two is equal bit for bit.  mismatch=<layer>: that reader's input scale is multiplied by 1.25, so it differs from its producer's
+    output scale, and the net differs from the twin.  bn=False: without the BatchNorm and Scale, a net every fusion level loads.  fc=False: without the InnerProduct, a net that takes any
+    input size (the output is `pool`)."""
+    def build(quant, outs=None, trace=False):
+        g = GraphBuilder(seed, dry, quant=quant)
+        g.trace = [] if trace else None
+        q = (lambda reader: None) if outs is None else (lambda reader: outs[reader])
+        x = g.input("data", 3, size, size)
+        x = g.relu("relu1", g.conv("conv1", x, 3, 16, 3, 1, 1, requant=q("conv2")))
+        x = g.relu("relu2", g.conv("conv2", x, 16, 32, 3, 1, 1, requant=q("conv3")))
+        x = g.pool("pool2", x, 2, 2)
+        x = g.conv("conv3", x, 32, 32, 3, 1, 1, requant=q("dw"))
+        x = g.relu("conv3_relu", g.scale("conv3_scale", g.bn("conv3_bn", x, 32), 32) if bn else x)
+        a, b = (x, x) if trace else g.split("split", x)  # (the calibration run has no Split and no sum: it draws the same weights)
+        a = g.relu("relu_dw", g.conv("dw", a, 32, 32, 3, 1, 1, group=32, requant=q("pw")))
+        a = g.relu("relu_pw", g.conv("pw", a, 32, 24, 1, bias=False))
+        b = g.conv("side", b, 32, 24, 1)
+        x = g.pool("pool", a if trace else g.eltwise("sum", a, b), 2, 2)
+        if fc:
+            g.fc("fc", x, 24 * (size // 4) ** 2, 10)
+        return g
+    readers = ("conv2", "conv3", "dw", "pw")
+    out = "fc" if fc else "pool"
+    if dry:
+        return build({}, None if twin else dict.fromkeys(readers, 1.0)).finish() + ("data", out)
+    calib = np.random.default_rng(seed + 1).uniform(-1, 1, (4, 3, size, size)).astype(np.float32)
+    scales = input_scales(build(None, trace=True).trace, "data", calib)
+    scales["side"] = scales["dw"]  # one output scale serves both readers of the Split
+    outs = {r: scales[r] for r in readers}  # fuse_requantize: a producer's output scale is its reader's input scale
+    if mismatch:
+        scales[mismatch] = float(np.float32(scales[mismatch] * 1.25))
+    return build(scales, None if twin else outs).finish() + ("data", out)
+
+
+def tiny_requant_twin(seed=31, size=16, dry=False):
+    """tiny_requant's twin: fp32 between the int8 layers (SetQuantized alone)."""
+    return tiny_requant(seed, size, dry, twin=True)
+
+
+def vgg16(seed=1234, classes=1000, size=224, dry=False, quant=None, requant=None):
+    g = GraphBuilder(seed, dry, quant, requant)
     x = g.input("data", 3, size, size)
     cin = 3
     for stage, (n, c) in enumerate([(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)], 1):
@@ -424,9 +506,9 @@ def vgg16(seed=1234, classes=1000, size=224, dry=False, quant=None):
     return g.finish() + ("data", "prob")
 
 
-def resnet50(seed=1234, classes=1000, size=224, dry=False, quant=None):
+def resnet50(seed=1234, classes=1000, size=224, dry=False, quant=None, requant=None):
     """Caffe ResNet-50: conv-BN-Scale-ReLU, stride on the first 1x1 of each stage, explicit Split for the shortcut."""
-    g = GraphBuilder(seed, dry, quant)
+    g = GraphBuilder(seed, dry, quant, requant)
     x = g.input("data", 3, size, size)
     x = g.conv_bn_relu("conv1", x, 3, 64, 7, 2, 3)
     x = g.pool("pool1", x, 3, 2)
@@ -448,8 +530,8 @@ def resnet50(seed=1234, classes=1000, size=224, dry=False, quant=None):
     return g.finish() + ("data", "prob")
 
 
-def mobilenet_v1(seed=1234, classes=1000, size=224, dry=False, quant=None):
-    g = GraphBuilder(seed, dry, quant)
+def mobilenet_v1(seed=1234, classes=1000, size=224, dry=False, quant=None, requant=None):
+    g = GraphBuilder(seed, dry, quant, requant)
     x = g.input("data", 3, size, size)
     x = g.conv_bn_relu("conv1", x, 3, 32, 3, 2, 1)
     cfg = [(32, 64, 1), (64, 128, 2), (128, 128, 1), (128, 256, 2), (256, 256, 1), (256, 512, 2)] + [(512, 512, 1)] * 5 + \
@@ -1236,7 +1318,9 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_resample": tiny_resample, "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small,
           "deeplab_largefov_full": deeplab_largefov_full, "unet_bilinear": unet_bilinear, "fpn_resnet50": fpn_resnet50,
           "tiny_lrn": tiny_lrn, "alexnet": alexnet, "caffenet": caffenet, "googlenet": googlenet,
-          "tiny_quant": tiny_quant, "vgg16_int8": vgg16_int8, "resnet50_int8": resnet50_int8, "mobilenet_v1_int8": mobilenet_v1_int8}
+          "tiny_quant": tiny_quant, "vgg16_int8": vgg16_int8, "resnet50_int8": resnet50_int8, "mobilenet_v1_int8": mobilenet_v1_int8,
+          "tiny_requant": tiny_requant, "tiny_requant_twin": tiny_requant_twin,
+          "vgg16_int8_rq": vgg16_int8_rq, "resnet50_int8_rq": resnet50_int8_rq, "mobilenet_v1_int8_rq": mobilenet_v1_int8_rq}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -1253,6 +1337,11 @@ EXTENDED_NETS = ("tiny_resample", "mobilenet_v3_large", "mobilenet_v3_small", "d
 # nets that need Net.SetQuantized(True) (int8 Convolution / InnerProduct layers: libfeather_qconv.so), and the quantised layers of the small one
 QUANTIZED_NETS = ("tiny_quant", "vgg16_int8", "resnet50_int8", "mobilenet_v1_int8")
 QUANT_LAYERS = {"tiny_quant": ("conv1", "conv2", "conv3", "dw", "pw", "fc")}
+# nets that need Net.SetRequantized(True) on top of it (int8 convolutions with a requantised int8 output: libfeather_q8.so) and, for the
+# BatchNorm behind such a layer, fusion level >= 2; the requantised layers and all int8 layers of the small one
+REQUANTIZED_NETS = ("tiny_requant", "vgg16_int8_rq", "resnet50_int8_rq", "mobilenet_v1_int8_rq")
+REQUANT_LAYERS = {"tiny_requant": ("conv1", "conv2", "conv3", "dw")}
+QUANT_LAYERS["tiny_requant"] = QUANT_LAYERS["tiny_requant_twin"] = ("conv1", "conv2", "conv3", "dw", "pw", "side", "fc")
 
 # the input size a builder's defaults describe, where it is not 224 px
 INPUT_SIZE = {"alexnet": 227, "caffenet": 227}

@@ -65,6 +65,12 @@ class Net:
         int8_scale_term; routed to libfeather_qconv.so) instead of refusing them at LoadParam.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_quantized(self._h, int(bool(on))), "fhip_net_set_quantized")
 
+    def SetRequantized(self, on: bool = True):
+        """feather::Net::SetRequantized: with SetQuantized, accept int8 Convolution / ConvolutionDepthWise layers with a requantised int8
+        output (int8_scale_term 101 .. 200) instead of refusing them at LoadParam; the activation between two int8 layers then stays int8
+        on the device (routed to libfeather_q8.so, reported as QCONV).  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_requantized(self._h, int(bool(on))), "fhip_net_set_requantized")
+
     def SetExtendedLayers(self, on: bool = True):
         """feather::Net::SetExtendedLayers: accept Interp and HardSwish layers (routed to libfeather_resample.so) and LRN layers
         (libfeather_lrn.so) instead of refusing them

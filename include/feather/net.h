@@ -191,6 +191,9 @@ class Net
     int SetDilated(bool on) { return fhip_net_set_dilated(net_, on ? 1 : 0); }
     // int8 Convolution / InnerProduct layers (ncnn's int8_scale_term) load and run through libfeather_qconv.so; before LoadParam
     int SetQuantized(bool on) { return fhip_net_set_quantized(net_, on ? 1 : 0); }
+    // with SetQuantized: int8 convolutions with a requantised int8 output (int8_scale_term 101 .. 200) load, and the activation between
+    // two int8 layers stays int8 on the device (libfeather_q8.so); before LoadParam (feather_net.h)
+    int SetRequantized(bool on) { return fhip_net_set_requantized(net_, on ? 1 : 0); }
     // accept Interp and HardSwish layers (libfeather_resample.so) and LRN layers (libfeather_lrn.so) instead of refusing them; before
     // LoadParam (feather_net.h)
     int SetExtendedLayers(bool on) { return fhip_net_set_extended_layers(net_, on ? 1 : 0); }

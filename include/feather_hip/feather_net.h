@@ -275,6 +275,17 @@ FHIP_API int fhip_net_set_extended_layers(fhip_net* net, int on);
  * partial group, a dilation and automatic pads stay -200, and param 8 on weights with any other tag is refused when the weights are read
  * (this runtime does not quantise at load).  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
 FHIP_API int fhip_net_set_quantized(fhip_net* net, int on);
+/* 1, in a net with fhip_net_set_quantized: a Convolution or ConvolutionDepthWise layer with int8_scale_term 101 .. 200 (ncnn's
+ * requantised int8 output, what ncnn2int8's fuse_requantize writes; one more raw fp32, the output scale, behind the input scale in the
+ * .bin) is loaded, and its top is a q8 blob: int8 in device memory, as feather_q8.h defines it, bit for bit.  The layer and the int8
+ * layers that read such a blob run through libfeather_q8.so and report FHIP_NET_ROUTE_QCONV like every int8 layer.  A q8 blob may be
+ * read by an int8 Convolution / ConvolutionDepthWise, a Split, a plain ReLU and a max Pooling (the last two keep it q8); a BatchNorm /
+ * Scale behind the producer exists only folded (fusion level 2) and is applied before the requantisation.  Every other reader -- average
+ * Pooling, Eltwise, Concat, InnerProduct, an fp32 convolution, an unfused BatchNorm, a layer of another library -- is refused at the first
+ * Forward with -300, and so is fhip_net_extract of the blob.  0 (default): such a layer is refused at LoadParam with -200 as before; without
+ * fhip_net_set_quantized the switch changes nothing.  InnerProduct with int8_scale_term > 100 and a term above 200 stay refused.  Call
+ * before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_requantized(fhip_net* net, int on);
 /* 1: independent branches run concurrently: a convolution that needs no scratch arena and whose output is only consumed
  * further down the layer list (ResNet's projection shortcut, SqueezeNet's expand1x1) is enqueued on a second stream owned by
  * the net while the main stream continues; fork and join are events (hipGraph-capturable).  0 (default): one stream. */

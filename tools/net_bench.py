@@ -15,13 +15,15 @@ from feathercnn_amd.net import Net  # noqa: E402
 
 
 def switches(net, name):
-    """The opt-in layer families a zoo net needs (Net.SetDilated, Net.SetExtendedLayers, Net.SetQuantized), set before LoadParam."""
+    """The opt-in layer families a zoo net needs (Net.SetDilated, Net.SetExtendedLayers, Net.SetQuantized, Net.SetRequantized), set before LoadParam."""
     if name in model_zoo.DILATED_LAYERS:
         net.SetDilated(True)
     if name in model_zoo.EXTENDED_NETS:
         net.SetExtendedLayers(True)
-    if name in model_zoo.QUANTIZED_NETS:
+    if name in model_zoo.QUANTIZED_NETS or name in model_zoo.REQUANTIZED_NETS:
         net.SetQuantized(True)
+    if name in model_zoo.REQUANTIZED_NETS:
+        net.SetRequantized(True)
 
 
 def run(name, batch, fusion, steps=10):

@@ -5,6 +5,8 @@ libfeather_qconv.so on the layers of the nets they are for, against the fp32 rou
 Per layer: VGG-16's 3x3 layers at batch 32, ResNet-50's first layer and its 1x1 and 3x3 layers at batch 64, MobileNet-V1's depthwise and pointwise layers at
 batch 256.  In one process, the two candidates alternating round by round:
   int8    fhip_qconv_forward (bias + ReLU), the route fhip_qconv_route names
+  q8      fhip_q8_forward of libfeather_q8.so, the chain form of the same layer: an int8 tensor in and a requantised int8 tensor out (a
+          C = 3 first layer: fp32 in, int8 out), bias + ReLU, on its own ring of int8 tensor sets of more than 256 MiB
   fp32    fhip_conv_forward on the route fhip_conv_select_algo_tuned picks for the geometry (bias + ReLU), with its scratch buffer
 Reported per layer: the median over the rounds in microseconds with the least and the largest round; int8 / fp32; the int8 route's achieved
 TOPS (2 * N * K * OH * OW * R operations over the median) and that as a fraction of the matrix pipe's int8 peak -- 2x the dense bf16 peak of
@@ -15,7 +17,8 @@ Cold: every candidate walks a ring of tensor sets of more than 256 MiB (the Infi
 around an eager loop of launches.  No figure here is a pass / fail bound of any test: the route is chosen by the model file, not by a
 selector, so a slower layer is a finding.
 --nets adds vgg16:32, resnet50:64 and mobilenet_v1:256 against their _int8 builds at fusion level 1 (the only level where both run the same
-set of launches), hipGraph replay, the two nets alternating.  Prints one JSON line per layer and net, and one at the end."""
+set of launches) and, at fusion level 2, the _int8 build against its _int8_rq build (int8 activations between the int8 layers), hipGraph
+replay, the nets alternating.  Prints one JSON line per layer and net, and one at the end."""
 import argparse
 import json
 import os
@@ -28,7 +31,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from benchkit import PEAK_HBM_GBS  # noqa: E402
-from feathercnn_amd import ConvLayer, ConvParam, QuantConv, QuantParam, ReLU, dequant_scales, model_zoo, qconv_route  # noqa: E402
+from feathercnn_amd import ConvLayer, ConvParam, Q8Conv, Q8Param, QuantConv, QuantParam, ReLU, dequant_scales, model_zoo, q8_route, qconv_route  # noqa: E402
+from feathercnn_amd.q8 import q8_shape  # noqa: E402
 from feathercnn_amd.booster import ALGO_NAMES  # noqa: E402
 from feathercnn_amd.net import Net  # noqa: E402
 
@@ -90,11 +94,24 @@ def layer_row(family, batch, spec, iters, rounds):
     per = (int(np.prod(in_shape)) + int(np.prod(out_shape))) * 4
     ring = max(2, -(-(L3 + (L3 >> 2)) // per))
     sets = [(torch.randn(in_shape, device="cuda"), torch.empty(out_shape, device="cuda")) for _ in range(ring)]
-    cands = [("int8", lambda x, y: conv.Forward(qp, y, x, packed, d, bias, s_in)), ("fp32", lambda x, y: flayer.Forward(x, out=y, scratch=scratch))]
-    t = {nm: [] for nm, _ in cands}
+    # the chain form: int8 in (but for a first layer), int8 out at an output scale that keeps the ReLU'd values inside the q range
+    in8 = c % 16 == 0 or group > 1
+    cp = Q8Param.make(c, k, plane, kernel, stride, pad, group=group, bias=True, act=ReLU, batch=batch, input_int8=in8, output_int8=True)
+    chain = Q8Conv()
+    _, cpacked_bytes = chain.GetBufferSize(cp)
+    cpacked = torch.empty(cpacked_bytes, dtype=torch.uint8, device="cuda")
+    chain.Init(cp, cpacked, torch.from_numpy(wq.reshape(k, c // group, kernel, kernel)).cuda())
+    cin_shape, cout_shape = (q8_shape(*in_shape) if in8 else in_shape), q8_shape(*out_shape)
+    cper = int(np.prod(cin_shape)) * (1 if in8 else 4) + int(np.prod(cout_shape))
+    cring = max(2, -(-(L3 + (L3 >> 2)) // cper))
+    csets = [((torch.randint(-127, 128, cin_shape, dtype=torch.int8, device="cuda") if in8 else torch.randn(in_shape, device="cuda")),
+              torch.empty(cout_shape, dtype=torch.int8, device="cuda")) for _ in range(cring)]
+    cands = [("int8", lambda x, y: conv.Forward(qp, y, x, packed, d, bias, s_in), sets), ("q8", lambda x, y: chain.Forward(cp, y, x, cpacked, d, bias, s_in, 16.0), csets),
+             ("fp32", lambda x, y: flayer.Forward(x, out=y, scratch=scratch), sets)]
+    t = {nm: [] for nm, _, _ in cands}
     for _ in range(rounds):
-        for nm, fn in cands:
-            t[nm].append(timed(fn, sets, iters))
+        for nm, fn, ring_sets in cands:
+            t[nm].append(timed(fn, ring_sets, iters))
     med = {nm: statistics.median(v) for nm, v in t.items()}
     # the two routes agree to the quantisation step (a sanity check of the set-up, not a test)
     x, y = sets[0]
@@ -103,23 +120,30 @@ def layer_row(family, batch, spec, iters, rounds):
     rel = float((y - ref).abs().max() / ref.abs().max())
     ops = 2.0 * batch * k * qp.output_h * qp.output_w * (c // group) * kernel * kernel
     moved = per + packed_bytes
-    row = {"family": family, "layer": label, "batch": batch, "route": qconv_route(qp).replace("fhip::", ""), "fp32_route": ALGO_NAMES.get(flayer.booster.algo, str(flayer.booster.algo)),
+    row = {"family": family, "layer": label, "batch": batch, "route": qconv_route(qp).replace("fhip::", ""), "q8_route": q8_route(cp).replace("fhip::", ""),
+           "q8_over_int8": round(med["q8"] / med["int8"], 3), "q8_over_fp32": round(med["q8"] / med["fp32"], 3), "q8_tops": round(ops / med["q8"] / 1e6, 1),
+           "q8_of_i8_peak": round(ops / med["q8"] / 1e6 / PEAK_I8_TOPS, 4), "q8_MB_moved": round((cper + cpacked_bytes) / 1e6, 1),
+           "q8_gbs": round((cper + cpacked_bytes) / med["q8"] / 1e3), "fp32_route": ALGO_NAMES.get(flayer.booster.algo, str(flayer.booster.algo)),
            "us": {nm: [round(med[nm], 1), round(min(v), 1), round(max(v), 1)] for nm, v in t.items()}, "int8_over_fp32": round(med["int8"] / med["fp32"], 3),
            "int8_tops": round(ops / med["int8"] / 1e6, 1), "of_i8_peak": round(ops / med["int8"] / 1e6 / PEAK_I8_TOPS, 4),
            "MB_moved": round(moved / 1e6, 1), "int8_gbs": round(moved / med["int8"] / 1e3), "max_rel_diff_to_fp32": round(rel, 4)}
     print(json.dumps(row), flush=True)
-    del sets, x, y, ref
+    del sets, csets, x, y, ref
     torch.cuda.empty_cache()
     return row
 
 
 def net_row(name, batch, steps, rounds):
     nets = {}
-    for which, build in (("fp32", model_zoo.MODELS[name]), ("int8", model_zoo.MODELS[name + "_int8"])):
+    # the requantised build needs fusion level 2 (its BatchNorm layers exist only folded): it runs next to the int8 build at that level
+    for which, build, level in (("fp32", model_zoo.MODELS[name], 1), ("int8", model_zoo.MODELS[name + "_int8"], 1),
+                                ("int8_f2", model_zoo.MODELS[name + "_int8"], 2), ("int8_rq_f2", model_zoo.MODELS[name + "_int8_rq"], 2)):
         p, b, i, o = build()
-        net = Net(fusion=1, graph=True, tuned=True)
-        if which == "int8":
+        net = Net(fusion=level, graph=True, tuned=True)
+        if which != "fp32":
             net.SetQuantized(True)
+        if which == "int8_rq_f2":
+            net.SetRequantized(True)
         net.LoadParam(p)
         net.LoadWeights(b)
         del b
@@ -128,7 +152,7 @@ def net_row(name, batch, steps, rounds):
             net.Forward()
         torch.cuda.synchronize()
         nets[which] = net
-    t = {"fp32": [], "int8": []}
+    t = {which: [] for which in nets}
     for _ in range(rounds):
         for which, net in nets.items():
             torch.cuda.synchronize()
@@ -138,9 +162,11 @@ def net_row(name, batch, steps, rounds):
             torch.cuda.synchronize()
             t[which].append((time.perf_counter() - t0) / steps * 1e3)
     med = {k: statistics.median(v) for k, v in t.items()}
-    quantised = sum(a == "QCONV" for _, _, a in nets["int8"].layers())
-    row = {"net": name, "batch": batch, "fusion": 1, "int8_layers": quantised, "ms": {k: [round(med[k], 3), round(min(v), 3), round(max(v), 3)] for k, v in t.items()},
-           "img_s": {k: round(batch / med[k] * 1e3) for k in t}, "int8_over_fp32": round(med["int8"] / med["fp32"], 3)}
+    levels = {"fp32": 1, "int8": 1, "int8_f2": 2, "int8_rq_f2": 2}  # the fusion level of each column
+    quantised = {k: sum(a == "QCONV" for _, _, a in net.layers()) for k, net in nets.items() if k != "fp32"}
+    row = {"net": name, "batch": batch, "fusion": levels, "int8_layers": quantised, "ms": {k: [round(med[k], 3), round(min(v), 3), round(max(v), 3)] for k, v in t.items()},
+           "img_s": {k: round(batch / med[k] * 1e3) for k in t}, "int8_over_fp32": round(med["int8"] / med["fp32"], 3),
+           "rq_over_int8_f2": round(med["int8_rq_f2"] / med["int8_f2"], 3), "rq_over_fp32": round(med["int8_rq_f2"] / med["fp32"], 3)}
     print(json.dumps(row), flush=True)
     for net in nets.values():
         net.close()
