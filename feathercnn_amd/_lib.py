@@ -107,6 +107,7 @@ SIGNATURES = {
     "fhip_net_set_quantized": (_I, [_V, _I]),
     "fhip_net_set_requantized": (_I, [_V, _I]),
     "fhip_net_set_extended_layers": (_I, [_V, _I]),
+    "fhip_net_set_detection": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -309,6 +310,23 @@ Q8_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_detect.h -- libfeather_detect.so, the layers of an SSD detection head: Permute, Normalize, a softmax along any
+# axis, PriorBox (a host function) and DetectionOutput (a library of its own)
+_FP = ctypes.POINTER(ctypes.c_float)
+DETECT_SIGNATURES = {
+    "fhip_permute_output_dim": (_I, [_I, _I, _I, _I, _I, _PI, _PI, _PI]),
+    "fhip_permute_forward": (_I, [_I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_permute_concat_forward": (_I, [_I, _PI, _PI, _I, _V, _PP, _V]),
+    "fhip_normalize_forward": (_I, [_I, _I, _I, _I, _I, _FL, _V, _V, _V, _V]),
+    "fhip_axis_softmax_forward": (_I, [_I, _I, _I, _V, _V, _V]),
+    "fhip_priorbox_fill": (_I, [_I, _I, _I, _I, _FP, _I, _FP, _I, _FP, _I, _FP, _I, _I, _FL, _FL, _FL, _PI, _FP, _SZ]),
+    "fhip_detection_output_get_buffer_size": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "fhip_detection_output_forward": (_I, [_I, _I, _I, _FL, _I, _I, _FL, _I, _V, _V, _V, _V, _V, _V]),
+    "fhip_detect_route": (_I, [_I, _I, _I, _I, _I, _I, _V, _V, ctypes.c_char_p, _I]),
+    "fhip_detect_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -371,6 +389,8 @@ MAIN = "hip"
 # into LIBRARIES.
 MORE_LIBRARIES = {
     "q8": Library("libfeather_q8.so", ("feather_q8.h",), "FHIP_Q8_API", Q8_SIGNATURES, "fhip_q8_last_error", (fhip_q8_param,), None),
+    # route: DETECT_ROUTE of net.py (FHIP_DETECT_NET_ROUTE of its own header), outside the closed ROUTE_* set
+    "detect": Library("libfeather_detect.so", ("feather_detect.h",), "FHIP_DETECT_API", DETECT_SIGNATURES, "fhip_detect_last_error", (), None),
 }
 
 

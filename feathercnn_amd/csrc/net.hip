@@ -17,13 +17,14 @@
 //
 // One translation unit, read in this order (no header includes a later one): net_side.h -- errors, the side libraries; net_model.h --
 // ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_conv.h -- the convolution layer, its side routes
-// and the weight staging it shares; net_layers.h -- the other layer classes; net_plan.h -- the fusion and planning passes, prepare,
+// and the weight staging it shares; net_layers.h -- the other layer classes; net_detect.h -- the detection-head layers and their factory; net_plan.h -- the fusion and planning passes, prepare,
 // forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
 #include "net_side.h"
 #include "net_model.h"
 #include "net_core.h"
 #include "net_conv.h"
 #include "net_layers.h"
+#include "net_detect.h"
 #include "net_plan.h"
 
 namespace fhip::net
@@ -96,12 +97,14 @@ static int load_param_text(Net& net, const char* text, size_t len)
     {
         std::string type, name, nb, nt;
         if (!next(type) || !next(name) || !next(nb) || !next(nt)) return failf(NET_E_IO, "param file ends after %d of %d layers", i, layer_count);
-        std::unique_ptr<Layer> layer(create_layer(type));
+        std::unique_ptr<Layer> layer(net.detection ? create_detection_layer(type) : nullptr); // asked first: it overrides Concat and Softmax
+        if (!layer) layer.reset(create_layer(type));
         if (!layer && net.extended) layer.reset(create_extended_layer(type));
         if (!layer)
         {
-            std::unique_ptr<Layer> opt_in(create_extended_layer(type));
-            return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered%s", type.c_str(), opt_in ? " (fhip_net_set_extended_layers lifts this)" : "");
+            std::unique_ptr<Layer> opt_in(create_extended_layer(type)), detect(create_detection_layer(type));
+            return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered%s", type.c_str(),
+                         opt_in ? " (fhip_net_set_extended_layers lifts this)" : (detect ? " (fhip_net_set_detection lifts this)" : ""));
         }
         layer->type = type;
         layer->name = name;
@@ -334,6 +337,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.tuned_selection = n->impl.tuned_selection;
         m->impl.dilated = n->impl.dilated;
         m->impl.extended = n->impl.extended;
+        m->impl.detection = n->impl.detection;
         m->impl.quantized = n->impl.quantized;
         m->impl.requantized = n->impl.requantized;
         m->impl.concurrency = n->impl.concurrency;
@@ -392,6 +396,15 @@ int fhip_net_set_extended_layers(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the extended-layers switch before LoadParam");
     n->impl.extended = on != 0;
     for (auto& m : n->more) m->impl.extended = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_detection(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the detection-layers switch before LoadParam");
+    n->impl.detection = on != 0;
+    for (auto& m : n->more) m->impl.detection = on != 0;
     return FHIP_OK;
 }
 

@@ -10,6 +10,7 @@ struct Blob
 {
     std::string name;
     int n = 0, c = 0, h = 0, w = 0;
+    int dims = 3; // ncnn's Mat::dims: 3 = (c, h, w), 2 = (h, w) with c = 1, 1 = (w) with c = h = 1; only the layers of net_detect.h set or read it
     float* data = nullptr;
     size_t capacity = 0;   // floats owned
     Blob* alias = nullptr; // data is another blob's
@@ -26,6 +27,7 @@ struct Blob
         c = c_;
         h = h_;
         w = w_;
+        dims = 3;
         alias = nullptr;
         // a blob the previous plan chained away has no storage and, as a rule, will have none after this Reshape either: plan_chains
         // allocates it afterwards if the new shapes un-chain it (no device malloc + free per chained blob and shape change)
@@ -52,6 +54,7 @@ struct Blob
         c = src->c;
         h = src->h;
         w = src->w;
+        dims = src->dims;
         if (data && capacity) (void)hipFree(data);
         capacity = 0;
         alias = src;
@@ -182,6 +185,7 @@ struct Net
     bool dilated = false;         // fhip_net_set_dilated: a Convolution with dilation > 1 is loaded (libfeather_atrous.so) instead of refused
     bool extended = false;        // fhip_net_set_extended_layers: Interp, HardSwish (libfeather_resample.so) and LRN (libfeather_lrn.so) are loaded instead of refused
     bool quantized = false;       // fhip_net_set_quantized: Convolution / InnerProduct layers with int8 weights (8=int8_scale_term) are loaded (libfeather_qconv.so) instead of refused
+    bool detection = false;       // fhip_net_set_detection: the SSD head's layers (net_detect.h, libfeather_detect.so) are loaded instead of refused, Concat and Softmax know a blob's rank
     bool requantized = false;     // fhip_net_set_requantized: an int8 Convolution with int8_scale_term 101 .. 200 (requantised int8 output) is loaded (libfeather_q8.so) instead of refused
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;

@@ -1,14 +1,16 @@
 // net_plan.h -- what runs between LoadWeights and the launches: the collapse passes and fuse_layers (once), plan_chains / plan_siblings /
 // plan_concurrency (after every Reshape), reshape_all, prepare, run_layers and forward.
 #pragma once
-#include "net_layers.h"
+#include "net_detect.h"
 
 namespace fhip::net
 {
 
 static bool is_channel_map_type(const Layer* l)
 {
-    return l->type == "ShuffleChannel" || l->type == "Slice" || (l->type == "Concat" && static_cast<const ConcatLayer*>(l)->axis == 0);
+    // a layer typed "Concat" need not be a ConcatLayer (the collapsed detection head of net_detect.h keeps the type string): ask the object
+    const ConcatLayer* cat = l->type == "Concat" ? dynamic_cast<const ConcatLayer*>(l) : nullptr;
+    return l->type == "ShuffleChannel" || l->type == "Slice" || (cat && cat->axis == 0);
 }
 
 // Fusion level 2: a run of Concat / ShuffleChannel / Slice layers, in any order, that follow each other in the layer list and are linked
@@ -266,6 +268,7 @@ static void fuse_layers(Net& net)
     if (net.fused) return;
     net.fused = true;
     if (net.fusion <= 0) return;
+    if (net.fusion >= 2) collapse_detection_heads(net);
     if (net.fusion >= 2) collapse_channel_maps(net);
     if (net.fusion >= 2) collapse_gate_blocks(net);
     if (net.fusion >= 2) collapse_upsample_adds(net);

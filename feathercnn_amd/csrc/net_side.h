@@ -1,5 +1,5 @@
 // net_side.h -- the Net runtime's errors and its side libraries: the table of each libfeather_<x>.so and side_api<X>(), which opens it.
-// First of the headers of net.hip (net_side.h, net_model.h, net_core.h, net_conv.h, net_layers.h, net_plan.h): none includes a later one.
+// First of the headers of net.hip (net_side.h, net_model.h, net_core.h, net_conv.h, net_layers.h, net_detect.h, net_plan.h): none includes a later one.
 #pragma once
 #include <ctype.h>
 #include <dlfcn.h>
@@ -23,6 +23,7 @@
 #include "feather_hip/feather_canvas.h" // declarations only: the library is opened at run time (canvas_api)
 #include "feather_hip/feather_atrous.h" // declarations only: the library is opened at run time (atrous_api)
 #include "feather_hip/feather_deconv.h" // declarations only: the library is opened at run time (deconv_api)
+#include "feather_hip/feather_detect.h" // declarations only: the library is opened at run time (detect_api)
 #include "feather_hip/feather_gate.h" // declarations only: the library is opened at run time (gate_api)
 #include "feather_hip/feather_gconv.h" // declarations only: the library is opened at run time (gconv_api)
 #include "feather_hip/feather_inorm.h" // declarations only: the library is opened at run time (inorm_api)
@@ -305,6 +306,30 @@ struct Q8Api
     }
 };
 static const Q8Api* q8_api() { return side_api<Q8Api>(); }
+
+// libfeather_detect.so, the layers of a net with fhip_net_set_detection: Permute, Normalize, PriorBox, DetectionOutput, the strided softmax
+// and the Concat of permuted heads collapsed at fusion level 2 (net_detect.h)
+struct DetectApi
+{
+    decltype(&fhip_permute_output_dim) permute_output_dim = nullptr;
+    decltype(&fhip_permute_forward) permute = nullptr;
+    decltype(&fhip_permute_concat_forward) permute_concat = nullptr;
+    decltype(&fhip_normalize_forward) normalize = nullptr;
+    decltype(&fhip_axis_softmax_forward) axis_softmax = nullptr;
+    decltype(&fhip_priorbox_fill) priorbox = nullptr;
+    decltype(&fhip_detection_output_get_buffer_size) detection_buffer_size = nullptr;
+    decltype(&fhip_detection_output_forward) detection_output = nullptr;
+    decltype(&fhip_detect_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_detect.so", "a detection-head layer (Permute, Normalize, PriorBox, DetectionOutput, Softmax along an axis)", "feather_detect.h",
+                {{&permute_output_dim, "fhip_permute_output_dim"}, {&permute, "fhip_permute_forward"}, {&permute_concat, "fhip_permute_concat_forward"},
+                 {&normalize, "fhip_normalize_forward"}, {&axis_softmax, "fhip_axis_softmax_forward"}, {&priorbox, "fhip_priorbox_fill"},
+                 {&detection_buffer_size, "fhip_detection_output_get_buffer_size"}, {&detection_output, "fhip_detection_output_forward"},
+                 {&last_error, "fhip_detect_last_error"}}};
+    }
+};
+static const DetectApi* detect_api() { return side_api<DetectApi>(); }
 
 // libfeather_canvas.so, the chained Winograd transforms of layers that run on 2x2 image canvases (plan_chains).  The canvas form is a
 // faster way to run the same run of layers, not a layer type: a net that qualifies and cannot find the library fails at plan_chains.

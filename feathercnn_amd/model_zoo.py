@@ -245,8 +245,71 @@ class GraphBuilder:
     def eltwise(self, name, a, b):
         return self.layer("Eltwise", name, [a, b], [name], {0: 1})
 
-    def concat(self, name, bottoms):
-        return self.layer("Concat", name, list(bottoms), [name], {0: 0})
+    def concat(self, name, bottoms, axis=0):
+        """axis: relative to the bottoms' rank; anything but 0 on blobs of rank 3 needs Net.SetDetection(True)."""
+        return self.layer("Concat", name, list(bottoms), [name], {0: axis})
+
+    # -- the SSD detection head (a net that holds one of these needs Net.SetDetection(True)) ------------------------
+    def permute(self, name, bottom, order):
+        """ncnn's Permute: 0=order_type (3: NCHW -> NHWC)."""
+        return self.layer("Permute", name, [bottom], [name], {0: int(order)})
+
+    def flatten(self, name, bottom):
+        return self.layer("Flatten", name, [bottom], [name])
+
+    def reshape(self, name, bottom, w, h=None, c=None):
+        """ncnn's Reshape: 0=w 1=h 2=c, an absent id = the dimension does not exist, 0 = the bottom's extent, -1 = inferred."""
+        params = {0: int(w)}
+        if h is not None:
+            params[1] = int(h)
+        if c is not None:
+            params[2] = int(c)
+        return self.layer("Reshape", name, [bottom], [name], params)
+
+    def normalize(self, name, bottom, c, scale=20.0, eps=1e-10, channel_shared=False):
+        """ncnn's Normalize in its SSD form (conv4_3_norm): across channels, per pixel, one learnt scale per channel drawn around `scale`."""
+        n = 1 if channel_shared else c
+        top = self.layer("Normalize", name, [bottom], [name], {0: 0, 1: int(channel_shared), 2: f"{eps:.6e}", 3: n, 4: 1})
+        self._raw(self._uniform(n, 0.9 * scale, 1.1 * scale))
+        return top
+
+    def priorbox(self, name, bottom, image, min_sizes, max_sizes=(), ratios=(), flip=True, clip=False, variances=(0.1, 0.1, 0.2, 0.2), offset=0.5,
+                 step=None):
+        """ncnn's PriorBox: bottoms (feature map, image blob); steps and image extents come from the bottoms unless `step` is given."""
+        arr = lambda v: ",".join([str(len(v))] + [f"{float(x):.6f}" for x in v])
+        params = {-23300: arr(min_sizes)}
+        if len(max_sizes):
+            params[-23301] = arr(max_sizes)
+        if len(ratios):
+            params[-23302] = arr(ratios)
+        params.update({3 + k: f"{variances[k]:.6f}" for k in range(4)})
+        params.update({7: int(flip), 8: int(clip), 9: -233, 10: -233, 11: f"{-233.0 if step is None else step:.6f}",
+                       12: f"{-233.0 if step is None else step:.6f}", 13: f"{offset:.6f}"})
+        return self.layer("PriorBox", name, [bottom, image], [name], params)
+
+    def detection_output(self, name, loc, conf, prior, num_class, nms_threshold=0.45, nms_top_k=100, keep_top_k=100, confidence_threshold=0.25):
+        return self.layer("DetectionOutput", name, [loc, conf, prior], [name],
+                          {0: int(num_class), 1: f"{nms_threshold:.6f}", 2: int(nms_top_k), 3: int(keep_top_k), 4: f"{confidence_threshold:.6f}"})
+
+    def ssd_head(self, image, sources, num_class, conf_gain, loc_gain=0.5, **detection):
+        """The SSD head over `sources` = [(tag, blob, channels, priors per cell, priorbox arguments)]: per source a 3x3 location and a 3x3
+        confidence convolution, each Permute(3) -> Flatten, and a PriorBox; the three Concats; the confidence as Reshape (num_class, -1) ->
+        Softmax(axis 1) -> Flatten; DetectionOutput "detection_out".  Every source is read three times, through a Split.  conf_gain
+        spreads the logits so that the scores cover (0, 1) instead of sitting at 1 / num_class."""
+        locs, confs, priors = [], [], []
+        for tag, x, c, per, box in sources:
+            a, b, p = self.split(tag + "_mbox_split", x, 3)
+            loc = self.conv(tag + "_mbox_loc", a, c, 4 * per, 3, 1, 1, gain=loc_gain)
+            locs.append(self.flatten(tag + "_mbox_loc_flat", self.permute(tag + "_mbox_loc_perm", loc, 3)))
+            conf = self.conv(tag + "_mbox_conf", b, c, num_class * per, 3, 1, 1, gain=conf_gain)
+            confs.append(self.flatten(tag + "_mbox_conf_flat", self.permute(tag + "_mbox_conf_perm", conf, 3)))
+            priors.append(self.priorbox(tag + "_mbox_priorbox", p, image, **box))
+        loc = self.concat("mbox_loc", locs, 0)
+        conf = self.concat("mbox_conf", confs, 0)
+        prior = self.concat("mbox_priorbox", priors, 1)
+        conf = self.reshape("mbox_conf_reshape", conf, num_class, -1)
+        conf = self.flatten("mbox_conf_flatten", self.softmax("mbox_conf_softmax", conf, axis=1))
+        return self.detection_output("detection_out", loc, conf, prior, num_class, **detection)
 
     def shuffle(self, name, bottom, group, reverse=False):
         """ncnn's ShuffleChannel: 0=group, 1=reverse (written only when set)."""
@@ -328,8 +391,9 @@ class GraphBuilder:
     def dropout(self, name, bottom, scale=None):
         return self.layer("Dropout", name, [bottom], [name], {} if scale is None else {0: f"{scale:.6f}"})
 
-    def softmax(self, name, bottom):
-        return self.layer("Softmax", name, [bottom], [name])
+    def softmax(self, name, bottom, axis=None):
+        """axis: ncnn's 0=axis with 1=fixbug0 (needs Net.SetDetection(True)); None writes no params, the plain layer."""
+        return self.layer("Softmax", name, [bottom], [name], None if axis is None else {0: int(axis), 1: 1})
 
     def conv_bn_relu(self, name, bottom, cin, cout, k, s=1, p=0, group=1, relu=True, dilation=1):
         # bias on every dense conv: the reference Winograd output transform reads bias[k] unconditionally and
@@ -1306,6 +1370,91 @@ def googlenet(seed=1234, classes=1000, size=224, dry=False):
     return g.finish() + ("data", "prob")
 
 
+def tiny_ssd(seed=43, size=(20, 28), dry=False):
+    """A small SSD (Net.SetDetection(True)): a 20 x 28 image, three source maps -- 10 x 14 behind a Normalize, 5 x 7 and 3 x 4 -- with 3, 6 and 4
+    priors per cell (678 priors), 3 classes.  size = (height, width)."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    data, image = g.split("data_split", g.input("data", 3, h, w), 2)
+    x = g.pool("pool1", g.relu("relu1", g.conv("conv1", data, 3, 16, 3, 1, 1)), 2, 2)
+    a = g.relu("relu2", g.conv("conv2", x, 16, 24, 3, 1, 1))
+    a, keep = g.split("split2", a, 2)
+    b = g.relu("relu3", g.conv("conv3", keep, 24, 32, 3, 2, 1))
+    b, keep = g.split("split3", b, 2)
+    c = g.relu("relu4", g.conv("conv4", keep, 32, 32, 3, 2, 1))
+    sources = [("conv2_norm", g.normalize("conv2_norm", a, 24, scale=2.0), 24, 3, dict(min_sizes=[4.0], ratios=[2.0])),
+               ("conv3", b, 32, 6, dict(min_sizes=[8.0], max_sizes=[12.0], ratios=[2.0, 3.0], clip=True)),
+               ("conv4", c, 32, 4, dict(min_sizes=[12.0], max_sizes=[16.0], ratios=[2.0, 3.0], flip=False))]
+    g.ssd_head(image, sources, 3, conf_gain=2.0, nms_threshold=0.45, nms_top_k=40, keep_top_k=20, confidence_threshold=0.95)
+    return g.finish() + ("data", "detection_out")
+
+
+def mobilenet_ssd(seed=1234, classes=21, size=300, dry=False, confidence_threshold=0.25, conf_gain=0.2):
+    """MobileNet-SSD (the Caffe model ncnn's example application runs): the MobileNet v1 trunk at 300 px, four extra 1x1 / 3x3-stride-2 pairs,
+    six source maps of 19, 10, 5, 3, 2 and 1 cells with 3, 6, 6, 6, 6, 6 priors per cell: 1917 priors.  Net.SetDetection(True)."""
+    g = GraphBuilder(seed, dry)
+    data, image = g.split("data_split", g.input("data", 3, size, size), 2)
+    x = g.conv_bn_relu("conv0", data, 3, 32, 3, 2, 1)
+    cfg = [(32, 64, 1), (64, 128, 2), (128, 128, 1), (128, 256, 2), (256, 256, 1), (256, 512, 2)] + [(512, 512, 1)] * 5 + \
+          [(512, 1024, 2), (1024, 1024, 1)]
+    maps = {}
+    for i, (c, k, s) in enumerate(cfg, 1):
+        x = g.conv_bn_relu(f"conv{i}_dw", x, c, c, 3, s, 1, group=c)
+        x = g.conv_bn_relu(f"conv{i}", x, c, k, 1, 1, 0)
+        if i in (11, 13):
+            maps[i], x = g.split(f"conv{i}_split", x, 2)
+    cin = 1024
+    for i, (mid, out) in enumerate([(256, 512), (128, 256), (128, 256), (64, 128)], 14):
+        x = g.conv_bn_relu(f"conv{i}_1", x, cin, mid, 1, 1, 0)
+        x = g.conv_bn_relu(f"conv{i}_2", x, mid, out, 3, 2, 1)
+        cin = out
+        if i < 17:
+            maps[i], x = g.split(f"conv{i}_split", x, 2)
+        else:
+            maps[i] = x
+    box = lambda mn, mx: dict(min_sizes=[mn], max_sizes=[mx], ratios=[2.0, 3.0])
+    sources = [("conv11", maps[11], 512, 3, dict(min_sizes=[60.0], ratios=[2.0])), ("conv13", maps[13], 1024, 6, box(105.0, 150.0)),
+               ("conv14_2", maps[14], 512, 6, box(150.0, 195.0)), ("conv15_2", maps[15], 256, 6, box(195.0, 240.0)),
+               ("conv16_2", maps[16], 256, 6, box(240.0, 285.0)), ("conv17_2", maps[17], 128, 6, box(285.0, 300.0))]
+    g.ssd_head(image, sources, classes, conf_gain=conf_gain, loc_gain=0.02, nms_threshold=0.45, nms_top_k=100, keep_top_k=100, confidence_threshold=confidence_threshold)
+    return g.finish() + ("data", "detection_out")
+
+
+def vgg16_ssd300(seed=1234, classes=21, size=300, dry=False, confidence_threshold=0.01):
+    """SSD300 on VGG-16 (Liu et al., ECCV 2016): conv4_3 behind a Normalize (scale 20), pool5 3x3 / stride 1, fc6 as a 3x3 convolution at
+    dilation 6, fc7 1x1, four extra pairs; source maps of 38, 19, 10, 5, 3 and 1 cells with 4, 6, 6, 6, 4, 4 priors per cell: 8732 priors.
+    Net.SetDetection(True) and Net.SetDilated(True)."""
+    g = GraphBuilder(seed, dry)
+    data, image = g.split("data_split", g.input("data", 3, size, size), 2)
+    x, cin, maps = data, 3, {}
+    for stage, (n, c) in enumerate([(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)], 1):
+        for i in range(1, n + 1):
+            x = g.relu(f"relu{stage}_{i}", g.conv(f"conv{stage}_{i}", x, cin, c, 3, 1, 1))
+            cin = c
+        if stage == 4:
+            maps["conv4_3"], x = g.split("conv4_3_split", x, 2)
+        x = g.pool(f"pool{stage}", x, 2, 2) if stage < 5 else g.pool("pool5", x, 3, 1, 1)  # ceil mode: 75 -> 38
+    x = g.relu("relu6", g.conv("fc6", x, 512, 1024, 3, 1, 6, dilation=6))
+    x = g.relu("relu7", g.conv("fc7", x, 1024, 1024, 1))
+    maps["fc7"], x = g.split("fc7_split", x, 2)
+    cin = 1024
+    for i, (mid, out, s, p) in enumerate([(256, 512, 2, 1), (128, 256, 2, 1), (128, 256, 1, 0), (128, 256, 1, 0)], 6):
+        x = g.relu(f"conv{i}_1_relu", g.conv(f"conv{i}_1", x, cin, mid, 1))
+        x = g.relu(f"conv{i}_2_relu", g.conv(f"conv{i}_2", x, mid, out, 3, s, p))
+        cin = out
+        if i < 9:
+            maps[f"conv{i}_2"], x = g.split(f"conv{i}_2_split", x, 2)
+        else:
+            maps[f"conv{i}_2"] = x
+    norm = g.normalize("conv4_3_norm", maps["conv4_3"], 512, scale=20.0)
+    box = lambda mn, mx, r, st: dict(min_sizes=[mn], max_sizes=[mx], ratios=r, step=st)
+    sources = [("conv4_3_norm", norm, 512, 4, box(30.0, 60.0, [2.0], 8.0)), ("fc7", maps["fc7"], 1024, 6, box(60.0, 111.0, [2.0, 3.0], 16.0)),
+               ("conv6_2", maps["conv6_2"], 512, 6, box(111.0, 162.0, [2.0, 3.0], 32.0)), ("conv7_2", maps["conv7_2"], 256, 6, box(162.0, 213.0, [2.0, 3.0], 64.0)),
+               ("conv8_2", maps["conv8_2"], 256, 4, box(213.0, 264.0, [2.0], 100.0)), ("conv9_2", maps["conv9_2"], 256, 4, box(264.0, 315.0, [2.0], 300.0))]
+    g.ssd_head(image, sources, classes, conf_gain=2.0, loc_gain=0.25, nms_threshold=0.45, nms_top_k=400, keep_top_k=200, confidence_threshold=confidence_threshold)
+    return g.finish() + ("data", "detection_out")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
@@ -1320,7 +1469,8 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_lrn": tiny_lrn, "alexnet": alexnet, "caffenet": caffenet, "googlenet": googlenet,
           "tiny_quant": tiny_quant, "vgg16_int8": vgg16_int8, "resnet50_int8": resnet50_int8, "mobilenet_v1_int8": mobilenet_v1_int8,
           "tiny_requant": tiny_requant, "tiny_requant_twin": tiny_requant_twin,
-          "vgg16_int8_rq": vgg16_int8_rq, "resnet50_int8_rq": resnet50_int8_rq, "mobilenet_v1_int8_rq": mobilenet_v1_int8_rq}
+          "vgg16_int8_rq": vgg16_int8_rq, "resnet50_int8_rq": resnet50_int8_rq, "mobilenet_v1_int8_rq": mobilenet_v1_int8_rq,
+          "tiny_ssd": tiny_ssd, "mobilenet_ssd": mobilenet_ssd, "vgg16_ssd300": vgg16_ssd300}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -1343,8 +1493,12 @@ REQUANTIZED_NETS = ("tiny_requant", "vgg16_int8_rq", "resnet50_int8_rq", "mobile
 REQUANT_LAYERS = {"tiny_requant": ("conv1", "conv2", "conv3", "dw")}
 QUANT_LAYERS["tiny_requant"] = QUANT_LAYERS["tiny_requant_twin"] = ("conv1", "conv2", "conv3", "dw", "pw", "side", "fc")
 
+# nets that need Net.SetDetection(True) (the SSD head: libfeather_detect.so); vgg16_ssd300 needs Net.SetDilated(True) as well (DILATED_LAYERS)
+DETECTION_NETS = ("tiny_ssd", "mobilenet_ssd", "vgg16_ssd300")
+DILATED_LAYERS["vgg16_ssd300"] = ("fc6",)
+
 # the input size a builder's defaults describe, where it is not 224 px
-INPUT_SIZE = {"alexnet": 227, "caffenet": 227}
+INPUT_SIZE = {"alexnet": 227, "caffenet": 227, "mobilenet_ssd": 300, "vgg16_ssd300": 300}
 
 # the LRN layers of each net that fusion level 2 makes one layer with the Pooling layer behind them, and those that must stay as written
 LRN_POOLS = {"tiny_lrn": (("norm1", "norm2", "norm5"), ("norm3", "norm4")), "alexnet": (("norm1", "norm2"), ()), "caffenet": ((), ("norm1", "norm2")),

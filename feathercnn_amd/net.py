@@ -31,6 +31,8 @@ ROUTE_LRN = 107  # FHIP_NET_ROUTE_LRN: an LRN layer, alone or with the Pooling l
 ROUTE_NAMES[ROUTE_LRN] = "LRN"
 ROUTE_QCONV = 108  # FHIP_NET_ROUTE_QCONV: a Convolution / InnerProduct layer with int8 weights, after SetQuantized(True) (libfeather_qconv.so)
 ROUTE_NAMES[ROUTE_QCONV] = "QCONV"
+DETECT_ROUTE = 109  # FHIP_DETECT_NET_ROUTE (feather_detect.h): a layer of an SSD detection head, after SetDetection(True) (libfeather_detect.so)
+ROUTE_NAMES[DETECT_ROUTE] = "DETECT"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -76,6 +78,12 @@ class Net:
         (libfeather_lrn.so) instead of refusing them
         at LoadParam.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_extended_layers(self._h, int(bool(on))), "fhip_net_set_extended_layers")
+
+    def SetDetection(self, on: bool = True):
+        """feather::Net::SetDetection: accept the layers of ncnn's SSD detection head -- Permute, Flatten, Reshape, Normalize, PriorBox,
+        DetectionOutput, and Concat / Softmax along any axis of a blob's rank (routed to libfeather_detect.so) -- instead of refusing them at
+        LoadParam.  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_detection(self._h, int(bool(on))), "fhip_net_set_detection")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")
@@ -202,6 +210,14 @@ class Net:
         _check(self._lib.fhip_net_extract_host(self._h, blob_name.encode(), out.ctypes.data_as(ctypes.c_void_p), out.size),
                "fhip_net_extract_host")
         return out
+
+    def ExtractDetections(self, blob_name: str):
+        """The top of a DetectionOutput layer as one (count_i, 6) array per image, rows (label, score, xmin, ymin, xmax, ymax): Extract, with
+        the zero rows past every image's count trimmed on the host."""
+        out = self.Extract(blob_name)
+        if out.shape[1] != 1 or out.shape[3] != 6:
+            raise FeatherHipError(f"blob {blob_name} of shape {out.shape} is not a DetectionOutput top [n][1][keep_top_k][6]")
+        return [img[0][:int((img[0][:, 0] > 0).sum())].copy() for img in out]
 
     def ExtractPixels(self, blob_name: str, ptype: int, target=None, mean=None, norm=None) -> np.ndarray:
         """The blob as uint8 images, converted on the device (fhip_float_to_pixels on the net's stream, after Forward): ncnn's

@@ -30,7 +30,8 @@
 //     as one layer of libfeather_gate.so (FHIP_NET_ROUTE_GATE, feather_net.h);
 //   * layer types beyond the reference's factory are loaded too: see feather_net.h's route codes (BinaryOp mul, Scale 0=-233, Swish and
 //     HardSigmoid are the newest); Interp and HardSwish (FHIP_NET_ROUTE_RESAMPLE) and LRN (FHIP_NET_ROUTE_LRN) after
-//     SetExtendedLayers(true).
+//     SetExtendedLayers(true); the SSD detection head (Permute, Flatten, Reshape, Normalize, PriorBox, DetectionOutput; feather_detect.h)
+//     after SetDetection(true), its result through ExtractDetections.
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -38,6 +39,7 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 #include "feather_hip/feather_net.h"
 #include "feather_hip/feather_pixout.h"
@@ -45,6 +47,13 @@
 
 namespace feather
 {
+
+// One row of a DetectionOutput top (ExtractDetections): ncnn's (label, score, xmin, ymin, xmax, ymax), the label as an int
+struct Detection
+{
+    int label;
+    float score, xmin, ymin, xmax, ymax;
+};
 
 class Net
 {
@@ -197,6 +206,31 @@ class Net
     // accept Interp and HardSwish layers (libfeather_resample.so) and LRN layers (libfeather_lrn.so) instead of refusing them; before
     // LoadParam (feather_net.h)
     int SetExtendedLayers(bool on) { return fhip_net_set_extended_layers(net_, on ? 1 : 0); }
+    // accept the layers of ncnn's SSD detection head -- Permute, Flatten, Reshape, Normalize, PriorBox, DetectionOutput, Concat / Softmax along
+    // any axis of a blob's rank (libfeather_detect.so) -- instead of refusing them; before LoadParam (feather_net.h)
+    int SetDetection(bool on) { return fhip_net_set_detection(net_, on ? 1 : 0); }
+    // The top of a DetectionOutput layer ([n][1][keep_top_k][6], zero rows past an image's count) as the detections of every image: a host
+    // copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if the blob has another shape.
+    int ExtractDetections(std::string blob_name, std::vector<std::vector<Detection> >& out)
+    {
+        float* dev = NULL;
+        int n = 0, c = 0, h = 0, w = 0;
+        int rc = Extract(blob_name, &dev, &n, &c, &h, &w);
+        if (rc) return rc;
+        if (c != 1 || w != 6) return -100;
+        std::vector<float> rows((size_t)n * h * 6);
+        if ((rc = ExtractHost(blob_name, rows.data(), rows.size()))) return rc;
+        out.assign(n, std::vector<Detection>());
+        for (int i = 0; i < n; ++i)
+            for (int r = 0; r < h; ++r)
+            {
+                const float* v = &rows[((size_t)i * h + r) * 6];
+                if (!(v[0] > 0.f)) break;
+                Detection d = {(int)v[0], v[1], v[2], v[3], v[4], v[5]};
+                out[i].push_back(d);
+            }
+        return 0;
+    }
     int SetConcurrency(bool on) { return fhip_net_set_concurrency(net_, on ? 1 : 0); }
     int SetSubBatches(int replicas) { return fhip_net_set_sub_batches(net_, replicas); } // before LoadParam (feather_net.h)
     int LayerCount() { return fhip_net_layer_count(net_); }

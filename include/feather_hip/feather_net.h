@@ -267,6 +267,15 @@ FHIP_API int fhip_net_set_dilated(fhip_net* net, int on);
  * lifting that refusal: PixelShuffle stays -200 and a bicubic Interp -100.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to
  * sub-batch replicas. */
 FHIP_API int fhip_net_set_extended_layers(fhip_net* net, int on);
+/* 1: the layers of ncnn's SSD detection head are loaded -- Permute, Flatten, Reshape, Normalize (the SSD form), PriorBox and DetectionOutput
+ * -- and Concat takes any axis of its bottoms' rank and Softmax its axis (0=axis, 1=fixbug0), as feather_detect.h defines them; they run
+ * through libfeather_detect.so and report the route FHIP_DETECT_NET_ROUTE (feather_detect.h).  A blob then has a rank (ncnn's Mat::dims): 3
+ * unless one of these layers says otherwise.  The top of DetectionOutput is [n][1][keep_top_k][6], rows (label, score, xmin, ymin, xmax,
+ * ymax) and zero rows past an image's count.  At fusion level 2 a Concat of Flatten of Permute order 3 heads is one launch, and a Concat of
+ * PriorBox tops is evaluated when shapes change and launches nothing.  0 (default): LoadParam refuses the new types with -200, Concat
+ * refuses every axis but channels and Softmax ignores its params, as before.  Its only effect is lifting those refusals: PixelShuffle and
+ * Padding stay -200.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_detection(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
