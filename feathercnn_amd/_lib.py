@@ -108,6 +108,7 @@ SIGNATURES = {
     "fhip_net_set_requantized": (_I, [_V, _I]),
     "fhip_net_set_extended_layers": (_I, [_V, _I]),
     "fhip_net_set_detection": (_I, [_V, _I]),
+    "fhip_net_set_colpass": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -128,6 +129,7 @@ SIGNATURES = {
     "fhip_net_layer_fused_pointwise": (_I, [_V, _I, _P, _PI]),
     "fhip_net_layer_chain": (_I, [_V, _I, _PI, _PI]),
     "fhip_net_layer_canvas": (_I, [_V, _I, _PI]),
+    "fhip_net_layer_colpass": (_I, [_V, _I, _PI]),
     "fhip_net_layer_sibling": (_I, [_V, _I, _PI]),
     "fhip_net_layer_residual": (_I, [_V, _I, _PI]),
     "fhip_net_forward_timed": (_I, [_V, ctypes.POINTER(ctypes.c_float)]),
@@ -327,6 +329,16 @@ DETECT_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_colpass.h -- libfeather_colpass.so, the Winograd tile GEMM of 64-input-channel layers that writes the
+# column-passed M (48 planes) and the chained transform that reads it (a library of its own)
+COLPASS_SIGNATURES = {
+    "fhip_colpass_supported": (_I, [_P, _I]),
+    "fhip_colpass_tile_gemm": (_I, [_P, _I, _PL, _V, _V, _V, _V]),
+    "fhip_colpass_output_to_next_input": (_I, [_P, _P, _I, _PL, _PL, _V, _V, _V, _I, _V]),
+    "fhip_colpass_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -392,21 +404,30 @@ MORE_LIBRARIES = {
     # route: DETECT_ROUTE of net.py (FHIP_DETECT_NET_ROUTE of its own header), outside the closed ROUTE_* set
     "detect": Library("libfeather_detect.so", ("feather_detect.h",), "FHIP_DETECT_API", DETECT_SIGNATURES, "fhip_detect_last_error", (), None),
 }
+# The rows of SIDE_THIRD of csrc/Makefile, the same tuple, for the same reason: MORE_LIBRARIES is closed as well;
+# tests/test_colpass_contract_cpu.py restates the contract for them.
+THIRD_LIBRARIES = {
+    # route: a faster way to run two layers of a chained Winograd run (fhip_net_set_colpass), not a layer type
+    "colpass": Library("libfeather_colpass.so", ("feather_colpass.h",), "FHIP_COLPASS_API", COLPASS_SIGNATURES, "fhip_colpass_last_error", (), None),
+}
 
 
 def row(name: str) -> Library:
-    """The row of the library `name`, from either table."""
-    return LIBRARIES[name] if name in LIBRARIES else MORE_LIBRARIES[name]
+    """The row of the library `name`, from any of the tables."""
+    for table in (LIBRARIES, MORE_LIBRARIES, THIRD_LIBRARIES):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 def path(name: str) -> str:
-    """Where the library `name` of LIBRARIES or MORE_LIBRARIES lies: next to this module; FEATHER_HIP_LIB names another main library."""
+    """Where the library `name` of LIBRARIES, MORE_LIBRARIES or THIRD_LIBRARIES lies: next to this module; FEATHER_HIP_LIB names another main library."""
     default = os.path.join(_HERE, row(name).file)
     return os.environ.get("FEATHER_HIP_LIB", default) if name == MAIN else default
 
 
 def load(name: str):
-    """Load the library `name` of either table and type every symbol of its table.  Fails loudly: there is no fallback implementation."""
+    """Load the library `name` of any table and type every symbol of its table.  Fails loudly: there is no fallback implementation."""
     return _load(path(name), row(name).signatures)
 
 
@@ -420,7 +441,7 @@ def load_library():
 
 
 # the names the wrappers, tools/ and the tests call: <x>_path() and load_<x>_library() of every side library
-for _name in (*LIBRARIES, *MORE_LIBRARIES):
+for _name in (*LIBRARIES, *MORE_LIBRARIES, *THIRD_LIBRARIES):
     if _name != MAIN:
         globals()[f"{_name}_path"] = functools.partial(path, _name)
         globals()[f"load_{_name}_library"] = functools.partial(load, _name)

@@ -341,6 +341,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.quantized = n->impl.quantized;
         m->impl.requantized = n->impl.requantized;
         m->impl.concurrency = n->impl.concurrency;
+        m->impl.colpass = n->impl.colpass;
         n->more.push_back(std::move(m));
     }
     if (replicas > 1 && !n->fork) FHIP_CHECK_HIP(hipEventCreateWithFlags(&n->fork, hipEventDisableTiming));
@@ -432,6 +433,16 @@ int fhip_net_set_concurrency(fhip_net* n, int on)
     n->impl.concurrency = on != 0;
     n->impl.shapes_dirty = true; // re-plan (and drop a captured graph) at the next Forward
     for (auto& m : n->more) (void)fhip_net_set_concurrency(m.get(), on);
+    return FHIP_OK;
+}
+
+int fhip_net_set_colpass(fhip_net* n, int mode)
+{
+    NET_GUARD(n);
+    if (mode < 0 || mode > 2) return fail(FHIP_E_BADARG, "colpass mode: 0 never, 1 where M is HBM-bound, 2 wherever the library accepts the layer");
+    n->impl.colpass = mode;
+    n->impl.shapes_dirty = true; // re-plan (and drop a captured graph) at the next Forward
+    for (auto& m : n->more) (void)fhip_net_set_colpass(m.get(), mode);
     return FHIP_OK;
 }
 
@@ -806,6 +817,14 @@ int fhip_net_layer_canvas(fhip_net* n, int index, int* canvas)
     NET_GUARD(n);
     if (index < 0 || index >= (int)n->impl.layers.size() || !canvas) return fail(FHIP_E_BADARG, "layer index out of range");
     *canvas = n->impl.layers[index]->canvas_state();
+    return FHIP_OK;
+}
+
+int fhip_net_layer_colpass(fhip_net* n, int index, int* colpass)
+{
+    NET_GUARD(n);
+    if (index < 0 || index >= (int)n->impl.layers.size() || !colpass) return fail(FHIP_E_BADARG, "layer index out of range");
+    *colpass = n->impl.layers[index]->colpass_state();
     return FHIP_OK;
 }
 

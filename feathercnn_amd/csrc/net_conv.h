@@ -248,6 +248,7 @@ struct ChainPlan
     bool canvas = false;       // V and M hold 2x2 image canvases (feather_canvas.h): the tile GEMM runs on canvas_p at a quarter of the batch
     fhip_conv_param canvas_p = {};
     fhip_winograd_plan run_plan = {}; // the plan this chained layer runs with (plain or canvas)
+    bool colpass = false;             // tile GEMM and boundary run through libfeather_colpass.so: M holds 48 column-passed planes (feather_colpass.h)
     ConvLayer* head_of = nullptr;     // on a first layer: the consumer that computes it inside its input transform (this layer launches nothing)
     ConvLayer* head = nullptr;        // on that consumer: the first layer
 
@@ -580,6 +581,7 @@ struct ConvLayer : Layer
             if (rc) return rc;
         }
         if (chain.canvas || (chain.next && chain.next->chain.canvas)) return forward_canvas(n, in, v, m, vn, b, s);
+        if (chain.colpass) return forward_colpass(n, in, v, m, vn, b, s);
         if (chain.next) return fhip_conv_forward_chained(&p, n, nullptr, in, packed.d, v, m, b, &chain.next->p, vn, pool, s);
         if (!ep.fuse_pool || ep.pool_fast) return fhip_conv_forward_chained(&p, n, tops[0]->data, in, packed.d, v, m, b, nullptr, nullptr, pool, s);
         return pool_tail(fhip_conv_forward_chained(&p, n, ep.pre_pool.d, in, packed.d, v, m, b, nullptr, nullptr, 0, s), s);
@@ -606,6 +608,19 @@ struct ConvLayer : Layer
         }
         else
             rc = api->output(&p, n, &chain.run_plan, tops[0]->data, m, b, ep.fuse_pool ? 1 : 0, s);
+        return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
+    }
+    // A chained layer with a plain chained successor on the column-passed tile GEMM (plan_chains): input transform (a first layer of a run
+    // only) -> the library's GEMM, 48 planes into the M slot -> the library's chained transform.
+    int forward_colpass(int n, const float* in, float* v, float* m, float* vn, const float* b, hipStream_t s)
+    {
+        const ColpassApi* api = colpass_api();
+        if (!api) return FHIP_E_UNSUPPORTED; // message set by colpass_api
+        int rc;
+        if (in && (rc = fhip_winograd_f63_input_transform(&p, n, v, in, s))) return rc;
+        const ConvLayer* nx = chain.next;
+        rc = api->tile_gemm(&p, n, &chain.run_plan, m, packed.d, v, s);
+        if (!rc) rc = api->chain(&p, &nx->p, n, &chain.run_plan, &nx->chain.run_plan, vn, m, b, ep.fuse_pool ? 1 : 0, s);
         return rc ? failf(rc, "layer %s: %s", name.c_str(), api->last_error()) : 0;
     }
     // the main library's route with the epilogues Fuse absorbed: a residual add, a pooling, or neither
@@ -666,6 +681,7 @@ struct ConvLayer : Layer
         *writes_next_v = chain.head_of ? 2 : chain.next ? 1 : 0;
     }
     int canvas_state() const override { return chain.canvas ? 1 : 0; }
+    int colpass_state() const override { return chain.colpass ? 1 : 0; }
 };
 
 inline void ChainPlan::link(ConvLayer* a, ConvLayer* b) { a->chain.next = b, b->chain.in = true, b->chain.pos = a->chain.pos + 1; }

@@ -158,6 +158,7 @@ struct Layer
     virtual const fhip_conv_param* fused_pointwise(int*) const { return nullptr; } // the 1x1 convolution a depthwise layer absorbed
     virtual void chain_state(int* v_from_previous, int* writes_next_v) const { *v_from_previous = *writes_next_v = 0; }
     virtual int canvas_state() const { return 0; }
+    virtual int colpass_state() const { return 0; }
     virtual int sibling_state() const { return 0; } // 1: launches the GEMM that also computes the NEXT layer; 2: computed by the layer before
     virtual int residual_state() const { return 0; } // 1: an Eltwise SUM operand is added in this layer's GEMM epilogue; 2: absorbed, added by a separate launch
 };
@@ -187,6 +188,7 @@ struct Net
     bool quantized = false;       // fhip_net_set_quantized: Convolution / InnerProduct layers with int8 weights (8=int8_scale_term) are loaded (libfeather_qconv.so) instead of refused
     bool detection = false;       // fhip_net_set_detection: the SSD head's layers (net_detect.h, libfeather_detect.so) are loaded instead of refused, Concat and Softmax know a blob's rank
     bool requantized = false;     // fhip_net_set_requantized: an int8 Convolution with int8_scale_term 101 .. 200 (requantised int8 output) is loaded (libfeather_q8.so) instead of refused
+    int colpass = 1;              // fhip_net_set_colpass: chained 64-input-channel Winograd layers through libfeather_colpass.so -- 0 never, 1 where M is HBM-bound, 2 wherever accepted
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;
     // fusion level 3 (plan_chains): runs of Winograd layers hand their transformed input from one to the next; the arena then holds two V

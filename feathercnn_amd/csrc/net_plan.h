@@ -2,6 +2,7 @@
 // plan_concurrency (after every Reshape), reshape_all, prepare, run_layers and forward.
 #pragma once
 #include "net_detect.h"
+#include "wino_gemm_policy.h" // FHIP_M_NT_BYTES: the size class of M the colpass rule shares with the tile GEMM's store policy
 
 namespace fhip::net
 {
@@ -441,6 +442,24 @@ static int plan_chains(Net& net)
         slot[c->chain.pos & 1] = std::max(slot[c->chain.pos & 1], up(c->chain.run_plan.v_bytes));
         msz = std::max(msz, up(c->chain.run_plan.m_bytes));
     }
+    // The column-passed tile GEMM (feather_colpass.h, fhip_net_set_colpass): a chained layer the library accepts, followed by a plain chained
+    // layer, neither on canvases.  Mode 1 takes it where M is of the size class in which GEMM and boundary are HBM-bound (FHIP_M_NT_BYTES,
+    // csrc/wino_gemm_policy.h: VGG-16 b32's conv1_2 and conv2_1) and keeps the main route in a tree without the library; mode 2 takes it
+    // wherever accepted and needs the library.  M48 fits the M slot sized above.
+    if (net.colpass)
+        for (ConvLayer* c : conv)
+        {
+            if (!c || !c->chain.next || c->chain.canvas || c->chain.next->chain.canvas) continue;
+            if (net.colpass == 1 && c->chain.run_plan.m_bytes < (size_t)FHIP_M_NT_BYTES) continue;
+            // the library's rule, stated here too so that a net it would refuse anyway never opens it
+            const fhip_conv_param& q = c->p;
+            if (q.input_channels != 64 || q.output_channels < 64 || (q.output_channels & 63) || c->chain.run_plan.frequency_points != 64) continue;
+            if (q.activation != FHIP_ACT_NONE && q.activation != FHIP_ACT_RELU) continue;
+            const ColpassApi* api = net.colpass == 2 ? colpass_api() : colpass_api_quiet();
+            if (!api && net.colpass == 2) return FHIP_E_UNSUPPORTED; // message set by colpass_api
+            if (!api) break;
+            c->chain.colpass = api->supported(&q, c->bottoms[0]->n) == FHIP_OK;
+        }
     net.chain_slot[0] = 0;
     net.chain_slot[1] = slot[0];
     net.chain_m = slot[0] + slot[1];

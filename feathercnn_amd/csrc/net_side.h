@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "feather_hip/feather_canvas.h" // declarations only: the library is opened at run time (canvas_api)
+#include "feather_hip/feather_colpass.h" // declarations only: the library is opened at run time (colpass_api)
 #include "feather_hip/feather_atrous.h" // declarations only: the library is opened at run time (atrous_api)
 #include "feather_hip/feather_deconv.h" // declarations only: the library is opened at run time (deconv_api)
 #include "feather_hip/feather_detect.h" // declarations only: the library is opened at run time (detect_api)
@@ -345,5 +346,31 @@ struct CanvasApi
     }
 };
 static const CanvasApi* canvas_api() { return side_api<CanvasApi>(); }
+
+// libfeather_colpass.so, the tile GEMM of chained 64-input-channel Winograd layers that writes the column-passed M and the chained transform
+// that reads it (plan_chains, fhip_net_set_colpass).  Like the canvas form a faster way to run the same layers, not a layer type: at mode
+// 1 a tree without the library keeps the main route (colpass_api_quiet), at mode 2 the net fails at plan_chains.
+struct ColpassApi
+{
+    decltype(&fhip_colpass_supported) supported = nullptr;
+    decltype(&fhip_colpass_tile_gemm) tile_gemm = nullptr;
+    decltype(&fhip_colpass_output_to_next_input) chain = nullptr;
+    decltype(&fhip_colpass_last_error) last_error = nullptr;
+    SideLibrary library()
+    {
+        return {"libfeather_colpass.so", "a chained Winograd layer on the column-passed tile GEMM (fhip_net_set_colpass 2)", "feather_colpass.h",
+                {{&supported, "fhip_colpass_supported"}, {&tile_gemm, "fhip_colpass_tile_gemm"}, {&chain, "fhip_colpass_output_to_next_input"},
+                 {&last_error, "fhip_colpass_last_error"}}};
+    }
+};
+static const ColpassApi* colpass_api() { return side_api<ColpassApi>(); }
+// the default mode: a tree without the library is no error, and the thread's last error stays what it was
+static const ColpassApi* colpass_api_quiet()
+{
+    const std::string kept = fhip_last_error();
+    const ColpassApi* api = colpass_api();
+    if (!api) fail(FHIP_OK, kept.c_str());
+    return api;
+}
 
 } // namespace fhip::net

@@ -92,6 +92,12 @@ class Net:
         """fhip_net_set_tuned_selection, legal between Forwards: the routes are chosen again at the next Forward."""
         _check(self._lib.fhip_net_set_tuned_selection(self._h, int(bool(on))), "fhip_net_set_tuned_selection")
 
+    def SetColpass(self, mode: int = 1):
+        """feather::Net::SetColpass (fhip_net_set_colpass), legal between Forwards: how chained Winograd layers with 64 input channels run their
+        tile GEMM and boundary -- 0 on the main route, 1 through libfeather_colpass.so where M is HBM-bound (default), 2 wherever the library
+        accepts the layer.  Planned again (and a captured graph dropped) at the next Forward."""
+        _check(self._lib.fhip_net_set_colpass(self._h, int(mode)), "fhip_net_set_colpass")
+
     def set_concurrency(self, on: bool):
         """fhip_net_set_concurrency, legal between Forwards: the side stream is planned again (and a captured graph dropped) at the next Forward."""
         _check(self._lib.fhip_net_set_concurrency(self._h, int(bool(on))), "fhip_net_set_concurrency")
@@ -323,6 +329,15 @@ class Net:
         for i in range(self._lib.fhip_net_layer_count(self._h)):
             c = ctypes.c_int()
             if self._lib.fhip_net_layer_canvas(self._h, i, ctypes.byref(c)) == 0 and c.value:
+                out.append(i)
+        return out
+
+    def colpasses(self):
+        """[layer index] of the chained Winograd layers that run through libfeather_colpass.so (fhip_net_layer_colpass; fusion level 3)."""
+        out = []
+        for i in range(self._lib.fhip_net_layer_count(self._h)):
+            c = ctypes.c_int()
+            if self._lib.fhip_net_layer_colpass(self._h, i, ctypes.byref(c)) == 0 and c.value:
                 out.append(i)
         return out
 

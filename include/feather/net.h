@@ -232,6 +232,7 @@ class Net
         return 0;
     }
     int SetConcurrency(bool on) { return fhip_net_set_concurrency(net_, on ? 1 : 0); }
+    int SetColpass(int mode) { return fhip_net_set_colpass(net_, mode); } // 0 never, 1 where M is HBM-bound (default), 2 wherever accepted
     int SetSubBatches(int replicas) { return fhip_net_set_sub_batches(net_, replicas); } // before LoadParam (feather_net.h)
     int LayerCount() { return fhip_net_layer_count(net_); }
     static const char* LastError() { return fhip_last_error(); }

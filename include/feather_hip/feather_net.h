@@ -299,6 +299,13 @@ FHIP_API int fhip_net_set_requantized(fhip_net* net, int on);
  * further down the layer list (ResNet's projection shortcut, SqueezeNet's expand1x1) is enqueued on a second stream owned by
  * the net while the main stream continues; fork and join are events (hipGraph-capturable).  0 (default): one stream. */
 FHIP_API int fhip_net_set_concurrency(fhip_net* net, int on);
+/* How a chained Winograd layer (fusion level 3) with 64 input channels and a multiple of 64 output channels, followed by a plain chained layer,
+ * runs its tile GEMM and its boundary: through libfeather_colpass.so (feather_colpass.h: the GEMM applies the output transform's column
+ * pass and writes 48 planes of M instead of 64; every value behind it is bit-identical).  0: never.  1 (default): where the layer's M has
+ * at least 150 MB, the size class in which these launches are HBM-bound (VGG-16 at batch 32: conv1_2 and conv2_1); a tree without the library
+ * keeps the main route, silently.  2: wherever the library accepts the layer; a tree without it then fails at Reshape, like the canvas
+ * library.  The route is decided again at every Reshape.  Other values: FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_colpass(fhip_net* net, int mode);
 /* 1: after the first Forward for a shape, record the layer sequence into a hipGraph and replay it.  Capture is not
  * allowed on the NULL stream: if no stream was set, the net creates and uses its own non-blocking stream (order device
  * inputs produced on other streams yourself). */
@@ -432,6 +439,9 @@ FHIP_API int fhip_net_layer_chain(fhip_net* net, int index, int* v_from_previous
  * one (2H + 2)-pixel image, fhip_winograd_f63_plan_canvas(.., 2) sizes its V and M), 0 otherwise.  VGG-16 at a batch that is a multiple
  * of 4: conv3_1 .. conv3_3 (56 pixels) and conv5_1 .. conv5_3 (14 pixels). */
 FHIP_API int fhip_net_layer_canvas(fhip_net* net, int index, int* canvas);
+/* Fusion level 3: *colpass = 1 when this chained Winograd layer runs its tile GEMM and its boundary through libfeather_colpass.so
+ * (fhip_net_set_colpass; its M holds 48 column-passed planes), 0 otherwise.  VGG-16 at batch 32: conv1_2 and conv2_1. */
+FHIP_API int fhip_net_layer_colpass(fhip_net* net, int index, int* colpass);
 /* Fusion level 2: *state = 1 when this 1x1 convolution's launch also computes the NEXT layer of the list (a 1x1 convolution of the same
  * input: fhip_conv_forward_siblings), 2 when this layer is that next one (it launches nothing), 0 otherwise. */
 FHIP_API int fhip_net_layer_sibling(fhip_net* net, int index, int* state);
