@@ -22,11 +22,15 @@ from .q8 import Q8Conv, Q8Param, q8_max_pool, q8_pack, q8_relu, q8_route, q8_unp
 from .lrn import lrn, lrn_pool, lrn_pool_route, lrn_route
 from .resample import hard_swish, interp, interp_output_dim, interp_route
 from .shuffle import ChannelMap, channel_map, channel_shuffle, channel_slice
+from .yolo import reorg, reorg_output_dim, yolo_detection, yolo_route
+from .yolo import (CHUNK as YOLO_CHUNK, MAX_BOXES as YOLO_MAX_BOXES, MAX_CELLS as YOLO_MAX_CELLS, MAX_CLASSES as YOLO_MAX_CLASSES,
+                   MAX_ROWS as YOLO_MAX_ROWS, MAX_SCALES as YOLO_MAX_SCALES, NET_ROUTE as YOLO_NET_ROUTE)
 from .pixels import (PIXEL_BGR, PIXEL_BGR2GRAY, PIXEL_BGR2RGB, PIXEL_GRAY, PIXEL_GRAY2BGR, PIXEL_GRAY2RGB, PIXEL_RGB, PIXEL_RGB2BGR,
                      PIXEL_RGB2GRAY, PIXEL_RGBA, PIXEL_RGBA2BGR, PIXEL_RGBA2GRAY, PIXEL_RGBA2RGB, float_to_pixels, pixels_images_to_float,
                      pixels_to_float, yuv420sp_to_float)
 
-__all__ = ["permute", "permute_concat", "normalize", "priorbox", "axis_softmax", "detection_output", "detect_route", "Q8Conv", "Q8Param", "q8_pack", "q8_unpack", "q8_relu", "q8_max_pool", "q8_route", "QuantConv", "QuantParam", "quantize", "qconv_route", "dequant_scales", "ConvParam", "ConvBooster", "ConvLayer", "GroupedConv", "GroupedConvLayer", "Deconv", "DeconvLayer", "DeconvParam", "AtrousConv", "AtrousLayer", "AtrousParam", "instance_norm", "instance_norm_route", "activation", "channel_gate", "squeeze", "excite", "gate_activation", "interp", "interp_output_dim", "interp_route", "hard_swish", "lrn", "lrn_pool", "lrn_route", "lrn_pool_route", "channel_shuffle", "channel_slice", "channel_map", "ChannelMap", "FeatherHipError", "load_library", "lib_path", "NAIVE", "IM2COL",
+__all__ = ["reorg", "reorg_output_dim", "yolo_detection", "yolo_route", "YOLO_NET_ROUTE", "YOLO_MAX_SCALES", "YOLO_MAX_BOXES", "YOLO_MAX_CLASSES",
+           "YOLO_MAX_CELLS", "YOLO_MAX_ROWS", "YOLO_CHUNK", "permute", "permute_concat", "normalize", "priorbox", "axis_softmax", "detection_output", "detect_route", "Q8Conv", "Q8Param", "q8_pack", "q8_unpack", "q8_relu", "q8_max_pool", "q8_route", "QuantConv", "QuantParam", "quantize", "qconv_route", "dequant_scales", "ConvParam", "ConvBooster", "ConvLayer", "GroupedConv", "GroupedConvLayer", "Deconv", "DeconvLayer", "DeconvParam", "AtrousConv", "AtrousLayer", "AtrousParam", "instance_norm", "instance_norm_route", "activation", "channel_gate", "squeeze", "excite", "gate_activation", "interp", "interp_output_dim", "interp_route", "hard_swish", "lrn", "lrn_pool", "lrn_route", "lrn_pool_route", "channel_shuffle", "channel_slice", "channel_map", "ChannelMap", "FeatherHipError", "load_library", "lib_path", "NAIVE", "IM2COL",
            "SGECONV", "DEPTHWISE", "WINOGRADF63", "WINOGRADF63FUSED", "WINOGRADF23", "None_", "ReLU", "ALGO_NAMES", "pixels_to_float", "pixels_images_to_float", "float_to_pixels", "yuv420sp_to_float", "PIXEL_RGB", "PIXEL_BGR", "PIXEL_GRAY", "PIXEL_RGBA",
            "PIXEL_RGB2BGR", "PIXEL_RGB2GRAY", "PIXEL_BGR2RGB", "PIXEL_BGR2GRAY", "PIXEL_GRAY2RGB", "PIXEL_GRAY2BGR", "PIXEL_RGBA2RGB",
            "PIXEL_RGBA2BGR", "PIXEL_RGBA2GRAY"]

@@ -109,6 +109,7 @@ SIGNATURES = {
     "fhip_net_set_extended_layers": (_I, [_V, _I]),
     "fhip_net_set_detection": (_I, [_V, _I]),
     "fhip_net_set_colpass": (_I, [_V, _I]),
+    "fhip_net_set_yolo": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -339,6 +340,18 @@ COLPASS_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_yolo.h -- libfeather_yolo.so, the layers of a YOLO detection head: Reorg, YoloDetectionOutput and
+# Yolov3DetectionOutput (a library of its own)
+YOLO_SIGNATURES = {
+    "fhip_reorg_output_dim": (_I, [_I, _I, _I, _I, _PI, _PI, _PI]),
+    "fhip_reorg_forward": (_I, [_I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_yolo_get_buffer_size": (_I, [_I, _I, _I, _I, _PI, _PI, ctypes.POINTER(_SZ)]),
+    "fhip_yolo_detection_forward": (_I, [_I, _I, _I, _I, _I, _PI, _PI, _FL, _FL, _FP, _I, _PI, _FP, _I, _V, _PP, _V, _V]),
+    "fhip_yolo_route": (_I, [_I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_yolo_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -410,18 +423,26 @@ THIRD_LIBRARIES = {
     # route: a faster way to run two layers of a chained Winograd run (fhip_net_set_colpass), not a layer type
     "colpass": Library("libfeather_colpass.so", ("feather_colpass.h",), "FHIP_COLPASS_API", COLPASS_SIGNATURES, "fhip_colpass_last_error", (), None),
 }
+# The rows of SIDE_OPEN of csrc/Makefile, the same tuple: the last table, and an open one.  tests/test_open_contract_cpu.py holds EVERY row
+# of it to the contract the libraries share and takes a row's sweep table from a naming rule (tests/<name>_cases.py: targets(), KERNELS, LIB),
+# so the next library adds a row here, a name to SIDE_OPEN and a cases file -- not a fifth table.
+OPEN_LIBRARIES = {
+    # route: YOLO_ROUTE of net.py (FHIP_YOLO_NET_ROUTE of its own header), outside the closed ROUTE_* set
+    "yolo": Library("libfeather_yolo.so", ("feather_yolo.h",), "FHIP_YOLO_API", YOLO_SIGNATURES, "fhip_yolo_last_error", (), None),
+}
+TABLES = (LIBRARIES, MORE_LIBRARIES, THIRD_LIBRARIES, OPEN_LIBRARIES)
 
 
 def row(name: str) -> Library:
     """The row of the library `name`, from any of the tables."""
-    for table in (LIBRARIES, MORE_LIBRARIES, THIRD_LIBRARIES):
+    for table in TABLES:
         if name in table:
             return table[name]
     raise KeyError(name)
 
 
 def path(name: str) -> str:
-    """Where the library `name` of LIBRARIES, MORE_LIBRARIES or THIRD_LIBRARIES lies: next to this module; FEATHER_HIP_LIB names another main library."""
+    """Where the library `name` of any table lies: next to this module; FEATHER_HIP_LIB names another main library."""
     default = os.path.join(_HERE, row(name).file)
     return os.environ.get("FEATHER_HIP_LIB", default) if name == MAIN else default
 
@@ -441,7 +462,7 @@ def load_library():
 
 
 # the names the wrappers, tools/ and the tests call: <x>_path() and load_<x>_library() of every side library
-for _name in (*LIBRARIES, *MORE_LIBRARIES, *THIRD_LIBRARIES):
+for _name in (n for t in TABLES for n in t):
     if _name != MAIN:
         globals()[f"{_name}_path"] = functools.partial(path, _name)
         globals()[f"load_{_name}_library"] = functools.partial(load, _name)

@@ -17,7 +17,8 @@
 //
 // One translation unit, read in this order (no header includes a later one): net_side.h -- errors, the side libraries; net_model.h --
 // ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_conv.h -- the convolution layer, its side routes
-// and the weight staging it shares; net_layers.h -- the other layer classes; net_detect.h -- the detection-head layers and their factory; net_plan.h -- the fusion and planning passes, prepare,
+// and the weight staging it shares; net_layers.h -- the other layer classes; net_detect.h -- the detection-head layers and their factory; net_yolo.h -- the YOLO-head layers and
+// theirs; net_plan.h -- the fusion and planning passes, prepare,
 // forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
 #include "net_side.h"
 #include "net_model.h"
@@ -25,6 +26,7 @@
 #include "net_conv.h"
 #include "net_layers.h"
 #include "net_detect.h"
+#include "net_yolo.h"
 #include "net_plan.h"
 
 namespace fhip::net
@@ -100,11 +102,13 @@ static int load_param_text(Net& net, const char* text, size_t len)
         std::unique_ptr<Layer> layer(net.detection ? create_detection_layer(type) : nullptr); // asked first: it overrides Concat and Softmax
         if (!layer) layer.reset(create_layer(type));
         if (!layer && net.extended) layer.reset(create_extended_layer(type));
+        if (!layer && net.yolo) layer.reset(create_yolo_layer(type));
         if (!layer)
         {
-            std::unique_ptr<Layer> opt_in(create_extended_layer(type)), detect(create_detection_layer(type));
+            std::unique_ptr<Layer> opt_in(create_extended_layer(type)), detect(create_detection_layer(type)), yolo(create_yolo_layer(type));
             return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered%s", type.c_str(),
-                         opt_in ? " (fhip_net_set_extended_layers lifts this)" : (detect ? " (fhip_net_set_detection lifts this)" : ""));
+                         opt_in ? " (fhip_net_set_extended_layers lifts this)"
+                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : "")));
         }
         layer->type = type;
         layer->name = name;
@@ -342,6 +346,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.requantized = n->impl.requantized;
         m->impl.concurrency = n->impl.concurrency;
         m->impl.colpass = n->impl.colpass;
+        m->impl.yolo = n->impl.yolo;
         n->more.push_back(std::move(m));
     }
     if (replicas > 1 && !n->fork) FHIP_CHECK_HIP(hipEventCreateWithFlags(&n->fork, hipEventDisableTiming));
@@ -406,6 +411,16 @@ int fhip_net_set_detection(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the detection-layers switch before LoadParam");
     n->impl.detection = on != 0;
     for (auto& m : n->more) m->impl.detection = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_yolo(fhip_net* n, int rows)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the YOLO-layers switch before LoadParam");
+    if (rows < 0 || rows > FHIP_YOLO_MAX_ROWS) return fail(FHIP_E_BADARG, "rows of the YOLO detection top: 0 (off) or 1 .. FHIP_YOLO_MAX_ROWS (1024)");
+    n->impl.yolo = rows;
+    for (auto& m : n->more) m->impl.yolo = rows;
     return FHIP_OK;
 }
 

@@ -239,6 +239,7 @@ class GraphBuilder:
 
     def split(self, name, bottom, n=2):
         tops = [f"{name}_{i}" for i in range(n)]
+        self._note("split", name, bottom, tops, {})
         self.layer("Split", name, [bottom], tops)
         return tops
 
@@ -247,6 +248,7 @@ class GraphBuilder:
 
     def concat(self, name, bottoms, axis=0):
         """axis: relative to the bottoms' rank; anything but 0 on blobs of rank 3 needs Net.SetDetection(True)."""
+        self._note("concat", name, list(bottoms), name, dict(axis=axis))
         return self.layer("Concat", name, list(bottoms), [name], {0: axis})
 
     # -- the SSD detection head (a net that holds one of these needs Net.SetDetection(True)) ------------------------
@@ -310,6 +312,30 @@ class GraphBuilder:
         conf = self.reshape("mbox_conf_reshape", conf, num_class, -1)
         conf = self.flatten("mbox_conf_flatten", self.softmax("mbox_conf_softmax", conf, axis=1))
         return self.detection_output("detection_out", loc, conf, prior, num_class, **detection)
+
+    # -- the YOLO heads (a net that holds one of these needs Net.SetYolo()) ----------------------------------------------
+    def reorg(self, name, bottom, stride, mode=None):
+        """ncnn's Reorg: 0=stride, 1=mode (written only when given): [c][h][w] -> [c * stride^2][h / stride][w / stride]."""
+        self._note("reorg", name, bottom, name, dict(stride=int(stride), mode=int(mode or 0)))
+        return self.layer("Reorg", name, [bottom], [name], {0: int(stride)} if mode is None else {0: int(stride), 1: int(mode)})
+
+    @staticmethod
+    def _array(values, fmt):
+        return ",".join([str(len(values))] + [fmt(v) for v in values])
+
+    def yolo_detection_output(self, name, bottoms, num_class, num_box, biases, confidence_threshold=0.01, nms_threshold=0.45):
+        """ncnn's YoloDetectionOutput (YOLOv2): -23304=biases, num_box pairs (width, height) in cells."""
+        return self.layer("YoloDetectionOutput", name, list(bottoms), [name],
+                          {0: int(num_class), 1: int(num_box), 2: f"{confidence_threshold:.6f}", 3: f"{nms_threshold:.6f}",
+                           -23304: self._array(biases, lambda v: f"{float(v):.6f}")})
+
+    def yolov3_detection_output(self, name, bottoms, num_class, num_box, biases, mask, anchors_scale, confidence_threshold=0.01, nms_threshold=0.45):
+        """ncnn's Yolov3DetectionOutput: -23304=biases (anchor pairs in pixels), -23305=mask (num_box anchors per bottom), -23306=anchors_scale
+        (the stride of every bottom)."""
+        return self.layer("Yolov3DetectionOutput", name, list(bottoms), [name],
+                          {0: int(num_class), 1: int(num_box), 2: f"{confidence_threshold:.6f}", 3: f"{nms_threshold:.6f}",
+                           -23304: self._array(biases, lambda v: f"{float(v):.6f}"), -23305: self._array(mask, lambda v: f"{float(v):.6f}"),
+                           -23306: self._array(anchors_scale, lambda v: f"{float(v):.6f}")})
 
     def shuffle(self, name, bottom, group, reverse=False):
         """ncnn's ShuffleChannel: 0=group, 1=reverse (written only when set)."""
@@ -377,6 +403,7 @@ class GraphBuilder:
             params.update({1: f"{hs:.6f}", 2: f"{ws:.6f}"})
         if align_corner:
             params[6] = 1
+        self._note("interp", name, bottom, name, dict(mode=mode, scale=scale, size=size, like=like))
         return self.layer("Interp", name, [bottom] + ([like] if like is not None else []), [name], params)
 
     def lrn(self, name, bottom, local_size, alpha, beta, bias=1.0, region=0):
@@ -411,11 +438,26 @@ class GraphBuilder:
 
 def numpy_forward(trace, input_name, x):
     """A plain numpy forward (fp32 values, sums in float64) of the layers a GraphBuilder recorded in `trace` -- Convolution, InnerProduct,
-    plain ReLU, BatchNorm, Scale, Pooling -- from the input `x` [N][C][H][W]: every blob by name.  It exists to calibrate input scales."""
+    ReLU (plain or leaky), BatchNorm, Scale, Pooling, Split, Concat on channels, Reorg, nearest Interp by a whole scale -- from the input `x`
+    [N][C][H][W]: every blob by name.  It exists to calibrate input scales and to feed the restatement of a detection head."""
     blobs = {input_name: np.asarray(x, np.float32)}
     for kind, name, bottom, top, a in trace:
-        v = blobs[bottom]
-        if kind == "conv":
+        v = blobs[bottom] if isinstance(bottom, str) else [blobs[b] for b in bottom]
+        if kind == "split":
+            for t in top:
+                blobs[t] = v
+            continue
+        if kind == "concat" and a["axis"] == 0:
+            y = np.concatenate(v, axis=1)
+        elif kind == "reorg":
+            st, (n, c, h, wd) = a["stride"], v.shape
+            t = v[:, :, :h // st * st, :wd // st * st].reshape(n, c, h // st, st, wd // st, st).transpose(0, 1, 3, 5, 2, 4)  # [n][q][sh][sw][i][j]
+            y = (t if a["mode"] == 0 else t.transpose(0, 2, 3, 1, 4, 5)).reshape(n, c * st * st, h // st, wd // st)
+        elif kind == "interp" and a["mode"] == "nearest" and a["like"] is None and a["size"] is None and float(a["scale"]) == int(a["scale"]):
+            y = v.repeat(int(a["scale"]), axis=2).repeat(int(a["scale"]), axis=3)
+        elif kind == "relu" and a["slope"] is not None:
+            y = np.where(v > 0, v, v * np.float32(a["slope"]))
+        elif kind == "conv":
             w, s, p, group = a["w"].astype(np.float64), a["s"], a["p"], a["group"]
             k, cg, kh, kw = w.shape
             n, c, h, wd = v.shape
@@ -1455,6 +1497,100 @@ def vgg16_ssd300(seed=1234, classes=21, size=300, dry=False, confidence_threshol
     return g.finish() + ("data", "detection_out")
 
 
+def tiny_yolov2(seed=47, size=(12, 20), dry=False, trace=None, confidence_threshold=0.3, nms_threshold=0.45):
+    """A small YOLOv2 (Net.SetYolo()): a 12 x 20 image, convolutions of 3 -> 8 channels, the passthrough of YOLOv2 -- a Reorg 0=2 of the
+    full-resolution map concatenated with the trunk behind a pooling -- a 1x1 head of 2 boxes x (5 + 3 classes) on 6 x 10 cells and
+    YoloDetectionOutput.  size = (height, width); trace: a list that receives the layers for numpy_forward."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    x = g.relu("relu1", g.conv("conv1", g.input("data", 3, h, w), 3, 8, 3, 1, 1))
+    fine, x = g.split("split1", x, 2)
+    x = g.relu("relu2", g.conv("conv2", g.pool("pool1", x, 2, 2), 8, 8, 3, 1, 1))
+    x = g.concat("route", [g.reorg("reorg", fine, 2), x])
+    head = g.conv("head", x, 40, 2 * (5 + 3), 1, gain=3.0)
+    g.yolo_detection_output("detection_out", [head], 3, 2, [1.5, 2.0, 3.0, 2.5], confidence_threshold, nms_threshold)
+    return g.finish() + ("data", "detection_out")
+
+
+def tiny_yolov3(seed=53, size=(16, 24), dry=False, trace=None, confidence_threshold=0.3, nms_threshold=0.45):
+    """A small YOLOv3 (Net.SetYolo() and Net.SetExtendedLayers(True)): a 16 x 24 image, a head on 4 x 6 cells (stride 4), a nearest Interp x2
+    of its branch concatenated with the 8 x 12 map and a second head there (stride 2); Yolov3DetectionOutput with 2 of 4 anchors per scale
+    through masks, 3 classes.  size = (height, width); trace: a list that receives the layers for numpy_forward."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    x = g.pool("pool1", g.relu("relu1", g.conv("conv1", g.input("data", 3, h, w), 3, 8, 3, 1, 1)), 2, 2)
+    fine, x = g.split("split1", x, 2)
+    x = g.relu("relu2", g.conv("conv2", x, 8, 16, 3, 2, 1))
+    coarse, x = g.split("split2", x, 2)
+    head1 = g.conv("head1", coarse, 16, 2 * (5 + 3), 1, gain=3.0)
+    x = g.interp("up", g.relu("relu3", g.conv("conv3", x, 16, 8, 1)), mode="nearest", scale=2.0)
+    x = g.relu("relu4", g.conv("conv4", g.concat("route", [x, fine]), 16, 8, 3, 1, 1))
+    head2 = g.conv("head2", x, 8, 2 * (5 + 3), 1, gain=3.0)
+    g.yolov3_detection_output("detection_out", [head1, head2], 3, 2, [3.0, 4.0, 5.0, 3.0, 7.0, 9.0, 10.0, 6.0], [2, 3, 0, 1], [4.0, 2.0],
+                              confidence_threshold, nms_threshold)
+    return g.finish() + ("data", "detection_out")
+
+
+def yolov2_tiny_voc(seed=1234, classes=20, size=416, dry=False, confidence_threshold=0.25, nms_threshold=0.45):
+    """YOLOv2-tiny for VOC (Redmon & Farhadi 2017, tiny-yolo-voc.cfg as darknet2ncnn writes it): six 3x3 convolutions of 16 .. 512 channels,
+    each BatchNorm + Scale + leaky ReLU 0.1 and a 2x2 max pooling (the sixth with stride 1, padded right and below), two of 1024, a linear 1x1
+    head of 5 boxes x (5 + 20) = 125 channels on 13 x 13 cells at 416 px, YoloDetectionOutput.  Net.SetYolo()."""
+    g = GraphBuilder(seed, dry)
+    x, cin = g.input("data", 3, size, size), 3
+    for i, c in enumerate((16, 32, 64, 128, 256, 512), 1):
+        x = g.relu(f"conv{i}_leaky", g.scale(f"conv{i}_scale", g.bn(f"conv{i}_bn", g.conv(f"conv{i}", x, cin, c, 3, 1, 1, bias=False), c), c), 0.1)
+        x = g.pool(f"pool{i}", x, 2, 2) if i < 6 else g.layer("Pooling", "pool6", [x], ["pool6"], {0: 0, 1: 2, 2: 1, 3: 0, 4: 0, 14: 1, 15: 1})
+        cin = c
+    for i in (7, 8):
+        x = g.relu(f"conv{i}_leaky", g.scale(f"conv{i}_scale", g.bn(f"conv{i}_bn", g.conv(f"conv{i}", x, cin, 1024, 3, 1, 1, bias=False), 1024), 1024), 0.1)
+        cin = 1024
+    head = g.conv("conv9", x, 1024, 5 * (5 + classes), 1)
+    g.yolo_detection_output("detection_out", [head], classes, 5, [1.08, 1.19, 3.42, 4.41, 6.63, 11.38, 9.42, 5.11, 16.62, 10.52], confidence_threshold,
+                            nms_threshold)
+    return g.finish() + ("data", "detection_out")
+
+
+def mobilenetv2_yolov3(seed=1234, classes=20, size=352, dry=False, confidence_threshold=0.25, nms_threshold=0.45):
+    """MobileNetV2-YOLOv3 at 352 px, the topology of the MobileNet-YOLO model ncnn's yolov3 example runs: the MobileNetV2 trunk (Sandler et al.
+    2018) to 1280 channels on 11 x 11 cells, depthwise-separable head convolutions, a linear 1x1 head of 3 boxes x (5 + 20) = 75 channels
+    there; a DeconvolutionDepthWise x2 of the head's trunk added (Eltwise SUM) to a lateral of the 22 x 22 map, and a second head on it;
+    Yolov3DetectionOutput over both with masks 3, 4, 5 and 0, 1, 2 and strides 32 and 16.  Net.SetYolo()."""
+    g = GraphBuilder(seed, dry)
+    x = g.conv_bn_relu("conv1", g.input("data", 3, size, size), 3, 32, 3, 2, 1)
+    cin, unit, maps = 32, 0, {}
+
+    def dwpw(name, x, cin, cout, s=1, relu=True):
+        x = g.conv_bn_relu(name + "/dw", x, cin, cin, 3, s, 1, group=cin)
+        return g.conv_bn_relu(name, x, cin, cout, 1, relu=relu)
+
+    for t, c, n, s in ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)):
+        for i in range(n):
+            unit += 1
+            stride = s if i == 0 else 1
+            keep = None
+            if stride == 1 and cin == c:
+                keep, x = g.split(f"block{unit}_split", x, 2)
+            y = g.conv_bn_relu(f"block{unit}_expand", x, cin, cin * t, 1) if t != 1 else x
+            y = g.conv_bn_relu(f"block{unit}_dw", y, cin * t, cin * t, 3, stride, 1, group=cin * t)
+            y = g.conv_bn_relu(f"block{unit}_project", y, cin * t, c, 1, relu=False)
+            x = g.eltwise(f"block{unit}_sum", keep, y) if keep is not None else y
+            cin = c
+        if c == 96:
+            maps[16], x = g.split("stride16_split", x, 2)
+    x = g.conv_bn_relu("conv_last", x, 320, 1280, 1)
+    x = dwpw("yolo/conv1", x, 1280, 1024)
+    up, x = g.split("yolo/split", x, 2)
+    head1 = g.conv("yolo/conv4", dwpw("yolo/conv2", x, 1024, 1024), 1024, 3 * (5 + classes), 1)
+    up = g.deconv("upsample", g.conv_bn_relu("yolo/reduce", up, 1024, 512, 1), 512, 512, 4, 2, 1, group=512, bias=False)
+    x = g.eltwise("yolo/sum", up, dwpw("yolo/lateral", maps[16], 96, 512))
+    head2 = g.conv("yolo/conv5", dwpw("yolo/conv3", x, 512, 512), 512, 3 * (5 + classes), 1)
+    g.yolov3_detection_output("detection_out", [head1, head2], classes, 3, [20, 37, 49, 94, 73, 201, 143, 265, 153, 121, 280, 279], [3, 4, 5, 0, 1, 2],
+                              [32.0, 16.0], confidence_threshold, nms_threshold)
+    return g.finish() + ("data", "detection_out")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
@@ -1470,7 +1606,8 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_quant": tiny_quant, "vgg16_int8": vgg16_int8, "resnet50_int8": resnet50_int8, "mobilenet_v1_int8": mobilenet_v1_int8,
           "tiny_requant": tiny_requant, "tiny_requant_twin": tiny_requant_twin,
           "vgg16_int8_rq": vgg16_int8_rq, "resnet50_int8_rq": resnet50_int8_rq, "mobilenet_v1_int8_rq": mobilenet_v1_int8_rq,
-          "tiny_ssd": tiny_ssd, "mobilenet_ssd": mobilenet_ssd, "vgg16_ssd300": vgg16_ssd300}
+          "tiny_ssd": tiny_ssd, "mobilenet_ssd": mobilenet_ssd, "vgg16_ssd300": vgg16_ssd300,
+          "tiny_yolov2": tiny_yolov2, "tiny_yolov3": tiny_yolov3, "yolov2_tiny_voc": yolov2_tiny_voc, "mobilenetv2_yolov3": mobilenetv2_yolov3}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -1497,8 +1634,11 @@ QUANT_LAYERS["tiny_requant"] = QUANT_LAYERS["tiny_requant_twin"] = ("conv1", "co
 DETECTION_NETS = ("tiny_ssd", "mobilenet_ssd", "vgg16_ssd300")
 DILATED_LAYERS["vgg16_ssd300"] = ("fc6",)
 
+# nets that need Net.SetYolo() (the YOLO heads: libfeather_yolo.so); tiny_yolov3 needs Net.SetExtendedLayers(True) as well (its Interp)
+YOLO_NETS = ("tiny_yolov2", "tiny_yolov3", "yolov2_tiny_voc", "mobilenetv2_yolov3")
+
 # the input size a builder's defaults describe, where it is not 224 px
-INPUT_SIZE = {"alexnet": 227, "caffenet": 227, "mobilenet_ssd": 300, "vgg16_ssd300": 300}
+INPUT_SIZE = {"alexnet": 227, "caffenet": 227, "mobilenet_ssd": 300, "vgg16_ssd300": 300, "yolov2_tiny_voc": 416, "mobilenetv2_yolov3": 352}
 
 # the LRN layers of each net that fusion level 2 makes one layer with the Pooling layer behind them, and those that must stay as written
 LRN_POOLS = {"tiny_lrn": (("norm1", "norm2", "norm5"), ("norm3", "norm4")), "alexnet": (("norm1", "norm2"), ()), "caffenet": ((), ("norm1", "norm2")),

@@ -33,6 +33,8 @@ ROUTE_QCONV = 108  # FHIP_NET_ROUTE_QCONV: a Convolution / InnerProduct layer wi
 ROUTE_NAMES[ROUTE_QCONV] = "QCONV"
 DETECT_ROUTE = 109  # FHIP_DETECT_NET_ROUTE (feather_detect.h): a layer of an SSD detection head, after SetDetection(True) (libfeather_detect.so)
 ROUTE_NAMES[DETECT_ROUTE] = "DETECT"
+YOLO_ROUTE = 110  # FHIP_YOLO_NET_ROUTE (feather_yolo.h): a layer of a YOLO head, after SetYolo() (libfeather_yolo.so)
+ROUTE_NAMES[YOLO_ROUTE] = "YOLO"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -84,6 +86,12 @@ class Net:
         DetectionOutput, and Concat / Softmax along any axis of a blob's rank (routed to libfeather_detect.so) -- instead of refusing them at
         LoadParam.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_detection(self._h, int(bool(on))), "fhip_net_set_detection")
+
+    def SetYolo(self, rows: int = 256):
+        """feather::Net::SetYolo: accept the layers of ncnn's YOLO heads -- Reorg, YoloDetectionOutput and Yolov3DetectionOutput (routed to
+        libfeather_yolo.so) -- instead of refusing them at LoadParam.  `rows` (1 .. 1024) is the height of the detection top: the first `rows`
+        detections of every image, read by ExtractDetections; 0 switches the layers off again.  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_yolo(self._h, int(rows)), "fhip_net_set_yolo")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

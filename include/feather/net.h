@@ -231,6 +231,10 @@ class Net
             }
         return 0;
     }
+    // accept the layers of ncnn's YOLO heads -- Reorg, YoloDetectionOutput, Yolov3DetectionOutput (libfeather_yolo.so) -- instead of refusing
+    // them; `rows` is the height of the detection top ExtractDetections reads (the first `rows` detections of an image), 0 switches it off;
+    // before LoadParam (feather_net.h)
+    int SetYolo(int rows = 256) { return fhip_net_set_yolo(net_, rows); }
     int SetConcurrency(bool on) { return fhip_net_set_concurrency(net_, on ? 1 : 0); }
     int SetColpass(int mode) { return fhip_net_set_colpass(net_, mode); } // 0 never, 1 where M is HBM-bound (default), 2 wherever accepted
     int SetSubBatches(int replicas) { return fhip_net_set_sub_batches(net_, replicas); } // before LoadParam (feather_net.h)

@@ -276,6 +276,14 @@ FHIP_API int fhip_net_set_extended_layers(fhip_net* net, int on);
  * refuses every axis but channels and Softmax ignores its params, as before.  Its only effect is lifting those refusals: PixelShuffle and
  * Padding stay -200.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
 FHIP_API int fhip_net_set_detection(fhip_net* net, int on);
+/* rows >= 1: the layers of ncnn's YOLO heads are loaded -- Reorg, YoloDetectionOutput (YOLOv2) and Yolov3DetectionOutput, as feather_yolo.h
+ * defines them; they run through libfeather_yolo.so and report the route FHIP_YOLO_NET_ROUTE (feather_yolo.h).  The top of either detection
+ * layer is [n][1][rows][6] of rank 2 -- rows (label + 1, score, xmin, ymin, xmax, ymax), the first `rows` survivors of the NMS, zero rows past
+ * an image's count -- the shape Net::ExtractDetections reads.  Nothing fuses into these layers: every fusion level runs them as written.
+ * 0 (default): LoadParam refuses the three types with -200.  Its only effect is lifting that refusal: PixelShuffle and Padding stay -200.
+ * rows outside 0 .. FHIP_YOLO_MAX_ROWS (1024): FHIP_E_BADARG.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch
+ * replicas. */
+FHIP_API int fhip_net_set_yolo(fhip_net* net, int rows);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
