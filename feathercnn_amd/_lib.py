@@ -110,6 +110,7 @@ SIGNATURES = {
     "fhip_net_set_detection": (_I, [_V, _I]),
     "fhip_net_set_colpass": (_I, [_V, _I]),
     "fhip_net_set_yolo": (_I, [_V, _I]),
+    "fhip_net_set_roi": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -352,6 +353,20 @@ YOLO_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_roi.h -- libfeather_roi.so, the layers of a two-stage detector: Proposal, ROIPooling, ROIAlign and PSROIPooling
+# (a library of its own)
+ROI_SIGNATURES = {
+    "fhip_roi_generate_anchors": (_I, [_I, _FP, _I, _FP, _I, _FP]),
+    "fhip_proposal_get_buffer_size": (_I, [_I, _I, _I, _I, ctypes.POINTER(_SZ)]),
+    "fhip_proposal_forward": (_I, [_I, _I, _I, _I, _I, _I, _I, _FL, _FL, _FP, _V, _V, _V, _V, _V, _V, _V]),
+    "fhip_roi_pool_forward": (_I, [_I, _I, _I, _I, _I, _I, _I, _FL, _V, _V, _V, _V]),
+    "fhip_roi_align_forward": (_I, [_I, _I, _I, _I, _I, _I, _I, _FL, _I, _I, _I, _V, _V, _V, _V]),
+    "fhip_psroi_pool_forward": (_I, [_I, _I, _I, _I, _I, _I, _I, _FL, _I, _V, _V, _V, _V]),
+    "fhip_roi_route": (_I, [_I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_roi_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -429,6 +444,8 @@ THIRD_LIBRARIES = {
 OPEN_LIBRARIES = {
     # route: YOLO_ROUTE of net.py (FHIP_YOLO_NET_ROUTE of its own header), outside the closed ROUTE_* set
     "yolo": Library("libfeather_yolo.so", ("feather_yolo.h",), "FHIP_YOLO_API", YOLO_SIGNATURES, "fhip_yolo_last_error", (), None),
+    # route: ROI_ROUTE of net.py (FHIP_ROI_NET_ROUTE of its own header)
+    "roi": Library("libfeather_roi.so", ("feather_roi.h",), "FHIP_ROI_API", ROI_SIGNATURES, "fhip_roi_last_error", (), None),
 }
 TABLES = (LIBRARIES, MORE_LIBRARIES, THIRD_LIBRARIES, OPEN_LIBRARIES)
 

@@ -189,6 +189,7 @@ struct Net
     bool detection = false;       // fhip_net_set_detection: the SSD head's layers (net_detect.h, libfeather_detect.so) are loaded instead of refused, Concat and Softmax know a blob's rank
     bool requantized = false;     // fhip_net_set_requantized: an int8 Convolution with int8_scale_term 101 .. 200 (requantised int8 output) is loaded (libfeather_q8.so) instead of refused
     int yolo = 0;                 // fhip_net_set_yolo: > 0: Reorg, YoloDetectionOutput and Yolov3DetectionOutput (net_yolo.h, libfeather_yolo.so) are loaded instead of refused; the rows of the detection top
+    bool roi = false;             // fhip_net_set_roi: Proposal, ROIPooling, ROIAlign and PSROIPooling (net_roi.h, libfeather_roi.so) are loaded instead of refused
     int colpass = 1;              // fhip_net_set_colpass: chained 64-input-channel Winograd layers through libfeather_colpass.so -- 0 never, 1 where M is HBM-bound, 2 wherever accepted
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;

@@ -337,6 +337,47 @@ class GraphBuilder:
                            -23304: self._array(biases, lambda v: f"{float(v):.6f}"), -23305: self._array(mask, lambda v: f"{float(v):.6f}"),
                            -23306: self._array(anchors_scale, lambda v: f"{float(v):.6f}")})
 
+    # -- the two-stage detectors (a net that holds one of these needs Net.SetRoi(); rpn_softmax needs Net.SetDetection(True)) ----------
+    def rpn_softmax(self, name, bottom, anchors=9):
+        """The RPN's two-way softmax as py-faster-rcnn writes it: Reshape [2A][h][w] -> [2][A * h][w], Softmax along the channels, Reshape back
+        to [2A][h][w].  Foreground plane A + q against background plane q."""
+        trace, self.trace = self.trace, None  # one note for the three layers
+        x = self.reshape(name + "_reshape", bottom, 0, -1, 2)
+        x = self.softmax(name + "_prob", x, axis=0)
+        top = self.reshape(name + "_prob_reshape", x, 0, -1, 2 * anchors)
+        self.trace = trace
+        self._note("rpn_softmax", name, bottom, top, dict(anchors=anchors))
+        return top
+
+    def proposal(self, name, score, bbox, im_info, feat_stride=16, base_size=16, pre_nms_topN=6000, after_nms_topN=300, nms_thresh=0.7, min_size=16,
+                 with_scores=False):
+        """ncnn's Proposal: 0=feat_stride 1=base_size 2=pre_nms_topN 3=after_nms_topN 4=nms_thresh 5=min_size; the top [after_nms_topN][1][4]
+        (and, with_scores, a second top name + "_scores")."""
+        tops = [name, name + "_scores"] if with_scores else [name]
+        a = dict(feat_stride=int(feat_stride), base_size=int(base_size), pre_nms_topN=int(pre_nms_topN), after_nms_topN=int(after_nms_topN),
+                 nms_thresh=float(nms_thresh), min_size=int(min_size))
+        self._note("proposal", name, [score, bbox, im_info], tops, a)
+        self.layer("Proposal", name, [score, bbox, im_info], tops, {0: a["feat_stride"], 1: a["base_size"], 2: a["pre_nms_topN"], 3: a["after_nms_topN"],
+                                                                     4: f"{nms_thresh:.6f}", 5: a["min_size"]})
+        return tops if with_scores else name
+
+    def roi_pooling(self, name, features, rois, pooled_w=7, pooled_h=7, spatial_scale=0.0625):
+        """ncnn's ROIPooling: 0=pooled_width 1=pooled_height 2=spatial_scale; the top holds one row per ROI."""
+        self._note("roi_pooling", name, [features, rois], name, dict(pooled_w=pooled_w, pooled_h=pooled_h, spatial_scale=spatial_scale))
+        return self.layer("ROIPooling", name, [features, rois], [name], {0: int(pooled_w), 1: int(pooled_h), 2: f"{spatial_scale:.6f}"})
+
+    def roi_align(self, name, features, rois, pooled_w=7, pooled_h=7, spatial_scale=0.0625, sampling_ratio=0, aligned=False, version=0):
+        """ncnn's ROIAlign: + 3=sampling_ratio 4=aligned 5=version (0 ncnn's original, 1 detectron2's)."""
+        a = dict(pooled_w=pooled_w, pooled_h=pooled_h, spatial_scale=spatial_scale, sampling_ratio=int(sampling_ratio), aligned=int(aligned), version=int(version))
+        self._note("roi_align", name, [features, rois], name, a)
+        return self.layer("ROIAlign", name, [features, rois], [name],
+                          {0: int(pooled_w), 1: int(pooled_h), 2: f"{spatial_scale:.6f}", 3: a["sampling_ratio"], 4: a["aligned"], 5: a["version"]})
+
+    def psroi_pooling(self, name, features, rois, output_dim, pooled_w=7, pooled_h=7, spatial_scale=0.0625):
+        """ncnn's PSROIPooling: + 3=output_dim; the features hold output_dim * pooled_h * pooled_w channels."""
+        self._note("psroi_pooling", name, [features, rois], name, dict(output_dim=int(output_dim), pooled_w=pooled_w, pooled_h=pooled_h, spatial_scale=spatial_scale))
+        return self.layer("PSROIPooling", name, [features, rois], [name], {0: int(pooled_w), 1: int(pooled_h), 2: f"{spatial_scale:.6f}", 3: int(output_dim)})
+
     def shuffle(self, name, bottom, group, reverse=False):
         """ncnn's ShuffleChannel: 0=group, 1=reverse (written only when set)."""
         return self.layer("ShuffleChannel", name, [bottom], [name], {0: group, 1: 1} if reverse else {0: group})
@@ -420,6 +461,7 @@ class GraphBuilder:
 
     def softmax(self, name, bottom, axis=None):
         """axis: ncnn's 0=axis with 1=fixbug0 (needs Net.SetDetection(True)); None writes no params, the plain layer."""
+        self._note("softmax", name, bottom, name, dict(axis=axis))
         return self.layer("Softmax", name, [bottom], [name], None if axis is None else {0: int(axis), 1: 1})
 
     def conv_bn_relu(self, name, bottom, cin, cout, k, s=1, p=0, group=1, relu=True, dilation=1):
@@ -436,19 +478,58 @@ class GraphBuilder:
         return text.encode(), (self.nbytes if self.dry else bytes(self.bin))  # dry: the .bin size instead of the .bin
 
 
-def numpy_forward(trace, input_name, x):
+def _roi_ref():
+    """tests/roi_ref.py, the float32 restatement of feather_roi.h: numpy_forward's Proposal and ROI layers are that text, not a second one."""
+    try:
+        import roi_ref
+    except ImportError:
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import roi_ref
+    return roi_ref
+
+
+def numpy_forward(trace, input_name, x=None):
     """A plain numpy forward (fp32 values, sums in float64) of the layers a GraphBuilder recorded in `trace` -- Convolution, InnerProduct,
-    ReLU (plain or leaky), BatchNorm, Scale, Pooling, Split, Concat on channels, Reorg, nearest Interp by a whole scale -- from the input `x`
-    [N][C][H][W]: every blob by name.  It exists to calibrate input scales and to feed the restatement of a detection head."""
-    blobs = {input_name: np.asarray(x, np.float32)}
+    ReLU (plain or leaky), BatchNorm, Scale, Pooling, Split, Concat on channels, Reorg, nearest Interp by a whole scale, the RPN's softmax, a
+    Softmax over the channels of [N][C][1][1], Proposal and the three ROI layers (tests/roi_ref.py in float32) -- from the input `x`
+    [N][C][H][W], or from several: `input_name` a dict {name: array} and no `x`.  Every blob by name.  It exists to calibrate input scales
+    and to feed the restatement of a detection head."""
+    blobs = {k: np.asarray(v, np.float32) for k, v in input_name.items()} if isinstance(input_name, dict) else {input_name: np.asarray(x, np.float32)}
     for kind, name, bottom, top, a in trace:
         v = blobs[bottom] if isinstance(bottom, str) else [blobs[b] for b in bottom]
         if kind == "split":
             for t in top:
                 blobs[t] = v
             continue
+        if kind == "proposal":
+            ref = _roi_ref()
+            rois, scores = ref.proposal(v[0], v[1], v[2].reshape(-1, 3), ref.generate_anchors(a["base_size"]), a["feat_stride"], a["pre_nms_topN"],
+                                        a["after_nms_topN"], a["nms_thresh"], a["min_size"])
+            blobs[top[0]] = rois.reshape(rois.shape[0], -1, 1, 4)
+            if len(top) > 1:
+                blobs[top[1]] = scores.reshape(scores.shape[0], -1, 1, 1)
+            continue
         if kind == "concat" and a["axis"] == 0:
             y = np.concatenate(v, axis=1)
+        elif kind == "rpn_softmax":
+            A = a["anchors"]
+            bg, fg = v[:, :A].astype(np.float64), v[:, A:].astype(np.float64)
+            m = np.maximum(bg, fg)
+            eb, ef = np.exp(bg - m), np.exp(fg - m)
+            y = np.concatenate([eb / (eb + ef), ef / (eb + ef)], axis=1)
+        elif kind == "softmax" and a["axis"] is None and v.shape[2:] == (1, 1):
+            e = np.exp(v.astype(np.float64) - v.max(axis=1, keepdims=True))
+            y = e / e.sum(axis=1, keepdims=True)
+        elif kind == "roi_pooling":
+            y = _roi_ref().roi_pool(v[0], v[1], a["pooled_w"], a["pooled_h"], a["spatial_scale"])
+        elif kind == "roi_align":
+            y = _roi_ref().roi_align(v[0], v[1], a["pooled_w"], a["pooled_h"], a["spatial_scale"], a["sampling_ratio"], a["aligned"], a["version"])
+        elif kind == "psroi_pooling":
+            y = _roi_ref().psroi_pool(v[0], v[1], a["output_dim"], a["pooled_w"], a["pooled_h"], a["spatial_scale"])
+        elif kind == "pool" and a["global_"] and a["avg"]:
+            y = v.astype(np.float64).mean(axis=(2, 3), keepdims=True)
         elif kind == "reorg":
             st, (n, c, h, wd) = a["stride"], v.shape
             t = v[:, :, :h // st * st, :wd // st * st].reshape(n, c, h // st, st, wd // st, st).transpose(0, 1, 3, 5, 2, 4)  # [n][q][sh][sw][i][j]
@@ -1591,6 +1672,116 @@ def mobilenetv2_yolov3(seed=1234, classes=20, size=352, dry=False, confidence_th
     return g.finish() + ("data", "detection_out")
 
 
+def _rpn(g, x, cin, mid, im_info, gain=1.0, **proposal):
+    """The region proposal network of py-faster-rcnn on the map `x`: a 3x3 convolution + ReLU, the 1x1 score (2 * 9) and delta (4 * 9) heads, the
+    two-way softmax and Proposal -> the ROIs."""
+    x = g.relu("rpn_relu/3x3", g.conv("rpn_conv/3x3", x, cin, mid, 3, 1, 1))
+    a, b = g.split("rpn_split", x, 2)
+    score = g.rpn_softmax("rpn_cls", g.conv("rpn_cls_score", a, mid, 18, 1, gain=gain))
+    bbox = g.conv("rpn_bbox_pred", b, mid, 36, 1, gain=0.3)
+    return g.proposal("rois", score, bbox, im_info, **proposal)
+
+
+def tiny_faster_rcnn(seed=59, size=(48, 64), dry=False, trace=None, rois=16):
+    """A small Faster R-CNN (Net.SetDetection(True) for the RPN's softmax, Net.SetRoi()): a 48 x 64 image, a trunk of two convolutions and two
+    poolings to 16 channels on 12 x 16 cells (stride 4), a 3x3 RPN convolution, rpn_cls_score through Reshape -> Softmax -> Reshape into
+    Proposal (feat_stride 4, base_size 2: anchors of 8 .. 64 px; 200 -> `rois` ROIs), ROIPooling 3 x 3, two InnerProduct layers over the
+    batch of n * rois regions, cls_prob (Softmax, 5 classes) and bbox_pred.  Inputs "data" and "im_info" ([n][1][1][3]); outputs "rois",
+    "cls_prob", "bbox_pred".  size = (height, width); trace: a list that receives the layers for numpy_forward."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    x = g.pool("pool1", g.relu("relu1", g.conv("conv1", g.input("data", 3, h, w), 3, 8, 3, 1, 1)), 2, 2)
+    x = g.pool("pool2", g.relu("relu2", g.conv("conv2", x, 8, 16, 3, 1, 1)), 2, 2)
+    im_info = g.input("im_info", 1, 1, 3)
+    feat, x = g.split("feat_split", x, 2)
+    r = _rpn(g, x, 16, 16, im_info, gain=0.25, feat_stride=4, base_size=2, pre_nms_topN=200, after_nms_topN=rois, nms_thresh=0.7, min_size=4)
+    x = g.roi_pooling("roi_pool", feat, r, 3, 3, 0.25)
+    x = g.relu("relu6", g.fc("fc6", x, 16 * 9, 32))
+    x = g.relu("relu7", g.fc("fc7", x, 32, 32))
+    a, b = g.split("fc7_split", x, 2)
+    g.softmax("cls_prob", g.fc("cls_score", a, 32, 5))
+    g.fc("bbox_pred", b, 32, 20)
+    return g.finish() + ("data", "cls_prob")
+
+
+def tiny_rfcn(seed=61, size=(48, 64), dry=False, trace=None, rois=16):
+    """A small R-FCN (Net.SetDetection(True), Net.SetRoi()): the trunk and the RPN of tiny_faster_rcnn, a 1x1 convolution to 5 classes x 3 x 3
+    position-sensitive score maps, PSROIPooling 3 x 3 and a global average Pooling: the vote.  Inputs "data" and "im_info"; outputs "rois" and
+    "cls_score" ([n * rois][5][1][1])."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    x = g.pool("pool1", g.relu("relu1", g.conv("conv1", g.input("data", 3, h, w), 3, 8, 3, 1, 1)), 2, 2)
+    x = g.pool("pool2", g.relu("relu2", g.conv("conv2", x, 8, 16, 3, 1, 1)), 2, 2)
+    im_info = g.input("im_info", 1, 1, 3)
+    feat, x = g.split("feat_split", x, 2)
+    r = _rpn(g, x, 16, 16, im_info, gain=0.25, feat_stride=4, base_size=2, pre_nms_topN=200, after_nms_topN=rois, nms_thresh=0.7, min_size=4)
+    maps = g.conv("rfcn_cls", feat, 16, 5 * 9, 1)
+    g.pool("cls_score", g.psroi_pooling("psroi_cls", maps, r, 5, 3, 3, 0.25), 3, 3, avg=True, global_=True)
+    return g.finish() + ("data", "cls_score")
+
+
+def faster_rcnn_vgg16(seed=1234, classes=21, size=(600, 800), dry=False):
+    """Faster R-CNN on VGG-16 (Ren et al., NIPS 2015; py-faster-rcnn's VGG16 test.prototxt): conv1_1 .. conv5_3 without pool5 (stride 16: 38 x 50
+    cells at 600 x 800), the RPN on 512 channels, Proposal 6000 -> 300, ROIPooling 7 x 7, fc6 / fc7 of 4096 over the 300 regions of every
+    image, cls_prob over 21 classes and bbox_pred.  Net.SetDetection(True) and Net.SetRoi(); inputs "data" and "im_info"."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    x, cin = g.input("data", 3, h, w), 3
+    for stage, (n, c) in enumerate([(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)], 1):
+        for i in range(1, n + 1):
+            x = g.relu(f"relu{stage}_{i}", g.conv(f"conv{stage}_{i}", x, cin, c, 3, 1, 1))
+            cin = c
+        if stage < 5:
+            x = g.pool(f"pool{stage}", x, 2, 2)
+    im_info = g.input("im_info", 1, 1, 3)
+    feat, x = g.split("conv5_3_split", x, 2)
+    r = _rpn(g, x, 512, 512, im_info)
+    x = g.roi_pooling("roi_pool5", feat, r, 7, 7, 0.0625)
+    x = g.dropout("drop6", g.relu("relu6", g.fc("fc6", x, 512 * 49, 4096)))
+    x = g.dropout("drop7", g.relu("relu7", g.fc("fc7", x, 4096, 4096)))
+    a, b = g.split("fc7_split", x, 2)
+    g.softmax("cls_prob", g.fc("cls_score", a, 4096, classes))
+    g.fc("bbox_pred", b, 4096, 4 * classes)
+    return g.finish() + ("data", "cls_prob")
+
+
+def rfcn_resnet50(seed=1234, classes=21, size=(600, 800), dry=False):
+    """R-FCN on ResNet-50 (Dai et al., NIPS 2016): conv1 .. conv4 at stride 16, conv5 at stride 1 and dilation 2, a 1x1 convolution to 1024
+    channels, the RPN on conv4, position-sensitive score maps of 21 x 7 x 7 and class-agnostic box maps of 8 x 7 x 7, PSROIPooling 7 x 7 over
+    300 ROIs and a global average Pooling each: cls_prob and bbox_pred.  Net.SetDetection(True), Net.SetRoi() and Net.SetDilated(True)."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, h, w)
+    x = g.pool("pool1", g.conv_bn_relu("conv1", x, 3, 64, 7, 2, 3), 3, 2)
+    im_info = g.input("im_info", 1, 1, 3)
+    cin, rois = 64, None
+    for si, (mid, out, blocks, stride, dilation) in enumerate([(64, 256, 3, 1, 1), (128, 512, 4, 2, 1), (256, 1024, 6, 2, 1), (512, 2048, 3, 1, 2)]):
+        for b in range(blocks):
+            s = stride if b == 0 else 1
+            tag = f"res{si + 2}{chr(ord('a') + b)}"
+            main, short = g.split(tag + "_split", x)
+            if b == 0:
+                short = g.conv_bn_relu(tag + "_branch1", short, cin, out, 1, s, 0, relu=False)
+            y = g.conv_bn_relu(tag + "_branch2a", main, cin, mid, 1, s, 0)
+            y = g.conv_bn_relu(tag + "_branch2b", y, mid, mid, 3, 1, dilation, dilation=dilation)
+            y = g.conv_bn_relu(tag + "_branch2c", y, mid, out, 1, 1, 0, relu=False)
+            x = g.relu(tag + "_relu", g.eltwise(tag, short, y))
+            cin = out
+        if si == 2:  # the RPN reads conv4
+            x, rpn = g.split("res4f_split", x, 2)
+            rois = _rpn(g, rpn, 1024, 512, im_info)
+    x = g.relu("conv_new_1_relu", g.conv("conv_new_1", x, 2048, 1024, 1))
+    a, b = g.split("conv_new_1_split", x, 2)
+    ra, rb = g.split("rois_split", rois, 2)
+    cls = g.psroi_pooling("psroipooled_cls_rois", g.conv("rfcn_cls", a, 1024, classes * 49, 1), ra, classes, 7, 7, 0.0625)
+    g.softmax("cls_prob", g.pool("ave_cls_score_rois", cls, 7, 7, avg=True, global_=True))
+    box = g.psroi_pooling("psroipooled_loc_rois", g.conv("rfcn_bbox", b, 1024, 8 * 49, 1), rb, 8, 7, 7, 0.0625)
+    g.pool("bbox_pred", box, 7, 7, avg=True, global_=True)
+    return g.finish() + ("data", "cls_prob")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
@@ -1607,7 +1798,8 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_requant": tiny_requant, "tiny_requant_twin": tiny_requant_twin,
           "vgg16_int8_rq": vgg16_int8_rq, "resnet50_int8_rq": resnet50_int8_rq, "mobilenet_v1_int8_rq": mobilenet_v1_int8_rq,
           "tiny_ssd": tiny_ssd, "mobilenet_ssd": mobilenet_ssd, "vgg16_ssd300": vgg16_ssd300,
-          "tiny_yolov2": tiny_yolov2, "tiny_yolov3": tiny_yolov3, "yolov2_tiny_voc": yolov2_tiny_voc, "mobilenetv2_yolov3": mobilenetv2_yolov3}
+          "tiny_yolov2": tiny_yolov2, "tiny_yolov3": tiny_yolov3, "yolov2_tiny_voc": yolov2_tiny_voc, "mobilenetv2_yolov3": mobilenetv2_yolov3,
+          "tiny_faster_rcnn": tiny_faster_rcnn, "tiny_rfcn": tiny_rfcn, "faster_rcnn_vgg16": faster_rcnn_vgg16, "rfcn_resnet50": rfcn_resnet50}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -1636,6 +1828,10 @@ DILATED_LAYERS["vgg16_ssd300"] = ("fc6",)
 
 # nets that need Net.SetYolo() (the YOLO heads: libfeather_yolo.so); tiny_yolov3 needs Net.SetExtendedLayers(True) as well (its Interp)
 YOLO_NETS = ("tiny_yolov2", "tiny_yolov3", "yolov2_tiny_voc", "mobilenetv2_yolov3")
+
+# nets that need Net.SetRoi() (Proposal and the ROI layers: libfeather_roi.so) and Net.SetDetection(True) (the RPN's Reshape and axis Softmax);
+# rfcn_resnet50 needs Net.SetDilated(True) as well (its conv5).  Each has a second Input, "im_info" [n][1][1][3], and the top "rois"
+ROI_NETS = ("tiny_faster_rcnn", "tiny_rfcn", "faster_rcnn_vgg16", "rfcn_resnet50")
 
 # the input size a builder's defaults describe, where it is not 224 px
 INPUT_SIZE = {"alexnet": 227, "caffenet": 227, "mobilenet_ssd": 300, "vgg16_ssd300": 300, "yolov2_tiny_voc": 416, "mobilenetv2_yolov3": 352}

@@ -35,6 +35,8 @@ DETECT_ROUTE = 109  # FHIP_DETECT_NET_ROUTE (feather_detect.h): a layer of an SS
 ROUTE_NAMES[DETECT_ROUTE] = "DETECT"
 YOLO_ROUTE = 110  # FHIP_YOLO_NET_ROUTE (feather_yolo.h): a layer of a YOLO head, after SetYolo() (libfeather_yolo.so)
 ROUTE_NAMES[YOLO_ROUTE] = "YOLO"
+ROI_ROUTE = 111  # FHIP_ROI_NET_ROUTE (feather_roi.h): Proposal, ROIPooling, ROIAlign or PSROIPooling, after SetRoi() (libfeather_roi.so)
+ROUTE_NAMES[ROI_ROUTE] = "ROI"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -92,6 +94,12 @@ class Net:
         libfeather_yolo.so) -- instead of refusing them at LoadParam.  `rows` (1 .. 1024) is the height of the detection top: the first `rows`
         detections of every image, read by ExtractDetections; 0 switches the layers off again.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_yolo(self._h, int(rows)), "fhip_net_set_yolo")
+
+    def SetRoi(self, on: bool = True):
+        """feather::Net::SetRoi: accept the layers of ncnn's two-stage detectors -- Proposal, ROIPooling, ROIAlign and PSROIPooling (routed to
+        libfeather_roi.so) -- instead of refusing them at LoadParam.  im_info is a second Input: FeedInput(name, [N][1][1][3]) with (height,
+        width, scale) per image.  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_roi(self._h, int(bool(on))), "fhip_net_set_roi")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")
@@ -232,6 +240,23 @@ class Net:
         if out.shape[1] != 1 or out.shape[3] != 6:
             raise FeatherHipError(f"blob {blob_name} of shape {out.shape} is not a DetectionOutput top [n][1][keep_top_k][6]")
         return [img[0][:int((img[0][:, 0] > 0).sum())].copy() for img in out]
+
+    def ExtractProposals(self, rois_blob: str, scores_blob: str = None):
+        """The top of a Proposal layer as one (count_i, 4) array per image, rows (x1, y1, x2, y2): Extract, with the sentinel rows (0, 0, -1, -1)
+        past every image's count trimmed on the host.  With `scores_blob` (the layer's second top): (rois, scores), the scores one (count_i,)
+        array per image."""
+        out = self.Extract(rois_blob)
+        if out.shape[2] != 1 or out.shape[3] != 4:
+            raise FeatherHipError(f"blob {rois_blob} of shape {out.shape} is not a Proposal top [n][R][1][4]")
+        rows = out[:, :, 0]
+        counts = [int((img[:, 2] >= img[:, 0]).sum()) for img in rows]
+        rois = [img[:k].copy() for img, k in zip(rows, counts)]
+        if scores_blob is None:
+            return rois
+        s = self.Extract(scores_blob)
+        if s.shape != out.shape[:2] + (1, 1):
+            raise FeatherHipError(f"blob {scores_blob} of shape {s.shape} is not the score top [n][R][1][1] of {rois_blob}")
+        return rois, [img[:k, 0, 0].copy() for img, k in zip(s, counts)]
 
     def ExtractPixels(self, blob_name: str, ptype: int, target=None, mean=None, norm=None) -> np.ndarray:
         """The blob as uint8 images, converted on the device (fhip_float_to_pixels on the net's stream, after Forward): ncnn's

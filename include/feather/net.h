@@ -31,7 +31,8 @@
 //   * layer types beyond the reference's factory are loaded too: see feather_net.h's route codes (BinaryOp mul, Scale 0=-233, Swish and
 //     HardSigmoid are the newest); Interp and HardSwish (FHIP_NET_ROUTE_RESAMPLE) and LRN (FHIP_NET_ROUTE_LRN) after
 //     SetExtendedLayers(true); the SSD detection head (Permute, Flatten, Reshape, Normalize, PriorBox, DetectionOutput; feather_detect.h)
-//     after SetDetection(true), its result through ExtractDetections.
+//     after SetDetection(true), its result through ExtractDetections; the YOLO heads after SetYolo(rows); Proposal, ROIPooling, ROIAlign
+//     and PSROIPooling (feather_roi.h) after SetRoi(true), the ROIs through ExtractProposals.
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -53,6 +54,12 @@ struct Detection
 {
     int label;
     float score, xmin, ymin, xmax, ymax;
+};
+
+// One row of a Proposal top (ExtractProposals): the box in image pixels and, where the scores were asked for, its foreground score
+struct Roi
+{
+    float x1, y1, x2, y2, score;
 };
 
 class Net
@@ -235,6 +242,40 @@ class Net
     // them; `rows` is the height of the detection top ExtractDetections reads (the first `rows` detections of an image), 0 switches it off;
     // before LoadParam (feather_net.h)
     int SetYolo(int rows = 256) { return fhip_net_set_yolo(net_, rows); }
+    // accept the layers of ncnn's two-stage detectors -- Proposal, ROIPooling, ROIAlign, PSROIPooling (libfeather_roi.so) -- instead of
+    // refusing them; before LoadParam (feather_net.h)
+    int SetRoi(bool on = true) { return fhip_net_set_roi(net_, on ? 1 : 0); }
+    // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
+    // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
+    // blob has another shape.  scores_blob "" asks for none.
+    int ExtractProposals(std::string rois_blob, std::vector<std::vector<Roi> >& out, std::string scores_blob = "")
+    {
+        float* dev = NULL;
+        int n = 0, c = 0, h = 0, w = 0;
+        int rc = Extract(rois_blob, &dev, &n, &c, &h, &w);
+        if (rc) return rc;
+        if (h != 1 || w != 4) return -100;
+        std::vector<float> rows((size_t)n * c * 4), scores;
+        if ((rc = ExtractHost(rois_blob, rows.data(), rows.size()))) return rc;
+        if (!scores_blob.empty())
+        {
+            int sn = 0, sc = 0, sh = 0, sw = 0;
+            if ((rc = Extract(scores_blob, &dev, &sn, &sc, &sh, &sw))) return rc;
+            if (sn != n || sc != c || sh != 1 || sw != 1) return -100;
+            scores.resize((size_t)n * c);
+            if ((rc = ExtractHost(scores_blob, scores.data(), scores.size()))) return rc;
+        }
+        out.assign(n, std::vector<Roi>());
+        for (int i = 0; i < n; ++i)
+            for (int r = 0; r < c; ++r)
+            {
+                const float* v = &rows[((size_t)i * c + r) * 4];
+                if (!(v[2] >= v[0])) break;
+                Roi roi = {v[0], v[1], v[2], v[3], scores.empty() ? 0.f : scores[(size_t)i * c + r]};
+                out[i].push_back(roi);
+            }
+        return 0;
+    }
     int SetConcurrency(bool on) { return fhip_net_set_concurrency(net_, on ? 1 : 0); }
     int SetColpass(int mode) { return fhip_net_set_colpass(net_, mode); } // 0 never, 1 where M is HBM-bound (default), 2 wherever accepted
     int SetSubBatches(int replicas) { return fhip_net_set_sub_batches(net_, replicas); } // before LoadParam (feather_net.h)

@@ -284,6 +284,16 @@ FHIP_API int fhip_net_set_detection(fhip_net* net, int on);
  * rows outside 0 .. FHIP_YOLO_MAX_ROWS (1024): FHIP_E_BADARG.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch
  * replicas. */
 FHIP_API int fhip_net_set_yolo(fhip_net* net, int rows);
+/* 1: the layers of the second stage of ncnn's two-stage detectors (Faster R-CNN, R-FCN) are loaded -- Proposal, ROIPooling, ROIAlign and
+ * PSROIPooling, as feather_roi.h defines them; they run through libfeather_roi.so and report the route FHIP_ROI_NET_ROUTE (feather_roi.h).
+ * Proposal reads score [n][18][h][w], bbox [n][36][h][w] and im_info, a second Input fed with fhip_net_feed_input(name, n, 1, 1, 3, ...) --
+ * (height, width, scale) per image -- and writes rois [n][R][1][4], R = after_nms_topN, rows past an image's count the sentinel
+ * (0, 0, -1, -1), and optionally scores [n][R][1][1].  An ROI layer reads features [n][C][h][w] and rois [n][R][1][4] (a Proposal top or an
+ * Input) and writes [n * R][channels][pooled_h][pooled_w], row i * R + r from image i: the layers behind it see a batch of n * R.  With
+ * sub-batch replicas every Input is dealt out with the images and fhip_net_extract gathers the rows in image order.  Nothing fuses into
+ * these layers.  0 (default): LoadParam refuses the four types with -200; on-then-off equals the default.  Call before LoadParam; later it
+ * is FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_roi(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
