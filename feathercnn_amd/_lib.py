@@ -111,6 +111,7 @@ SIGNATURES = {
     "fhip_net_set_colpass": (_I, [_V, _I]),
     "fhip_net_set_yolo": (_I, [_V, _I]),
     "fhip_net_set_roi": (_I, [_V, _I]),
+    "fhip_net_set_frame": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -367,6 +368,18 @@ ROI_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_frame.h -- libfeather_frame.so, the layers that frame an image-to-image net: Padding, Crop (one window) and
+# PixelShuffle (a library of its own)
+FRAME_SIGNATURES = {
+    "fhip_frame_window_output_dim": (_I, [_I] * 9 + [ctypes.POINTER(_I)] * 3),
+    "fhip_frame_window_forward": (_I, [_I, _FL, _V] + [_I] * 10 + [_V, _V, _V]),
+    "fhip_pixel_shuffle_output_dim": (_I, [_I] * 4 + [ctypes.POINTER(_I)] * 3),
+    "fhip_pixel_shuffle_forward": (_I, [_I, _I, _I, _FL, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_frame_route": (_I, [_I, _I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_frame_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -448,11 +461,19 @@ OPEN_LIBRARIES = {
     "roi": Library("libfeather_roi.so", ("feather_roi.h",), "FHIP_ROI_API", ROI_SIGNATURES, "fhip_roi_last_error", (), None),
 }
 TABLES = (LIBRARIES, MORE_LIBRARIES, THIRD_LIBRARIES, OPEN_LIBRARIES)
+# Rows that stand in none of the tables, the same tuple, built by STANDALONE of csrc/Makefile.  The open table was meant to take the next
+# library, but tests/test_roi_cpu.py holds it to its two rows and tests/test_open_contract_cpu.py the tables and lists to four, so
+# libfeather_frame.so stands here; tests/test_frame_contract_cpu.py restates the open table's contract for these rows, by the same naming
+# rule (tests/<name>_cases.py: targets(), KERNELS, LIB).  A change that may touch those tests folds the rows into OPEN_LIBRARIES.
+STANDALONE_LIBRARIES = {
+    # route: FRAME_ROUTE of net.py (FHIP_FRAME_NET_ROUTE of its own header)
+    "frame": Library("libfeather_frame.so", ("feather_frame.h",), "FHIP_FRAME_API", FRAME_SIGNATURES, "fhip_frame_last_error", (), None),
+}
 
 
 def row(name: str) -> Library:
-    """The row of the library `name`, from any of the tables."""
-    for table in TABLES:
+    """The row of the library `name`, from any of the tables or from the rows outside them."""
+    for table in TABLES + (STANDALONE_LIBRARIES,):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -479,7 +500,7 @@ def load_library():
 
 
 # the names the wrappers, tools/ and the tests call: <x>_path() and load_<x>_library() of every side library
-for _name in (n for t in TABLES for n in t):
+for _name in (n for t in TABLES + (STANDALONE_LIBRARIES,) for n in t):
     if _name != MAIN:
         globals()[f"{_name}_path"] = functools.partial(path, _name)
         globals()[f"load_{_name}_library"] = functools.partial(load, _name)

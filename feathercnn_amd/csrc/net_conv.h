@@ -660,6 +660,17 @@ struct ConvLayer : Layer
         bottoms.push_back(other); // so that dependency scans (fusion, branch concurrency) see the second input
         return true;
     }
+    // take over the (top, bottom, left, right) margins of a Padding layer that only zero-pads this layer's input (fold_zero_paddings, before
+    // any other fusion): the main and the grouped fp32 route alone, and only onto pads that are pads (>= 0)
+    bool FoldPadding(const int* m)
+    {
+        if ((route != ROUTE_MAIN && route != ROUTE_GROUPED) || p.pad_top < 0 || p.pad_bottom < 0 || p.pad_left < 0 || p.pad_right < 0) return false;
+        const long long sums[4] = {(long long)p.pad_top + m[0], (long long)p.pad_bottom + m[1], (long long)p.pad_left + m[2], (long long)p.pad_right + m[3]};
+        for (long long v : sums)
+            if (v > (1 << 16)) return false; // a pad no plane has: the Padding layer stays and answers for it
+        p.pad_top = (int)sums[0], p.pad_bottom = (int)sums[1], p.pad_left = (int)sums[2], p.pad_right = (int)sums[3];
+        return true;
+    }
     size_t weight_bytes() const override
     {
         return packed.bytes + bias.bytes + ep.pre_pool.bytes + ep.mid.bytes + first_raw.bytes + sibs.packed.bytes + sibs.bias.bytes + qr.bytes() +

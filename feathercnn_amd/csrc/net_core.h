@@ -125,6 +125,7 @@ struct Layer
     virtual EltwiseLayer* as_eltwise() { return nullptr; }   // Eltwise
     virtual InterpLayer* as_interp() { return nullptr; }     // Interp
     virtual const float* relu_slope() const { return nullptr; } // ReLU: its slope
+    virtual const int* zero_pad_margins() const { return nullptr; } // Padding that only zero-pads the plane: its (top, bottom, left, right)
     // q8 blobs (Blob::q8, the int8 activation between two int8 layers): a layer that can read one says so, every other layer that meets
     // one is refused by reshape_all; writes_q8() is asked there too, after the layer's bottoms are settled and before its Reshape
     virtual bool reads_q8() const { return false; }
@@ -190,6 +191,7 @@ struct Net
     bool requantized = false;     // fhip_net_set_requantized: an int8 Convolution with int8_scale_term 101 .. 200 (requantised int8 output) is loaded (libfeather_q8.so) instead of refused
     int yolo = 0;                 // fhip_net_set_yolo: > 0: Reorg, YoloDetectionOutput and Yolov3DetectionOutput (net_yolo.h, libfeather_yolo.so) are loaded instead of refused; the rows of the detection top
     bool roi = false;             // fhip_net_set_roi: Proposal, ROIPooling, ROIAlign and PSROIPooling (net_roi.h, libfeather_roi.so) are loaded instead of refused
+    bool frame = false;           // fhip_net_set_frame: Padding, Crop and PixelShuffle (net_frame.h, libfeather_frame.so) are loaded instead of refused
     int colpass = 1;              // fhip_net_set_colpass: chained 64-input-channel Winograd layers through libfeather_colpass.so -- 0 never, 1 where M is HBM-bound, 2 wherever accepted
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;

@@ -263,12 +263,37 @@ static void collapse_upsample_adds(Net& net)
     }
 }
 
+// Fusion level >= 2, in a net with fhip_net_set_frame: a Padding layer that only zero-pads the plane (type 0, value 0, no per-channel
+// values, no channel margins: Layer::zero_pad_margins) and whose top is read by exactly one Convolution / ConvolutionDepthWise on the main
+// or the grouped fp32 route with pads >= 0 (ConvLayer::FoldPadding) is removed: the convolution reads the Padding's bottom with the margins
+// added to its own four pads, and the blob between them refuses Extract.  This is what a converter writes in front of TensorFlow's
+// stride-2 "SAME" convolutions (0, 1, 0, 1), where the Padding is a copy of the whole tensor that buys nothing.  Runs before every other
+// pass, so the algorithm and every later fusion are chosen on the folded parameters.
+static void fold_zero_paddings(Net& net)
+{
+    for (size_t i = 0; i < net.layers.size(); ++i)
+    {
+        Layer* pad = net.layers[i].get();
+        const int* margins = pad->zero_pad_margins();
+        if (!margins || pad->tops.size() != 1 || pad->bottoms.size() != 1) continue;
+        const int reader = readers(net, pad->tops[0], i + 1).sole();
+        if (reader < 0) continue;
+        ConvLayer* conv = net.layers[reader]->as_conv();
+        if (!conv || conv->bottoms.size() != 1 || !conv->FoldPadding(margins)) continue;
+        conv->bottoms[0] = pad->bottoms[0];
+        pad->tops[0]->fused_away = true;
+        net.layers.erase(net.layers.begin() + i);
+        --i;
+    }
+}
+
 // The fusion pass of layer.cpp:82-101 (TryFuse): a layer absorbs the single consumer of its single top.
 static void fuse_layers(Net& net)
 {
     if (net.fused) return;
     net.fused = true;
     if (net.fusion <= 0) return;
+    if (net.fusion >= 2) fold_zero_paddings(net);
     if (net.fusion >= 2) collapse_detection_heads(net);
     if (net.fusion >= 2) collapse_channel_maps(net);
     if (net.fusion >= 2) collapse_gate_blocks(net);

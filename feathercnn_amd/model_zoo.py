@@ -378,6 +378,47 @@ class GraphBuilder:
         self._note("psroi_pooling", name, [features, rois], name, dict(output_dim=int(output_dim), pooled_w=pooled_w, pooled_h=pooled_h, spatial_scale=spatial_scale))
         return self.layer("PSROIPooling", name, [features, rois], [name], {0: int(pooled_w), 1: int(pooled_h), 2: f"{spatial_scale:.6f}", 3: int(output_dim)})
 
+    # -- the framing layers (a net that holds one of these needs Net.SetFrame()) ------------------------------------------------
+    def padding(self, name, bottom, top=0, bottom_=0, left=0, right=0, type_=0, value=None, per_channel=0, front=0, behind=0):
+        """ncnn's Padding: 0=top 1=bottom 2=left 3=right, and where set 4=type (0 constant, 1 replicate, 2 reflect), 5=value,
+        6=per_channel_pad_data_size (that many raw floats in the .bin, U(-1, 1)), 7=front, 8=behind."""
+        params = {0: int(top), 1: int(bottom_), 2: int(left), 3: int(right)}
+        if type_:
+            params[4] = int(type_)
+        if value is not None:
+            params[5] = f"{value:.6f}"
+        if per_channel:
+            params[6] = int(per_channel)
+        if front or behind:
+            params.update({7: int(front), 8: int(behind)})
+        pc = self._uniform(int(per_channel), -1, 1) if per_channel else None
+        if per_channel:
+            self._raw(pc)
+        self._note("padding", name, bottom, name, dict(top=top, bottom=bottom_, left=left, right=right, type_=type_, value=0.0 if value is None else float(f"{value:.6f}"),
+                                                       per_channel=pc, front=front, behind=behind))
+        return self.layer("Padding", name, [bottom], [name], params)
+
+    def crop(self, name, bottom, woffset=0, hoffset=0, coffset=0, outw=None, outh=None, outc=None, woffset2=0, hoffset2=0, coffset2=0, like=None):
+        """ncnn's Crop: 0=woffset 1=hoffset 2=coffset, and where set 3=outw 4=outh 5=outc (else -233: what the offsets leave) and 6=woffset2
+        7=hoffset2 8=coffset2; like: the reference blob of the two-bottom form, whose (c, h, w) the top takes."""
+        params = {0: int(woffset), 1: int(hoffset), 2: int(coffset)}
+        for k, v in ((3, outw), (4, outh), (5, outc)):
+            if v is not None:
+                params[k] = int(v)
+        for k, v in ((6, woffset2), (7, hoffset2), (8, coffset2)):
+            if v:
+                params[k] = int(v)
+        bottoms = [bottom] if like is None else [bottom, like]
+        self._note("crop", name, bottoms if like is not None else bottom, name,
+                   dict(woffset=woffset, hoffset=hoffset, coffset=coffset, outw=-233 if outw is None else outw, outh=-233 if outh is None else outh,
+                        outc=-233 if outc is None else outc, woffset2=woffset2, hoffset2=hoffset2, coffset2=coffset2))
+        return self.layer("Crop", name, bottoms, [name], params)
+
+    def pixel_shuffle(self, name, bottom, r, mode=None):
+        """ncnn's PixelShuffle: 0=upscale_factor, 1=mode (written only when given): [C * r^2][h][w] -> [C][h * r][w * r]."""
+        self._note("pixel_shuffle", name, bottom, name, dict(r=int(r), mode=int(mode or 0)))
+        return self.layer("PixelShuffle", name, [bottom], [name], {0: int(r)} if mode is None else {0: int(r), 1: int(mode)})
+
     def shuffle(self, name, bottom, group, reverse=False):
         """ncnn's ShuffleChannel: 0=group, 1=reverse (written only when set)."""
         return self.layer("ShuffleChannel", name, [bottom], [name], {0: group, 1: 1} if reverse else {0: group})
@@ -490,10 +531,23 @@ def _roi_ref():
     return roi_ref
 
 
+def _frame_ref():
+    """tests/frame_ref.py, the restatement of feather_frame.h: numpy_forward's Padding, Crop and PixelShuffle are that text, not a second one."""
+    try:
+        import frame_ref
+    except ImportError:
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import frame_ref
+    return frame_ref
+
+
 def numpy_forward(trace, input_name, x=None):
     """A plain numpy forward (fp32 values, sums in float64) of the layers a GraphBuilder recorded in `trace` -- Convolution, InnerProduct,
     ReLU (plain or leaky), BatchNorm, Scale, Pooling, Split, Concat on channels, Reorg, nearest Interp by a whole scale, the RPN's softmax, a
-    Softmax over the channels of [N][C][1][1], Proposal and the three ROI layers (tests/roi_ref.py in float32) -- from the input `x`
+    Softmax over the channels of [N][C][1][1], Proposal and the three ROI layers (tests/roi_ref.py in float32), Padding, Crop and PixelShuffle
+    (tests/frame_ref.py, bit copies) -- from the input `x`
     [N][C][H][W], or from several: `input_name` a dict {name: array} and no `x`.  Every blob by name.  It exists to calibrate input scales
     and to feed the restatement of a detection head."""
     blobs = {k: np.asarray(v, np.float32) for k, v in input_name.items()} if isinstance(input_name, dict) else {input_name: np.asarray(x, np.float32)}
@@ -528,6 +582,13 @@ def numpy_forward(trace, input_name, x=None):
             y = _roi_ref().roi_align(v[0], v[1], a["pooled_w"], a["pooled_h"], a["spatial_scale"], a["sampling_ratio"], a["aligned"], a["version"])
         elif kind == "psroi_pooling":
             y = _roi_ref().psroi_pool(v[0], v[1], a["output_dim"], a["pooled_w"], a["pooled_h"], a["spatial_scale"])
+        elif kind == "padding":
+            y = _frame_ref().pad(v, a["top"], a["bottom"], a["left"], a["right"], a["type_"], a["value"], a["per_channel"], a["front"], a["behind"])
+        elif kind == "crop":
+            two = not isinstance(bottom, str)
+            y = _frame_ref().crop(v[0] if two else v, like=v[1] if two else None, **a)
+        elif kind == "pixel_shuffle":
+            y = _frame_ref().pixel_shuffle(v, a["r"], a["mode"])
         elif kind == "pool" and a["global_"] and a["avg"]:
             y = v.astype(np.float64).mean(axis=(2, 3), keepdims=True)
         elif kind == "reorg":
@@ -1782,6 +1843,106 @@ def rfcn_resnet50(seed=1234, classes=21, size=(600, 800), dry=False):
     return g.finish() + ("data", "cls_prob")
 
 
+def tiny_frame(seed=67, size=(8, 10), dry=False, trace=None):
+    """A small image-to-image net with every framing layer (Net.SetFrame()), nothing above 24 px: a reflect Padding in front of the first
+    convolution; branch a -- a zero Padding (0, 1, 0, 1) in front of a stride-2 pad-0 convolution (TensorFlow's "SAME": fusion level 2 folds
+    it), a PixelShuffle 0=2 and the plain ReLU it absorbs; branch b -- a replicate Padding, a one-bottom Crop by sizes, a constant Padding with
+    per-channel values, a PixelShuffle 0=3 1=1 and a one-bottom Crop by second offsets; branch c -- a channel Padding (7=1 8=2, value 0.5) and a
+    two-bottom Crop whose reference is branch a.  size = (height, width), both even; trace: a list that receives the layers for numpy_forward."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    x = g.padding("pad_reflect", g.input("data", 3, h, w), 2, 2, 2, 2, type_=2)
+    x = g.relu("relu1", g.conv("conv1", x, 3, 8, 3))  # (h + 2, w + 2)
+    a, b, c = g.split("split1", x, 3)
+    a = g.relu("relu2", g.conv("conv_s2", g.padding("pad_same", a, 0, 1, 0, 1), 8, 8, 3, 2))  # (h / 2 + 1, w / 2 + 1)
+    a = g.relu("relu_ps", g.pixel_shuffle("ps0", g.conv("conv_up", a, 8, 16, 1), 2))  # 4 x (h + 2, w + 2)
+    a, ref = g.split("split2", a, 2)
+    b = g.padding("pad_rep", b, 1, 2, 3, 0, type_=1)
+    b = g.crop("crop_one", b, 2, 1, outw=w + 2, outh=h + 2)
+    b = g.pool("pool_b", g.conv("conv_b", b, 8, 9, 1), 2, 2)  # 9 x (h / 2 + 1, w / 2 + 1)
+    b = g.padding("pad_pc", b, 1, 0, 0, 1, per_channel=9)
+    b = g.pixel_shuffle("ps1", b, 3, mode=1)  # 1 x (3 h / 2 + 6, 3 w / 2 + 6)
+    b = g.crop("crop_b", b, 2, 1, woffset2=w // 2 + 2, hoffset2=h // 2 + 3)
+    c = g.crop("crop_ref", g.padding("pad_ch", c, value=0.5, front=1, behind=2), coffset=2, like=ref)
+    g.conv("out", g.concat("cat", [a, c, b]), 9, 3, 3, 1, 1)
+    return g.finish() + ("data", "out")
+
+
+def espcn_x3(seed=1234, size=(180, 240), channels=1, dry=False):
+    """ESPCN (Shi et al. 2016) x3: 5x5 -> 64, 3x3 -> 32, 3x3 -> channels * 9, TanH between them, and the sub-pixel layer, PixelShuffle 0=3
+    (Net.SetFrame()).  The paper runs it on the luma plane (channels = 1).  size = (height, width) of the low-resolution input."""
+    h, w = size
+    g = GraphBuilder(seed, dry)
+    x = g.tanh("tanh1", g.conv("conv1", g.input("data", channels, h, w), channels, 64, 5, 1, 2))
+    x = g.tanh("tanh2", g.conv("conv2", x, 64, 32, 3, 1, 1))
+    g.pixel_shuffle("out", g.conv("conv3", x, 32, channels * 9, 3, 1, 1), 3)
+    return g.finish() + ("data", "out")
+
+
+def srresnet_x4(seed=1234, size=96, dry=False, blocks=16):
+    """SRResNet (Ledig et al. 2017) x4 as published: 9x9 -> 64 and PReLU, 16 residual blocks (3x3, BatchNorm, PReLU, 3x3, BatchNorm, sum), a
+    3x3 + BatchNorm and the long skip, two up-sampling stages (3x3 -> 256, PixelShuffle 0=2, PReLU) and a 9x9 -> 3 (Net.SetFrame())."""
+    g = GraphBuilder(seed, dry)
+    x = g.prelu("prelu1", g.conv("conv1", g.input("data", 3, size, size), 3, 64, 9, 1, 4), 1)
+    x, skip = g.split("split0", x)
+    for i in range(1, blocks + 1):
+        a, b = g.split(f"res{i}_split", x)
+        a = g.prelu(f"res{i}_prelu", g.scale(f"res{i}a_scale", g.bn(f"res{i}a_bn", g.conv(f"res{i}a", a, 64, 64, 3, 1, 1), 64), 64), 1)
+        a = g.scale(f"res{i}b_scale", g.bn(f"res{i}b_bn", g.conv(f"res{i}b", a, 64, 64, 3, 1, 1), 64), 64)
+        x = g.eltwise(f"res{i}", a, b)
+    x = g.scale("conv2_scale", g.bn("conv2_bn", g.conv("conv2", x, 64, 64, 3, 1, 1), 64), 64)
+    x = g.eltwise("long_skip", x, skip)
+    for i in (1, 2):
+        x = g.prelu(f"up{i}_prelu", g.pixel_shuffle(f"up{i}_ps", g.conv(f"up{i}", x, 64, 256, 3, 1, 1), 2), 1)
+    g.conv("out", x, 64, 3, 9, 1, 4)
+    return g.finish() + ("data", "out")
+
+
+def cyclegan_resnet9(seed=1234, size=256, dry=False, blocks=9):
+    """CycleGAN's ResNet generator with 9 blocks as published (Net.SetFrame()): reflection Padding 3 and a 7x7, two stride-2 3x3, nine residual
+    blocks whose two 3x3 convolutions each stand behind a reflection Padding 1, two transposed 3x3 and reflection Padding 3 with a 7x7 and
+    TanH; InstanceNorm (no affine, as published) behind every convolution but the last."""
+    g = GraphBuilder(seed, dry)
+
+    def cir(name, x, cin, cout, k, s=1, p=0, relu=True):
+        x = g.instance_norm(name + "_in", g.conv(name, x, cin, cout, k, s, p), cout, affine=False)
+        return g.relu(name + "_relu", x) if relu else x
+
+    x = g.padding("pad1", g.input("data", 3, size, size), 3, 3, 3, 3, type_=2)
+    x = cir("conv1", x, 3, 64, 7)
+    x = cir("conv2", x, 64, 128, 3, 2, 1)
+    x = cir("conv3", x, 128, 256, 3, 2, 1)
+    for i in range(1, blocks + 1):
+        a, b = g.split(f"res{i}_split", x)
+        a = cir(f"res{i}a", g.padding(f"res{i}a_pad", a, 1, 1, 1, 1, type_=2), 256, 256, 3)
+        a = cir(f"res{i}b", g.padding(f"res{i}b_pad", a, 1, 1, 1, 1, type_=2), 256, 256, 3, relu=False)
+        x = g.eltwise(f"res{i}", a, b)
+    x = g.relu("deconv1_relu", g.instance_norm("deconv1_in", g.deconv("deconv1", x, 256, 128, 3, 2, 1, op=1), 128, affine=False))
+    x = g.relu("deconv2_relu", g.instance_norm("deconv2_in", g.deconv("deconv2", x, 128, 64, 3, 2, 1, op=1), 64, affine=False))
+    g.tanh("out", g.conv("conv_out", g.padding("pad_out", x, 3, 3, 3, 3, type_=2), 64, 3, 7))
+    return g.finish() + ("data", "out")
+
+
+def mobilenet_v1_tf(seed=1234, classes=1000, size=224, dry=False):
+    """`mobilenet_v1` as a converter writes it from TensorFlow (Net.SetFrame()): every stride-2 convolution has pad 0 and stands behind an
+    explicit `Padding 0=0 1=1 2=0 3=1`, TensorFlow's "SAME" on an even plane.  Fusion level 2 folds those Paddings into the convolutions."""
+    g = GraphBuilder(seed, dry)
+    x = g.input("data", 3, size, size)
+    x = g.conv_bn_relu("conv1", g.padding("conv1_pad", x, 0, 1, 0, 1), 3, 32, 3, 2, 0)
+    cfg = [(32, 64, 1), (64, 128, 2), (128, 128, 1), (128, 256, 2), (256, 256, 1), (256, 512, 2)] + [(512, 512, 1)] * 5 + \
+          [(512, 1024, 2), (1024, 1024, 1)]
+    for i, (c, k, s) in enumerate(cfg, 2):
+        if s == 2:
+            x = g.conv_bn_relu(f"conv{i}_dw", g.padding(f"conv{i}_pad", x, 0, 1, 0, 1), c, c, 3, 2, 0, group=c)
+        else:
+            x = g.conv_bn_relu(f"conv{i}_dw", x, c, c, 3, 1, 1, group=c)
+        x = g.conv_bn_relu(f"conv{i}_pw", x, c, k, 1, 1, 0)
+    x = g.pool("pool6", x, 7, 1, avg=True, global_=True)
+    x = g.softmax("prob", g.fc("fc7", x, 1024, classes))
+    return g.finish() + ("data", "prob")
+
+
 GROUPED_LAYERS = {"tiny_grouped": ("g1", "g2", "g3", "g4")}
 
 MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "squeezenet_v1.1": squeezenet_v11,
@@ -1799,7 +1960,9 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "vgg16_int8_rq": vgg16_int8_rq, "resnet50_int8_rq": resnet50_int8_rq, "mobilenet_v1_int8_rq": mobilenet_v1_int8_rq,
           "tiny_ssd": tiny_ssd, "mobilenet_ssd": mobilenet_ssd, "vgg16_ssd300": vgg16_ssd300,
           "tiny_yolov2": tiny_yolov2, "tiny_yolov3": tiny_yolov3, "yolov2_tiny_voc": yolov2_tiny_voc, "mobilenetv2_yolov3": mobilenetv2_yolov3,
-          "tiny_faster_rcnn": tiny_faster_rcnn, "tiny_rfcn": tiny_rfcn, "faster_rcnn_vgg16": faster_rcnn_vgg16, "rfcn_resnet50": rfcn_resnet50}
+          "tiny_faster_rcnn": tiny_faster_rcnn, "tiny_rfcn": tiny_rfcn, "faster_rcnn_vgg16": faster_rcnn_vgg16, "rfcn_resnet50": rfcn_resnet50,
+          "tiny_frame": tiny_frame, "espcn_x3": espcn_x3, "srresnet_x4": srresnet_x4, "cyclegan_resnet9": cyclegan_resnet9,
+          "mobilenet_v1_tf": mobilenet_v1_tf}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -1832,6 +1995,12 @@ YOLO_NETS = ("tiny_yolov2", "tiny_yolov3", "yolov2_tiny_voc", "mobilenetv2_yolov
 # nets that need Net.SetRoi() (Proposal and the ROI layers: libfeather_roi.so) and Net.SetDetection(True) (the RPN's Reshape and axis Softmax);
 # rfcn_resnet50 needs Net.SetDilated(True) as well (its conv5).  Each has a second Input, "im_info" [n][1][1][3], and the top "rois"
 ROI_NETS = ("tiny_faster_rcnn", "tiny_rfcn", "faster_rcnn_vgg16", "rfcn_resnet50")
+
+# nets that need Net.SetFrame() (Padding, Crop, PixelShuffle: libfeather_frame.so)
+FRAME_NETS = ("tiny_frame", "espcn_x3", "srresnet_x4", "cyclegan_resnet9", "mobilenet_v1_tf")
+# the zero Paddings of each net that fusion level 2 folds into the convolution behind them, and the Paddings that must stay
+ZERO_PADDINGS = {"tiny_frame": (("pad_same",), ("pad_reflect", "pad_rep", "pad_pc", "pad_ch")),
+                 "mobilenet_v1_tf": (("conv1_pad", "conv3_pad", "conv5_pad", "conv7_pad", "conv13_pad"), ())}
 
 # the input size a builder's defaults describe, where it is not 224 px
 INPUT_SIZE = {"alexnet": 227, "caffenet": 227, "mobilenet_ssd": 300, "vgg16_ssd300": 300, "yolov2_tiny_voc": 416, "mobilenetv2_yolov3": 352}

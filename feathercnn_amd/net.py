@@ -37,6 +37,8 @@ YOLO_ROUTE = 110  # FHIP_YOLO_NET_ROUTE (feather_yolo.h): a layer of a YOLO head
 ROUTE_NAMES[YOLO_ROUTE] = "YOLO"
 ROI_ROUTE = 111  # FHIP_ROI_NET_ROUTE (feather_roi.h): Proposal, ROIPooling, ROIAlign or PSROIPooling, after SetRoi() (libfeather_roi.so)
 ROUTE_NAMES[ROI_ROUTE] = "ROI"
+FRAME_ROUTE = 112  # FHIP_FRAME_NET_ROUTE (feather_frame.h): Padding, Crop or PixelShuffle, after SetFrame() (libfeather_frame.so)
+ROUTE_NAMES[FRAME_ROUTE] = "FRAME"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -100,6 +102,11 @@ class Net:
         libfeather_roi.so) -- instead of refusing them at LoadParam.  im_info is a second Input: FeedInput(name, [N][1][1][3]) with (height,
         width, scale) per image.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_roi(self._h, int(bool(on))), "fhip_net_set_roi")
+
+    def SetFrame(self, on: bool = True):
+        """feather::Net::SetFrame: accept ncnn's Padding, Crop and PixelShuffle (routed to libfeather_frame.so) instead of refusing them at
+        LoadParam.  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_frame(self._h, int(bool(on))), "fhip_net_set_frame")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

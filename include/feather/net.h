@@ -32,7 +32,8 @@
 //     HardSigmoid are the newest); Interp and HardSwish (FHIP_NET_ROUTE_RESAMPLE) and LRN (FHIP_NET_ROUTE_LRN) after
 //     SetExtendedLayers(true); the SSD detection head (Permute, Flatten, Reshape, Normalize, PriorBox, DetectionOutput; feather_detect.h)
 //     after SetDetection(true), its result through ExtractDetections; the YOLO heads after SetYolo(rows); Proposal, ROIPooling, ROIAlign
-//     and PSROIPooling (feather_roi.h) after SetRoi(true), the ROIs through ExtractProposals.
+//     and PSROIPooling (feather_roi.h) after SetRoi(true), the ROIs through ExtractProposals; Padding, Crop and PixelShuffle
+//     (feather_frame.h) after SetFrame(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -245,6 +246,8 @@ class Net
     // accept the layers of ncnn's two-stage detectors -- Proposal, ROIPooling, ROIAlign, PSROIPooling (libfeather_roi.so) -- instead of
     // refusing them; before LoadParam (feather_net.h)
     int SetRoi(bool on = true) { return fhip_net_set_roi(net_, on ? 1 : 0); }
+    // accept ncnn's Padding, Crop and PixelShuffle (libfeather_frame.so) instead of refusing them; before LoadParam (feather_net.h)
+    int SetFrame(bool on = true) { return fhip_net_set_frame(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
     // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
     // blob has another shape.  scores_blob "" asks for none.

@@ -294,6 +294,16 @@ FHIP_API int fhip_net_set_yolo(fhip_net* net, int rows);
  * these layers.  0 (default): LoadParam refuses the four types with -200; on-then-off equals the default.  Call before LoadParam; later it
  * is FHIP_E_BADARG.  Copied to sub-batch replicas. */
 FHIP_API int fhip_net_set_roi(fhip_net* net, int on);
+/* 1: the layers that frame an image-to-image net are loaded -- ncnn's Padding (constant with a value or per-channel values, replicate,
+ * reflect; channel pads), Crop (offsets and sizes, or a reference blob as second bottom) and PixelShuffle (both modes), as feather_frame.h
+ * defines them; they run through libfeather_frame.so and report the route FHIP_FRAME_NET_ROUTE (feather_frame.h).  Padding's dynamic form
+ * (a second bottom, -233 margins) and Crop by starts / ends / axes are refused with -100.  A layer that changes nothing (all margins 0, a
+ * crop of the whole blob, an upscale factor of 1) shares its bottom's storage and launches nothing.  At fusion level >= 2 a Padding that
+ * only zero-pads the plane in front of the one fp32 Convolution / ConvolutionDepthWise that reads it is folded into that convolution's pads
+ * (fhip_net_layer_conv_param shows the sums; the Padding's top is no longer extractable), and PixelShuffle absorbs a ReLU behind it, bit for
+ * bit.  0 (default): LoadParam refuses the three types with -200; on-then-off equals the default.  Call before LoadParam; later it is
+ * FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_frame(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
