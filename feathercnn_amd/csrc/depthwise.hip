@@ -140,12 +140,12 @@ __global__ __launch_bounds__(256) void depthwise3x3_direct_kernel(const DwParams
                 // A neighbouring lane is a neighbour in the IMAGE only inside one row block.  The first vector of a row never uses its
                 // left tap (xb == 0: padding, pad_left == 1); the last vector's right tap is padding too when OW * S == W, but a REAL
                 // pixel when pad_right < pad_left (OW * S < W) -- then the next lane belongs to another row and the tap is loaded.
-                if (lane == 0) lft = row[max(xb - 1, 0)];
+                if (lane == 0) lft = row[min(max(xb - 1, 0), q.W - 1)]; // (past the row where pad_right > 2: masked below, like the right tap)
                 if (lane == 63 || (xq == xvecs - 1 && xb + NV * VX < q.W)) rgt = row[min(xb + NV * VX, q.W - 1)];
             }
             else
             {
-                lft = row[max(xb - 1, 0)];
+                lft = row[min(max(xb - 1, 0), q.W - 1)];
                 rgt = row[min(xb + NV * VX, q.W - 1)];
             }
             x[r][0] = lft;
@@ -161,7 +161,9 @@ __global__ __launch_bounds__(256) void depthwise3x3_direct_kernel(const DwParams
             w[8] = cq.x; w[9] = cq.y; w[10] = cq.z; w[11] = cq.w;
         }
         const float b = q.has_bias ? q.bias[c] : 0.f;
-        const bool lok = xb > 0;
+        // the left tap is padding in the first vector of a row -- and, where the output runs two or more columns past the input's right edge
+        // (pad_right > pad_left + 1, which only a folded Padding gives a layer), in the vectors whose left tap lies past the row as well
+        const bool lok = xb > 0 && xb - 1 < q.W;
         const bool rrok = xb + NV * VX < q.W;
         float* op = q.out + (size_t)plane * OHW + (size_t)oy0 * q.OW + ox0;
 #pragma unroll

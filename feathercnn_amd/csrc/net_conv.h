@@ -368,6 +368,11 @@ struct ConvLayer : Layer
         p.input_channels = (int)(weight_data_size / per_channel);
         route = quant ? ROUTE_INT8 : atrous ? ROUTE_DILATED : p.group > 1 && p.group < p.input_channels ? ROUTE_GROUPED : ROUTE_MAIN;
         if (whole_k()) p.output_channels *= p.group;
+        // a depthwise layer has ONE filter per channel (conv_layer.h:69-75 and AssignOutputDim give it input_channels outputs whatever 0= says): with
+        // a channel multiplier the top would have a fraction of the channels the .param states and the rest of the filters would be ignored
+        if (route == ROUTE_MAIN && p.group > 1 && p.group == p.input_channels && p.output_channels != 1)
+            return failf(NET_E_UNKNOWN_LAYER, "layer %s: a depthwise convolution with a channel multiplier (%d filters per channel) is not supported", name.c_str(),
+                         p.output_channels);
         if ((route == ROUTE_INT8 || route == ROUTE_DILATED) && (p.pad_left < 0 || p.pad_top < 0))
             return failf(NET_E_UNKNOWN_LAYER, "layer %s: automatic padding is not supported", name.c_str());
         if (route == ROUTE_INT8)

@@ -121,6 +121,7 @@ def _conv(k, s, p, group=None, dilation=1, cout=None):
         grp = {None: 1, "dw": c}.get(group, group)
         _need(group == "dw" or (c % grp == 0 and cout % grp == 0))
         ko = c if group == "dw" else cout
+        _need(grp != c or ko == c)  # group == channels is a depthwise layer, which has one filter per channel: the runtime refuses a multiplier
         ho, wo = conv_out(h, k, s, p, dilation), conv_out(w, k, s, p, dilation)
         _need(ho >= 1 and wo >= 1)
         return b.g.conv(n, x, c, ko, k, s, p, group=grp, dilation=dilation), (ko, ho, wo)

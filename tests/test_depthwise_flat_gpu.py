@@ -59,6 +59,10 @@ NEIGHBOURS = [
     Geom(24, 24, 28, 28, 3, 3, 2, 2, 1, 0, 1, 0, 24, 1, 1),     # stride 2, pad 1 0 1 0 (TensorFlow-style SAME)
     conv_geom(24, 24, 14, 3, 1, 0, group=24),                   # no padding
     conv_geom(24, 24, 15, 3, 1, 1, group=24),                   # 15 x 15
+    # pad_left 1 with pad_right 3 (what a folded zero Padding gives a layer): the output runs two columns past the row, and in its last column
+    # the LEFT tap is padding too -- the direct kernel's first lane of a wave (stride 1) and every lane (stride 2, scalar) load that tap themselves
+    Geom(16, 16, 7, 9, 3, 3, 1, 1, 1, 3, 1, 1, 16, 1, 1),
+    Geom(16, 16, 17, 19, 3, 3, 2, 2, 1, 3, 1, 1, 16, 1, 1),
 ]
 
 
