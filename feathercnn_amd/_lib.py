@@ -112,6 +112,7 @@ SIGNATURES = {
     "fhip_net_set_yolo": (_I, [_V, _I]),
     "fhip_net_set_roi": (_I, [_V, _I]),
     "fhip_net_set_frame": (_I, [_V, _I]),
+    "fhip_net_set_transformer": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -380,6 +381,19 @@ FRAME_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_attn.h -- libfeather_attn.so, the layers of a Vision Transformer encoder: the attention core, LayerNorm, GELU
+# and the element-wise BinaryOp (a library of its own)
+ATTN_SIGNATURES = {
+    "fhip_attention_forward": (_I, [_I, _I, _I, _I, _I, _V, _I, _V, _I, _V, _I, _V, _V]),
+    "fhip_layer_norm_forward": (_I, [_I, _I, _V, _V, _FL, _V, _V, _V]),
+    "fhip_add_layer_norm_forward": (_I, [_I, _I, _V, _V, _FL, _V, _V, _V, _V, _V]),
+    "fhip_gelu_forward": (_I, [_I, _V, _V, _SZ, _V]),
+    "fhip_binary_forward": (_I, [_I, _I, _I, _V, _V, _V, _FL, _SZ, _SZ, _V]),
+    "fhip_attn_route": (_I, [_I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_attn_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -469,11 +483,19 @@ STANDALONE_LIBRARIES = {
     # route: FRAME_ROUTE of net.py (FHIP_FRAME_NET_ROUTE of its own header)
     "frame": Library("libfeather_frame.so", ("feather_frame.h",), "FHIP_FRAME_API", FRAME_SIGNATURES, "fhip_frame_last_error", (), None),
 }
+# The rows of LATER of csrc/Makefile, the same tuple: the libraries added after libfeather_frame.so, whose own list is pinned to its one
+# row as well.  tests/test_later_contract_cpu.py holds EVERY row here to the shared contract by the naming rule and asserts neither the
+# number of rows nor their names: the next library adds a row here, a name to LATER and a cases file.
+LATER_LIBRARIES = {
+    # route: ATTN_ROUTE of net.py (FHIP_ATTN_NET_ROUTE of its own header)
+    "attn": Library("libfeather_attn.so", ("feather_attn.h",), "FHIP_ATTN_API", ATTN_SIGNATURES, "fhip_attn_last_error", (), None),
+}
+_OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 
 
 def row(name: str) -> Library:
     """The row of the library `name`, from any of the tables or from the rows outside them."""
-    for table in TABLES + (STANDALONE_LIBRARIES,):
+    for table in TABLES + _OUTSIDE:
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -500,7 +522,7 @@ def load_library():
 
 
 # the names the wrappers, tools/ and the tests call: <x>_path() and load_<x>_library() of every side library
-for _name in (n for t in TABLES + (STANDALONE_LIBRARIES,) for n in t):
+for _name in (n for t in TABLES + _OUTSIDE for n in t):
     if _name != MAIN:
         globals()[f"{_name}_path"] = functools.partial(path, _name)
         globals()[f"load_{_name}_library"] = functools.partial(load, _name)

@@ -18,7 +18,7 @@
 // One translation unit, read in this order (no header includes a later one): net_side.h -- errors, the side libraries; net_model.h --
 // ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_conv.h -- the convolution layer, its side routes
 // and the weight staging it shares; net_layers.h -- the other layer classes; net_detect.h -- the detection-head layers and their factory; net_yolo.h -- the YOLO-head layers and
-// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_plan.h -- the fusion and planning passes, prepare,
+// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_plan.h -- the fusion and planning passes, prepare,
 // forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
 #include "net_side.h"
 #include "net_model.h"
@@ -29,6 +29,7 @@
 #include "net_yolo.h"
 #include "net_roi.h"
 #include "net_frame.h"
+#include "net_attn.h"
 #include "net_plan.h"
 
 namespace fhip::net
@@ -102,6 +103,14 @@ static int load_param_text(Net& net, const char* text, size_t len)
         std::string type, name, nb, nt;
         if (!next(type) || !next(name) || !next(nb) || !next(nt)) return failf(NET_E_IO, "param file ends after %d of %d layers", i, layer_count);
         std::unique_ptr<Layer> layer(net.detection ? create_detection_layer(type) : nullptr); // asked first: it overrides Concat and Softmax
+        if (!layer && net.transformer) // asked before create_layer: it overrides BinaryOp and InnerProduct
+        {
+            layer.reset(create_transformer_layer(type));
+            // without the blob ranks BinaryOp and InnerProduct stay what a default net knows; the new types are refused
+            if (layer && !net.detection && (type == "BinaryOp" || type == "InnerProduct")) layer.reset();
+            else if (layer && !net.detection)
+                return failf(NET_E_UNKNOWN_LAYER, "layer %s: the layers of fhip_net_set_transformer need the blob ranks fhip_net_set_detection maintains: set both", type.c_str());
+        }
         if (!layer) layer.reset(create_layer(type));
         if (!layer && net.extended) layer.reset(create_extended_layer(type));
         if (!layer && net.yolo) layer.reset(create_yolo_layer(type));
@@ -110,17 +119,17 @@ static int load_param_text(Net& net, const char* text, size_t len)
         if (!layer)
         {
             std::unique_ptr<Layer> opt_in(create_extended_layer(type)), detect(create_detection_layer(type)), yolo(create_yolo_layer(type)),
-                roi(create_roi_layer(type)), frame(create_frame_layer(type));
+                roi(create_roi_layer(type)), frame(create_frame_layer(type)), transformer(create_transformer_layer(type));
             return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered%s", type.c_str(),
                          opt_in ? " (fhip_net_set_extended_layers lifts this)"
-                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : (roi ? " (fhip_net_set_roi lifts this)" : (frame ? " (fhip_net_set_frame enables it)" : "")))));
+                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : (roi ? " (fhip_net_set_roi lifts this)" : (frame ? " (fhip_net_set_frame enables it)" : (transformer ? " (fhip_net_set_transformer lifts this)" : ""))))));
         }
         layer->type = type;
         layer->name = name;
         layer->net = &net;
         const int bottom_count = atoi(nb.c_str()), top_count = atoi(nt.c_str());
         // the reference uses both counts as read (net.cpp:98-137) and a layer without bottoms or tops faults at its first Reshape
-        if (bottom_count < 0 || top_count < 1 || (bottom_count == 0 && type != "Input"))
+        if (bottom_count < 0 || top_count < 1 || (bottom_count == 0 && type != "Input" && type != "MemoryData"))
             return failf(NET_E_TOPOLOGY, "Topology error: layer %s type %s has %d bottoms and %d tops.", name.c_str(), type.c_str(), bottom_count, top_count);
         for (int j = 0; j < bottom_count; ++j)
         {
@@ -354,6 +363,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.yolo = n->impl.yolo;
         m->impl.roi = n->impl.roi;
         m->impl.frame = n->impl.frame;
+        m->impl.transformer = n->impl.transformer;
         n->more.push_back(std::move(m));
     }
     if (replicas > 1 && !n->fork) FHIP_CHECK_HIP(hipEventCreateWithFlags(&n->fork, hipEventDisableTiming));
@@ -446,6 +456,15 @@ int fhip_net_set_frame(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the framing-layers switch (Padding, Crop, PixelShuffle) before LoadParam");
     n->impl.frame = on != 0;
     for (auto& m : n->more) m->impl.frame = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_transformer(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the transformer-layers switch (MemoryData, LayerNorm, GELU, MultiHeadAttention, BinaryOp) before LoadParam");
+    n->impl.transformer = on != 0;
+    for (auto& m : n->more) m->impl.transformer = on != 0;
     return FHIP_OK;
 }
 

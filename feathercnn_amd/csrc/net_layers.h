@@ -539,6 +539,9 @@ struct BinaryOpLayer : Layer
         if (bottoms.size() != 2 || tops.size() != 1) return failf(NET_E_SHAPE, "layer %s: BinaryOp needs two bottoms and one top", name.c_str());
         return 0;
     }
+    // whether the layer is a multiply of two blobs: what collapse_gate_blocks may take for an SE block's gate (always, here; the layer of a
+    // net with fhip_net_set_transformer knows other ops)
+    virtual bool multiplies() const { return true; }
     // the gate is the bottom with the 1 x 1 plane; two such bottoms: the second is the gate
     bool gate_first() const { return bottoms[0]->h == 1 && bottoms[0]->w == 1 && !(bottoms[1]->h == 1 && bottoms[1]->w == 1); }
     int Reshape() override { return gate_first() ? gate_reshape(this, bottoms[1], bottoms[0]) : gate_reshape(this, bottoms[0], bottoms[1]); }

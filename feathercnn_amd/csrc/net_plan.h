@@ -189,8 +189,10 @@ static void collapse_gate_blocks(Net& net)
         Blob* g = l->tops[0];
         if (!(l = step(g)) || l->bottoms.size() != 2 || l->tops.size() != 1) continue;
         Blob* x = nullptr;
-        if (l->type == "BinaryOp")
+        if (l->type == "BinaryOp" && static_cast<BinaryOpLayer*>(l)->multiplies())
             x = l->bottoms[0] == g ? l->bottoms[1] : l->bottoms[0];
+        else if (l->type == "BinaryOp")
+            continue; // an add, sub, div, max or min behind the gate's activation is no gate
         else if (l->type == "Scale" && static_cast<ScaleLayer*>(l)->gated && l->bottoms[1] == g)
             x = l->bottoms[0];
         if (!x || x == g || x == pool->bottoms[0]) continue;
@@ -298,6 +300,7 @@ static void fuse_layers(Net& net)
     if (net.fusion >= 2) collapse_channel_maps(net);
     if (net.fusion >= 2) collapse_gate_blocks(net);
     if (net.fusion >= 2) collapse_upsample_adds(net);
+    if (net.fusion >= 2 && net.transformer) collapse_add_norms(net);
     for (size_t i = 0; i < net.layers.size(); ++i)
     {
         for (;;)

@@ -246,14 +246,16 @@ class GraphBuilder:
     def eltwise(self, name, a, b):
         return self.layer("Eltwise", name, [a, b], [name], {0: 1})
 
-    def concat(self, name, bottoms, axis=0):
-        """axis: relative to the bottoms' rank; anything but 0 on blobs of rank 3 needs Net.SetDetection(True)."""
-        self._note("concat", name, list(bottoms), name, dict(axis=axis))
+    def concat(self, name, bottoms, axis=0, rank=None):
+        """axis: relative to the bottoms' rank; anything but 0 on blobs of rank 3 needs Net.SetDetection(True).  rank: the bottoms' rank where it
+        is not 3, for numpy_forward."""
+        self._note("concat", name, list(bottoms), name, dict(axis=axis) if rank is None else dict(axis=axis, rank=rank))
         return self.layer("Concat", name, list(bottoms), [name], {0: axis})
 
     # -- the SSD detection head (a net that holds one of these needs Net.SetDetection(True)) ------------------------
     def permute(self, name, bottom, order):
         """ncnn's Permute: 0=order_type (3: NCHW -> NHWC)."""
+        self._note("permute", name, bottom, name, dict(order=int(order)))
         return self.layer("Permute", name, [bottom], [name], {0: int(order)})
 
     def flatten(self, name, bottom):
@@ -266,6 +268,7 @@ class GraphBuilder:
             params[1] = int(h)
         if c is not None:
             params[2] = int(c)
+        self._note("reshape", name, bottom, name, dict(w=int(w), h=h, c=c))
         return self.layer("Reshape", name, [bottom], [name], params)
 
     def normalize(self, name, bottom, c, scale=20.0, eps=1e-10, channel_shared=False):
@@ -419,6 +422,74 @@ class GraphBuilder:
         self._note("pixel_shuffle", name, bottom, name, dict(r=int(r), mode=int(mode or 0)))
         return self.layer("PixelShuffle", name, [bottom], [name], {0: int(r)} if mode is None else {0: int(r), 1: int(mode)})
 
+    # -- the transformer layers (a net that holds one of these needs Net.SetTransformer() and Net.SetDetection()) -------------------
+    def memory_data(self, name, w, h=0, c=0, scale=1.0):
+        """ncnn's MemoryData: 0=w 1=h 2=c (written where non-zero: the rank), w * h * c raw floats, U(-1, 1) * scale."""
+        params = {0: int(w)}
+        if h:
+            params[1] = int(h)
+        if c:
+            params[2] = int(c)
+        data = self._uniform(int(w) * max(int(h), 1) * max(int(c), 1), -1, 1, scale)
+        self._raw(data)
+        self._note("memory_data", name, [], name, dict(data=data, shape=(max(int(c), 1), max(int(h), 1), int(w))))
+        return self.layer("MemoryData", name, [], [name], params)
+
+    def layer_norm(self, name, bottom, size, eps=None, affine=True):
+        """ncnn's LayerNorm: 0=affine_size, 1=eps (written only when given; 0.001), 2=affine (written only when off); gamma and beta raw."""
+        params = {0: int(size)}
+        if eps is not None:
+            params[1] = f"{eps:.6e}"
+        if not affine:
+            params[2] = 0
+        gamma = self._uniform(int(size), 0.5, 1.5) if affine else None
+        beta = self._uniform(int(size), -0.1, 0.1) if affine else None
+        if affine:
+            self._raw(gamma)
+            self._raw(beta)
+        self._note("layer_norm", name, bottom, name, dict(size=int(size), eps=0.001 if eps is None else float(f"{eps:.6e}"), gamma=gamma, beta=beta))
+        return self.layer("LayerNorm", name, [bottom], [name], params)
+
+    def gelu(self, name, bottom, fast=False):
+        """ncnn's GELU: 0=fast_gelu (written only when set)."""
+        self._note("gelu", name, bottom, name, dict(fast=bool(fast)))
+        return self.layer("GELU", name, [bottom], [name], {0: 1} if fast else {})
+
+    def binary(self, name, op, a, b):
+        """ncnn's BinaryOp 0=op (0 add, 1 sub, 2 mul, 3 div, 4 max, 5 min): b a blob name (two bottoms) or a number (1=1 2=b)."""
+        if isinstance(b, str):
+            self._note("binary", name, [a, b], name, dict(op=int(op), scalar=None))
+            return self.layer("BinaryOp", name, [a, b], [name], {0: int(op)})
+        self._note("binary", name, a, name, dict(op=int(op), scalar=float(f"{b:.6e}")))
+        return self.layer("BinaryOp", name, [a], [name], {0: int(op), 1: 1, 2: f"{b:.6e}"})
+
+    def multi_head_attention(self, name, q, embed, heads, k=None, v=None, gain=1.0, scale=None):
+        """ncnn's MultiHeadAttention: 0=embed_dim 1=num_heads 2=weight_data_size (6=scale only when given); bottoms q [, k [, v]]; the .bin holds
+        q, k, v and out weights (tagged, [out][in]) each followed by its raw bias."""
+        bottoms = [q] + ([k] if k is not None else []) + ([v] if v is not None else [])
+        params = {0: int(embed), 1: int(heads), 2: int(embed) * int(embed)}
+        if scale is not None:
+            params[6] = f"{scale:.6e}"
+        weights = []
+        for _ in range(4):
+            w = self._uniform(embed * embed, -1, 1, np.sqrt(6.0 / embed) * gain)
+            b = self._uniform(embed, -0.1, 0.1)
+            self._tagged(w)
+            self._raw(b)
+            weights += [w if self.dry else w.reshape(embed, embed), b]
+        self._note("mha", name, bottoms if len(bottoms) > 1 else q, name, dict(heads=int(heads), weights=weights, scale=None if scale is None else float(f"{scale:.6e}")))
+        return self.layer("MultiHeadAttention", name, bottoms, [name], params)
+
+    def fc_tokens(self, name, bottom, cin, cout, bias=True, gain=1.0):
+        """An InnerProduct on a blob of rank 2 [T][cin]: once per token, [T][cout] (Net.SetTransformer())."""
+        top = self.layer("InnerProduct", name, [bottom], [name], {0: cout, 1: int(bias), 2: cin * cout})
+        w = self._uniform(cin * cout, -1, 1, np.sqrt(6.0 / cin) * gain)
+        b = self._uniform(cout, -0.1, 0.1) if bias else None
+        self._weights(name, w, cout, b)
+        if self.trace is not None:
+            self._note("fc_tokens", name, bottom, top, dict(w=w.reshape(cout, cin), b=b))
+        return top
+
     def shuffle(self, name, bottom, group, reverse=False):
         """ncnn's ShuffleChannel: 0=group, 1=reverse (written only when set)."""
         return self.layer("ShuffleChannel", name, [bottom], [name], {0: group, 1: 1} if reverse else {0: group})
@@ -543,6 +614,18 @@ def _frame_ref():
     return frame_ref
 
 
+def _attn_ref():
+    """tests/attn_ref.py, the restatement of feather_attn.h: numpy_forward's transformer layers are that text, not a second one."""
+    try:
+        import attn_ref
+    except ImportError:
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import attn_ref
+    return attn_ref
+
+
 def numpy_forward(trace, input_name, x=None):
     """A plain numpy forward (fp32 values, sums in float64) of the layers a GraphBuilder recorded in `trace` -- Convolution, InnerProduct,
     ReLU (plain or leaky), BatchNorm, Scale, Pooling, Split, Concat on channels, Reorg, nearest Interp by a whole scale, the RPN's softmax, a
@@ -565,7 +648,33 @@ def numpy_forward(trace, input_name, x=None):
             if len(top) > 1:
                 blobs[top[1]] = scores.reshape(scores.shape[0], -1, 1, 1)
             continue
-        if kind == "concat" and a["axis"] == 0:
+        if kind == "memory_data":
+            batch = next(iter(blobs.values())).shape[0]
+            blobs[top] = np.broadcast_to(np.asarray(a["data"], np.float32).reshape((1,) + a["shape"]), (batch,) + a["shape"]).copy()
+            continue
+        if kind == "concat" and "rank" in a:
+            y = np.concatenate(v, axis=4 - a["rank"] + a["axis"])
+        elif kind == "reshape":
+            ext = [a["w"], 1 if a["h"] is None else a["h"], 1 if a["c"] is None else a["c"]]
+            ext = [v.shape[3 - i] if e == 0 else e for i, e in enumerate(ext)]
+            y = v.reshape(v.shape[0], ext[2], ext[1], ext[0])
+        elif kind == "permute" and a["order"] == 1 and v.shape[1] == 1:  # rank 2: (h, w) -> (w, h)
+            y = v.transpose(0, 1, 3, 2)
+        elif kind == "layer_norm":
+            rows = v.reshape(v.shape[0], -1, a["size"])
+            y = _attn_ref().layer_norm(rows, a["gamma"], a["beta"], a["eps"]).reshape(v.shape)
+        elif kind == "gelu":
+            y = _attn_ref().gelu(v, a["fast"])
+        elif kind == "binary":
+            y = _attn_ref().binary(a["op"], v, np.float32(a["scalar"])) if a["scalar"] is not None else _attn_ref().binary(a["op"], v[0], v[1])
+        elif kind == "mha":
+            q, k, w_ = (v, v, v) if isinstance(bottom, str) else (v[0], v[1], v[-1])
+            y = _attn_ref().multi_head_attention(q[:, 0], k[:, 0], w_[:, 0], a["heads"], a["weights"], a["scale"])[:, None]
+        elif kind == "fc_tokens":
+            y = v.astype(np.float64) @ a["w"].astype(np.float64).T
+            if a["b"] is not None:
+                y += a["b"]
+        elif kind == "concat" and a["axis"] == 0:
             y = np.concatenate(v, axis=1)
         elif kind == "rpn_softmax":
             A = a["anchors"]
@@ -1869,6 +1978,79 @@ def tiny_frame(seed=67, size=(8, 10), dry=False, trace=None):
     return g.finish() + ("data", "out")
 
 
+def _encoder_block(g, tag, x, embed, heads, hidden, gain=1.0):
+    """One pre-norm encoder block on tokens `x` [T][embed]: x + MHA(LN(x)), then x + FC(GELU(FC(LN(x)))).  -> (the block's output, written by a
+    BinaryOp add)."""
+    skip, y = g.split(tag + "_s1", x, 2)
+    y = g.multi_head_attention(tag + "_attn", g.layer_norm(tag + "_ln1", y, embed), embed, heads, gain=gain)
+    x = g.binary(tag + "_add1", 0, skip, y)
+    skip, y = g.split(tag + "_s2", x, 2)
+    y = g.fc_tokens(tag + "_fc1", g.layer_norm(tag + "_ln2", y, embed), embed, hidden, gain=gain)
+    y = g.fc_tokens(tag + "_fc2", g.gelu(tag + "_gelu", y), hidden, embed, gain=gain)
+    return g.binary(tag + "_add2", 0, skip, y)
+
+
+def _vit(g, size, patch, embed, heads, depth, hidden, classes, gain=1.0):
+    """The Vision Transformer (Dosovitskiy et al. 2021) as ncnn's converter writes it: a stride-`patch` convolution, Reshape to [embed][P], Permute
+    to [P][embed], the class token (MemoryData) concatenated in front, the position embedding (MemoryData) added, `depth` pre-norm encoder
+    blocks, a final LayerNorm, the class token taken by Reshape to rank 3 and Crop, and the head."""
+    h, w = size if isinstance(size, tuple) else (size, size)
+    tokens = (h // patch) * (w // patch) + 1
+    x = g.conv("patch_embed", g.input("data", 3, h, w), 3, embed, patch, patch)
+    x = g.permute("to_tokens", g.reshape("flat", x, -1, embed), 1)
+    x = g.concat("with_cls", [g.memory_data("cls_token", embed, 1, scale=0.5), x], 0, rank=2)
+    x = g.binary("add_pos", 0, x, g.memory_data("pos_embed", embed, tokens, scale=0.5))
+    for i in range(depth):
+        x = _encoder_block(g, f"blk{i}", x, embed, heads, hidden, gain)
+    x = g.layer_norm("norm", x, embed)
+    return x, tokens
+
+
+def tiny_vit(seed=71, size=16, dry=False, trace=None):
+    """A small Vision Transformer with every transformer layer (Net.SetTransformer(), SetDetection(), SetFrame()): a 16 x 16 input, 4-px patches,
+    E = 16, 2 heads, 2 encoder blocks, class token and position embedding from MemoryData.  Behind the encoder: one cross-attention layer whose
+    queries are the tokens and whose keys and values a second LayerNorm of the patch tokens alone (Tq = 17, Tk = 16), a scalar BinaryOp (mul
+    0.5), the fast GELU, the class token taken by Reshape to rank 3 and Crop, and the head.  trace: a list that receives the layers for
+    numpy_forward."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    embed, heads = 16, 2
+    h, w = size if isinstance(size, tuple) else (size, size)
+    x = g.conv("patch_embed", g.input("data", 3, h, w), 3, embed, 4, 4)
+    x = g.permute("to_tokens", g.reshape("flat", x, -1, embed), 1)
+    patches, x = g.split("split_patches", x, 2)
+    tokens = (h // 4) * (w // 4) + 1
+    x = g.concat("with_cls", [g.memory_data("cls_token", embed, 1, scale=0.5), x], 0, rank=2)
+    x = g.binary("add_pos", 0, x, g.memory_data("pos_embed", embed, tokens, scale=0.5))
+    for i in range(2):
+        x = _encoder_block(g, f"blk{i}", x, embed, heads, 32)
+    x = g.layer_norm("norm", x, embed)
+    memory = g.layer_norm("norm_mem", patches, embed, eps=1e-5, affine=False)
+    x = g.multi_head_attention("cross", x, embed, heads, k=memory, scale=0.3)
+    x = g.gelu("gelu_fast", g.binary("halve", 2, x, 0.5), fast=True)
+    x = g.crop("cls", g.reshape("as_rank3", x, embed, tokens, 1), outh=1)
+    g.fc("head", x, embed, 10)
+    return g.finish() + ("data", "head")
+
+
+def deit_tiny_patch16_224(seed=1234, classes=1000, size=224, dry=False):
+    """DeiT-tiny (Touvron et al. 2021) without the distillation token: patch 16, E = 192, 3 heads, 12 blocks, MLP 768; 197 tokens at 224 px.
+    Random weights.  Net.SetTransformer(), SetDetection(), SetFrame()."""
+    g = GraphBuilder(seed, dry)
+    x, tokens = _vit(g, size, 16, 192, 3, 12, 768, classes, gain=0.5)
+    g.fc("head", g.crop("cls", g.reshape("as_rank3", x, 192, tokens, 1), outh=1), 192, classes)
+    return g.finish() + ("data", "head")
+
+
+def vit_base_patch16_224(seed=1234, classes=1000, size=224, dry=False):
+    """ViT-B/16 (Dosovitskiy et al. 2021): patch 16, E = 768, 12 heads, 12 blocks, MLP 3072; 197 tokens at 224 px.  Random weights.
+    Net.SetTransformer(), SetDetection(), SetFrame()."""
+    g = GraphBuilder(seed, dry)
+    x, tokens = _vit(g, size, 16, 768, 12, 12, 3072, classes, gain=0.5)
+    g.fc("head", g.crop("cls", g.reshape("as_rank3", x, 768, tokens, 1), outh=1), 768, classes)
+    return g.finish() + ("data", "head")
+
+
 def espcn_x3(seed=1234, size=(180, 240), channels=1, dry=False):
     """ESPCN (Shi et al. 2016) x3: 5x5 -> 64, 3x3 -> 32, 3x3 -> channels * 9, TanH between them, and the sub-pixel layer, PixelShuffle 0=3
     (Net.SetFrame()).  The paper runs it on the luma plane (channels = 1).  size = (height, width) of the low-resolution input."""
@@ -1962,7 +2144,7 @@ MODELS = {"vgg16": vgg16, "resnet50": resnet50, "mobilenet_v1": mobilenet_v1, "s
           "tiny_yolov2": tiny_yolov2, "tiny_yolov3": tiny_yolov3, "yolov2_tiny_voc": yolov2_tiny_voc, "mobilenetv2_yolov3": mobilenetv2_yolov3,
           "tiny_faster_rcnn": tiny_faster_rcnn, "tiny_rfcn": tiny_rfcn, "faster_rcnn_vgg16": faster_rcnn_vgg16, "rfcn_resnet50": rfcn_resnet50,
           "tiny_frame": tiny_frame, "espcn_x3": espcn_x3, "srresnet_x4": srresnet_x4, "cyclegan_resnet9": cyclegan_resnet9,
-          "mobilenet_v1_tf": mobilenet_v1_tf}
+          "mobilenet_v1_tf": mobilenet_v1_tf, "tiny_vit": tiny_vit, "deit_tiny_patch16_224": deit_tiny_patch16_224, "vit_base_patch16_224": vit_base_patch16_224}
 
 DECONV_LAYERS = {"tiny_deconv": ("d1", "d2", "dw_up", "gd", "d3", "d4"), "style_transfer": ("deconv1", "deconv2"), "unet_k4": ("d5", "d4", "d3", "d2", "d1")}
 
@@ -1997,6 +2179,8 @@ YOLO_NETS = ("tiny_yolov2", "tiny_yolov3", "yolov2_tiny_voc", "mobilenetv2_yolov
 ROI_NETS = ("tiny_faster_rcnn", "tiny_rfcn", "faster_rcnn_vgg16", "rfcn_resnet50")
 
 # nets that need Net.SetFrame() (Padding, Crop, PixelShuffle: libfeather_frame.so)
+# nets that need Net.SetTransformer(), SetDetection() and SetFrame(): Vision Transformers
+TRANSFORMER_NETS = ("tiny_vit", "deit_tiny_patch16_224", "vit_base_patch16_224")
 FRAME_NETS = ("tiny_frame", "espcn_x3", "srresnet_x4", "cyclegan_resnet9", "mobilenet_v1_tf")
 # the zero Paddings of each net that fusion level 2 folds into the convolution behind them, and the Paddings that must stay
 ZERO_PADDINGS = {"tiny_frame": (("pad_same",), ("pad_reflect", "pad_rep", "pad_pc", "pad_ch")),

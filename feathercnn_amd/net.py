@@ -39,6 +39,8 @@ ROI_ROUTE = 111  # FHIP_ROI_NET_ROUTE (feather_roi.h): Proposal, ROIPooling, ROI
 ROUTE_NAMES[ROI_ROUTE] = "ROI"
 FRAME_ROUTE = 112  # FHIP_FRAME_NET_ROUTE (feather_frame.h): Padding, Crop or PixelShuffle, after SetFrame() (libfeather_frame.so)
 ROUTE_NAMES[FRAME_ROUTE] = "FRAME"
+ATTN_ROUTE = 113  # FHIP_ATTN_NET_ROUTE (feather_attn.h): MemoryData, LayerNorm, GELU, MultiHeadAttention or an element-wise BinaryOp, after SetTransformer() (libfeather_attn.so)
+ROUTE_NAMES[ATTN_ROUTE] = "ATTN"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -107,6 +109,12 @@ class Net:
         """feather::Net::SetFrame: accept ncnn's Padding, Crop and PixelShuffle (routed to libfeather_frame.so) instead of refusing them at
         LoadParam.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_frame(self._h, int(bool(on))), "fhip_net_set_frame")
+
+    def SetTransformer(self, on: bool = True):
+        """feather::Net::SetTransformer: accept ncnn's MemoryData, LayerNorm, GELU, MultiHeadAttention and the element-wise BinaryOp (routed to
+        libfeather_attn.so) and run an InnerProduct on a [T][F] blob once per token, instead of refusing them at LoadParam.  Needs
+        SetDetection() too (blob ranks).  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_transformer(self._h, int(bool(on))), "fhip_net_set_transformer")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

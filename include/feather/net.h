@@ -33,7 +33,8 @@
 //     SetExtendedLayers(true); the SSD detection head (Permute, Flatten, Reshape, Normalize, PriorBox, DetectionOutput; feather_detect.h)
 //     after SetDetection(true), its result through ExtractDetections; the YOLO heads after SetYolo(rows); Proposal, ROIPooling, ROIAlign
 //     and PSROIPooling (feather_roi.h) after SetRoi(true), the ROIs through ExtractProposals; Padding, Crop and PixelShuffle
-//     (feather_frame.h) after SetFrame(true).
+//     (feather_frame.h) after SetFrame(true); MemoryData, LayerNorm, GELU, MultiHeadAttention, the element-wise BinaryOp and the token-wise
+//     InnerProduct (feather_attn.h) after SetTransformer(true) and SetDetection(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -248,6 +249,9 @@ class Net
     int SetRoi(bool on = true) { return fhip_net_set_roi(net_, on ? 1 : 0); }
     // accept ncnn's Padding, Crop and PixelShuffle (libfeather_frame.so) instead of refusing them; before LoadParam (feather_net.h)
     int SetFrame(bool on = true) { return fhip_net_set_frame(net_, on ? 1 : 0); }
+    // accept the layers of a Vision Transformer encoder -- MemoryData, LayerNorm, GELU, MultiHeadAttention, the element-wise BinaryOp
+    // (libfeather_attn.so), an InnerProduct once per token -- instead of refusing them; needs SetDetection(true) too; before LoadParam (feather_net.h)
+    int SetTransformer(bool on = true) { return fhip_net_set_transformer(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
     // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
     // blob has another shape.  scores_blob "" asks for none.

@@ -304,6 +304,21 @@ FHIP_API int fhip_net_set_roi(fhip_net* net, int on);
  * bit.  0 (default): LoadParam refuses the three types with -200; on-then-off equals the default.  Call before LoadParam; later it is
  * FHIP_E_BADARG.  Copied to sub-batch replicas. */
 FHIP_API int fhip_net_set_frame(fhip_net* net, int on);
+/* 1: the layers of a Vision Transformer encoder are loaded -- ncnn's MemoryData (0=w 1=h 2=c and that many raw floats: a constant, replicated
+ * to the batch of the net's first Input when the shapes are planned and written once, at Init), LayerNorm (0=affine_size 1=eps 2=affine; rows
+ * of w floats, or planes of h * w on a blob of rank 3), GELU (0=fast_gelu), MultiHeadAttention (0=embed_dim 1=num_heads 2=weight_data_size
+ * 3=kdim 4=vdim 5=attn_mask 6=scale; one bottom, q and k = v, or q, k and v, each a blob of rank 2 [T][E]) and the element-wise BinaryOp (0=op
+ * 0 .. 5, 1=with_scalar 2=b; two bottoms of one shape, or one of them a single image), as feather_attn.h defines their kernels; they run
+ * through libfeather_attn.so and report the route FHIP_ATTN_NET_ROUTE (feather_attn.h).  An InnerProduct whose bottom is a blob of rank 2
+ * [T][F] with F its input size runs once per token and gives [T][num_output]; every GEMM of these layers is the main library's.  The
+ * multiply of a blob by a [n][c][1][1] gate stays on FHIP_NET_ROUTE_GATE.  Refused with -100: an attention mask, kdim or vdim other than
+ * embed_dim, weight_data_size other than embed_dim^2, embed_dim % num_heads != 0, an op code past 5, an affine_size that is neither w nor
+ * h * w, tensors of 2^31 elements or more.  The blobs of these layers have ranks, which fhip_net_set_detection maintains: without it
+ * LoadParam refuses the new types with -200 and says so (BinaryOp and InnerProduct stay what a default net loads).  At fusion level >= 2 a BinaryOp add whose top a Split hands to one LayerNorm (and to
+ * other layers) runs with that LayerNorm in one launch, bit for bit.  0 (default): LoadParam refuses the new types with -200, BinaryOp and
+ * InnerProduct are what they were; on-then-off equals the default.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch
+ * replicas. */
+FHIP_API int fhip_net_set_transformer(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
