@@ -31,11 +31,13 @@ from .frame import crop, frame_route, pad, pixel_shuffle, pixel_shuffle_output_d
 from .frame import NET_ROUTE as FRAME_NET_ROUTE
 from .attn import add_layer_norm, attention, attn_route, binary, gelu, layer_norm
 from .attn import NET_ROUTE as ATTN_NET_ROUTE
+from .rnn import GRU, LSTM, RNN, recurrent, rnn_route
+from .rnn import NET_ROUTE as RNN_NET_ROUTE
 from .pixels import (PIXEL_BGR, PIXEL_BGR2GRAY, PIXEL_BGR2RGB, PIXEL_GRAY, PIXEL_GRAY2BGR, PIXEL_GRAY2RGB, PIXEL_RGB, PIXEL_RGB2BGR,
                      PIXEL_RGB2GRAY, PIXEL_RGBA, PIXEL_RGBA2BGR, PIXEL_RGBA2GRAY, PIXEL_RGBA2RGB, float_to_pixels, pixels_images_to_float,
                      pixels_to_float, yuv420sp_to_float)
 
-__all__ = ["attention", "layer_norm", "add_layer_norm", "gelu", "binary", "attn_route", "ATTN_NET_ROUTE", "pad", "crop", "window", "window_output_dim", "pixel_shuffle", "pixel_shuffle_output_dim", "frame_route", "FRAME_NET_ROUTE", "generate_anchors", "proposal", "roi_pool", "roi_align", "psroi_pool", "roi_route", "ROI_NET_ROUTE", "reorg", "reorg_output_dim", "yolo_detection", "yolo_route", "YOLO_NET_ROUTE", "YOLO_MAX_SCALES", "YOLO_MAX_BOXES", "YOLO_MAX_CLASSES",
+__all__ = ["recurrent", "rnn_route", "LSTM", "GRU", "RNN", "RNN_NET_ROUTE", "attention", "layer_norm", "add_layer_norm", "gelu", "binary", "attn_route", "ATTN_NET_ROUTE", "pad", "crop", "window", "window_output_dim", "pixel_shuffle", "pixel_shuffle_output_dim", "frame_route", "FRAME_NET_ROUTE", "generate_anchors", "proposal", "roi_pool", "roi_align", "psroi_pool", "roi_route", "ROI_NET_ROUTE", "reorg", "reorg_output_dim", "yolo_detection", "yolo_route", "YOLO_NET_ROUTE", "YOLO_MAX_SCALES", "YOLO_MAX_BOXES", "YOLO_MAX_CLASSES",
            "YOLO_MAX_CELLS", "YOLO_MAX_ROWS", "YOLO_CHUNK", "permute", "permute_concat", "normalize", "priorbox", "axis_softmax", "detection_output", "detect_route", "Q8Conv", "Q8Param", "q8_pack", "q8_unpack", "q8_relu", "q8_max_pool", "q8_route", "QuantConv", "QuantParam", "quantize", "qconv_route", "dequant_scales", "ConvParam", "ConvBooster", "ConvLayer", "GroupedConv", "GroupedConvLayer", "Deconv", "DeconvLayer", "DeconvParam", "AtrousConv", "AtrousLayer", "AtrousParam", "instance_norm", "instance_norm_route", "activation", "channel_gate", "squeeze", "excite", "gate_activation", "interp", "interp_output_dim", "interp_route", "hard_swish", "lrn", "lrn_pool", "lrn_route", "lrn_pool_route", "channel_shuffle", "channel_slice", "channel_map", "ChannelMap", "FeatherHipError", "load_library", "lib_path", "NAIVE", "IM2COL",
            "SGECONV", "DEPTHWISE", "WINOGRADF63", "WINOGRADF63FUSED", "WINOGRADF23", "None_", "ReLU", "ALGO_NAMES", "pixels_to_float", "pixels_images_to_float", "float_to_pixels", "yuv420sp_to_float", "PIXEL_RGB", "PIXEL_BGR", "PIXEL_GRAY", "PIXEL_RGBA",
            "PIXEL_RGB2BGR", "PIXEL_RGB2GRAY", "PIXEL_BGR2RGB", "PIXEL_BGR2GRAY", "PIXEL_GRAY2RGB", "PIXEL_GRAY2BGR", "PIXEL_RGBA2RGB",

@@ -113,6 +113,7 @@ SIGNATURES = {
     "fhip_net_set_roi": (_I, [_V, _I]),
     "fhip_net_set_frame": (_I, [_V, _I]),
     "fhip_net_set_transformer": (_I, [_V, _I]),
+    "fhip_net_set_recurrent": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -394,6 +395,17 @@ ATTN_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_rnn.h -- libfeather_rnn.so, the recurrent core of ncnn's LSTM, GRU and RNN layers (a library of its own)
+_RNN_FORWARD = [_I, _I, _I, _I, _I, _V, _I, _V, _V, _V, _V, _V, _I, _V, _V, _V, _V]
+RNN_SIGNATURES = {
+    "fhip_rnn_sequence_fits": (_I, [_I, _I]),
+    "fhip_rnn_forward": (_I, _RNN_FORWARD),
+    "fhip_rnn_forward_route": (_I, _RNN_FORWARD + [_I]),
+    "fhip_rnn_route": (_I, [_I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_rnn_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -489,6 +501,8 @@ STANDALONE_LIBRARIES = {
 LATER_LIBRARIES = {
     # route: ATTN_ROUTE of net.py (FHIP_ATTN_NET_ROUTE of its own header)
     "attn": Library("libfeather_attn.so", ("feather_attn.h",), "FHIP_ATTN_API", ATTN_SIGNATURES, "fhip_attn_last_error", (), None),
+    # route: RNN_ROUTE of net.py (FHIP_RNN_NET_ROUTE of its own header)
+    "rnn": Library("libfeather_rnn.so", ("feather_rnn.h",), "FHIP_RNN_API", RNN_SIGNATURES, "fhip_rnn_last_error", (), None),
 }
 _OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 

@@ -18,7 +18,7 @@
 // One translation unit, read in this order (no header includes a later one): net_side.h -- errors, the side libraries; net_model.h --
 // ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_conv.h -- the convolution layer, its side routes
 // and the weight staging it shares; net_layers.h -- the other layer classes; net_detect.h -- the detection-head layers and their factory; net_yolo.h -- the YOLO-head layers and
-// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_plan.h -- the fusion and planning passes, prepare,
+// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_rnn.h -- the recurrent layers and theirs; net_plan.h -- the fusion and planning passes, prepare,
 // forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
 #include "net_side.h"
 #include "net_model.h"
@@ -30,6 +30,7 @@
 #include "net_roi.h"
 #include "net_frame.h"
 #include "net_attn.h"
+#include "net_rnn.h"
 #include "net_plan.h"
 
 namespace fhip::net
@@ -116,13 +117,19 @@ static int load_param_text(Net& net, const char* text, size_t len)
         if (!layer && net.yolo) layer.reset(create_yolo_layer(type));
         if (!layer && net.roi) layer.reset(create_roi_layer(type));
         if (!layer && net.frame) layer.reset(create_frame_layer(type));
+        if (!layer && net.recurrent)
+        {
+            layer.reset(create_recurrent_layer(type));
+            if (layer && !net.detection)
+                return failf(NET_E_UNKNOWN_LAYER, "layer %s: the layers of fhip_net_set_recurrent need the blob ranks fhip_net_set_detection maintains: set both", type.c_str());
+        }
         if (!layer)
         {
             std::unique_ptr<Layer> opt_in(create_extended_layer(type)), detect(create_detection_layer(type)), yolo(create_yolo_layer(type)),
-                roi(create_roi_layer(type)), frame(create_frame_layer(type)), transformer(create_transformer_layer(type));
+                roi(create_roi_layer(type)), frame(create_frame_layer(type)), transformer(create_transformer_layer(type)), recurrent(create_recurrent_layer(type));
             return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered%s", type.c_str(),
                          opt_in ? " (fhip_net_set_extended_layers lifts this)"
-                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : (roi ? " (fhip_net_set_roi lifts this)" : (frame ? " (fhip_net_set_frame enables it)" : (transformer ? " (fhip_net_set_transformer lifts this)" : ""))))));
+                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : (roi ? " (fhip_net_set_roi lifts this)" : (frame ? " (fhip_net_set_frame enables it)" : (transformer ? " (fhip_net_set_transformer lifts this)" : (recurrent ? " (fhip_net_set_recurrent lifts this)" : "")))))));
         }
         layer->type = type;
         layer->name = name;
@@ -364,6 +371,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.roi = n->impl.roi;
         m->impl.frame = n->impl.frame;
         m->impl.transformer = n->impl.transformer;
+        m->impl.recurrent = n->impl.recurrent;
         n->more.push_back(std::move(m));
     }
     if (replicas > 1 && !n->fork) FHIP_CHECK_HIP(hipEventCreateWithFlags(&n->fork, hipEventDisableTiming));
@@ -465,6 +473,15 @@ int fhip_net_set_transformer(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the transformer-layers switch (MemoryData, LayerNorm, GELU, MultiHeadAttention, BinaryOp) before LoadParam");
     n->impl.transformer = on != 0;
     for (auto& m : n->more) m->impl.transformer = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_recurrent(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the recurrent-layers switch (LSTM, GRU, RNN) before LoadParam");
+    n->impl.recurrent = on != 0;
+    for (auto& m : n->more) m->impl.recurrent = on != 0;
     return FHIP_OK;
 }
 

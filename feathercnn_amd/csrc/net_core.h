@@ -193,6 +193,7 @@ struct Net
     bool roi = false;             // fhip_net_set_roi: Proposal, ROIPooling, ROIAlign and PSROIPooling (net_roi.h, libfeather_roi.so) are loaded instead of refused
     bool frame = false;           // fhip_net_set_frame: Padding, Crop and PixelShuffle (net_frame.h, libfeather_frame.so) are loaded instead of refused
     bool transformer = false;     // fhip_net_set_transformer: MemoryData, LayerNorm, GELU, MultiHeadAttention, the element-wise BinaryOp and the token-wise InnerProduct (net_attn.h, libfeather_attn.so) are loaded instead of refused
+    bool recurrent = false;       // fhip_net_set_recurrent: LSTM, GRU and RNN (net_rnn.h, libfeather_rnn.so) are loaded instead of refused
     int colpass = 1;              // fhip_net_set_colpass: chained 64-input-channel Winograd layers through libfeather_colpass.so -- 0 never, 1 where M is HBM-bound, 2 wherever accepted
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;

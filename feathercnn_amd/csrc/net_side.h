@@ -1,5 +1,5 @@
 // net_side.h -- the Net runtime's errors and its side libraries: the table of each libfeather_<x>.so and side_api<X>(), which opens it.
-// First of the headers of net.hip (net_side.h, net_model.h, net_core.h, net_conv.h, net_layers.h, net_detect.h, net_yolo.h, net_roi.h, net_frame.h, net_attn.h, net_plan.h): none includes a later one.
+// First of the headers of net.hip (net_side.h, net_model.h, net_core.h, net_conv.h, net_layers.h, net_detect.h, net_yolo.h, net_roi.h, net_frame.h, net_attn.h, net_rnn.h, net_plan.h): none includes a later one.
 #pragma once
 #include <ctype.h>
 #include <dlfcn.h>

@@ -490,6 +490,52 @@ class GraphBuilder:
             self._note("fc_tokens", name, bottom, top, dict(w=w.reshape(cout, cin), b=b))
         return top
 
+    # -- the recurrent layers (a net that holds one of these needs Net.SetRecurrent() and Net.SetDetection()) -----------------------
+    def _recurrent(self, type_, cell, name, bottom, size, hidden, direction, states_in, states_out):
+        """ncnn's LSTM / GRU / RNN: 0=num_output 1=weight_data_size 2=direction (LSTM: 3=hidden_size); weight_xc [nd][G * H][size], bias_c
+        ([nd][4][H], RNN [nd][H]) and weight_hc [nd][G * H][H], each tagged, all U(-1, 1) / sqrt(H): the scaling at which a float32
+        recurrence stays next to the float64 one however long the sequence.  states_in: blob names of the initial hidden (and cell) state;
+        states_out: also write the final states as tops <name>_h (and <name>_c).  -> the sequence top, or the list of tops."""
+        gates, nd = {0: 4, 1: 3, 2: 1}[cell], 2 if direction == 2 else 1
+        k = 2 if cell == 0 else 1
+        if len(states_in) not in (0, k):
+            raise ValueError(f"layer {name}: {type_} takes {k} state bottoms or none")
+        params = {0: int(hidden), 1: nd * gates * int(hidden) * int(size), 2: int(direction)}
+        if cell == 0:
+            params[3] = int(hidden)
+        scale = 1.0 / np.sqrt(hidden)
+        wx = self._uniform(nd * gates * hidden * size, -1, 1, scale)
+        bias = self._uniform(nd * (1 if cell == 2 else 4) * hidden, -1, 1, scale)
+        wh = self._uniform(nd * gates * hidden * hidden, -1, 1, scale)
+        for a in (wx, bias, wh):
+            self._tagged(a)
+        bottoms = [bottom] + list(states_in)
+        tops = [name] + ([name + "_h", name + "_c"][:k] if states_out else [])
+        if self.trace is not None:
+            self._note("recurrent", name, bottoms if len(bottoms) > 1 else bottom, tops if len(tops) > 1 else name,
+                       dict(cell=cell, direction=int(direction), wx=wx.reshape(nd, gates * hidden, size), bias=bias.reshape(nd, -1, hidden), wh=wh.reshape(nd, gates * hidden, hidden)))
+        self.layer(type_, name, bottoms, tops, params)
+        return tops if len(tops) > 1 else name
+
+    def lstm(self, name, bottom, size, hidden, direction=0, states_in=(), states_out=False):
+        """ncnn's LSTM on a blob of rank 2 [T][size] -> [T][nd * hidden]; gate rows I, F, O, G."""
+        return self._recurrent("LSTM", 0, name, bottom, size, hidden, direction, states_in, states_out)
+
+    def gru(self, name, bottom, size, hidden, direction=0, states_in=(), states_out=False):
+        """ncnn's GRU; gate rows R, U, N, bias rows R, U, WN, BN."""
+        return self._recurrent("GRU", 1, name, bottom, size, hidden, direction, states_in, states_out)
+
+    def rnn(self, name, bottom, size, hidden, direction=0, states_in=(), states_out=False):
+        """ncnn's RNN (tanh)."""
+        return self._recurrent("RNN", 2, name, bottom, size, hidden, direction, states_in, states_out)
+
+    def pool_rect(self, name, bottom, kw, kh, sw, sh):
+        """A max Pooling with a rectangular kernel and stride, unpadded: ncnn's 1 / 11 and 2 / 12.  (A padded one is written as a zero Padding in
+        front of it where the bottom is not negative: the reference places a padded window at minus the SUM of both pads, and this runtime
+        with it.)"""
+        self._note("pool_rect", name, bottom, name, dict(kw=kw, kh=kh, sw=sw, sh=sh))
+        return self.layer("Pooling", name, [bottom], [name], {0: 0, 1: kw, 11: kh, 2: sw, 12: sh})
+
     def shuffle(self, name, bottom, group, reverse=False):
         """ncnn's ShuffleChannel: 0=group, 1=reverse (written only when set)."""
         return self.layer("ShuffleChannel", name, [bottom], [name], {0: group, 1: 1} if reverse else {0: group})
@@ -571,9 +617,10 @@ class GraphBuilder:
     def dropout(self, name, bottom, scale=None):
         return self.layer("Dropout", name, [bottom], [name], {} if scale is None else {0: f"{scale:.6f}"})
 
-    def softmax(self, name, bottom, axis=None):
-        """axis: ncnn's 0=axis with 1=fixbug0 (needs Net.SetDetection(True)); None writes no params, the plain layer."""
-        self._note("softmax", name, bottom, name, dict(axis=axis))
+    def softmax(self, name, bottom, axis=None, rank=None):
+        """axis: ncnn's 0=axis with 1=fixbug0 (needs Net.SetDetection(True)); None writes no params, the plain layer.  rank: the bottom's rank
+        where it is not 3, for numpy_forward."""
+        self._note("softmax", name, bottom, name, dict(axis=axis) if rank is None else dict(axis=axis, rank=rank))
         return self.layer("Softmax", name, [bottom], [name], None if axis is None else {0: int(axis), 1: 1})
 
     def conv_bn_relu(self, name, bottom, cin, cout, k, s=1, p=0, group=1, relu=True, dilation=1):
@@ -626,6 +673,18 @@ def _attn_ref():
     return attn_ref
 
 
+def _rnn_ref():
+    """tests/rnn_ref.py, the restatement of feather_rnn.h: numpy_forward's recurrent layers are that text, not a second one."""
+    try:
+        import rnn_ref
+    except ImportError:
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import rnn_ref
+    return rnn_ref
+
+
 def numpy_forward(trace, input_name, x=None):
     """A plain numpy forward (fp32 values, sums in float64) of the layers a GraphBuilder recorded in `trace` -- Convolution, InnerProduct,
     ReLU (plain or leaky), BatchNorm, Scale, Pooling, Split, Concat on channels, Reorg, nearest Interp by a whole scale, the RPN's softmax, a
@@ -652,8 +711,19 @@ def numpy_forward(trace, input_name, x=None):
             batch = next(iter(blobs.values())).shape[0]
             blobs[top] = np.broadcast_to(np.asarray(a["data"], np.float32).reshape((1,) + a["shape"]), (batch,) + a["shape"]).copy()
             continue
+        if kind == "recurrent":  # blobs of rank 2: [n][1][T][F]; the states [n][1][nd][H]
+            vs = [v] if isinstance(bottom, str) else v
+            got = _rnn_ref().layer(a["cell"], a["direction"], vs[0][:, 0], a["wx"], a["bias"], a["wh"], vs[1][:, 0] if len(vs) > 1 else None,
+                                   vs[2][:, 0] if len(vs) > 2 else None)
+            for t, y in zip([top] if isinstance(top, str) else top, got):
+                blobs[t] = y[:, None].astype(np.float32)
+            continue
         if kind == "concat" and "rank" in a:
             y = np.concatenate(v, axis=4 - a["rank"] + a["axis"])
+        elif kind == "softmax" and "rank" in a:
+            ax = 4 - a["rank"] + a["axis"]
+            e = np.exp(v.astype(np.float64) - v.max(axis=ax, keepdims=True))
+            y = e / e.sum(axis=ax, keepdims=True)
         elif kind == "reshape":
             ext = [a["w"], 1 if a["h"] is None else a["h"], 1 if a["c"] is None else a["c"]]
             ext = [v.shape[3 - i] if e == 0 else e for i, e in enumerate(ext)]
@@ -698,6 +768,9 @@ def numpy_forward(trace, input_name, x=None):
             y = _frame_ref().crop(v[0] if two else v, like=v[1] if two else None, **a)
         elif kind == "pixel_shuffle":
             y = _frame_ref().pixel_shuffle(v, a["r"], a["mode"])
+        elif kind == "pool_rect" and (v.shape[2] - a["kh"]) % a["sh"] == 0 and (v.shape[3] - a["kw"]) % a["sw"] == 0:
+            oh, ow = (v.shape[2] - a["kh"]) // a["sh"] + 1, (v.shape[3] - a["kw"]) // a["sw"] + 1
+            y = np.max([v[:, :, i:i + (oh - 1) * a["sh"] + 1:a["sh"], j:j + (ow - 1) * a["sw"] + 1:a["sw"]] for i in range(a["kh"]) for j in range(a["kw"])], axis=0)
         elif kind == "pool" and a["global_"] and a["avg"]:
             y = v.astype(np.float64).mean(axis=(2, 3), keepdims=True)
         elif kind == "reorg":
@@ -2049,6 +2122,96 @@ def vit_base_patch16_224(seed=1234, classes=1000, size=224, dry=False):
     x, tokens = _vit(g, size, 16, 768, 12, 12, 3072, classes, gain=0.5)
     g.fc("head", g.crop("cls", g.reshape("as_rank3", x, 768, tokens, 1), outh=1), 768, classes)
     return g.finish() + ("data", "head")
+
+
+def tiny_crnn(seed=73, size=(8, 24), dry=False, trace=None, classes=11):
+    """A small text recogniser with every recurrent layer (Net.SetRecurrent(), SetDetection(), SetTransformer() for the per-token InnerProduct):
+    an 8 x 24 image of three channels (a grey one arrives so through PIXEL_GRAY2RGB: a Convolution with ONE input channel is what the reference
+    takes for a depthwise layer, and this runtime with it), two 3x3 convolutions each with a 2x2 pooling and a 2x2 convolution that brings the height to 1, Reshape and Permute to
+    [T][32] tokens (T = width / 4 - 1), a bidirectional LSTM with H = 8 (a multiple of 4: the matrix kernel where the step route runs), a reverse
+    GRU with H = 6 (the direct kernel there) whose final hidden state is the blob gru_h, a forward RNN with H = 8, the per-token InnerProduct and
+    a Softmax along the class axis.  Up to FHIP_RNN_SEQUENCE_MAX_N images all three take the sequence route.  trace: a list that receives the
+    layers for numpy_forward."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    h, w = size
+    x = g.input("data", 3, h, w)
+    x = g.pool("pool1", g.relu("relu1", g.conv("conv1", x, 3, 8, 3, 1, 1)))
+    x = g.pool("pool2", g.relu("relu2", g.conv("conv2", x, 8, 16, 3, 1, 1)))
+    x = g.relu("relu3", g.conv("conv3", x, 16, 32, 2))
+    x = g.permute("to_tokens", g.reshape("flat", x, -1, 32), 1)
+    x = g.lstm("bilstm", x, 32, 8, direction=2)
+    x, _ = g.gru("gru", x, 16, 6, direction=1, states_out=True)
+    x = g.rnn("rnn", x, 6, 8)
+    x = g.fc_tokens("classes", x, 8, classes)
+    g.softmax("prob", x, axis=1, rank=2)
+    return g.finish() + ("data", "prob")
+
+
+def tiny_lstm_states(seed=79, size=5, hidden=4, steps=3, dry=False, trace=None):
+    """One forward LSTM fed its initial hidden and cell states through the Inputs `hidden` and `cell` ([1][1][hidden] each, per image) and
+    writing its final states as the tops l_h and l_c: a sequence net run in pieces.  The Input `data` is [1][steps][size], taken to rank 2 by
+    a Reshape.  Net.SetRecurrent(), SetDetection()."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    x = g.reshape("seq", g.input("data", 1, steps, size), size, steps)
+    g.input("hidden", 1, 1, hidden)
+    g.input("cell", 1, 1, hidden)
+    g.lstm("l", x, size, hidden, states_in=("hidden", "cell"), states_out=True)
+    return g.finish() + ("data", "l")
+
+
+def _crnn_conv(g, name, x, cin, cout, k=3, p=1, bn=False):
+    x = g.conv(name, x, cin, cout, k, 1, p)
+    if bn:
+        x = g.bn(name + "_bn", x, cout)
+    return g.relu(name + "_relu", x)
+
+
+def crnn_vgg_bilstm(seed=1234, classes=37, size=(32, 100), dry=False, trace=None):
+    """CRNN (Shi et al. 2015) as published but for its input: the grey 32 x 100 image arrives as three equal channels (PIXEL_GRAY2RGB), because a
+    Convolution with ONE input channel is what the reference takes for a depthwise layer, and this runtime with it: 1152 weights more than the
+    published 8.3 million.  Seven convolutions 64, 128, 256, 256, 512, 512, 512 (3x3 pad 1, the last
+    2x2 pad 0) with BatchNorm behind the third, fifth and seventh; max poolings 2x2 behind the first two and 2x2 stride (2, 1) pad (0, 1) behind
+    the fourth and sixth (each written as a zero Padding of one column on either side and an unpadded Pooling, the same numbers behind a ReLU),
+    which leave a [512][1][26] map; Reshape and Permute to 26 tokens; two BiLSTM(256), each with its linear layer (256,
+    then the 37 classes); Softmax along the class axis.  Random weights.  Net.SetRecurrent(), SetDetection(), SetTransformer(), SetFrame()."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace  # (numpy_forward has no rectangular Pooling: the trace serves the layers one by one)
+    h, w = size
+    x = g.input("data", 3, h, w)
+    x = g.pool("pool1", _crnn_conv(g, "conv1", x, 3, 64))
+    x = g.pool("pool2", _crnn_conv(g, "conv2", x, 64, 128))
+    x = _crnn_conv(g, "conv4", _crnn_conv(g, "conv3", x, 128, 256, bn=True), 256, 256)
+    x = g.pool_rect("pool3", g.padding("pad3", x, left=1, right=1), 2, 2, 1, 2)
+    x = _crnn_conv(g, "conv6", _crnn_conv(g, "conv5", x, 256, 512, bn=True), 512, 512)
+    x = g.pool_rect("pool4", g.padding("pad4", x, left=1, right=1), 2, 2, 1, 2)
+    x = _crnn_conv(g, "conv7", x, 512, 512, 2, 0, bn=True)
+    x = g.permute("to_tokens", g.reshape("flat", x, -1, 512), 1)
+    x = g.fc_tokens("embed1", g.lstm("bilstm1", x, 512, 256, direction=2), 512, 256)
+    x = g.fc_tokens("embed2", g.lstm("bilstm2", x, 256, 256, direction=2), 512, classes)
+    g.softmax("prob", x, axis=1, rank=2)
+    return g.finish() + ("data", "prob")
+
+
+def crnn_lite_lstm(seed=1234, classes=37, size=(32, 100), hidden=48, dry=False, trace=None):
+    """A mobile-sized recogniser in the manner of chineseocr-lite and PaddleOCR's mobile models: a 32 x 100 image of three channels, a 3x3 stride-2 convolution, three
+    depthwise-separable blocks (16 -> 32 -> 64 -> 96) with the poolings of CRNN, a 2x2 convolution that brings the height to 1, ONE BiLSTM with
+    H = 48 (or 96) and the per-token classifier.  Its Wh fits the chip's LDS, so a small batch takes the sequence route: one launch for the
+    whole recurrence.  Random weights.  Net.SetRecurrent(), SetDetection(), SetTransformer(), SetFrame()."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace  # (numpy_forward has no rectangular Pooling: the trace serves the layers one by one)
+    h, w = size
+    x = g.conv_bn_relu("conv1", g.input("data", 3, h, w), 3, 16, 3, 2, 1)
+    for i, (c, k) in enumerate(((16, 32), (32, 64), (64, 96)), 2):
+        x = g.conv_bn_relu(f"conv{i}_dw", x, c, c, 3, 1, 1, group=c)
+        x = g.conv_bn_relu(f"conv{i}_pw", x, c, k, 1, 1, 0)
+        x = g.pool(f"pool{i}", x) if i == 2 else g.pool_rect(f"pool{i}", g.padding(f"pad{i}", x, left=1, right=1), 2, 2, 1, 2)
+    x = g.conv_bn_relu("conv5", x, 96, 96, 2)
+    x = g.permute("to_tokens", g.reshape("flat", x, -1, 96), 1)
+    x = g.fc_tokens("classes", g.lstm("bilstm", x, 96, hidden, direction=2), 2 * hidden, classes)
+    g.softmax("prob", x, axis=1, rank=2)
+    return g.finish() + ("data", "prob")
 
 
 def espcn_x3(seed=1234, size=(180, 240), channels=1, dry=False):

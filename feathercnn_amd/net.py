@@ -41,6 +41,8 @@ FRAME_ROUTE = 112  # FHIP_FRAME_NET_ROUTE (feather_frame.h): Padding, Crop or Pi
 ROUTE_NAMES[FRAME_ROUTE] = "FRAME"
 ATTN_ROUTE = 113  # FHIP_ATTN_NET_ROUTE (feather_attn.h): MemoryData, LayerNorm, GELU, MultiHeadAttention or an element-wise BinaryOp, after SetTransformer() (libfeather_attn.so)
 ROUTE_NAMES[ATTN_ROUTE] = "ATTN"
+RNN_ROUTE = 114  # FHIP_RNN_NET_ROUTE (feather_rnn.h): LSTM, GRU or RNN, after SetRecurrent() (libfeather_rnn.so)
+ROUTE_NAMES[RNN_ROUTE] = "RNN"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -115,6 +117,11 @@ class Net:
         libfeather_attn.so) and run an InnerProduct on a [T][F] blob once per token, instead of refusing them at LoadParam.  Needs
         SetDetection() too (blob ranks).  Call before LoadParam."""
         _check(self._lib.fhip_net_set_transformer(self._h, int(bool(on))), "fhip_net_set_transformer")
+
+    def SetRecurrent(self, on: bool = True):
+        """feather::Net::SetRecurrent: accept ncnn's LSTM, GRU and RNN (routed to libfeather_rnn.so) instead of refusing them at LoadParam.
+        Needs SetDetection() too (blob ranks).  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_recurrent(self._h, int(bool(on))), "fhip_net_set_recurrent")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

@@ -34,7 +34,8 @@
 //     after SetDetection(true), its result through ExtractDetections; the YOLO heads after SetYolo(rows); Proposal, ROIPooling, ROIAlign
 //     and PSROIPooling (feather_roi.h) after SetRoi(true), the ROIs through ExtractProposals; Padding, Crop and PixelShuffle
 //     (feather_frame.h) after SetFrame(true); MemoryData, LayerNorm, GELU, MultiHeadAttention, the element-wise BinaryOp and the token-wise
-//     InnerProduct (feather_attn.h) after SetTransformer(true) and SetDetection(true).
+//     InnerProduct (feather_attn.h) after SetTransformer(true) and SetDetection(true); LSTM, GRU and RNN (feather_rnn.h) after
+//     SetRecurrent(true) and SetDetection(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -252,6 +253,9 @@ class Net
     // accept the layers of a Vision Transformer encoder -- MemoryData, LayerNorm, GELU, MultiHeadAttention, the element-wise BinaryOp
     // (libfeather_attn.so), an InnerProduct once per token -- instead of refusing them; needs SetDetection(true) too; before LoadParam (feather_net.h)
     int SetTransformer(bool on = true) { return fhip_net_set_transformer(net_, on ? 1 : 0); }
+    // accept ncnn's recurrent layers -- LSTM, GRU, RNN (libfeather_rnn.so) -- instead of refusing them; needs SetDetection(true) too; before
+    // LoadParam (feather_net.h)
+    int SetRecurrent(bool on = true) { return fhip_net_set_recurrent(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
     // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
     // blob has another shape.  scores_blob "" asks for none.

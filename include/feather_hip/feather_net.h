@@ -319,6 +319,20 @@ FHIP_API int fhip_net_set_frame(fhip_net* net, int on);
  * InnerProduct are what they were; on-then-off equals the default.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch
  * replicas. */
 FHIP_API int fhip_net_set_transformer(fhip_net* net, int on);
+/* 1: ncnn's recurrent layers are loaded -- LSTM (0=num_output 1=weight_data_size 2=direction 3=hidden_size), GRU and RNN (0=num_output
+ * 1=weight_data_size 2=direction); weights weight_xc [nd][G * H][size], bias_c ([nd][4][H] for LSTM and GRU, [nd][H] for RNN) and weight_hc
+ * [nd][G * H][H], each tagged, with nd = 2 for direction 2 and size = weight_data_size / nd / G / H -- as feather_rnn.h defines the
+ * recurrence; they run through libfeather_rnn.so and report the route FHIP_RNN_NET_ROUTE (feather_rnn.h).  Bottom 0 is a blob of rank 2
+ * [T][size]; the optional further bottoms are the initial hidden state [nd][H] (then the cell state, LSTM: 1 or 3 bottoms and tops; GRU and
+ * RNN: 1 or 2); top 0 is [T][nd * H] of rank 2, the optional further tops the final states.  The input projections of all steps and both
+ * directions are one GEMM of the main library into the net's arena; the recurrence reads them there.  Nothing fuses into these layers.
+ * Refused with -100 at LoadParam, naming the layer and the param: num_output < 1, a direction outside 0 .. 2, a weight_data_size that is no
+ * positive multiple of nd * G * H, an LSTM projection (3= other than num_output), 8= (int8) other than 0, other bottom or top counts, 2^31
+ * elements or more; at Reshape: a bottom of another rank or width, a state blob of another shape or batch.  The blobs of these layers have
+ * ranks, which fhip_net_set_detection maintains: without it LoadParam refuses the types with -200 and says so.  0 (default): LoadParam
+ * refuses the three types with -200; on-then-off equals the default.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to
+ * sub-batch replicas. */
+FHIP_API int fhip_net_set_recurrent(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
