@@ -114,6 +114,7 @@ SIGNATURES = {
     "fhip_net_set_frame": (_I, [_V, _I]),
     "fhip_net_set_transformer": (_I, [_V, _I]),
     "fhip_net_set_recurrent": (_I, [_V, _I]),
+    "fhip_net_set_conv1d": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -406,6 +407,17 @@ RNN_SIGNATURES = {
 }
 
 
+# include/feather_hip/feather_conv1d.h -- libfeather_conv1d.so, ncnn's Convolution1D, ConvolutionDepthWise1D and Pooling1D (a library of its own)
+CONV1D_SIGNATURES = {
+    "fhip_conv1d_output_dim": (_I, [_I, _I, _I, _I, _I, _I, _IP, _IP, _IP]),
+    "fhip_conv1d_forward": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _FL, _I, _I, _FL, _FL, _V, _I, _V, _V, _V, _I, _I, _V]),
+    "fhip_pool1d_output_dim": (_I, [_I, _I, _I, _I, _I, _I, _IP, _IP, _IP]),
+    "fhip_pool1d_forward": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _V, _I, _V, _I, _I, _V]),
+    "fhip_conv1d_route": (_I, [_I, _I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_conv1d_last_error": (ctypes.c_char_p, []),
+}
+
+
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
     lib = _LOADED.get(path)
@@ -503,6 +515,8 @@ LATER_LIBRARIES = {
     "attn": Library("libfeather_attn.so", ("feather_attn.h",), "FHIP_ATTN_API", ATTN_SIGNATURES, "fhip_attn_last_error", (), None),
     # route: RNN_ROUTE of net.py (FHIP_RNN_NET_ROUTE of its own header)
     "rnn": Library("libfeather_rnn.so", ("feather_rnn.h",), "FHIP_RNN_API", RNN_SIGNATURES, "fhip_rnn_last_error", (), None),
+    # route: CONV1D_ROUTE of net.py (FHIP_CONV1D_NET_ROUTE of its own header)
+    "conv1d": Library("libfeather_conv1d.so", ("feather_conv1d.h",), "FHIP_CONV1D_API", CONV1D_SIGNATURES, "fhip_conv1d_last_error", (), None),
 }
 _OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 

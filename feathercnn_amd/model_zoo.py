@@ -529,6 +529,43 @@ class GraphBuilder:
         """ncnn's RNN (tanh)."""
         return self._recurrent("RNN", 2, name, bottom, size, hidden, direction, states_in, states_out)
 
+    # -- the 1-D layers (a net that holds one of these needs Net.SetConv1d() and Net.SetDetection()) -------------------------------------
+    def conv1d(self, name, bottom, cin, cout, kw, s=1, d=1, pl=0, pr=None, pad_value=None, group=1, bias=True, act=0, act_params=(), gain=1.0):
+        """ncnn's Convolution1D (group 1) or ConvolutionDepthWise1D on a blob of rank 2 [cin][L] -> [cout][Lo]: weights [cout][cin / group][kw]
+        tagged, then the raw bias.  pl -233 / -234: SAME_UPPER / SAME_LOWER.  act: ncnn's activation_type 0 .. 6 with its activation_params."""
+        wsize = cout * (cin // group) * kw
+        params = {0: cout, 1: kw, 2: d, 3: s, 4: pl, 5: int(bias), 6: wsize}
+        if group > 1:
+            params[7] = group
+        if act:
+            params[9] = act
+            if act_params:
+                params[-23310] = ",".join([str(len(act_params))] + ["%r" % float(v) for v in act_params])
+        if pr is not None:
+            params[15] = pr
+        if pad_value is not None:
+            params[18] = "%r" % float(pad_value)
+        top = self.layer("ConvolutionDepthWise1D" if group > 1 else "Convolution1D", name, [bottom], [name], params)
+        w = self._uniform(wsize, -1, 1, np.sqrt(6.0 / (cin // group * kw)) * gain)
+        b = self._uniform(cout, -0.1, 0.1) if bias else None
+        self._weights(name, w, cout, b)
+        if self.trace is not None:
+            a0, a1 = (tuple(act_params) + (0.0, 0.0))[:2]
+            self._note("conv1d", name, bottom, top, dict(w=w.reshape(cout, cin // group, kw), bias=b, s=s, d=d, pl=pl, pr=pr, pad_value=pad_value or 0.0, group=group, act=act,
+                                                         a0=a0, a1=a1))
+        return top
+
+    def pool1d(self, name, bottom, kw=0, s=1, pl=0, pr=None, pad_mode=0, avg=False, include_pad=False, global_=False, out_w=None):
+        """ncnn's Pooling1D on a blob of rank 2; global_: a blob of rank 1 [C]; out_w: adaptive."""
+        params = {0: int(avg), 1: kw, 2: s, 3: pl, 4: int(global_), 5: pad_mode, 6: int(include_pad)}
+        if pr is not None:
+            params[14] = pr
+        if out_w is not None:
+            params.update({7: 1, 8: out_w})
+        top = self.layer("Pooling1D", name, [bottom], [name], params)
+        self._note("pool1d", name, bottom, top, dict(kw=kw, s=s, pl=pl, pr=pr, pad_mode=pad_mode, avg=avg, include_pad=include_pad, global_=global_, out_w=out_w))
+        return top
+
     def pool_rect(self, name, bottom, kw, kh, sw, sh):
         """A max Pooling with a rectangular kernel and stride, unpadded: ncnn's 1 / 11 and 2 / 12.  (A padded one is written as a zero Padding in
         front of it where the bottom is not negative: the reference places a padded window at minus the SUM of both pads, and this runtime
@@ -685,6 +722,18 @@ def _rnn_ref():
     return rnn_ref
 
 
+def _conv1d_ref():
+    """tests/conv1d_ref.py, the restatement of feather_conv1d.h: numpy_forward's 1-D layers are that text, not a second one."""
+    try:
+        import conv1d_ref
+    except ImportError:
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import conv1d_ref
+    return conv1d_ref
+
+
 def numpy_forward(trace, input_name, x=None):
     """A plain numpy forward (fp32 values, sums in float64) of the layers a GraphBuilder recorded in `trace` -- Convolution, InnerProduct,
     ReLU (plain or leaky), BatchNorm, Scale, Pooling, Split, Concat on channels, Reorg, nearest Interp by a whole scale, the RPN's softmax, a
@@ -740,6 +789,11 @@ def numpy_forward(trace, input_name, x=None):
         elif kind == "mha":
             q, k, w_ = (v, v, v) if isinstance(bottom, str) else (v[0], v[1], v[-1])
             y = _attn_ref().multi_head_attention(q[:, 0], k[:, 0], w_[:, 0], a["heads"], a["weights"], a["scale"])[:, None]
+        elif kind == "conv1d":  # blobs of rank 2: [n][1][C][L]
+            y = _conv1d_ref().conv1d(v[:, 0].astype(np.float64), **a)[:, None]
+        elif kind == "pool1d":  # global pooling: rank 1, [n][1][1][C]
+            y = _conv1d_ref().pool1d(v[:, 0], **a)
+            y = y[:, None, None, :, 0] if a["global_"] else y[:, None]
         elif kind == "fc_tokens":
             y = v.astype(np.float64) @ a["w"].astype(np.float64).T
             if a["b"] is not None:
@@ -2159,6 +2213,50 @@ def tiny_lstm_states(seed=79, size=5, hidden=4, steps=3, dry=False, trace=None):
     g.input("cell", 1, 1, hidden)
     g.lstm("l", x, size, hidden, states_in=("hidden", "cell"), states_out=True)
     return g.finish() + ("data", "l")
+
+
+def tiny_tcn(seed=83, size=(5, 40), dry=False, trace=None, classes=7):
+    """A small temporal convolution net that feeds the recurrent layers (Net.SetConv1d(), SetRecurrent(), SetDetection(), SetTransformer() for
+    the per-token InnerProduct): an Input [1][5][L] taken as a 1-D blob of five channels, a Convolution1D with stride 2 and ReLU, a dilated
+    one with SAME_UPPER padding and a leaky ReLU, a depthwise one with 31 taps and SAME_LOWER padding, a pointwise one with hard-swish, a max
+    Pooling1D, Permute to [T][12] tokens, a GRU and the per-token InnerProduct.  trace: a list that receives the layers for numpy_forward."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    c, l = size
+    x = g.input("data", 1, c, l)
+    x = g.conv1d("c1", x, c, 8, 3, s=2, pl=1, act=1)
+    x = g.conv1d("c2", x, 8, 8, 3, d=2, pl=-233, act=2, act_params=(0.1,))
+    x = g.conv1d("dw", x, 8, 8, 31, pl=-234, group=8)
+    x = g.conv1d("pw", x, 8, 12, 1, act=6, act_params=(1.0 / 6, 0.5))
+    x = g.pool1d("pool", x, 2, 2)
+    x = g.permute("to_tokens", x, 1)
+    x = g.gru("gru", x, 12, 6)
+    g.fc_tokens("classes", x, 6, classes)
+    return g.finish() + ("data", "classes")
+
+
+# (channels out, taps, stride, dilation, repeats) of the depthwise-separable blocks of QuartzNet-5x5: C1, B1 .. B5, C2; then C3 and C4 pointwise
+QUARTZNET_5X5 = ((256, 33, 2, 1, 1), (256, 33, 1, 1, 5), (256, 39, 1, 1, 5), (512, 51, 1, 1, 5), (512, 63, 1, 1, 5), (512, 75, 1, 1, 5), (512, 87, 1, 2, 1))
+
+
+def quartznet_5x5(seed=1234, classes=29, size=(64, 512), dry=False, trace=None):
+    """A QuartzNet-5x5-style acoustic model on [64 mel bands][L frames] (Net.SetConv1d(), SetDetection()): time-channel separable blocks -- a
+    ConvolutionDepthWise1D of 33 .. 87 taps with SAME padding, then a pointwise Convolution1D with the BatchNorm folded into its weights and
+    bias and ReLU as activation type 1 --, 256 -> 512 channels, a pointwise layer to 1024 and one to the classes, [classes][L / 2].  The
+    residual connections of the published net are left out: they need an element-wise add on blobs of rank 2, which is another switch."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    c, l = size
+    x = g.input("data", 1, c, l)
+    tag = 0
+    for cout, kw, s, d, repeats in QUARTZNET_5X5:
+        for _ in range(repeats):
+            x = g.conv1d("dw%d" % tag, x, c, c, kw, s=s, d=d, pl=-233, group=c, bias=False)
+            x = g.conv1d("pw%d" % tag, x, c, cout, 1, act=1)
+            c, tag = cout, tag + 1
+    x = g.conv1d("c3", x, c, 1024, 1, act=1)
+    g.conv1d("c4", x, 1024, classes, 1)
+    return g.finish() + ("data", "c4")
 
 
 def _crnn_conv(g, name, x, cin, cout, k=3, p=1, bn=False):

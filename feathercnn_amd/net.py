@@ -43,6 +43,8 @@ ATTN_ROUTE = 113  # FHIP_ATTN_NET_ROUTE (feather_attn.h): MemoryData, LayerNorm,
 ROUTE_NAMES[ATTN_ROUTE] = "ATTN"
 RNN_ROUTE = 114  # FHIP_RNN_NET_ROUTE (feather_rnn.h): LSTM, GRU or RNN, after SetRecurrent() (libfeather_rnn.so)
 ROUTE_NAMES[RNN_ROUTE] = "RNN"
+CONV1D_ROUTE = 115  # FHIP_CONV1D_NET_ROUTE (feather_conv1d.h): Convolution1D, ConvolutionDepthWise1D or Pooling1D, after SetConv1d() (libfeather_conv1d.so)
+ROUTE_NAMES[CONV1D_ROUTE] = "CONV1D"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -122,6 +124,11 @@ class Net:
         """feather::Net::SetRecurrent: accept ncnn's LSTM, GRU and RNN (routed to libfeather_rnn.so) instead of refusing them at LoadParam.
         Needs SetDetection() too (blob ranks).  Call before LoadParam."""
         _check(self._lib.fhip_net_set_recurrent(self._h, int(bool(on))), "fhip_net_set_recurrent")
+
+    def SetConv1d(self, on: bool = True):
+        """feather::Net::SetConv1d: accept ncnn's Convolution1D, ConvolutionDepthWise1D and Pooling1D (routed to libfeather_conv1d.so) instead of
+        refusing them at LoadParam.  Needs SetDetection() too (blob ranks).  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_conv1d(self._h, int(bool(on))), "fhip_net_set_conv1d")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

@@ -35,7 +35,8 @@
 //     and PSROIPooling (feather_roi.h) after SetRoi(true), the ROIs through ExtractProposals; Padding, Crop and PixelShuffle
 //     (feather_frame.h) after SetFrame(true); MemoryData, LayerNorm, GELU, MultiHeadAttention, the element-wise BinaryOp and the token-wise
 //     InnerProduct (feather_attn.h) after SetTransformer(true) and SetDetection(true); LSTM, GRU and RNN (feather_rnn.h) after
-//     SetRecurrent(true) and SetDetection(true).
+//     SetRecurrent(true) and SetDetection(true); Convolution1D, ConvolutionDepthWise1D and Pooling1D (feather_conv1d.h) after
+//     SetConv1d(true) and SetDetection(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -256,6 +257,9 @@ class Net
     // accept ncnn's recurrent layers -- LSTM, GRU, RNN (libfeather_rnn.so) -- instead of refusing them; needs SetDetection(true) too; before
     // LoadParam (feather_net.h)
     int SetRecurrent(bool on = true) { return fhip_net_set_recurrent(net_, on ? 1 : 0); }
+    // accept ncnn's 1-D layers -- Convolution1D, ConvolutionDepthWise1D, Pooling1D (libfeather_conv1d.so) -- instead of refusing them; needs
+    // SetDetection(true) too; before LoadParam (feather_net.h)
+    int SetConv1d(bool on = true) { return fhip_net_set_conv1d(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
     // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
     // blob has another shape.  scores_blob "" asks for none.

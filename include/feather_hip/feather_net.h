@@ -333,6 +333,19 @@ FHIP_API int fhip_net_set_transformer(fhip_net* net, int on);
  * refuses the three types with -200; on-then-off equals the default.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to
  * sub-batch replicas. */
 FHIP_API int fhip_net_set_recurrent(fhip_net* net, int on);
+/* 1: ncnn's 1-D layers are loaded -- Convolution1D (0=num_output 1=kernel_w 2=dilation_w 3=stride_w 4=pad_left 15=pad_right 18=pad_value
+ * 5=bias_term 6=weight_data_size 9=activation_type 10=activation_params), ConvolutionDepthWise1D (the same and 7=group; weights tagged
+ * [num_output][C / group][kernel_w], then the raw bias) and Pooling1D (0=pooling_type 1=kernel_w 2=stride_w 3=pad_left 14=pad_right
+ * 4=global_pooling 5=pad_mode 6=avgpool_count_include_pad 7=adaptive_pooling 8=out_w) -- as feather_conv1d.h defines them; they run through
+ * libfeather_conv1d.so and report the route FHIP_CONV1D_NET_ROUTE (feather_conv1d.h).  The bottom is a blob of rank 2 [C][L] (or the
+ * rank-3 [1][C][L] an Input yields), the top [num_output][Lo] of rank 2; global pooling gives a blob of rank 1 [C].  Nothing fuses into
+ * these layers.  Refused with -100 at LoadParam, naming the layer and the param: dynamic_weight (19=), int8 (8=), num_output, kernel_w,
+ * stride or dilation < 1, a negative pad other than -233 / -234, a weight_data_size that is no num_output / group * C * kernel_w, a group
+ * that does not divide, an activation or pooling type or a pad_mode out of range, 2^31 elements or more; at Reshape: a bottom of another
+ * rank or channel count, Lo < 1.  The blobs of these layers have ranks, which fhip_net_set_detection maintains: without it LoadParam
+ * refuses the types with -200 and says so.  0 (default): LoadParam refuses the three types with -200; on-then-off equals the default.
+ * Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_conv1d(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
