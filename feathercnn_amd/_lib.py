@@ -115,6 +115,7 @@ SIGNATURES = {
     "fhip_net_set_transformer": (_I, [_V, _I]),
     "fhip_net_set_recurrent": (_I, [_V, _I]),
     "fhip_net_set_conv1d": (_I, [_V, _I]),
+    "fhip_net_set_deformable": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -417,6 +418,16 @@ CONV1D_SIGNATURES = {
     "fhip_conv1d_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_dcn.h -- libfeather_dcn.so, deformable convolution (ncnn's DeformableConv2D; a library of its own)
+DCN_SIGNATURES = {
+    "fhip_dcn_output_dim": (_I, [_I] * 12 + [_IP, _IP]),
+    "fhip_dcn_packed_floats": (ctypes.c_longlong, [_I, _I, _I, _I, _I]),
+    "fhip_dcn_pack_weights": (_I, [_I, _I, _I, _I, _I, _V, _V, _V]),
+    "fhip_dcn_forward": (_I, [_I] * 17 + [_FL, _FL, _V, _V, _V, _V, _V, _V, _I, _I, _V]),
+    "fhip_dcn_route": (_I, [_I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_dcn_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -517,6 +528,8 @@ LATER_LIBRARIES = {
     "rnn": Library("libfeather_rnn.so", ("feather_rnn.h",), "FHIP_RNN_API", RNN_SIGNATURES, "fhip_rnn_last_error", (), None),
     # route: CONV1D_ROUTE of net.py (FHIP_CONV1D_NET_ROUTE of its own header)
     "conv1d": Library("libfeather_conv1d.so", ("feather_conv1d.h",), "FHIP_CONV1D_API", CONV1D_SIGNATURES, "fhip_conv1d_last_error", (), None),
+    # route: DCN_ROUTE of net.py (FHIP_DCN_NET_ROUTE of its own header)
+    "dcn": Library("libfeather_dcn.so", ("feather_dcn.h",), "FHIP_DCN_API", DCN_SIGNATURES, "fhip_dcn_last_error", (), None),
 }
 _OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 

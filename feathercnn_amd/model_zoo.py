@@ -184,6 +184,7 @@ class GraphBuilder:
         return self.layer("TanH", name, [bottom], [name])
 
     def sigmoid(self, name, bottom):
+        self._note("sigmoid", name, bottom, name, {})
         return self.layer("Sigmoid", name, [bottom], [name])
 
     def clip(self, name, bottom, lo, hi):
@@ -566,6 +567,29 @@ class GraphBuilder:
         self._note("pool1d", name, bottom, top, dict(kw=kw, s=s, pl=pl, pr=pr, pad_mode=pad_mode, avg=avg, include_pad=include_pad, global_=global_, out_w=out_w))
         return top
 
+    # -- deformable convolution (a net that holds one needs Net.SetDeformable()) -------------------------------------------------------------
+    def deform_conv(self, name, bottom, offset, mask, cin, cout, k, s=1, d=1, p=0, bias=True, act=0, act_params=(), gain=1.0):
+        """ncnn's DeformableConv2D on `bottom` with the blobs `offset` [2 kh kw][Ho][Wo] and `mask` [kh kw][Ho][Wo] (None: DCN v1): weights
+        [cout][cin][kh][kw] tagged, then the raw bias.  k, s, d: an int or (vertical, horizontal); p: an int or (top, bottom, left, right)."""
+        (kh, kw), (sh, sw), (dh, dw) = ((v, v) if isinstance(v, int) else tuple(v) for v in (k, s, d))
+        pt, pb, pl, pr = (p,) * 4 if isinstance(p, int) else p
+        wsize = cout * cin * kh * kw
+        params = {0: cout, 1: kw, 11: kh, 2: dw, 12: dh, 3: sw, 13: sh, 4: pl, 15: pr, 14: pt, 16: pb, 5: int(bias), 6: wsize}
+        if act:
+            params[9] = act
+            if act_params:
+                params[-23310] = ",".join([str(len(act_params))] + ["%r" % float(v) for v in act_params])
+        bottoms = [bottom, offset] + ([] if mask is None else [mask])
+        top = self.layer("DeformableConv2D", name, bottoms, [name], params)
+        w = self._uniform(wsize, -1, 1, np.sqrt(6.0 / (cin * kh * kw)) * gain)
+        b = self._uniform(cout, -0.1, 0.1) if bias else None
+        self._weights(name, w, cout, b)
+        if self.trace is not None:
+            a0, a1 = (tuple(act_params) + (0.0, 0.0))[:2]
+            self._note("deform_conv", name, bottoms, top, dict(w=w.reshape(cout, cin, kh, kw), bias=b, stride=(sh, sw), dilation=(dh, dw), pads=(pt, pb, pl, pr), act=act, a0=a0,
+                                                             a1=a1))
+        return top
+
     def pool_rect(self, name, bottom, kw, kh, sw, sh):
         """A max Pooling with a rectangular kernel and stride, unpadded: ncnn's 1 / 11 and 2 / 12.  (A padded one is written as a zero Padding in
         front of it where the bottom is not negative: the reference places a padded window at minus the SUM of both pads, and this runtime
@@ -580,6 +604,7 @@ class GraphBuilder:
     def slice(self, name, bottom, sizes):
         """ncnn's Slice along the channels: -23300=count,sizes (an entry of -233: an equal share of what is left), 1=axis 0."""
         tops = [f"{name}_{i}" for i in range(len(sizes))]
+        self._note("slice", name, bottom, tops, dict(sizes=list(sizes)))
         self.layer("Slice", name, [bottom], tops, {-23300: ",".join(map(str, [len(sizes)] + list(sizes))), 1: 0})
         return tops
 
@@ -734,6 +759,18 @@ def _conv1d_ref():
     return conv1d_ref
 
 
+def _dcn_ref():
+    """tests/dcn_ref.py, the restatement of feather_dcn.h: numpy_forward's DeformableConv2D is that text, not a second one."""
+    try:
+        import dcn_ref
+    except ImportError:
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import dcn_ref
+    return dcn_ref
+
+
 def numpy_forward(trace, input_name, x=None):
     """A plain numpy forward (fp32 values, sums in float64) of the layers a GraphBuilder recorded in `trace` -- Convolution, InnerProduct,
     ReLU (plain or leaky), BatchNorm, Scale, Pooling, Split, Concat on channels, Reorg, nearest Interp by a whole scale, the RPN's softmax, a
@@ -747,6 +784,11 @@ def numpy_forward(trace, input_name, x=None):
         if kind == "split":
             for t in top:
                 blobs[t] = v
+            continue
+        if kind == "slice":  # along the channels, explicit sizes
+            at = np.cumsum([0] + a["sizes"])
+            for t, lo, hi in zip(top, at[:-1], at[1:]):
+                blobs[t] = v[:, lo:hi]
             continue
         if kind == "proposal":
             ref = _roi_ref()
@@ -789,6 +831,10 @@ def numpy_forward(trace, input_name, x=None):
         elif kind == "mha":
             q, k, w_ = (v, v, v) if isinstance(bottom, str) else (v[0], v[1], v[-1])
             y = _attn_ref().multi_head_attention(q[:, 0], k[:, 0], w_[:, 0], a["heads"], a["weights"], a["scale"])[:, None]
+        elif kind == "sigmoid":
+            y = 1 / (1 + np.exp(-v.astype(np.float64)))
+        elif kind == "deform_conv":
+            y = _dcn_ref().deform_conv2d(v[0], v[1], v[2] if len(v) > 2 else None, **a)
         elif kind == "conv1d":  # blobs of rank 2: [n][1][C][L]
             y = _conv1d_ref().conv1d(v[:, 0].astype(np.float64), **a)[:, None]
         elif kind == "pool1d":  # global pooling: rank 1, [n][1][1][C]
@@ -2257,6 +2303,57 @@ def quartznet_5x5(seed=1234, classes=29, size=(64, 512), dry=False, trace=None):
     x = g.conv1d("c3", x, c, 1024, 1, act=1)
     g.conv1d("c4", x, 1024, classes, 1)
     return g.finish() + ("data", "c4")
+
+
+def tiny_dcn(seed=97, size=(10, 12), dry=False, trace=None, classes=5):
+    """A small net around a modulated deformable convolution (Net.SetDeformable()): a 3x3 convolution with ReLU, a 27-channel 3x3 convolution
+    whose output a Slice cuts into the 18 offsets and the 9 masks, a Sigmoid on the mask, the DeformableConv2D 8 -> 12, ReLU, a 2x2 max
+    pooling, a global average pooling and an InnerProduct -- no layer depends on the input size, so one weight file serves every size.
+    trace: a list that receives the layers for numpy_forward."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    h, w = size
+    x = g.relu("c1_relu", g.conv("c1", g.input("data", 3, h, w), 3, 8, 3, 1, 1))
+    feat, side = g.split("c1_split", x)
+    offset, mask = g.slice("om_slice", g.conv("om", side, 8, 27, 3, 1, 1, gain=2.0), (18, 9))
+    x = g.deform_conv("dcn", feat, offset, g.sigmoid("mask", mask), 8, 12, 3, p=1)
+    x = g.pool("pool", g.relu("dcn_relu", x), 2, 2)
+    x = g.pool("gap", x, avg=True, global_=True)
+    g.fc("fc", x, 12, classes)
+    return g.finish() + ("data", "fc")
+
+
+def centernet_resdcn18(seed=1234, classes=80, size=512, dry=False):
+    """CenterNet with the ResNet-18 DCN backbone (Net.SetDeformable()): ResNet-18 to stride 32, three up-sampling stages -- a 3x3 convolution to
+    the 27 offset and mask channels, Slice, Sigmoid, DeformableConv2D 3x3, BatchNorm, ReLU, Deconvolution 4x4 at stride 2, BatchNorm, ReLU -- over
+    256, 128 and 64 channels, and the three heads (heat map, size, offset: 3x3 to 64 channels, ReLU, 1x1) on the stride-4 map."""
+    g = GraphBuilder(seed, dry)
+    x = g.conv_bn_relu("conv1", g.input("data", 3, size, size), 3, 64, 7, 2, 3)
+    x = g.pool("pool1", x, 3, 2)
+    cin = 64
+    for si, (out, stride) in enumerate([(64, 1), (128, 2), (256, 2), (512, 2)]):
+        for b in range(2):
+            s = stride if b == 0 else 1
+            tag = f"res{si + 2}{chr(ord('a') + b)}"
+            main, short = g.split(tag + "_split", x)
+            if cin != out or s != 1:
+                short = g.conv_bn_relu(tag + "_branch1", short, cin, out, 1, s, 0, relu=False)
+            y = g.conv_bn_relu(tag + "_branch2a", main, cin, out, 3, s, 1)
+            y = g.conv_bn_relu(tag + "_branch2b", y, out, out, 3, 1, 1, relu=False)
+            x = g.relu(tag + "_relu", g.eltwise(tag, short, y))
+            cin = out
+    for i, out in enumerate((256, 128, 64)):
+        tag = f"up{i + 1}"
+        feat, side = g.split(tag + "_split", x)
+        offset, mask = g.slice(tag + "_om_slice", g.conv(tag + "_om", side, cin, 27, 3, 1, 1, gain=0.5), (18, 9))
+        x = g.deform_conv(tag + "_dcn", feat, offset, g.sigmoid(tag + "_mask", mask), cin, out, 3, p=1)
+        x = g.relu(tag + "_dcn_relu", g.scale(tag + "_dcn_scale", g.bn(tag + "_dcn_bn", x, out), out))
+        x = g.deconv_bn_relu(tag + "_deconv", x, out, out, 4, 2, 1)
+        cin = out
+    tops = g.split("heads_split", x, 3)
+    for top, (name, cout) in zip(tops, (("hm", classes), ("wh", 2), ("reg", 2))):
+        g.conv(name, g.relu(name + "_relu", g.conv(name + "_conv", top, 64, 64, 3, 1, 1)), 64, cout, 1)
+    return g.finish() + ("data", "hm")
 
 
 def _crnn_conv(g, name, x, cin, cout, k=3, p=1, bn=False):

@@ -45,6 +45,8 @@ RNN_ROUTE = 114  # FHIP_RNN_NET_ROUTE (feather_rnn.h): LSTM, GRU or RNN, after S
 ROUTE_NAMES[RNN_ROUTE] = "RNN"
 CONV1D_ROUTE = 115  # FHIP_CONV1D_NET_ROUTE (feather_conv1d.h): Convolution1D, ConvolutionDepthWise1D or Pooling1D, after SetConv1d() (libfeather_conv1d.so)
 ROUTE_NAMES[CONV1D_ROUTE] = "CONV1D"
+DCN_ROUTE = 116  # FHIP_DCN_NET_ROUTE (feather_dcn.h): DeformableConv2D, after SetDeformable() (libfeather_dcn.so)
+ROUTE_NAMES[DCN_ROUTE] = "DCN"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -129,6 +131,11 @@ class Net:
         """feather::Net::SetConv1d: accept ncnn's Convolution1D, ConvolutionDepthWise1D and Pooling1D (routed to libfeather_conv1d.so) instead of
         refusing them at LoadParam.  Needs SetDetection() too (blob ranks).  Call before LoadParam."""
         _check(self._lib.fhip_net_set_conv1d(self._h, int(bool(on))), "fhip_net_set_conv1d")
+
+    def SetDeformable(self, on: bool = True):
+        """feather::Net::SetDeformable: accept ncnn's DeformableConv2D, DCN v1 and v2 (routed to libfeather_dcn.so), instead of refusing it at
+        LoadParam.  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_deformable(self._h, int(bool(on))), "fhip_net_set_deformable")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

@@ -36,7 +36,7 @@
 //     (feather_frame.h) after SetFrame(true); MemoryData, LayerNorm, GELU, MultiHeadAttention, the element-wise BinaryOp and the token-wise
 //     InnerProduct (feather_attn.h) after SetTransformer(true) and SetDetection(true); LSTM, GRU and RNN (feather_rnn.h) after
 //     SetRecurrent(true) and SetDetection(true); Convolution1D, ConvolutionDepthWise1D and Pooling1D (feather_conv1d.h) after
-//     SetConv1d(true) and SetDetection(true).
+//     SetConv1d(true) and SetDetection(true); DeformableConv2D (feather_dcn.h) after SetDeformable(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -260,6 +260,8 @@ class Net
     // accept ncnn's 1-D layers -- Convolution1D, ConvolutionDepthWise1D, Pooling1D (libfeather_conv1d.so) -- instead of refusing them; needs
     // SetDetection(true) too; before LoadParam (feather_net.h)
     int SetConv1d(bool on = true) { return fhip_net_set_conv1d(net_, on ? 1 : 0); }
+    // accept ncnn's DeformableConv2D, DCN v1 and v2 (libfeather_dcn.so), instead of refusing it; before LoadParam (feather_net.h)
+    int SetDeformable(bool on = true) { return fhip_net_set_deformable(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
     // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
     // blob has another shape.  scores_blob "" asks for none.

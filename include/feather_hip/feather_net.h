@@ -346,6 +346,17 @@ FHIP_API int fhip_net_set_recurrent(fhip_net* net, int on);
  * refuses the types with -200 and says so.  0 (default): LoadParam refuses the three types with -200; on-then-off equals the default.
  * Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
 FHIP_API int fhip_net_set_conv1d(fhip_net* net, int on);
+/* 1: ncnn's DeformableConv2D is loaded (0=num_output 1=kernel_w 11=kernel_h 2=dilation_w 12=dilation_h 3=stride_w 13=stride_h 4=pad_left
+ * 15=pad_right 14=pad_top 16=pad_bottom 5=bias_term 6=weight_data_size 9=activation_type 10=activation_params; weights tagged
+ * [num_output][C][kernel_h][kernel_w], then the raw bias) as feather_dcn.h defines it: two or three bottoms -- x, the offsets
+ * [2 * kh * kw][Ho][Wo] and an optional mask [kh * kw][Ho][Wo] (DCN v2) --, one offset group.  It runs through libfeather_dcn.so and
+ * reports the route FHIP_DCN_NET_ROUTE (feather_dcn.h).  Nothing fuses into or out of the layer.  Refused with -100 at LoadParam, naming
+ * the layer and the param: a group (7=), int8 (8=), dynamic_weight (19=), num_output, a kernel extent, stride or dilation < 1, a negative
+ * pad, a weight_data_size that is no num_output * C * kernel_h * kernel_w, an activation type out of range, 2^31 elements or more, other
+ * bottom counts; at Reshape, naming the blob: an offset or mask blob of another shape, an x of other channels than the weights', Ho or
+ * Wo < 1.  0 (default): LoadParam refuses the type with -200; on-then-off equals the default.  Call before LoadParam; later it is
+ * FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_deformable(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
