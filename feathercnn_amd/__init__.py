@@ -38,6 +38,9 @@ from .conv1d import conv1d_output_dim, conv1d_route, pool1d_output_dim
 from .conv1d import NET_ROUTE as CONV1D_NET_ROUTE
 from .dcn import deform_conv2d, dcn_output_dim, dcn_pack, dcn_route
 from .dcn import NET_ROUTE as DCN_NET_ROUTE
+from .conv3d import conv3d as convolution3d, pool3d as pooling3d  # (feathercnn_amd.conv3d stays the module)
+from .conv3d import conv3d_output_dim, conv3d_route, pool3d_output_dim
+from .conv3d import NET_ROUTE as CONV3D_NET_ROUTE
 from .pixels import (PIXEL_BGR, PIXEL_BGR2GRAY, PIXEL_BGR2RGB, PIXEL_GRAY, PIXEL_GRAY2BGR, PIXEL_GRAY2RGB, PIXEL_RGB, PIXEL_RGB2BGR,
                      PIXEL_RGB2GRAY, PIXEL_RGBA, PIXEL_RGBA2BGR, PIXEL_RGBA2GRAY, PIXEL_RGBA2RGB, float_to_pixels, pixels_images_to_float,
                      pixels_to_float, yuv420sp_to_float)

@@ -116,6 +116,7 @@ SIGNATURES = {
     "fhip_net_set_recurrent": (_I, [_V, _I]),
     "fhip_net_set_conv1d": (_I, [_V, _I]),
     "fhip_net_set_deformable": (_I, [_V, _I]),
+    "fhip_net_set_conv3d": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -124,11 +125,13 @@ SIGNATURES = {
     "fhip_net_load_weights_mem": (_I, [_V, _V, _SZ]),
     "fhip_net_load_weights_device": (_I, [_V, _V, _SZ]),
     "fhip_net_feed_input": (_I, [_V, ctypes.c_char_p, _I, _I, _I, _I, _V, _I]),
+    "fhip_net_feed_volume": (_I, [_V, ctypes.c_char_p, _I, _I, _I, _I, _I, _V, _I]),
     "fhip_net_feed_pixels": (_I, [_V, ctypes.c_char_p, _I, _V, _I, _I, _I, _I, _I, _V, _V, _I]),
     "fhip_net_feed_yuv420sp": (_I, [_V, ctypes.c_char_p, _I, _V, _I, _I, _I, _I, _I, _I, _V, _V, _I]),
     "fhip_net_feed_pixel_images": (_I, [_V, ctypes.c_char_p, _I, _V, _I, _I, _I, _V, _V, _I]),
     "fhip_net_forward": (_I, [_V]),
     "fhip_net_extract": (_I, [_V, ctypes.c_char_p, ctypes.POINTER(_V), _PI, _PI, _PI, _PI]),
+    "fhip_net_extract_volume": (_I, [_V, ctypes.c_char_p, ctypes.POINTER(_V), _PI, _PI, _PI, _PI, _PI]),
     "fhip_net_extract_host": (_I, [_V, ctypes.c_char_p, _V, _SZ]),
     "fhip_net_layer_count": (_I, [_V]),
     "fhip_net_layer_info": (_I, [_V, _I, ctypes.c_char_p, ctypes.c_char_p, _I, _PI]),
@@ -428,6 +431,18 @@ DCN_SIGNATURES = {
     "fhip_dcn_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_conv3d.h -- libfeather_conv3d.so, ncnn's Convolution3D, ConvolutionDepthWise3D and Pooling3D (a library of its own)
+CONV3D_SIGNATURES = {
+    "fhip_conv3d_output_dim": (_I, [_I] * 6 + [_IP] * 3),
+    "fhip_conv3d_packed_floats": (ctypes.c_longlong, [_I] * 10),
+    "fhip_conv3d_pack_weights": (_I, [_I] * 5 + [_V, _V, _V]),
+    "fhip_conv3d_forward": (_I, [_I] * 21 + [_FL, _I, _I, _FL, _FL, _V, _V, _V, _V, _V, _I, _I, _I, _V]),
+    "fhip_pool3d_output_dim": (_I, [_I] * 6 + [_IP] * 3),
+    "fhip_pool3d_forward": (_I, [_I] * 18 + [_V, _V, _I, _I, _I, _V]),
+    "fhip_conv3d_route": (_I, [_I] * 11 + [ctypes.c_char_p, _I]),
+    "fhip_conv3d_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -530,6 +545,8 @@ LATER_LIBRARIES = {
     "conv1d": Library("libfeather_conv1d.so", ("feather_conv1d.h",), "FHIP_CONV1D_API", CONV1D_SIGNATURES, "fhip_conv1d_last_error", (), None),
     # route: DCN_ROUTE of net.py (FHIP_DCN_NET_ROUTE of its own header)
     "dcn": Library("libfeather_dcn.so", ("feather_dcn.h",), "FHIP_DCN_API", DCN_SIGNATURES, "fhip_dcn_last_error", (), None),
+    # route: CONV3D_ROUTE of net.py (FHIP_CONV3D_NET_ROUTE of its own header)
+    "conv3d": Library("libfeather_conv3d.so", ("feather_conv3d.h",), "FHIP_CONV3D_API", CONV3D_SIGNATURES, "fhip_conv3d_last_error", (), None),
 }
 _OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 

@@ -18,7 +18,7 @@
 // One translation unit, read in this order (no header includes a later one): net_side.h -- errors, the side libraries; net_model.h --
 // ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_conv.h -- the convolution layer, its side routes
 // and the weight staging it shares; net_layers.h -- the other layer classes; net_detect.h -- the detection-head layers and their factory; net_yolo.h -- the YOLO-head layers and
-// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_rnn.h -- the recurrent layers and theirs; net_conv1d.h -- the 1-D layers and theirs; net_dcn.h -- the deformable convolution and its factory; net_plan.h -- the fusion and planning passes, prepare,
+// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_rnn.h -- the recurrent layers and theirs; net_conv1d.h -- the 1-D layers and theirs; net_dcn.h -- the deformable convolution and its factory; net_conv3d.h -- the 3-D layers and theirs; net_plan.h -- the fusion and planning passes, prepare,
 // forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
 #include "net_side.h"
 #include "net_model.h"
@@ -33,6 +33,7 @@
 #include "net_rnn.h"
 #include "net_conv1d.h"
 #include "net_dcn.h"
+#include "net_conv3d.h"
 #include "net_plan.h"
 
 namespace fhip::net
@@ -132,13 +133,19 @@ static int load_param_text(Net& net, const char* text, size_t len)
                 return failf(NET_E_UNKNOWN_LAYER, "layer %s: the layers of fhip_net_set_conv1d need the blob ranks fhip_net_set_detection maintains: set both", type.c_str());
         }
         if (!layer && net.deformable) layer.reset(create_deformable_layer(type));
+        if (!layer && net.conv3d)
+        {
+            layer.reset(create_conv3d_layer(type));
+            if (layer && !net.detection)
+                return failf(NET_E_UNKNOWN_LAYER, "layer %s: the layers of fhip_net_set_conv3d need the blob ranks fhip_net_set_detection maintains: set both", type.c_str());
+        }
         if (!layer)
         {
             std::unique_ptr<Layer> opt_in(create_extended_layer(type)), detect(create_detection_layer(type)), yolo(create_yolo_layer(type)),
-                roi(create_roi_layer(type)), frame(create_frame_layer(type)), transformer(create_transformer_layer(type)), recurrent(create_recurrent_layer(type)), conv1d(create_conv1d_layer(type)), deformable(create_deformable_layer(type));
+                roi(create_roi_layer(type)), frame(create_frame_layer(type)), transformer(create_transformer_layer(type)), recurrent(create_recurrent_layer(type)), conv1d(create_conv1d_layer(type)), deformable(create_deformable_layer(type)), conv3d(create_conv3d_layer(type));
             return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered%s", type.c_str(),
                          opt_in ? " (fhip_net_set_extended_layers lifts this)"
-                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : (roi ? " (fhip_net_set_roi lifts this)" : (frame ? " (fhip_net_set_frame enables it)" : (transformer ? " (fhip_net_set_transformer lifts this)" : (recurrent ? " (fhip_net_set_recurrent lifts this)" : (conv1d ? " (fhip_net_set_conv1d lifts this)" : (deformable ? " (fhip_net_set_deformable lifts this)" : "")))))))));
+                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : (roi ? " (fhip_net_set_roi lifts this)" : (frame ? " (fhip_net_set_frame enables it)" : (transformer ? " (fhip_net_set_transformer lifts this)" : (recurrent ? " (fhip_net_set_recurrent lifts this)" : (conv1d ? " (fhip_net_set_conv1d lifts this)" : (deformable ? " (fhip_net_set_deformable lifts this)" : (conv3d ? " (fhip_net_set_conv3d lifts this)" : ""))))))))));
         }
         layer->type = type;
         layer->name = name;
@@ -274,7 +281,7 @@ static int feed_shares(fhip_net* n, const char* blob_name, int num, int cout, in
     const auto into_blob = [&](fhip_net* m, int first, int cnt) -> int {
         Blob* b = m->impl.find(blob_name);
         if (!b) return failf(NET_E_IO, "Invalid input blob %s, not found in map.", blob_name);
-        if (b->n != cnt || b->c != cout || b->h != target_h || b->w != target_w)
+        if (b->n != cnt || b->c != cout || b->h != target_h || b->w != target_w || b->dims == 4)
         {
             const float* old = b->data;
             const int rc = b->reshape(cnt, cout, target_h, target_w);
@@ -383,6 +390,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.recurrent = n->impl.recurrent;
         m->impl.conv1d = n->impl.conv1d;
         m->impl.deformable = n->impl.deformable;
+        m->impl.conv3d = n->impl.conv3d;
         n->more.push_back(std::move(m));
     }
     if (replicas > 1 && !n->fork) FHIP_CHECK_HIP(hipEventCreateWithFlags(&n->fork, hipEventDisableTiming));
@@ -511,6 +519,15 @@ int fhip_net_set_deformable(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the deformable convolution switch (DeformableConv2D) before LoadParam");
     n->impl.deformable = on != 0;
     for (auto& m : n->more) m->impl.deformable = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_conv3d(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the 3-D layers switch (Convolution3D, ConvolutionDepthWise3D, Pooling3D) before LoadParam");
+    n->impl.conv3d = on != 0;
+    for (auto& m : n->more) m->impl.conv3d = on != 0;
     return FHIP_OK;
 }
 
@@ -653,10 +670,32 @@ int fhip_net_feed_input(fhip_net* n, const char* blob_name, int num, int c, int 
     }
     Blob* b = n->impl.find(blob_name);
     if (!b) return failf(NET_E_IO, "Invalid input blob %s, not found in map.", blob_name);
-    if (b->n != num || b->c != c || b->h != h || b->w != w)
+    if (b->n != num || b->c != c || b->h != h || b->w != w || b->dims == 4)
     {
         const float* old = b->data;
         const int rc = b->reshape(num, c, h, w);
+        if (rc) return rc;
+        n->impl.shapes_dirty = true;
+        if (old != b->data) n->impl.drop_graph();
+    }
+    FHIP_CHECK_HIP(hipMemcpyAsync(b->data, data, b->count() * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, n->impl.stream));
+    return FHIP_OK;
+}
+
+int fhip_net_feed_volume(fhip_net* n, const char* blob_name, int num, int c, int d, int h, int w, const float* data, int on_device)
+{
+    NET_GUARD(n);
+    if (!blob_name || !data || num < 1 || c < 1 || d < 1 || h < 1 || w < 1) return fail(FHIP_E_BADARG, "bad argument");
+    if (!n->more.empty()) return fail(FHIP_E_UNSUPPORTED, "a volume cannot be fed to a net with sub-batch replicas (fhip_net_set_sub_batches above 1)");
+    if (!n->impl.conv3d) return fail(FHIP_E_UNSUPPORTED, "a volume needs the 3-D layers: fhip_net_set_conv3d");
+    if (volume_elements(num, c, d, h, w) >= (1ll << 31))
+        return fail(FHIP_E_BADARG, "tensors of 2^31 elements or more are not supported");
+    Blob* b = n->impl.find(blob_name);
+    if (!b) return failf(NET_E_IO, "Invalid input blob %s, not found in map.", blob_name);
+    if (b->n != num || b->c != c || b->d != d || b->h != h || b->w != w || b->dims != 4)
+    {
+        const float* old = b->data;
+        const int rc = b->reshape_volume(num, c, d, h, w);
         if (rc) return rc;
         n->impl.shapes_dirty = true;
         if (old != b->data) n->impl.drop_graph();
@@ -796,6 +835,7 @@ int fhip_net_extract(fhip_net* n, const char* blob_name, float** ptr, int* num, 
     if (b->chained)
         return failf(NET_E_IO, "blob %s exists only as the next layer's transformed input at fusion level 3; use level 2 to extract it", blob_name);
     if (b->q8) return failf(NET_E_TOPOLOGY, "blob %s holds the int8 output of a requantised layer: it has no fp32 values to extract", blob_name);
+    if (b->dims == 4) return failf(NET_E_SHAPE, "blob %s is a volume (rank 4, depth %d): fhip_net_extract_volume returns its five extents", blob_name, b->d);
     if (b->alias) b->data = b->alias->data;
     *ptr = b->data;
     if (num) *num = b->n;
@@ -840,13 +880,35 @@ int fhip_net_extract(fhip_net* n, const char* blob_name, float** ptr, int* num, 
     return FHIP_OK;
 }
 
+int fhip_net_extract_volume(fhip_net* n, const char* blob_name, float** ptr, int* num, int* c, int* d, int* h, int* w)
+{
+    NET_GUARD(n);
+    if (!blob_name || !ptr) return fail(FHIP_E_BADARG, "null argument");
+    Blob* b = n->impl.find(blob_name);
+    if (!b) return failf(NET_E_IO, "Cannot find output blob %s", blob_name);
+    if (b->dims != 4) // a blob of a lower rank: its image form, depth 0
+    {
+        if (d) *d = 0;
+        return fhip_net_extract(n, blob_name, ptr, num, c, h, w);
+    }
+    if (b->fused_away) return failf(NET_E_IO, "blob %s was fused into its consumer; disable fusion to extract it", blob_name);
+    if (b->alias) b->data = b->alias->data;
+    *ptr = b->data;
+    if (num) *num = b->n;
+    if (c) *c = b->c;
+    if (d) *d = b->d;
+    if (h) *h = b->h;
+    if (w) *w = b->w;
+    return FHIP_OK; // (a net with sub-batch replicas holds no volume: fhip_net_feed_volume refuses it)
+}
+
 int fhip_net_extract_host(fhip_net* n, const char* blob_name, float* host, size_t capacity)
 {
     float* d = nullptr;
-    int num, c, h, w;
-    const int rc = fhip_net_extract(n, blob_name, &d, &num, &c, &h, &w);
+    int num, c, h, w, depth = 0;
+    const int rc = fhip_net_extract_volume(n, blob_name, &d, &num, &c, &depth, &h, &w);
     if (rc) return rc;
-    const size_t count = (size_t)num * c * h * w;
+    const size_t count = (size_t)num * c * (depth ? depth : 1) * h * w;
     if (!host || capacity < count) return fail(FHIP_E_BADARG, "host buffer too small");
     if (!d) return fail(FHIP_E_BADARG, "blob has no data yet (run Forward first)");
     FHIP_CHECK_HIP(hipMemcpyAsync(host, d, count * sizeof(float), hipMemcpyDeviceToHost, n->impl.stream));

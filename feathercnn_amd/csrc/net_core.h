@@ -10,7 +10,8 @@ struct Blob
 {
     std::string name;
     int n = 0, c = 0, h = 0, w = 0;
-    int dims = 3; // ncnn's Mat::dims: 3 = (c, h, w), 2 = (h, w) with c = 1, 1 = (w) with c = h = 1; only the layers of net_detect.h set or read it
+    int d = 1; // the depth of a volume (dims == 4), else 1
+    int dims = 3; // ncnn's Mat::dims: 4 = (c, d, h, w), a volume (net_conv3d.h), 3 = (c, h, w), 2 = (h, w) with c = 1, 1 = (w) with c = h = 1; only the layers of net_detect.h set or read it
     float* data = nullptr;
     size_t capacity = 0;   // floats owned
     Blob* alias = nullptr; // data is another blob's
@@ -18,16 +19,20 @@ struct Blob
     bool chained = false; // fusion level 3: lives only as the next layer's Winograd-domain input (plan_chains); shape kept, no storage
     bool q8 = false;      // a q8 tensor (feather_q8.h: signed char [n][ceil(c / 16)][h][w][16]) instead of fp32 NCHW; reshape_all sets it before the producer's Reshape
 
-    size_t count() const { return (size_t)n * c * h * w; }
+    size_t count() const { return (size_t)n * c * d * h * w; }
     size_t q8_bytes() const { return (size_t)n * ((c + 15) / 16) * h * w * 16; }
     size_t floats() const { return q8 ? q8_bytes() / 4 : count(); } // the storage, in floats
-    int reshape(int n_, int c_, int h_, int w_)
+    int reshape(int n_, int c_, int h_, int w_) { return resize(n_, c_, 1, h_, w_, 3); }
+    int reshape_volume(int n_, int c_, int d_, int h_, int w_) { return resize(n_, c_, d_, h_, w_, 4); } // a blob of rank 4, [n][c][d][h][w]
+    int reshape_like(const Blob* b) { return resize(b->n, b->c, b->d, b->h, b->w, b->dims == 4 ? 4 : 3); }  // b's extents; a volume stays one
+    int resize(int n_, int c_, int d_, int h_, int w_, int dims_)
     {
         n = n_;
         c = c_;
+        d = d_;
         h = h_;
         w = w_;
-        dims = 3;
+        dims = dims_;
         alias = nullptr;
         // a blob the previous plan chained away has no storage and, as a rule, will have none after this Reshape either: plan_chains
         // allocates it afterwards if the new shapes un-chain it (no device malloc + free per chained blob and shape change)
@@ -52,6 +57,7 @@ struct Blob
     {
         n = src->n;
         c = src->c;
+        d = src->d;
         h = src->h;
         w = src->w;
         dims = src->dims;
@@ -130,6 +136,9 @@ struct Layer
     // one is refused by reshape_all; writes_q8() is asked there too, after the layer's bottoms are settled and before its Reshape
     virtual bool reads_q8() const { return false; }
     virtual bool writes_q8() const { return false; }
+    // volumes (Blob::dims == 4, the blobs of net_conv3d.h): the same rule -- a layer that carries the depth through says so, every other
+    // layer that meets one is refused by reshape_all
+    virtual bool reads_volume() const { return false; }
     // The one form of a call into a side library: FHIP_E_UNSUPPORTED where the library is missing (side_api has set the message), else
     // the call's code -- `code` in its place, for an entry point that only says yes or no -- with the library's message behind the
     // layer's name and `prefix`.
@@ -146,7 +155,7 @@ struct Layer
     virtual int Reshape()
     {
         if (tops.size() != 1 || bottoms.size() != 1) return failf(NET_E_BASE_RESHAPE, "layer %s: base Reshape needs 1 bottom and 1 top", name.c_str());
-        return tops[0]->reshape(bottoms[0]->n, bottoms[0]->c, bottoms[0]->h, bottoms[0]->w);
+        return tops[0]->reshape_like(bottoms[0]);
     }
     int reshape_with(const void* side_library) { return side_library ? Layer::Reshape() : FHIP_E_UNSUPPORTED; } // (message set by side_api)
     virtual int Init(hipStream_t) { return 0; }
@@ -196,6 +205,7 @@ struct Net
     bool recurrent = false;       // fhip_net_set_recurrent: LSTM, GRU and RNN (net_rnn.h, libfeather_rnn.so) are loaded instead of refused
     bool conv1d = false;          // fhip_net_set_conv1d: Convolution1D, ConvolutionDepthWise1D and Pooling1D (net_conv1d.h, libfeather_conv1d.so) are loaded instead of refused
     bool deformable = false;      // fhip_net_set_deformable: DeformableConv2D (net_dcn.h, libfeather_dcn.so) is loaded instead of refused
+    bool conv3d = false;          // fhip_net_set_conv3d: Convolution3D, ConvolutionDepthWise3D and Pooling3D (net_conv3d.h, libfeather_conv3d.so) are loaded instead of refused
     int colpass = 1;              // fhip_net_set_colpass: chained 64-input-channel Winograd layers through libfeather_colpass.so -- 0 never, 1 where M is HBM-bound, 2 wherever accepted
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;

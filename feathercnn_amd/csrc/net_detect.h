@@ -39,6 +39,7 @@ static void view_as(Blob* top, Blob* src, int c, int h, int w, int dims)
 {
     top->share(src);
     top->c = c;
+    top->d = 1;
     top->h = h;
     top->w = w;
     top->dims = dims;
@@ -89,11 +90,12 @@ struct PermuteLayer : DetectLayer
 struct FlattenLayer : DetectLayer
 {
     int LoadParam(const ParamDict&) override { return one_to_one_counts(this); }
+    bool reads_volume() const override { return true; } // a volume flattens to rank 1 like any blob
     int Reshape() override
     {
         Blob* b = bottoms[0];
         if (b->count() / std::max(b->n, 1) >= ((size_t)1 << 31)) return failf(NET_E_SHAPE, "layer %s: Flatten: an image of 2^31 elements or more", name.c_str());
-        view_as(tops[0], b, 1, 1, b->c * b->h * b->w, 1);
+        view_as(tops[0], b, 1, 1, b->c * b->d * b->h * b->w, 1);
         return 0;
     }
     int Forward(hipStream_t) override { return 0; } // the top aliases the bottom

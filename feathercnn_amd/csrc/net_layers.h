@@ -110,6 +110,7 @@ struct ReluLayer : Layer
     // a plain ReLU on a q8 blob is max(q, 0) on its bytes (libfeather_q8.so): quantise commutes with it
     bool reads_q8() const override { return slope == 0.f; }
     bool writes_q8() const override { return bottoms[0]->q8; }
+    bool reads_volume() const override { return slope == 0.f; } // fhip_relu works on count() alone
     int Reshape() override
     {
         if (slope != 0.f) return reshape_with(inorm_api());
@@ -954,6 +955,7 @@ struct EltwiseLayer : Layer
 {
     bool relu = false;
     EltwiseLayer* as_eltwise() override { return this; }
+    bool reads_volume() const override { return true; } // fhip_add works on count() alone
     int LoadParam(const ParamDict& pd) override // eltwise_layer.h:53-68
     {
         if (pd.has_array(1)) return failf(NET_E_SHAPE, "layer %s: coeffs in eltwise layer are not supported", name.c_str());
@@ -966,11 +968,11 @@ struct EltwiseLayer : Layer
         if (bottoms.size() < 2) return failf(NET_E_TOPOLOGY, "layer %s: eltwise needs two bottoms", name.c_str());
         const Blob* a = bottoms[0];
         for (size_t i = 1; i < bottoms.size(); ++i)
-            if (bottoms[i]->n != a->n || bottoms[i]->c != a->c || bottoms[i]->h != a->h || bottoms[i]->w != a->w)
+            if (bottoms[i]->n != a->n || bottoms[i]->c != a->c || bottoms[i]->d != a->d || bottoms[i]->h != a->h || bottoms[i]->w != a->w)
                 return failf(NET_E_SHAPE, "Shape mismatch among bottoms of layer %s.", name.c_str());
         for (Blob* t : tops)
         {
-            int rc = t->reshape(a->n, a->c, a->h, a->w);
+            int rc = t->reshape_like(a);
             if (rc) return rc;
         }
         return 0;
@@ -1175,6 +1177,7 @@ struct ChannelMapLayer : Layer
 struct SplitLayer : Layer
 {
     bool reads_q8() const override { return true; } // the tops share the blob, whatever it holds
+    bool reads_volume() const override { return true; }
     bool writes_q8() const override { return bottoms[0]->q8; }
     int Reshape() override
     {
@@ -1188,6 +1191,7 @@ struct DropoutLayer : Layer
 {
     float scale = 1.f;
     DeviceVec d_scale;
+    bool reads_volume() const override { return true; } // shares the blob, or scales every value of a channel
     int LoadParam(const ParamDict& pd) override
     {
         scale = pd.get(0, 1.f);
@@ -1215,7 +1219,7 @@ struct DropoutLayer : Layer
     {
         if (scale == 1.f) return 0;
         const Blob* b = bottoms[0];
-        return fhip_affine(tops[0]->data, b->data, d_scale.d, nullptr, b->n, b->c, b->h * b->w, 0, s);
+        return fhip_affine(tops[0]->data, b->data, d_scale.d, nullptr, b->n, b->c, b->d * b->h * b->w, 0, s);
     }
 };
 

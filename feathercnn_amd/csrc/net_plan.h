@@ -559,6 +559,17 @@ static int reshape_all(Net& net)
                 return failf(NET_E_TOPOLOGY, "blob %s holds the int8 output of layer %s, which %s layer %s cannot read", b->name.c_str(),
                              from ? from->name.c_str() : "?", l->type.c_str(), l->name.c_str());
             }
+        // volumes: the same rule.  No layer reads a blob of rank 4 as if it were an image.
+        for (const Blob* b : l->bottoms)
+            if (b->dims == 4 && !l->reads_volume())
+            {
+                const Layer* from = nullptr;
+                for (auto& w : net.layers)
+                    for (const Blob* t : w->tops)
+                        if (t == b) from = w.get();
+                return failf(NET_E_TOPOLOGY, "blob %s of layer %s is a volume (rank 4, depth %d), which %s layer %s cannot read", b->name.c_str(),
+                             from ? from->name.c_str() : "?", b->d, l->type.c_str(), l->name.c_str());
+            }
         const bool q8 = !l->bottoms.empty() && l->writes_q8();
         for (Blob* t : l->tops) t->q8 = q8;
         const int rc = l->Reshape();

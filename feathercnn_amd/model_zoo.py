@@ -590,6 +590,77 @@ class GraphBuilder:
                                                              a1=a1))
         return top
 
+    # -- the 3-D layers (a net that holds one needs Net.SetConv3d() and Net.SetDetection()) -----------------------------------------------------
+    def input3d(self, name, c, d, h, w):
+        return self.layer("Input", name, [], [name], {0: w, 1: h, 11: d, 2: c})
+
+    def conv3d(self, name, bottom, cin, cout, k, s=1, d=1, p=0, pad_value=None, group=1, bias=True, act=0, act_params=(), gain=1.0, bn=False):
+        """ncnn's Convolution3D (group 1) or ConvolutionDepthWise3D on a volume [cin][D][H][W]: weights [cout][cin / group][kd][kh][kw] tagged,
+        then the raw bias.  k, s, d: an int or (depth, row, column); p: an int, (depth, row, column), (front, behind, top, bottom, left, right), or
+        -233 / -234 (SAME_UPPER / SAME_LOWER on every axis).  act: ncnn's activation_type 0 .. 6 with its activation_params.  bn: a BatchNorm
+        drawn behind the layer and folded into its weights and bias, as a converter's optimiser leaves it."""
+        three = lambda v: (v,) * 3 if isinstance(v, int) else tuple(v)
+        (kd, kh, kw), (sd, sh, sw), (dd, dh, dw) = three(k), three(s), three(d)
+        pads = (p,) * 6 if isinstance(p, int) else (tuple(q for q in p for _ in (0, 1)) if len(p) == 3 else tuple(p))
+        wsize = cout * (cin // group) * kd * kh * kw
+        params = {0: cout, 1: kw, 11: kh, 21: kd, 2: dw, 12: dh, 22: dd, 3: sw, 13: sh, 23: sd, 4: pads[4], 5: int(bias or bn), 6: wsize}
+        if pads[4] >= 0:
+            params.update({15: pads[5], 14: pads[2], 16: pads[3], 24: pads[0], 17: pads[1]})
+        if group > 1:
+            params[7] = group
+        if act:
+            params[9] = act
+            if act_params:
+                params[-23310] = ",".join([str(len(act_params))] + ["%r" % float(v) for v in act_params])
+        if pad_value is not None:
+            params[18] = "%r" % float(pad_value)
+        top = self.layer("ConvolutionDepthWise3D" if group > 1 else "Convolution3D", name, [bottom], [name], params)
+        w = self._uniform(wsize, -1, 1, np.sqrt(6.0 / (cin // group * kd * kh * kw)) * gain)
+        b = self._uniform(cout, -0.1, 0.1) if bias else None
+        if bn:
+            slope, mean, var, beta = self._uniform(cout, 0.5, 1.5), self._uniform(cout, -0.1, 0.1), self._uniform(cout, 0.5, 1.5), self._uniform(cout, -0.1, 0.1)
+            if not self.dry:
+                mul = slope / np.sqrt(var + np.float32(1e-5))
+                w = (w.reshape(cout, -1) * mul[:, None]).reshape(-1)
+                b = beta + ((0 if b is None else b) - mean) * mul
+            else:
+                b = cout
+        self._weights(name, w, cout, b)
+        if self.trace is not None:
+            a0, a1 = (tuple(act_params) + (0.0, 0.0))[:2]
+            self._note("conv3d", name, bottom, top, dict(w=w.reshape(cout, cin // group, kd, kh, kw), bias=b, stride=(sd, sh, sw), dilation=(dd, dh, dw),
+                                                         pads=pads if pads[4] >= 0 else pads[4], pad_value=pad_value or 0.0, group=group, act=act, a0=a0, a1=a1))
+        return top
+
+    def pool3d(self, name, bottom, k=0, s=1, p=0, pad_mode=0, avg=False, include_pad=False, global_=False, out_dhw=None):
+        """ncnn's Pooling3D on a volume; k, s, p as conv3d takes them; global_: a blob of rank 1 [C]; out_dhw: adaptive onto (depth, row, column)."""
+        three = lambda v: (v,) * 3 if isinstance(v, int) else tuple(v)
+        (kd, kh, kw), (sd, sh, sw) = three(k), three(s)
+        pads = (p,) * 6 if isinstance(p, int) else (tuple(q for q in p for _ in (0, 1)) if len(p) == 3 else tuple(p))
+        params = {0: int(avg), 1: kw, 11: kh, 21: kd, 2: sw, 12: sh, 22: sd, 3: pads[4], 14: pads[5], 13: pads[2], 15: pads[3], 23: pads[0], 16: pads[1], 4: int(global_),
+                  5: pad_mode, 6: int(include_pad)}
+        if out_dhw is not None:
+            params.update({7: 1, 8: out_dhw[2], 18: out_dhw[1], 28: out_dhw[0]})
+        top = self.layer("Pooling3D", name, [bottom], [name], params)
+        self._note("pool3d", name, bottom, top, dict(kernel=(kd, kh, kw), stride=(sd, sh, sw), pads=pads, pad_mode=pad_mode, avg=avg, include_pad=include_pad, global_=global_,
+                                                     out_dhw=out_dhw))
+        return top
+
+    def sum_(self, name, a, b):
+        """An Eltwise SUM that numpy_forward knows (eltwise() records nothing)."""
+        self._note("sum", name, [a, b], name, {})
+        return self.eltwise(name, a, b)
+
+    def drop(self, name, bottom):
+        """A Dropout at scale 1 that numpy_forward knows (dropout() records nothing): the identity."""
+        self._note("identity", name, bottom, name, {})
+        return self.dropout(name, bottom)
+
+    def flat(self, name, bottom):
+        """A Flatten that numpy_forward knows (flatten() records nothing): rank 1, [n][1][1][c d h w]."""
+        self._note("flat", name, bottom, name, {})
+        return self.flatten(name, bottom)
+
     def pool_rect(self, name, bottom, kw, kh, sw, sh):
         """A max Pooling with a rectangular kernel and stride, unpadded: ncnn's 1 / 11 and 2 / 12.  (A padded one is written as a zero Padding in
         front of it where the bottom is not negative: the reference places a padded window at minus the SUM of both pads, and this runtime
@@ -759,6 +830,18 @@ def _conv1d_ref():
     return conv1d_ref
 
 
+def _conv3d_ref():
+    """tests/conv3d_ref.py, the restatement of feather_conv3d.h: numpy_forward's 3-D layers are that text, not a second one."""
+    try:
+        import conv3d_ref
+    except ImportError:
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import conv3d_ref
+    return conv3d_ref
+
+
 def _dcn_ref():
     """tests/dcn_ref.py, the restatement of feather_dcn.h: numpy_forward's DeformableConv2D is that text, not a second one."""
     try:
@@ -835,6 +918,17 @@ def numpy_forward(trace, input_name, x=None):
             y = 1 / (1 + np.exp(-v.astype(np.float64)))
         elif kind == "deform_conv":
             y = _dcn_ref().deform_conv2d(v[0], v[1], v[2] if len(v) > 2 else None, **a)
+        elif kind == "conv3d":  # volumes: [n][C][D][H][W]
+            y = _conv3d_ref().conv3d(v, **a)
+        elif kind == "pool3d":  # global pooling: rank 1, [n][1][1][C]
+            y = _conv3d_ref().pool3d(v, **a)
+            y = y.reshape(y.shape[0], 1, 1, -1) if a["global_"] else y
+        elif kind == "sum":
+            y = v[0].astype(np.float64) + v[1]
+        elif kind == "identity":
+            y = v
+        elif kind == "flat":
+            y = v.reshape(v.shape[0], 1, 1, -1)
         elif kind == "conv1d":  # blobs of rank 2: [n][1][C][L]
             y = _conv1d_ref().conv1d(v[:, 0].astype(np.float64), **a)[:, None]
         elif kind == "pool1d":  # global pooling: rank 1, [n][1][1][C]
@@ -1030,8 +1124,8 @@ def vgg16(seed=1234, classes=1000, size=224, dry=False, quant=None, requant=None
             cin = c
         x = g.pool(f"pool{stage}", x, 2, 2)
     feat = 512 * (size // 32) ** 2
-    x = g.dropout("drop6", g.relu("relu6", g.fc("fc6", x, feat, 4096)))
-    x = g.dropout("drop7", g.relu("relu7", g.fc("fc7", x, 4096, 4096)))
+    x = g.drop("drop6", g.relu("relu6", g.fc("fc6", x, feat, 4096)))
+    x = g.drop("drop7", g.relu("relu7", g.fc("fc7", x, 4096, 4096)))
     x = g.softmax("prob", g.fc("fc8", x, 4096, classes))
     return g.finish() + ("data", "prob")
 
@@ -1781,8 +1875,8 @@ def _alexnet(seed, classes, size, dry, norm_first):
     x = g.relu("relu5", g.conv("conv5", x, 384, 256, 3, 1, 1, 2))
     x = g.pool("pool5", x, 3, 2)
     feat = 256 * _pool3s2(_pool3s2(_pool3s2((size - 11) // 4 + 1))) ** 2
-    x = g.dropout("drop6", g.relu("relu6", g.fc("fc6", x, feat, 4096)))
-    x = g.dropout("drop7", g.relu("relu7", g.fc("fc7", x, 4096, 4096)))
+    x = g.drop("drop6", g.relu("relu6", g.fc("fc6", x, feat, 4096)))
+    x = g.drop("drop7", g.relu("relu7", g.fc("fc7", x, 4096, 4096)))
     x = g.softmax("prob", g.fc("fc8", x, 4096, classes))
     return g.finish() + ("data", "prob")
 
@@ -2082,8 +2176,8 @@ def faster_rcnn_vgg16(seed=1234, classes=21, size=(600, 800), dry=False):
     feat, x = g.split("conv5_3_split", x, 2)
     r = _rpn(g, x, 512, 512, im_info)
     x = g.roi_pooling("roi_pool5", feat, r, 7, 7, 0.0625)
-    x = g.dropout("drop6", g.relu("relu6", g.fc("fc6", x, 512 * 49, 4096)))
-    x = g.dropout("drop7", g.relu("relu7", g.fc("fc7", x, 4096, 4096)))
+    x = g.drop("drop6", g.relu("relu6", g.fc("fc6", x, 512 * 49, 4096)))
+    x = g.drop("drop7", g.relu("relu7", g.fc("fc7", x, 4096, 4096)))
     a, b = g.split("fc7_split", x, 2)
     g.softmax("cls_prob", g.fc("cls_score", a, 4096, classes))
     g.fc("bbox_pred", b, 4096, 4 * classes)
@@ -2558,3 +2652,81 @@ UPSAMPLE_ADDS = {"tiny_resample": (("up1",), ("up2", "shrink", "aligned", "to_re
 # the squeeze-and-excitation blocks of each net (the name fusion level 2 keeps: the block's Pooling layer) that collapse into one layer,
 # and those that must not
 SE_BLOCKS = {"tiny_se": (("a_gap", "b_gap", "c_gap"), ("d_gap",))}
+
+
+def tiny_c3d(seed=101, size=(5, 12, 14), dry=False, trace=None, classes=5):
+    """A small volumetric net with every form of the 3-D layers (Net.SetConv3d(), SetDetection()): a 3x3x3 Convolution3D with ReLU as its
+    activation, one with stride (1, 2, 1), asymmetric pads and a pad value, a dilated one with SAME_UPPER pads, activations 2 to 6 on 1x1x1,
+    3x1x1 and 1x3x3 kernels, a grouped and a depthwise ConvolutionDepthWise3D, Pooling3D max, average (both divisors), SAME, valid, adaptive
+    and global, two Splits, two Eltwise adds, a ReLU layer, a Dropout and Flatten in front of the InnerProduct.  No pair of layers fuses, so
+    every blob can be extracted at every fusion level.  trace: a list that receives the layers for numpy_forward."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    ref = _conv3d_ref()
+    d, h, w = size
+    x = g.conv3d("c1", g.input3d("data", 3, d, h, w), 3, 8, 3, p=1, act=1)
+    x = g.conv3d("c2", x, 8, 9, 3, s=(1, 2, 1), p=(1, 0, 0, 1, 2, 1), pad_value=0.5, act=2, act_params=(0.1,))
+    a, b = g.split("c2_split", x)
+    a = g.conv3d("c3", a, 9, 12, 3, d=(1, 2, 1), p=-233, act=3, act_params=(-0.5, 0.75))
+    b = g.conv3d("c4", b, 9, 12, 1, act=4)
+    x = g.relu("sum_relu", g.drop("drop", g.sum_("sum", a, b)))
+    x = g.conv3d("g2", x, 12, 12, (3, 1, 1), p=(1, 0, 0), group=2, act=5)
+    x = g.conv3d("dw", x, 12, 12, 3, p=-234, group=12, act=6, act_params=(1.0 / 6, 0.5))
+    x = g.pool3d("pool_max", g.conv3d("c5", x, 12, 16, (1, 3, 3), p=(0, 1, 1)), (1, 2, 2), (1, 2, 2))
+    x = g.pool3d("pool_avg", x, 3, 2, p=1, avg=True)
+    x = g.pool3d("pool_inc", x, 2, 1, p=(0, 1, 0, 1, 0, 1), avg=True, include_pad=True)
+    p1, p2, p3 = g.split("pools", x, 3)
+    # the volume here: c2 alone changes it among the convolutions, then the three poolings; pool_same halves it, rounding up
+    dims = [ref.conv_axis(e, 3, 1, s, lo, hi)[2] for e, s, lo, hi in zip(size, (1, 2, 1), (1, 0, 2), (0, 1, 1))]
+    dims = [ref.pool_axis(e, k, s, 0, 0, 0)[2] for e, k, s in zip(dims, (1, 2, 2), (1, 2, 2))]
+    dims = [-(-ref.pool_axis(e, 3, 2, 1, 1, 0)[2] // 2) for e in dims]
+    x = g.sum_("pool_sum", g.pool3d("pool_same", p1, 2, 2, pad_mode=2), g.pool3d("pool_adapt", p3, avg=True, out_dhw=tuple(dims)))
+    g.fc("fc_gap", g.pool3d("gap", g.pool3d("pool_valid", p2, 2, 2, pad_mode=1), avg=True, global_=True), 16, classes)
+    g.fc("fc", g.flat("flat", x), 16 * int(np.prod(dims)), classes)
+    return g.finish() + ("data", "fc")
+
+
+def c3d(seed=1234, classes=487, size=(16, 112, 112), dry=False, trace=None, fc=4096):
+    """C3D (Net.SetConv3d(), SetDetection()): eight 3x3x3 convolutions of 64 to 512 channels with ReLU as their activation, five max poolings of
+    which the first is 1x2x2, Flatten, fc6 and fc7 of `fc` units with ReLU and Dropout, and the classifier.  The classifier's input size is
+    derived from `size`; the published net takes 3 x 16 x 112 x 112."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    d, h, w = size
+    x, c = g.input3d("data", 3, d, h, w), 3
+    for stage, (cout, convs, pool) in enumerate(((64, 1, (1, 2, 2)), (128, 1, 2), (256, 2, 2), (512, 2, 2), (512, 2, 2)), 1):
+        for i in range(convs):
+            x = g.conv3d("conv%d%s" % (stage, "ab"[i] if convs > 1 else ""), x, c, cout, 3, p=1, act=1)
+            c = cout
+        kd, kh, kw = (pool,) * 3 if isinstance(pool, int) else pool
+        last = stage == 5  # pool5 pads the plane by one row and one column in front, as the published net's 7 x 7 plane needs
+        x = g.pool3d("pool%d" % stage, x, (kd, kh, kw), (kd, kh, kw), p=(0, 0, 1, 0, 1, 0) if last else 0, pad_mode=1)
+        d, h, w = (d - kd) // kd + 1, (h + last - kh) // kh + 1, (w + last - kw) // kw + 1
+    x = g.flat("flat", x)
+    x = g.drop("drop6", g.relu("relu6", g.fc("fc6", x, c * d * h * w, fc)))
+    x = g.drop("drop7", g.relu("relu7", g.fc("fc7", x, fc, fc)))
+    g.fc("fc8", x, fc, classes)
+    return g.finish() + ("data", "fc8")
+
+
+def r3d_18(seed=1234, classes=400, size=(16, 112, 112), dry=False, trace=None):
+    """R3D-18 (Net.SetConv3d(), SetDetection()): a 3x7x7 stem at stride (1, 2, 2), four stages of two basic blocks -- two 3x3x3 convolutions, the
+    shortcut a 1x1x1 stride-2 projection where the stage halves the volume, Eltwise add, ReLU --, a global average Pooling3D and the
+    InnerProduct.  Every BatchNorm is folded into the convolution in front of it by the generator, as a converter would leave it."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    d, h, w = size
+    x = g.conv3d("stem", g.input3d("data", 3, d, h, w), 3, 64, (3, 7, 7), s=(1, 2, 2), p=(1, 3, 3), bias=False, bn=True, act=1)
+    c = 64
+    for stage, cout in enumerate((64, 128, 256, 512), 1):
+        for block in range(2):
+            tag, s = "l%db%d" % (stage, block), 2 if (stage > 1 and block == 0) else 1
+            main, short = g.split(tag + "_split", x)
+            y = g.conv3d(tag + "_c1", main, c, cout, 3, s=s, p=1, bias=False, bn=True, act=1)
+            y = g.conv3d(tag + "_c2", y, cout, cout, 3, p=1, bias=False, bn=True, gain=0.5)
+            if s > 1 or c != cout:
+                short = g.conv3d(tag + "_proj", short, c, cout, 1, s=s, bias=False, bn=True)
+            x = g.relu(tag + "_relu", g.sum_(tag + "_sum", y, short))
+            c = cout
+    g.fc("fc", g.pool3d("gap", x, avg=True, global_=True), c, classes)
+    return g.finish() + ("data", "fc")

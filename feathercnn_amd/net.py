@@ -47,6 +47,8 @@ CONV1D_ROUTE = 115  # FHIP_CONV1D_NET_ROUTE (feather_conv1d.h): Convolution1D, C
 ROUTE_NAMES[CONV1D_ROUTE] = "CONV1D"
 DCN_ROUTE = 116  # FHIP_DCN_NET_ROUTE (feather_dcn.h): DeformableConv2D, after SetDeformable() (libfeather_dcn.so)
 ROUTE_NAMES[DCN_ROUTE] = "DCN"
+CONV3D_ROUTE = 117  # FHIP_CONV3D_NET_ROUTE (feather_conv3d.h): Convolution3D, ConvolutionDepthWise3D or Pooling3D, after SetConv3d() (libfeather_conv3d.so)
+ROUTE_NAMES[CONV3D_ROUTE] = "CONV3D"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -137,6 +139,11 @@ class Net:
         LoadParam.  Call before LoadParam."""
         _check(self._lib.fhip_net_set_deformable(self._h, int(bool(on))), "fhip_net_set_deformable")
 
+    def SetConv3d(self, on: bool = True):
+        """feather::Net::SetConv3d: accept ncnn's Convolution3D, ConvolutionDepthWise3D and Pooling3D (routed to libfeather_conv3d.so) instead of
+        refusing them at LoadParam.  Needs SetDetection() too (blob ranks); FeedInput then takes a volume [N][C][D][H][W].  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_conv3d(self._h, int(bool(on))), "fhip_net_set_conv3d")
+
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")
 
@@ -191,10 +198,13 @@ class Net:
             keep = a
         if len(shape) == 3:
             shape = (1,) + tuple(shape)
-        if len(shape) != 4:
-            raise FeatherHipError("FeedInput wants [N][C][H][W] or [C][H][W]")
-        n, c, h, w = (int(v) for v in shape)
-        _check(self._lib.fhip_net_feed_input(self._h, input_name.encode(), n, c, h, w, ptr, dev), "fhip_net_feed_input")
+        if len(shape) == 5:  # a volume [N][C][D][H][W] (SetConv3d)
+            _check(self._lib.fhip_net_feed_volume(self._h, input_name.encode(), *(int(v) for v in shape), ptr, dev), "fhip_net_feed_volume")
+        elif len(shape) != 4:
+            raise FeatherHipError("FeedInput wants [N][C][H][W], [C][H][W] or a volume [N][C][D][H][W]")
+        else:
+            n, c, h, w = (int(v) for v in shape)
+            _check(self._lib.fhip_net_feed_input(self._h, input_name.encode(), n, c, h, w, ptr, dev), "fhip_net_feed_input")
         self.synchronize()  # the host array / device tensor may be freed or overwritten by the caller
         del keep
         return 0
@@ -262,8 +272,8 @@ class Net:
         return 0
 
     def Extract(self, blob_name: str) -> np.ndarray:
-        """Net::Extract (net.cpp:263-296): the blob as a host [N][C][H][W] array (synchronises the stream)."""
-        ptr, shape = self.ExtractDevice(blob_name)
+        """Net::Extract (net.cpp:263-296): the blob as a host [N][C][H][W] array, a volume as [N][C][D][H][W] (synchronises the stream)."""
+        ptr, shape = self.ExtractVolumeDevice(blob_name)
         out = np.empty(shape, dtype=np.float32)
         _check(self._lib.fhip_net_extract_host(self._h, blob_name.encode(), out.ctypes.data_as(ctypes.c_void_p), out.size),
                "fhip_net_extract_host")
@@ -325,6 +335,14 @@ class Net:
         _check(self._lib.fhip_net_extract(self._h, blob_name.encode(), ctypes.byref(p), *[ctypes.byref(d) for d in dims]),
                "fhip_net_extract")
         return p.value, tuple(d.value for d in dims)
+
+    def ExtractVolumeDevice(self, blob_name: str):
+        """(device pointer, shape) of a blob: (n, c, d, h, w) for a volume (fhip_net_extract_volume), (n, c, h, w) for every other blob."""
+        p = ctypes.c_void_p()
+        dims = [ctypes.c_int() for _ in range(5)]
+        _check(self._lib.fhip_net_extract_volume(self._h, blob_name.encode(), ctypes.byref(p), *[ctypes.byref(d) for d in dims]), "fhip_net_extract_volume")
+        n, c, d, h, w = (v.value for v in dims)
+        return p.value, (n, c, d, h, w) if d else (n, c, h, w)  # depth 0: no volume
 
     # -- introspection ------------------------------------------------------------------------------------------
     def synchronize(self):

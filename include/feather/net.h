@@ -36,7 +36,8 @@
 //     (feather_frame.h) after SetFrame(true); MemoryData, LayerNorm, GELU, MultiHeadAttention, the element-wise BinaryOp and the token-wise
 //     InnerProduct (feather_attn.h) after SetTransformer(true) and SetDetection(true); LSTM, GRU and RNN (feather_rnn.h) after
 //     SetRecurrent(true) and SetDetection(true); Convolution1D, ConvolutionDepthWise1D and Pooling1D (feather_conv1d.h) after
-//     SetConv1d(true) and SetDetection(true); DeformableConv2D (feather_dcn.h) after SetDeformable(true).
+//     SetConv1d(true) and SetDetection(true); DeformableConv2D (feather_dcn.h) after SetDeformable(true); Convolution3D,
+//     ConvolutionDepthWise3D and Pooling3D (feather_conv3d.h) after SetConv3d(true) and SetDetection(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -262,6 +263,9 @@ class Net
     int SetConv1d(bool on = true) { return fhip_net_set_conv1d(net_, on ? 1 : 0); }
     // accept ncnn's DeformableConv2D, DCN v1 and v2 (libfeather_dcn.so), instead of refusing it; before LoadParam (feather_net.h)
     int SetDeformable(bool on = true) { return fhip_net_set_deformable(net_, on ? 1 : 0); }
+    // accept ncnn's 3-D layers -- Convolution3D, ConvolutionDepthWise3D, Pooling3D (libfeather_conv3d.so) -- instead of refusing them; needs
+    // SetDetection(true) too; before LoadParam.  Their input is fed with fhip_net_feed_volume (feather_net.h)
+    int SetConv3d(bool on = true) { return fhip_net_set_conv3d(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
     // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
     // blob has another shape.  scores_blob "" asks for none.

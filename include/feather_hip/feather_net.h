@@ -357,6 +357,24 @@ FHIP_API int fhip_net_set_conv1d(fhip_net* net, int on);
  * Wo < 1.  0 (default): LoadParam refuses the type with -200; on-then-off equals the default.  Call before LoadParam; later it is
  * FHIP_E_BADARG.  Copied to sub-batch replicas. */
 FHIP_API int fhip_net_set_deformable(fhip_net* net, int on);
+/* 1: ncnn's 3-D layers are loaded -- Convolution3D (0=num_output 1/11/21=kernel w/h/d 2/12/22=dilation 3/13/23=stride 4/15=pad left/right
+ * 14/16=pad top/bottom 24/17=pad front/behind 18=pad_value 5=bias_term 6=weight_data_size 9=activation_type 10=activation_params; an absent
+ * id of h or d takes its w counterpart's value; pad_left -233 / -234: SAME on every axis), ConvolutionDepthWise3D (the same and 7=group;
+ * weights tagged [num_output][C / group][kd][kh][kw], then the raw bias) and Pooling3D (0=pooling_type 1/11/21=kernel 2/12/22=stride
+ * 3/14=pad left/right 13/15=pad top/bottom 23/16=pad front/behind 4=global_pooling 5=pad_mode 6=avgpool_count_include_pad
+ * 7=adaptive_pooling 8/18/28=out w/h/d) -- as feather_conv3d.h defines them; they run through libfeather_conv3d.so and report the route
+ * FHIP_CONV3D_NET_ROUTE (feather_conv3d.h).  Their blobs are volumes, blobs of rank 4 [n][C][D][H][W]: fhip_net_feed_volume makes one of
+ * an Input, fhip_net_extract_volume returns one.  Besides these layers a volume is read by Split, Dropout, a ReLU without slope, an
+ * Eltwise SUM and Flatten (rank 1); every other layer that meets one -- BatchNorm, Scale, Concat, Softmax, InnerProduct, a 2-D layer -- is
+ * refused at the first Forward with -300, naming both layers.  Global pooling gives a blob of rank 1 [C].  Weights are uploaded and packed
+ * once at Init; nothing fuses into or out of these layers.  Refused with -100 at LoadParam, naming the layer and the param:
+ * dynamic_weight (19=), int8 (8=), num_output, a kernel extent, stride or dilation < 1, a negative pad other than pad_left -233 / -234,
+ * a weight_data_size that fits no channel count, a group that divides not both channel counts, an activation or pooling type out of
+ * range; at the first Forward, naming the blob: a bottom that is no volume or has another channel count, an output extent < 1.  The blobs
+ * of these layers have ranks, which fhip_net_set_detection maintains: without it LoadParam refuses the types with -200 and says so.
+ * 0 (default): LoadParam refuses the three types with -200; on-then-off equals the default.  Call before LoadParam; later it is
+ * FHIP_E_BADARG.  Copied to sub-batch replicas, which no volume can be fed to. */
+FHIP_API int fhip_net_set_conv3d(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
@@ -419,6 +437,9 @@ FHIP_API int fhip_net_load_weights_device(fhip_net* net, const void* device_data
  * whether it is a device pointer (copied device-to-device on the net's stream) or a host pointer. */
 FHIP_API int fhip_net_feed_input(fhip_net* net, const char* blob_name, int n, int c, int h, int w, const float* data,
                                  int on_device);
+/* fhip_net_feed_input for a volume: `data` holds n*c*d*h*w floats and the blob becomes one of rank 4, [n][c][d][h][w].  Needs
+ * fhip_net_set_conv3d.  FHIP_E_UNSUPPORTED: the switch is off, or the net has sub-batch replicas (fhip_net_set_sub_batches above 1). */
+FHIP_API int fhip_net_feed_volume(fhip_net* net, const char* blob_name, int n, int c, int d, int h, int w, const float* data, int on_device);
 /* Net::FeedInput of `n` uint8 images: fhip_pixels_to_float (same type, sizes, mean, norm) straight into the input blob, which becomes
  * [n][cout][target_h][target_w] (reshaped, and the graph dropped, only when that shape changes).  Enqueued on the net's stream; with
  * sub-batch replicas each replica's share of the images is converted into its own blob, forked and joined like fhip_net_feed_input.
@@ -444,6 +465,9 @@ FHIP_API int fhip_net_forward(fhip_net* net);
  * The pointer stays valid until the next Reshape.  With sub-batch replicas the pointer is a per-name buffer the shares are gathered
  * into (on the net's stream); it is re-allocated only when that blob's total size grows, i.e. after a FeedInput with a larger shape. */
 FHIP_API int fhip_net_extract(fhip_net* net, const char* blob_name, float** device_ptr, int* n, int* c, int* h, int* w);
+/* fhip_net_extract with the depth of a volume (0 for a blob of a lower rank: d tells the two apart).  fhip_net_extract itself refuses a volume with -100 and names
+ * this entry: it never returns four extents of five.  fhip_net_extract_host copies either kind. */
+FHIP_API int fhip_net_extract_volume(fhip_net* net, const char* blob_name, float** device_ptr, int* n, int* c, int* d, int* h, int* w);
 /* Convenience: synchronise the stream and copy the blob to a host buffer of `capacity` floats. */
 FHIP_API int fhip_net_extract_host(fhip_net* net, const char* blob_name, float* host, size_t capacity);
 
