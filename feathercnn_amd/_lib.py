@@ -117,6 +117,7 @@ SIGNATURES = {
     "fhip_net_set_conv1d": (_I, [_V, _I]),
     "fhip_net_set_deformable": (_I, [_V, _I]),
     "fhip_net_set_conv3d": (_I, [_V, _I]),
+    "fhip_net_set_audio": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -443,6 +444,16 @@ CONV3D_SIGNATURES = {
     "fhip_conv3d_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_stft.h -- libfeather_stft.so, ncnn's Spectrogram and UnaryOp (a library of its own)
+STFT_SIGNATURES = {
+    "fhip_stft_output_dim": (_I, [_I] * 6 + [_IP] * 2),
+    "fhip_stft_basis": (_I, [_I] * 5 + [_V, ctypes.c_longlong]),
+    "fhip_stft_forward": (_I, [_I] * 8 + [_V, _V, _V, _I, _V]),
+    "fhip_unary_forward": (_I, [_I, _V, _V, ctypes.c_longlong, _V]),
+    "fhip_stft_route": (_I, [_I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_stft_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -547,6 +558,8 @@ LATER_LIBRARIES = {
     "dcn": Library("libfeather_dcn.so", ("feather_dcn.h",), "FHIP_DCN_API", DCN_SIGNATURES, "fhip_dcn_last_error", (), None),
     # route: CONV3D_ROUTE of net.py (FHIP_CONV3D_NET_ROUTE of its own header)
     "conv3d": Library("libfeather_conv3d.so", ("feather_conv3d.h",), "FHIP_CONV3D_API", CONV3D_SIGNATURES, "fhip_conv3d_last_error", (), None),
+    # route: STFT_ROUTE of net.py (FHIP_STFT_NET_ROUTE of its own header)
+    "stft": Library("libfeather_stft.so", ("feather_stft.h",), "FHIP_STFT_API", STFT_SIGNATURES, "fhip_stft_last_error", (), None),
 }
 _OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 

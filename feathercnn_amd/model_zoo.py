@@ -661,6 +661,21 @@ class GraphBuilder:
         self._note("flat", name, bottom, name, {})
         return self.flatten(name, bottom)
 
+    # -- the audio front end (a net that holds one of these needs Net.SetAudio() and Net.SetDetection()) -----------------------------------
+    def spectrogram(self, name, bottom, n_fft, power=0, hoplen=None, winlen=None, window_type=0, center=1, pad_type=2, normalized=0, onesided=1):
+        """ncnn's Spectrogram on a waveform, a blob of rank 1 [L] -> [freqs][frames] of rank 2, or [freqs][frames][2] with power 0.  Ids that
+        keep their default are not written."""
+        given = {1: (power, 0), 2: (hoplen, None), 3: (winlen, None), 4: (window_type, 0), 5: (center, 1), 6: (pad_type, 2), 7: (normalized, 0), 8: (onesided, 1)}
+        params = {0: int(n_fft), **{k: int(v) for k, (v, default) in given.items() if v != default}}
+        self._note("spectrogram", name, bottom, name, dict(n_fft=n_fft, power=power, hoplen=hoplen, winlen=winlen, window_type=window_type, center=center, pad_type=pad_type,
+                                                          normalized=normalized, onesided=onesided))
+        return self.layer("Spectrogram", name, [bottom], [name], params)
+
+    def unary(self, name, op, bottom):
+        """ncnn's UnaryOp 0=op_type (0 abs, 1 neg, 4 square, 5 sqrt, 6 rsqrt, 7 exp, 8 log, 15 reciprocal, 17 log10) on a blob of any rank."""
+        self._note("unary", name, bottom, name, dict(op=int(op)))
+        return self.layer("UnaryOp", name, [bottom], [name], {0: int(op)})
+
     def pool_rect(self, name, bottom, kw, kh, sw, sh):
         """A max Pooling with a rectangular kernel and stride, unpadded: ncnn's 1 / 11 and 2 / 12.  (A padded one is written as a zero Padding in
         front of it where the bottom is not negative: the reference places a padded window at minus the SUM of both pads, and this runtime
@@ -842,6 +857,18 @@ def _conv3d_ref():
     return conv3d_ref
 
 
+def _stft_ref():
+    """tests/stft_ref.py, the restatement of feather_stft.h: numpy_forward's Spectrogram and UnaryOp are that text, not a second one."""
+    try:
+        import stft_ref
+    except ImportError:
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import stft_ref
+    return stft_ref
+
+
 def _dcn_ref():
     """tests/dcn_ref.py, the restatement of feather_dcn.h: numpy_forward's DeformableConv2D is that text, not a second one."""
     try:
@@ -914,6 +941,11 @@ def numpy_forward(trace, input_name, x=None):
         elif kind == "mha":
             q, k, w_ = (v, v, v) if isinstance(bottom, str) else (v[0], v[1], v[-1])
             y = _attn_ref().multi_head_attention(q[:, 0], k[:, 0], w_[:, 0], a["heads"], a["weights"], a["scale"])[:, None]
+        elif kind == "spectrogram":  # a waveform [n][1][1][L] -> rank 2 [n][1][freqs][frames], or with power 0 rank 3 [n][freqs][frames][2]
+            y = _stft_ref().spectrogram(v[:, 0, 0], **a)
+            y = y if a["power"] == 0 else y[:, None]
+        elif kind == "unary":
+            y = _stft_ref().unary(a["op"], v)
         elif kind == "sigmoid":
             y = 1 / (1 + np.exp(-v.astype(np.float64)))
         elif kind == "deform_conv":
@@ -2387,7 +2419,11 @@ def quartznet_5x5(seed=1234, classes=29, size=(64, 512), dry=False, trace=None):
     g = GraphBuilder(seed, dry)
     g.trace = trace
     c, l = size
-    x = g.input("data", 1, c, l)
+    _quartznet_body(g, g.input("data", 1, c, l), c, classes)
+    return g.finish() + ("data", "c4")
+
+
+def _quartznet_body(g, x, c, classes):
     tag = 0
     for cout, kw, s, d, repeats in QUARTZNET_5X5:
         for _ in range(repeats):
@@ -2395,8 +2431,52 @@ def quartznet_5x5(seed=1234, classes=29, size=(64, 512), dry=False, trace=None):
             x = g.conv1d("pw%d" % tag, x, c, cout, 1, act=1)
             c, tag = cout, tag + 1
     x = g.conv1d("c3", x, c, 1024, 1, act=1)
-    g.conv1d("c4", x, 1024, classes, 1)
+    return g.conv1d("c4", x, 1024, classes, 1)
+
+
+def mel_weights(bands=64, n_fft=512, rate=16000.0):
+    """[bands][n_fft / 2 + 1] triangular filters, evenly spaced on the mel scale 2595 log10(1 + f / 700) from 0 to rate / 2, peak 1: the
+    weights of the pointwise Convolution1D behind a power Spectrogram.  None is negative, and every band holds a bin."""
+    mel = lambda f: 2595.0 * np.log10(1.0 + f / 700.0)
+    edges = 700.0 * (10.0 ** (np.linspace(0.0, mel(rate / 2), bands + 2) / 2595.0) - 1.0)
+    f = np.arange(n_fft // 2 + 1) * rate / n_fft
+    up = (f[None, :] - edges[:-2, None]) / (edges[1:-1] - edges[:-2])[:, None]
+    down = (edges[2:, None] - f[None, :]) / (edges[2:] - edges[1:-1])[:, None]
+    return np.maximum(0.0, np.minimum(up, down)).astype(np.float32)
+
+
+def quartznet_5x5_wave(seed=1234, classes=29, samples=5120, dry=False, trace=None):
+    """quartznet_5x5 from the waveform (Net.SetAudio(), SetConv1d(), SetTransformer() for the BinaryOp, SetDetection()): an Input of `samples`
+    samples at 16 kHz, a Spectrogram (n_fft 512, hop 160, a Hann window of 400, power 2) -> [257][samples / 160 + 1], the mel filter bank as a
+    pointwise Convolution1D with the 64 x 257 weights of mel_weights, BinaryOp add 1e-6, UnaryOp log, and the body of quartznet_5x5 with the
+    same weights for the same seed."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    x = g.spectrogram("stft", g.input("data", 1, 1, samples), 512, power=2, hoplen=160, winlen=400, window_type=1)
+    w = 64 * 257 if dry else mel_weights().reshape(-1)
+    x = g.layer("Convolution1D", "mel", [x], ["mel"], {0: 64, 1: 1, 5: 0, 6: 64 * 257})
+    g._weights("mel", w, 64, None)
+    if trace is not None:
+        g._note("conv1d", "mel", "stft", "mel", dict(w=w.reshape(64, 257, 1), bias=None, s=1, d=1, pl=0, pr=None, pad_value=0.0, group=1, act=0, a0=0.0, a1=0.0))
+    x = g.unary("log", 8, g.binary("floor", 0, x, 1e-6))
+    _quartznet_body(g, x, 64, classes)
     return g.finish() + ("data", "c4")
+
+
+def tiny_audio(seed=101, samples=70, dry=False, trace=None):
+    """Every form of the audio front end on one waveform (Net.SetAudio(), SetTransformer() for the BinaryOp, SetDetection()): a Split feeds
+    four Spectrograms -- complex with a Hann window and reflect padding; magnitude with a Hamming window of 7 in 10, replicate padding and
+    normalized 1; two-sided power with a window of ones, zero padding and normalized 2, then add 1e-3 and log; magnitude without centring, a
+    window of 5 in 8 and a hop of 9 (past n_fft), then sqrt.  No weights."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    a, b, c, d = g.split("fan", g.input("data", 1, 1, samples), 4)
+    g.spectrogram("complex", a, 16, power=0, hoplen=4, window_type=1)
+    g.spectrogram("magnitude", b, 10, power=1, hoplen=3, winlen=7, window_type=2, pad_type=1, normalized=1)
+    x = g.spectrogram("power", c, 12, power=2, hoplen=5, pad_type=0, normalized=2, onesided=0)
+    g.unary("log", 8, g.binary("floor", 0, x, 1e-3))
+    g.unary("root", 5, g.spectrogram("gaps", d, 8, power=1, hoplen=9, winlen=5, window_type=1, center=0))
+    return g.finish() + ("data", "log")
 
 
 def tiny_dcn(seed=97, size=(10, 12), dry=False, trace=None, classes=5):

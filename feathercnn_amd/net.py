@@ -49,6 +49,8 @@ DCN_ROUTE = 116  # FHIP_DCN_NET_ROUTE (feather_dcn.h): DeformableConv2D, after S
 ROUTE_NAMES[DCN_ROUTE] = "DCN"
 CONV3D_ROUTE = 117  # FHIP_CONV3D_NET_ROUTE (feather_conv3d.h): Convolution3D, ConvolutionDepthWise3D or Pooling3D, after SetConv3d() (libfeather_conv3d.so)
 ROUTE_NAMES[CONV3D_ROUTE] = "CONV3D"
+STFT_ROUTE = 118  # FHIP_STFT_NET_ROUTE (feather_stft.h): Spectrogram or UnaryOp, after SetAudio() (libfeather_stft.so)
+ROUTE_NAMES[STFT_ROUTE] = "STFT"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -143,6 +145,11 @@ class Net:
         """feather::Net::SetConv3d: accept ncnn's Convolution3D, ConvolutionDepthWise3D and Pooling3D (routed to libfeather_conv3d.so) instead of
         refusing them at LoadParam.  Needs SetDetection() too (blob ranks); FeedInput then takes a volume [N][C][D][H][W].  Call before LoadParam."""
         _check(self._lib.fhip_net_set_conv3d(self._h, int(bool(on))), "fhip_net_set_conv3d")
+
+    def SetAudio(self, on: bool = True):
+        """feather::Net::SetAudio: accept ncnn's Spectrogram and UnaryOp (routed to libfeather_stft.so) instead of refusing them at LoadParam: a
+        net may then take a waveform.  Needs SetDetection() too (blob ranks).  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_audio(self._h, int(bool(on))), "fhip_net_set_audio")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

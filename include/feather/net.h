@@ -37,7 +37,8 @@
 //     InnerProduct (feather_attn.h) after SetTransformer(true) and SetDetection(true); LSTM, GRU and RNN (feather_rnn.h) after
 //     SetRecurrent(true) and SetDetection(true); Convolution1D, ConvolutionDepthWise1D and Pooling1D (feather_conv1d.h) after
 //     SetConv1d(true) and SetDetection(true); DeformableConv2D (feather_dcn.h) after SetDeformable(true); Convolution3D,
-//     ConvolutionDepthWise3D and Pooling3D (feather_conv3d.h) after SetConv3d(true) and SetDetection(true).
+//     ConvolutionDepthWise3D and Pooling3D (feather_conv3d.h) after SetConv3d(true) and SetDetection(true); Spectrogram and UnaryOp
+//     (feather_stft.h) after SetAudio(true) and SetDetection(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -266,6 +267,9 @@ class Net
     // accept ncnn's 3-D layers -- Convolution3D, ConvolutionDepthWise3D, Pooling3D (libfeather_conv3d.so) -- instead of refusing them; needs
     // SetDetection(true) too; before LoadParam.  Their input is fed with fhip_net_feed_volume (feather_net.h)
     int SetConv3d(bool on = true) { return fhip_net_set_conv3d(net_, on ? 1 : 0); }
+    // accept ncnn's audio front end -- Spectrogram, UnaryOp (libfeather_stft.so) -- instead of refusing it; needs SetDetection(true) too; before
+    // LoadParam (feather_net.h)
+    int SetAudio(bool on = true) { return fhip_net_set_audio(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
     // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
     // blob has another shape.  scores_blob "" asks for none.

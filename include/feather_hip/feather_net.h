@@ -375,6 +375,19 @@ FHIP_API int fhip_net_set_deformable(fhip_net* net, int on);
  * 0 (default): LoadParam refuses the three types with -200; on-then-off equals the default.  Call before LoadParam; later it is
  * FHIP_E_BADARG.  Copied to sub-batch replicas, which no volume can be fed to. */
 FHIP_API int fhip_net_set_conv3d(fhip_net* net, int on);
+/* 1: ncnn's audio front end is loaded -- Spectrogram (0=n_fft 1=power 2=hoplen 3=winlen 4=window_type 5=center 6=pad_type 7=normalized
+ * 8=onesided; feather_stft.h has the table and the definition) and UnaryOp (0=op_type: 0 abs, 1 neg, 4 square, 5 sqrt, 6 rsqrt, 7 exp,
+ * 8 log, 15 reciprocal, 17 log10) -- through libfeather_stft.so, under the route FHIP_STFT_NET_ROUTE (feather_stft.h).  Spectrogram reads a
+ * waveform, a blob of rank 1 [L] (an Input 0=L 1=1 2=1), and writes [freqs][frames] of rank 2 -- Convolution1D's [C][L], so a pointwise
+ * Convolution1D behind it is the mel filter bank -- or, with power 0, [freqs][frames][2] of rank 3.  Its basis, with the window and the
+ * normalisation folded in, is made on the host and uploaded at Init.  UnaryOp works on a blob of any rank.  Nothing fuses into these layers.
+ * Refused with -100 at LoadParam, naming the layer and the param: n_fft outside 2 .. 4096, hoplen < 1, winlen outside 1 .. n_fft, an
+ * unknown power, window_type, pad_type, normalized, center or onesided, a second bottom, another UnaryOp id; at Reshape, naming the blob: a
+ * bottom that is no waveform, a padded row shorter than n_fft, reflect padding with n_fft / 2 >= L, 2^31 elements or more; an int8 bottom
+ * -300.  The blobs of these layers have ranks, which fhip_net_set_detection maintains: without it LoadParam refuses the types with -200 and
+ * says so.  0 (default): LoadParam refuses both types with -200; on-then-off equals the default.  Call before LoadParam; later it is
+ * FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_audio(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
