@@ -454,6 +454,16 @@ STFT_SIGNATURES = {
     "fhip_stft_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_istft.h -- libfeather_istft.so, ncnn's InverseSpectrogram (a library of its own)
+ISTFT_SIGNATURES = {
+    "fhip_istft_output_dim": (_I, [_I] * 4 + [_IP]),
+    "fhip_istft_basis": (_I, [_I] * 5 + [_V, ctypes.c_longlong]),
+    "fhip_istft_envelope": (_I, [_I] * 6 + [_V, ctypes.c_longlong]),
+    "fhip_istft_forward": (_I, [_I] * 6 + [_V, _V, _V, _V, _I, _V]),
+    "fhip_istft_route": (_I, [_I, _I, ctypes.c_char_p, _I]),
+    "fhip_istft_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -560,6 +570,8 @@ LATER_LIBRARIES = {
     "conv3d": Library("libfeather_conv3d.so", ("feather_conv3d.h",), "FHIP_CONV3D_API", CONV3D_SIGNATURES, "fhip_conv3d_last_error", (), None),
     # route: STFT_ROUTE of net.py (FHIP_STFT_NET_ROUTE of its own header)
     "stft": Library("libfeather_stft.so", ("feather_stft.h",), "FHIP_STFT_API", STFT_SIGNATURES, "fhip_stft_last_error", (), None),
+    # route: ISTFT_ROUTE of net.py (FHIP_ISTFT_NET_ROUTE of its own header)
+    "istft": Library("libfeather_istft.so", ("feather_istft.h",), "FHIP_ISTFT_API", ISTFT_SIGNATURES, "fhip_istft_last_error", (), None),
 }
 _OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 

@@ -18,7 +18,7 @@
 // One translation unit, read in this order (no header includes a later one): net_side.h -- errors, the side libraries; net_model.h --
 // ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_conv.h -- the convolution layer, its side routes
 // and the weight staging it shares; net_layers.h -- the other layer classes; net_detect.h -- the detection-head layers and their factory; net_yolo.h -- the YOLO-head layers and
-// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_rnn.h -- the recurrent layers and theirs; net_conv1d.h -- the 1-D layers and theirs; net_dcn.h -- the deformable convolution and its factory; net_conv3d.h -- the 3-D layers and theirs; net_stft.h -- Spectrogram, UnaryOp and theirs; net_plan.h -- the fusion and planning passes, prepare,
+// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_rnn.h -- the recurrent layers and theirs; net_conv1d.h -- the 1-D layers and theirs; net_dcn.h -- the deformable convolution and its factory; net_conv3d.h -- the 3-D layers and theirs; net_istft.h -- InverseSpectrogram; net_stft.h -- Spectrogram, UnaryOp and the audio layers' factory; net_plan.h -- the fusion and planning passes, prepare,
 // forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
 #include "net_side.h"
 #include "net_model.h"
@@ -34,6 +34,7 @@
 #include "net_conv1d.h"
 #include "net_dcn.h"
 #include "net_conv3d.h"
+#include "net_istft.h"
 #include "net_stft.h"
 #include "net_plan.h"
 

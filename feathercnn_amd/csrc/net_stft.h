@@ -5,7 +5,7 @@
 // fhip_net_set_detection maintains: the switch needs it.  Nothing fuses into these layers.  A default net never creates one of these classes.
 #pragma once
 #include "feather_hip/feather_stft.h" // declarations only: the library is opened at run time (stft_api)
-#include "net_conv3d.h"
+#include "net_istft.h" // InverseSpectrogramLayer, which create_audio_layer creates
 
 namespace fhip::net
 {
@@ -127,6 +127,7 @@ static Layer* create_audio_layer(const std::string& type)
 {
     if (type == "Spectrogram") return new SpectrogramLayer;
     if (type == "UnaryOp") return new UnaryOpLayer;
+    if (type == "InverseSpectrogram") return new InverseSpectrogramLayer; // net_istft.h, libfeather_istft.so
     return nullptr;
 }
 

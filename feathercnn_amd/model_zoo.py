@@ -671,6 +671,14 @@ class GraphBuilder:
                                                           normalized=normalized, onesided=onesided))
         return self.layer("Spectrogram", name, [bottom], [name], params)
 
+    def inverse_spectrogram(self, name, bottom, n_fft, hoplen=None, winlen=None, window_type=0, center=1, normalized=0):
+        """ncnn's InverseSpectrogram on a complex spectrogram, a blob of rank 3 [freqs][frames][2] -> a waveform of rank 1 [out_len]; one- or
+        two-sided is read off the bottom.  Ids that keep their default are not written."""
+        given = {2: (hoplen, None), 3: (winlen, None), 4: (window_type, 0), 5: (center, 1), 7: (normalized, 0)}
+        params = {0: int(n_fft), **{k: int(v) for k, (v, default) in given.items() if v != default}}
+        self._note("inverse_spectrogram", name, bottom, name, dict(n_fft=n_fft, hoplen=hoplen, winlen=winlen, window_type=window_type, center=center, normalized=normalized))
+        return self.layer("InverseSpectrogram", name, [bottom], [name], params)
+
     def unary(self, name, op, bottom):
         """ncnn's UnaryOp 0=op_type (0 abs, 1 neg, 4 square, 5 sqrt, 6 rsqrt, 7 exp, 8 log, 15 reciprocal, 17 log10) on a blob of any rank."""
         self._note("unary", name, bottom, name, dict(op=int(op)))
@@ -869,6 +877,13 @@ def _stft_ref():
     return stft_ref
 
 
+def _istft_ref():
+    """tests/istft_ref.py, the restatement of feather_istft.h: numpy_forward's InverseSpectrogram is that text, not a second one."""
+    _stft_ref()  # puts tests/ on the path where it is not
+    import istft_ref
+    return istft_ref
+
+
 def _dcn_ref():
     """tests/dcn_ref.py, the restatement of feather_dcn.h: numpy_forward's DeformableConv2D is that text, not a second one."""
     try:
@@ -944,6 +959,8 @@ def numpy_forward(trace, input_name, x=None):
         elif kind == "spectrogram":  # a waveform [n][1][1][L] -> rank 2 [n][1][freqs][frames], or with power 0 rank 3 [n][freqs][frames][2]
             y = _stft_ref().spectrogram(v[:, 0, 0], **a)
             y = y if a["power"] == 0 else y[:, None]
+        elif kind == "inverse_spectrogram":  # rank 3 [n][freqs][frames][2] -> a waveform [n][1][1][out_len]
+            y = _istft_ref().inverse_spectrogram(v, onesided=int(v.shape[1] == a["n_fft"] // 2 + 1), **a)[:, None, None]
         elif kind == "unary":
             y = _stft_ref().unary(a["op"], v)
         elif kind == "sigmoid":
@@ -2477,6 +2494,17 @@ def tiny_audio(seed=101, samples=70, dry=False, trace=None):
     g.unary("log", 8, g.binary("floor", 0, x, 1e-3))
     g.unary("root", 5, g.spectrogram("gaps", d, 8, power=1, hoplen=9, winlen=5, window_type=1, center=0))
     return g.finish() + ("data", "log")
+
+
+def tiny_resynth(seed=103, samples=70, dry=False, trace=None):
+    """A waveform through a Spectrogram and back (Net.SetAudio(), SetDetection()): Input -> Spectrogram (n_fft 16, hop 4, Hann, complex,
+    normalized 1) -> InverseSpectrogram with the same parameters -> UnaryOp neg.  The top is minus the input: perfect reconstruction.  No
+    weights; the input length is free (re-planning re-makes the window envelope)."""
+    g = GraphBuilder(seed, dry)
+    g.trace = trace
+    x = g.spectrogram("stft", g.input("data", 1, 1, samples), 16, power=0, hoplen=4, window_type=1, normalized=1)
+    g.unary("neg", 1, g.inverse_spectrogram("wave", x, 16, hoplen=4, window_type=1, normalized=1))
+    return g.finish() + ("data", "neg")
 
 
 def tiny_dcn(seed=97, size=(10, 12), dry=False, trace=None, classes=5):

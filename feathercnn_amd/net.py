@@ -51,6 +51,8 @@ CONV3D_ROUTE = 117  # FHIP_CONV3D_NET_ROUTE (feather_conv3d.h): Convolution3D, C
 ROUTE_NAMES[CONV3D_ROUTE] = "CONV3D"
 STFT_ROUTE = 118  # FHIP_STFT_NET_ROUTE (feather_stft.h): Spectrogram or UnaryOp, after SetAudio() (libfeather_stft.so)
 ROUTE_NAMES[STFT_ROUTE] = "STFT"
+ISTFT_ROUTE = 119  # FHIP_ISTFT_NET_ROUTE (feather_istft.h): InverseSpectrogram, after SetAudio() (libfeather_istft.so)
+ROUTE_NAMES[ISTFT_ROUTE] = "ISTFT"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -148,7 +150,7 @@ class Net:
 
     def SetAudio(self, on: bool = True):
         """feather::Net::SetAudio: accept ncnn's Spectrogram and UnaryOp (routed to libfeather_stft.so) instead of refusing them at LoadParam: a
-        net may then take a waveform.  Needs SetDetection() too (blob ranks).  Call before LoadParam."""
+        net may then take a waveform -- and InverseSpectrogram (libfeather_istft.so): it may give one back.  Needs SetDetection() too (blob ranks).  Call before LoadParam."""
         _check(self._lib.fhip_net_set_audio(self._h, int(bool(on))), "fhip_net_set_audio")
 
     def set_graph(self, on: bool):

@@ -38,7 +38,7 @@
 //     SetRecurrent(true) and SetDetection(true); Convolution1D, ConvolutionDepthWise1D and Pooling1D (feather_conv1d.h) after
 //     SetConv1d(true) and SetDetection(true); DeformableConv2D (feather_dcn.h) after SetDeformable(true); Convolution3D,
 //     ConvolutionDepthWise3D and Pooling3D (feather_conv3d.h) after SetConv3d(true) and SetDetection(true); Spectrogram and UnaryOp
-//     (feather_stft.h) after SetAudio(true) and SetDetection(true).
+//     (feather_stft.h) and InverseSpectrogram (feather_istft.h) after SetAudio(true) and SetDetection(true).
 // Header-only: every method forwards to the C-ABI in feather_hip/feather_net.h.
 #pragma once
 
@@ -267,7 +267,7 @@ class Net
     // accept ncnn's 3-D layers -- Convolution3D, ConvolutionDepthWise3D, Pooling3D (libfeather_conv3d.so) -- instead of refusing them; needs
     // SetDetection(true) too; before LoadParam.  Their input is fed with fhip_net_feed_volume (feather_net.h)
     int SetConv3d(bool on = true) { return fhip_net_set_conv3d(net_, on ? 1 : 0); }
-    // accept ncnn's audio front end -- Spectrogram, UnaryOp (libfeather_stft.so) -- instead of refusing it; needs SetDetection(true) too; before
+    // accept ncnn's audio layers -- Spectrogram, UnaryOp (libfeather_stft.so), InverseSpectrogram (libfeather_istft.so) -- instead of refusing it; needs SetDetection(true) too; before
     // LoadParam (feather_net.h)
     int SetAudio(bool on = true) { return fhip_net_set_audio(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])

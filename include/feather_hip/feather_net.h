@@ -386,7 +386,14 @@ FHIP_API int fhip_net_set_conv3d(fhip_net* net, int on);
  * bottom that is no waveform, a padded row shorter than n_fft, reflect padding with n_fft / 2 >= L, 2^31 elements or more; an int8 bottom
  * -300.  The blobs of these layers have ranks, which fhip_net_set_detection maintains: without it LoadParam refuses the types with -200 and
  * says so.  0 (default): LoadParam refuses both types with -200; on-then-off equals the default.  Call before LoadParam; later it is
- * FHIP_E_BADARG.  Copied to sub-batch replicas. */
+ * FHIP_E_BADARG.  Copied to sub-batch replicas.
+ * The same switch loads InverseSpectrogram (0=n_fft 1=returns 2=hoplen 3=winlen 4=window_type 5=center 7=normalized; feather_istft.h has the
+ * table and the definition) through libfeather_istft.so, under the route FHIP_ISTFT_NET_ROUTE: it reads a blob of rank 3
+ * [freqs][frames][2], Spectrogram's power-0 top, one-sided where freqs == n_fft / 2 + 1 and two-sided where freqs == n_fft, and writes a
+ * waveform of rank 1 [out_len].  Its basis is uploaded at Init and its window envelope again whenever the number of frames has changed.
+ * Refused with -100 at LoadParam: the ranges above, returns other than 1 (real), a second bottom; at Reshape or Init: a bottom of another
+ * rank, last extent or frequency count, out_len < 1, a window envelope below 1e-11 at a kept sample (hoplen above winlen; a Hann window
+ * without center). */
 FHIP_API int fhip_net_set_audio(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
