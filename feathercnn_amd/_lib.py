@@ -118,6 +118,7 @@ SIGNATURES = {
     "fhip_net_set_deformable": (_I, [_V, _I]),
     "fhip_net_set_conv3d": (_I, [_V, _I]),
     "fhip_net_set_audio": (_I, [_V, _I]),
+    "fhip_net_set_decoder": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -464,6 +465,19 @@ ISTFT_SIGNATURES = {
     "fhip_istft_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_decoder.h -- libfeather_decoder.so, the layers of a decoder-only language model (a library of its own); the
+# description of an SDPA call goes by address (feathercnn_amd.decoder.SdpaDesc)
+DECODER_SIGNATURES = {
+    "fhip_sdpa_get_buffer_size": (_I, [_V, ctypes.POINTER(ctypes.c_size_t), _IP]),
+    "fhip_sdpa_forward": (_I, [_V] * 8),
+    "fhip_kv_concat_forward": (_I, [_I] * 5 + [_V] * 4),
+    "fhip_rms_norm_forward": (_I, [_I, _I, _V, ctypes.c_float, _V, _V, _V]),
+    "fhip_rotary_forward": (_I, [_I] * 5 + [_V, _V, _I, _V, _V, _V]),
+    "fhip_embed_forward": (_I, [_I] * 3 + [_V] * 5),
+    "fhip_decoder_route": (_I, [_I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fhip_decoder_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -572,6 +586,8 @@ LATER_LIBRARIES = {
     "stft": Library("libfeather_stft.so", ("feather_stft.h",), "FHIP_STFT_API", STFT_SIGNATURES, "fhip_stft_last_error", (), None),
     # route: ISTFT_ROUTE of net.py (FHIP_ISTFT_NET_ROUTE of its own header)
     "istft": Library("libfeather_istft.so", ("feather_istft.h",), "FHIP_ISTFT_API", ISTFT_SIGNATURES, "fhip_istft_last_error", (), None),
+    # route: DECODER_ROUTE of net.py (FHIP_DECODER_NET_ROUTE of its own header)
+    "decoder": Library("libfeather_decoder.so", ("feather_decoder.h",), "FHIP_DECODER_API", DECODER_SIGNATURES, "fhip_decoder_last_error", (), None),
 }
 _OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 

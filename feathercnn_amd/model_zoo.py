@@ -2507,6 +2507,99 @@ def tiny_resynth(seed=103, samples=70, dry=False, trace=None):
     return g.finish() + ("data", "neg")
 
 
+def _decoder_ref():
+    """tests/decoder_ref.py, the restatement of feather_decoder.h: tiny_llama_forward's layers are that text, not a second one."""
+    _stft_ref()  # puts tests/ on the path where it is not
+    import decoder_ref
+    return decoder_ref
+
+
+LLAMA = dict(E=32, heads=4, kv_heads=2, d=8, hidden=48, vocab=50, blocks=2, eps=1e-5)
+
+
+def tiny_llama(seed=107, dry=False, trace=None, tokens=7):
+    """A decoder-only language model (Net.SetDecoder(), SetTransformer() for the token-wise InnerProduct and the BinaryOp, SetDetection()):
+    Embed, 2 blocks of RMSNorm -> q / k / v projections -> rotary -> SDPA (4 heads on 2 kv heads, d 8) -> output projection -> residual ->
+    RMSNorm -> SwiGLU (hidden 48) -> residual, a final norm and the logits over 50 words.  -> (prefill_param, decode_param, weights): the
+    prefill net (SDPA 7=0; the first caches are its blobs b<i>_krot and b<i>_vh) and the decode net (7=1: Inputs past_k<i>, past_v<i>, tops
+    b<i>_present_k / _v) read the same weight file.  Inputs: ids (int32 bit patterns), cos and sin [T][d / 2], mask [Tq][Tk] additive (the
+    causal mask).  trace: a dict that receives the weights for tiny_llama_forward."""
+    c = LLAMA
+    E, H, KV, d, hidden, vocab = c["E"], c["heads"], c["kv_heads"], c["d"], c["hidden"], c["vocab"]
+    out = []
+    for cache in (0, 1):
+        g = GraphBuilder(seed, dry)
+        g.trace = None if dry else []
+        extra = {}
+        tq = 1 if cache else tokens
+        g.layer("Input", "ids", [], ["ids"], {0: tq})
+        cos, sin = (g.split(nm + "_s", g.layer("Input", nm, [], [nm], {0: d // 2, 1: tq}), 2 * c["blocks"]) for nm in ("cos", "sin"))
+        mask = g.split("mask_s", g.input("mask", 1, tq, tokens + cache), c["blocks"])
+        w = g._uniform(vocab * E, -1, 1)
+        g._tagged(w)
+        extra["embed"] = w if dry else w.reshape(vocab, E)
+        x = g.layer("Embed", "embed", ["ids"], ["embed"], {0: E, 1: vocab, 2: 0, 3: vocab * E})
+
+        def norm(name, bottom):
+            gamma = g._uniform(E, 0.5, 1.5)
+            g._raw(gamma)
+            extra[name] = gamma
+            return g.layer("RMSNorm", name, [bottom], [name], {0: E, 1: f"{c['eps']:.6e}"})
+
+        def heads_of(name, bottom, n):  # [T][n d] -> [T][n][d] -> [n][T][d]
+            return g.permute(name + "h", g.reshape(name + "r", bottom, d, n, -1), 2)
+
+        for b in range(c["blocks"]):
+            t = f"b{b}_"
+            xa, xb = g.split(t + "s1", x)
+            na, nb, nc = g.split(t + "s2", norm(t + "norm1", xa), 3)
+            q, k, v = (heads_of(t + nm, g.fc_tokens(t + nm, src, E, n * d, bias=False), n) for nm, src, n in (("q", na, H), ("k", nb, KV), ("v", nc, KV)))
+            q = g.layer("RotaryEmbed", t + "qrot", [q, cos[2 * b], sin[2 * b]], [t + "qrot"])
+            k = g.layer("RotaryEmbed", t + "krot", [k, cos[2 * b + 1], sin[2 * b + 1]], [t + "krot"])
+            bottoms, tops = [q, k, v, mask[b]], [t + "att"]
+            if cache:
+                bottoms += [g.input(f"past_k{b}", KV, tokens, d), g.input(f"past_v{b}", KV, tokens, d)]
+                tops += [t + "present_k", t + "present_v"]
+            att = g.layer("SDPA", t + "att", bottoms, tops, {5: 1, 7: cache})
+            att = g.reshape(t + "attr", g.permute(t + "atth", att, 2), E, -1)  # [heads][T][d] -> [T][heads][d] -> [T][E]
+            x = g.binary(t + "add1", 0, xb, g.fc_tokens(t + "o", att, E, E, bias=False))
+            xa, xb = g.split(t + "s3", x)
+            na, nb = g.split(t + "s4", norm(t + "norm2", xa))
+            gate = g.swish(t + "swish", g.fc_tokens(t + "gate", na, E, hidden, bias=False))
+            h = g.binary(t + "mul", 2, gate, g.fc_tokens(t + "up", nb, E, hidden, bias=False))
+            x = g.binary(t + "add2", 0, xb, g.fc_tokens(t + "down", h, hidden, E, bias=False))
+        g.fc_tokens("logits", norm("final_norm", x), E, vocab, bias=False)
+        if trace is not None and not cache and not dry:
+            trace.update(extra)
+            trace.update({name: a["w"] for kind, name, _, _, a in g.trace if kind == "fc_tokens"})
+        out.append(g.finish())
+    assert dry or out[0][1] == out[1][1]  # one weight file for both nets
+    return out[0][0], out[1][0], out[0][1]
+
+
+def tiny_llama_forward(weights, ids, cos, sin, mask, past=None):
+    """tiny_llama in float64 (tests/decoder_ref.py): ids [n][T] integers, cos and sin [T][d / 2], mask [T][Tp + T] additive, past: None or one
+    (k, v) pair [n][kv_heads][Tp][d] per block -> (logits [n][T][vocab], the present (k, v) pairs)."""
+    R, c, W = _decoder_ref(), LLAMA, {k: np.asarray(v, np.float64) for k, v in weights.items()}
+    n, T = np.shape(ids)
+    heads_of = lambda y, h: y.reshape(n, T, h, c["d"]).transpose(0, 2, 1, 3)  # noqa: E731
+    x, present = R.embed(np.asarray(ids), W["embed"]), []
+    for b in range(c["blocks"]):
+        t = f"b{b}_"
+        y = R.rms_norm(x, W[t + "norm1"], c["eps"])
+        q, k, v = (heads_of(y @ W[t + nm].T, h) for nm, h in (("q", c["heads"]), ("k", c["kv_heads"]), ("v", c["kv_heads"])))
+        q, k = R.rotary(q, cos, sin), R.rotary(k, cos, sin)
+        if past is not None:
+            k, v = R.kv_concat(past[b][0], k), R.kv_concat(past[b][1], v)
+        present.append((k, v))
+        att = R.sdpa(q, k, v, mask).transpose(0, 2, 1, 3).reshape(n, T, c["E"])
+        x = x + att @ W[t + "o"].T
+        y = R.rms_norm(x, W[t + "norm2"], c["eps"])
+        gate = y @ W[t + "gate"].T
+        x = x + (gate / (1 + np.exp(-gate)) * (y @ W[t + "up"].T)) @ W[t + "down"].T
+    return R.rms_norm(x, W["final_norm"], c["eps"]) @ W["logits"].T, present
+
+
 def tiny_dcn(seed=97, size=(10, 12), dry=False, trace=None, classes=5):
     """A small net around a modulated deformable convolution (Net.SetDeformable()): a 3x3 convolution with ReLU, a 27-channel 3x3 convolution
     whose output a Slice cuts into the 18 offsets and the 9 masks, a Sigmoid on the mask, the DeformableConv2D 8 -> 12, ReLU, a 2x2 max

@@ -53,6 +53,8 @@ STFT_ROUTE = 118  # FHIP_STFT_NET_ROUTE (feather_stft.h): Spectrogram or UnaryOp
 ROUTE_NAMES[STFT_ROUTE] = "STFT"
 ISTFT_ROUTE = 119  # FHIP_ISTFT_NET_ROUTE (feather_istft.h): InverseSpectrogram, after SetAudio() (libfeather_istft.so)
 ROUTE_NAMES[ISTFT_ROUTE] = "ISTFT"
+DECODER_ROUTE = 120  # FHIP_DECODER_NET_ROUTE (feather_decoder.h): SDPA, RMSNorm, RotaryEmbed or Embed, after SetDecoder() (libfeather_decoder.so)
+ROUTE_NAMES[DECODER_ROUTE] = "DECODER"
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -152,6 +154,11 @@ class Net:
         """feather::Net::SetAudio: accept ncnn's Spectrogram and UnaryOp (routed to libfeather_stft.so) instead of refusing them at LoadParam: a
         net may then take a waveform -- and InverseSpectrogram (libfeather_istft.so): it may give one back.  Needs SetDetection() too (blob ranks).  Call before LoadParam."""
         _check(self._lib.fhip_net_set_audio(self._h, int(bool(on))), "fhip_net_set_audio")
+
+    def SetDecoder(self, on: bool = True):
+        """feather::Net::SetDecoder: accept ncnn's SDPA, RMSNorm, RotaryEmbed and Embed (routed to libfeather_decoder.so) instead of refusing
+        them at LoadParam: a decoder-only language model loads.  Needs SetDetection() too (blob ranks).  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_decoder(self._h, int(bool(on))), "fhip_net_set_decoder")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")

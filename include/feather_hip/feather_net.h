@@ -395,6 +395,18 @@ FHIP_API int fhip_net_set_conv3d(fhip_net* net, int on);
  * rank, last extent or frequency count, out_len < 1, a window envelope below 1e-11 at a kept sample (hoplen above winlen; a Hann window
  * without center). */
 FHIP_API int fhip_net_set_audio(fhip_net* net, int on);
+/* 1: the layers of a decoder-only language model -- ncnn's SDPA (5=attn_mask 6=scale, 0 = 1 / sqrt(d), 7=kv_cache), RMSNorm (0=affine_size
+ * 1=eps 2=affine, gamma raw), RotaryEmbed (0=interleaved; bottoms x, cos, sin) and Embed (0=num_output 1=input_dim 2=bias_term
+ * 3=weight_data_size; the weight tagged, the bias raw; the bottom holds int32 bit patterns; the top is rank 2 [T][num_output]) -- are loaded
+ * and run through libfeather_decoder.so (feather_decoder.h has the definitions), under the route FHIP_DECODER_NET_ROUTE; a Swish then keeps
+ * its bottom's rank.  SDPA reads q [heads][Tq][d], k and v [kv_heads][Tn][d] of rank 3, then the mask if 5=1 (rank 2 [Tq][Tk], or rank 3
+ * [heads or 1][Tq][Tk], batch n or 1), then past_k and past_v if 7=1, and writes out [heads][Tq][d] and with 7=1 present_k and present_v
+ * [kv_heads][Tp + Tn][d] (one concat launch per cache, then the core over the present blobs).  A row that sees no key is zeros.  Refused with
+ * -100 at LoadParam: values out of range, other bottom or top counts; at Reshape: other ranks, a dv other than d, heads no multiple of
+ * kv_heads, a mask or past blob that does not fit, a d the core refuses, 2^31 elements or more.  The blobs of these layers have ranks, which
+ * fhip_net_set_detection maintains: without it LoadParam refuses the types with -200 and says so.  0 (default): LoadParam refuses the four
+ * types with -200; on-then-off equals the default.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_decoder(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
