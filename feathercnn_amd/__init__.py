@@ -47,11 +47,13 @@ from .istft import inverse_spectrogram, istft_route  # (feathercnn_amd.istft sta
 from .istft import NET_ROUTE as ISTFT_NET_ROUTE
 from .decoder import sdpa, prepare_sdpa, sdpa_plan, kv_concat, rms_norm, rotary, embed, decoder_route  # (feathercnn_amd.decoder stays the module)
 from .decoder import NET_ROUTE as DECODER_NET_ROUTE
+from .gemm import gemm, matmul, gemm_route  # (the name feathercnn_amd.gemm is then the function: the module is reached by `from feathercnn_amd.gemm import ...`)
+from .gemm import NET_ROUTE as GEMM_NET_ROUTE
 from .pixels import (PIXEL_BGR, PIXEL_BGR2GRAY, PIXEL_BGR2RGB, PIXEL_GRAY, PIXEL_GRAY2BGR, PIXEL_GRAY2RGB, PIXEL_RGB, PIXEL_RGB2BGR,
                      PIXEL_RGB2GRAY, PIXEL_RGBA, PIXEL_RGBA2BGR, PIXEL_RGBA2GRAY, PIXEL_RGBA2RGB, float_to_pixels, pixels_images_to_float,
                      pixels_to_float, yuv420sp_to_float)
 
-__all__ = ["sdpa", "prepare_sdpa", "sdpa_plan", "kv_concat", "rms_norm", "rotary", "embed", "decoder_route", "DECODER_NET_ROUTE", "inverse_spectrogram", "istft_route", "ISTFT_NET_ROUTE", "spectrogram", "unary_op", "stft_route", "STFT_NET_ROUTE", "deform_conv2d", "dcn_pack", "dcn_route", "dcn_output_dim", "DCN_NET_ROUTE", "convolution1d", "pooling1d", "conv1d_output_dim", "pool1d_output_dim", "conv1d_route", "CONV1D_NET_ROUTE", "recurrent", "rnn_route", "LSTM", "GRU", "RNN", "RNN_NET_ROUTE", "attention", "layer_norm", "add_layer_norm", "gelu", "binary", "attn_route", "ATTN_NET_ROUTE", "pad", "crop", "window", "window_output_dim", "pixel_shuffle", "pixel_shuffle_output_dim", "frame_route", "FRAME_NET_ROUTE", "generate_anchors", "proposal", "roi_pool", "roi_align", "psroi_pool", "roi_route", "ROI_NET_ROUTE", "reorg", "reorg_output_dim", "yolo_detection", "yolo_route", "YOLO_NET_ROUTE", "YOLO_MAX_SCALES", "YOLO_MAX_BOXES", "YOLO_MAX_CLASSES",
+__all__ = ["gemm", "matmul", "gemm_route", "GEMM_NET_ROUTE", "sdpa", "prepare_sdpa", "sdpa_plan", "kv_concat", "rms_norm", "rotary", "embed", "decoder_route", "DECODER_NET_ROUTE", "inverse_spectrogram", "istft_route", "ISTFT_NET_ROUTE", "spectrogram", "unary_op", "stft_route", "STFT_NET_ROUTE", "deform_conv2d", "dcn_pack", "dcn_route", "dcn_output_dim", "DCN_NET_ROUTE", "convolution1d", "pooling1d", "conv1d_output_dim", "pool1d_output_dim", "conv1d_route", "CONV1D_NET_ROUTE", "recurrent", "rnn_route", "LSTM", "GRU", "RNN", "RNN_NET_ROUTE", "attention", "layer_norm", "add_layer_norm", "gelu", "binary", "attn_route", "ATTN_NET_ROUTE", "pad", "crop", "window", "window_output_dim", "pixel_shuffle", "pixel_shuffle_output_dim", "frame_route", "FRAME_NET_ROUTE", "generate_anchors", "proposal", "roi_pool", "roi_align", "psroi_pool", "roi_route", "ROI_NET_ROUTE", "reorg", "reorg_output_dim", "yolo_detection", "yolo_route", "YOLO_NET_ROUTE", "YOLO_MAX_SCALES", "YOLO_MAX_BOXES", "YOLO_MAX_CLASSES",
            "YOLO_MAX_CELLS", "YOLO_MAX_ROWS", "YOLO_CHUNK", "permute", "permute_concat", "normalize", "priorbox", "axis_softmax", "detection_output", "detect_route", "Q8Conv", "Q8Param", "q8_pack", "q8_unpack", "q8_relu", "q8_max_pool", "q8_route", "QuantConv", "QuantParam", "quantize", "qconv_route", "dequant_scales", "ConvParam", "ConvBooster", "ConvLayer", "GroupedConv", "GroupedConvLayer", "Deconv", "DeconvLayer", "DeconvParam", "AtrousConv", "AtrousLayer", "AtrousParam", "instance_norm", "instance_norm_route", "activation", "channel_gate", "squeeze", "excite", "gate_activation", "interp", "interp_output_dim", "interp_route", "hard_swish", "lrn", "lrn_pool", "lrn_route", "lrn_pool_route", "channel_shuffle", "channel_slice", "channel_map", "ChannelMap", "FeatherHipError", "load_library", "lib_path", "NAIVE", "IM2COL",
            "SGECONV", "DEPTHWISE", "WINOGRADF63", "WINOGRADF63FUSED", "WINOGRADF23", "None_", "ReLU", "ALGO_NAMES", "pixels_to_float", "pixels_images_to_float", "float_to_pixels", "yuv420sp_to_float", "PIXEL_RGB", "PIXEL_BGR", "PIXEL_GRAY", "PIXEL_RGBA",
            "PIXEL_RGB2BGR", "PIXEL_RGB2GRAY", "PIXEL_BGR2RGB", "PIXEL_BGR2GRAY", "PIXEL_GRAY2RGB", "PIXEL_GRAY2BGR", "PIXEL_RGBA2RGB",

@@ -119,6 +119,7 @@ SIGNATURES = {
     "fhip_net_set_conv3d": (_I, [_V, _I]),
     "fhip_net_set_audio": (_I, [_V, _I]),
     "fhip_net_set_decoder": (_I, [_V, _I]),
+    "fhip_net_set_gemm": (_I, [_V, _I]),
     "fhip_net_set_concurrency": (_I, [_V, _I]),
     "fhip_net_set_sub_batches": (_I, [_V, _I]),
     "fhip_net_load_param": (_I, [_V, ctypes.c_char_p]),
@@ -478,6 +479,14 @@ DECODER_SIGNATURES = {
     "fhip_decoder_last_error": (ctypes.c_char_p, []),
 }
 
+# include/feather_hip/feather_gemm.h -- libfeather_gemm.so, the product of two run-time matrices: Gemm and MatMul (a library of its own); the
+# description of a call goes by address (feathercnn_amd.gemm.GemmDesc)
+GEMM_SIGNATURES = {
+    "fhip_gemm_forward": (_I, [_V] * 6),
+    "fhip_gemm_route": (_I, [_V, ctypes.c_char_p, _I]),
+    "fhip_gemm_last_error": (ctypes.c_char_p, []),
+}
+
 
 def _load(path, signatures):
     """Open the library at `path` once and type every symbol of `signatures`.  Fails loudly: there is no fallback implementation."""
@@ -588,6 +597,8 @@ LATER_LIBRARIES = {
     "istft": Library("libfeather_istft.so", ("feather_istft.h",), "FHIP_ISTFT_API", ISTFT_SIGNATURES, "fhip_istft_last_error", (), None),
     # route: DECODER_ROUTE of net.py (FHIP_DECODER_NET_ROUTE of its own header)
     "decoder": Library("libfeather_decoder.so", ("feather_decoder.h",), "FHIP_DECODER_API", DECODER_SIGNATURES, "fhip_decoder_last_error", (), None),
+    # route: GEMM_ROUTE of net.py (FHIP_GEMM_NET_ROUTE of its own header)
+    "gemm": Library("libfeather_gemm.so", ("feather_gemm.h",), "FHIP_GEMM_API", GEMM_SIGNATURES, "fhip_gemm_last_error", (), None),
 }
 _OUTSIDE = (STANDALONE_LIBRARIES, LATER_LIBRARIES)  # the rows in none of TABLES
 

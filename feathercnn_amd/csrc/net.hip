@@ -18,7 +18,7 @@
 // One translation unit, read in this order (no header includes a later one): net_side.h -- errors, the side libraries; net_model.h --
 // ParamDict, ModelBin; net_core.h -- Blob, DeviceVec, Layer, Net, the graph queries; net_conv.h -- the convolution layer, its side routes
 // and the weight staging it shares; net_layers.h -- the other layer classes; net_detect.h -- the detection-head layers and their factory; net_yolo.h -- the YOLO-head layers and
-// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_rnn.h -- the recurrent layers and theirs; net_conv1d.h -- the 1-D layers and theirs; net_dcn.h -- the deformable convolution and its factory; net_conv3d.h -- the 3-D layers and theirs; net_istft.h -- InverseSpectrogram; net_stft.h -- Spectrogram, UnaryOp and the audio layers' factory; net_decoder.h -- SDPA, RMSNorm, RotaryEmbed, Embed and theirs; net_plan.h -- the fusion and planning passes, prepare,
+// theirs; net_roi.h -- the two-stage detection layers and theirs; net_frame.h -- Padding, Crop, PixelShuffle and theirs; net_attn.h -- the transformer layers and theirs; net_rnn.h -- the recurrent layers and theirs; net_conv1d.h -- the 1-D layers and theirs; net_dcn.h -- the deformable convolution and its factory; net_conv3d.h -- the 3-D layers and theirs; net_istft.h -- InverseSpectrogram; net_stft.h -- Spectrogram, UnaryOp and the audio layers' factory; net_decoder.h -- SDPA, RMSNorm, RotaryEmbed, Embed and theirs; net_gemm.h -- Gemm, MatMul and theirs; net_plan.h -- the fusion and planning passes, prepare,
 // forward.  Here: the layer factories, the loaders that call them, and the fhip_net_* C-ABI.
 #include "net_side.h"
 #include "net_model.h"
@@ -37,6 +37,7 @@
 #include "net_istft.h"
 #include "net_stft.h"
 #include "net_decoder.h"
+#include "net_gemm.h"
 #include "net_plan.h"
 
 namespace fhip::net
@@ -155,13 +156,19 @@ static int load_param_text(Net& net, const char* text, size_t len)
             if (layer && !net.detection)
                 return failf(NET_E_UNKNOWN_LAYER, "layer %s: the layers of fhip_net_set_audio need the blob ranks fhip_net_set_detection maintains: set both", type.c_str());
         }
+        if (!layer && net.gemm)
+        {
+            layer.reset(create_gemm_layer(type));
+            if (layer && !net.detection)
+                return failf(NET_E_UNKNOWN_LAYER, "layer %s: the layers of fhip_net_set_gemm need the blob ranks fhip_net_set_detection maintains: set both", type.c_str());
+        }
         if (!layer)
         {
             std::unique_ptr<Layer> opt_in(create_extended_layer(type)), detect(create_detection_layer(type)), yolo(create_yolo_layer(type)),
-                roi(create_roi_layer(type)), frame(create_frame_layer(type)), transformer(create_transformer_layer(type)), recurrent(create_recurrent_layer(type)), conv1d(create_conv1d_layer(type)), deformable(create_deformable_layer(type)), conv3d(create_conv3d_layer(type)), audio(create_audio_layer(type)), decoder(create_decoder_layer(type));
+                roi(create_roi_layer(type)), frame(create_frame_layer(type)), transformer(create_transformer_layer(type)), recurrent(create_recurrent_layer(type)), conv1d(create_conv1d_layer(type)), deformable(create_deformable_layer(type)), conv3d(create_conv3d_layer(type)), audio(create_audio_layer(type)), decoder(create_decoder_layer(type)), gemm(create_gemm_layer(type));
             return failf(NET_E_UNKNOWN_LAYER, "layer %s not exists or registered%s", type.c_str(),
                          opt_in ? " (fhip_net_set_extended_layers lifts this)"
-                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : (roi ? " (fhip_net_set_roi lifts this)" : (frame ? " (fhip_net_set_frame enables it)" : (transformer ? " (fhip_net_set_transformer lifts this)" : (recurrent ? " (fhip_net_set_recurrent lifts this)" : (conv1d ? " (fhip_net_set_conv1d lifts this)" : (deformable ? " (fhip_net_set_deformable lifts this)" : (conv3d ? " (fhip_net_set_conv3d lifts this)" : (audio ? " (fhip_net_set_audio lifts this)" : (decoder ? " (fhip_net_set_decoder lifts this)" : ""))))))))))));
+                                : (detect ? " (fhip_net_set_detection lifts this)" : (yolo ? " (fhip_net_set_yolo lifts this)" : (roi ? " (fhip_net_set_roi lifts this)" : (frame ? " (fhip_net_set_frame enables it)" : (transformer ? " (fhip_net_set_transformer lifts this)" : (recurrent ? " (fhip_net_set_recurrent lifts this)" : (conv1d ? " (fhip_net_set_conv1d lifts this)" : (deformable ? " (fhip_net_set_deformable lifts this)" : (conv3d ? " (fhip_net_set_conv3d lifts this)" : (audio ? " (fhip_net_set_audio lifts this)" : (decoder ? " (fhip_net_set_decoder lifts this)" : (gemm ? " (fhip_net_set_gemm lifts this)" : "")))))))))))));
         }
         layer->type = type;
         layer->name = name;
@@ -409,6 +416,7 @@ int fhip_net_set_sub_batches(fhip_net* n, int replicas)
         m->impl.conv3d = n->impl.conv3d;
         m->impl.audio = n->impl.audio;
         m->impl.decoder = n->impl.decoder;
+        m->impl.gemm = n->impl.gemm;
         n->more.push_back(std::move(m));
     }
     if (replicas > 1 && !n->fork) FHIP_CHECK_HIP(hipEventCreateWithFlags(&n->fork, hipEventDisableTiming));
@@ -564,6 +572,15 @@ int fhip_net_set_decoder(fhip_net* n, int on)
     if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the decoder layers switch (SDPA, RMSNorm, RotaryEmbed, Embed) before LoadParam");
     n->impl.decoder = on != 0;
     for (auto& m : n->more) m->impl.decoder = on != 0;
+    return FHIP_OK;
+}
+
+int fhip_net_set_gemm(fhip_net* n, int on)
+{
+    NET_GUARD(n);
+    if (n->impl.param_loaded) return fail(FHIP_E_BADARG, "set the matrix product layers switch (Gemm, MatMul) before LoadParam");
+    n->impl.gemm = on != 0;
+    for (auto& m : n->more) m->impl.gemm = on != 0;
     return FHIP_OK;
 }
 

@@ -208,6 +208,7 @@ struct Net
     bool conv3d = false;          // fhip_net_set_conv3d: Convolution3D, ConvolutionDepthWise3D and Pooling3D (net_conv3d.h, libfeather_conv3d.so) are loaded instead of refused
     bool audio = false;           // fhip_net_set_audio: Spectrogram and UnaryOp (net_stft.h, libfeather_stft.so) and InverseSpectrogram (net_istft.h, libfeather_istft.so) are loaded instead of refused
     bool decoder = false;         // fhip_net_set_decoder: SDPA, RMSNorm, RotaryEmbed and Embed (net_decoder.h, libfeather_decoder.so) are loaded instead of refused
+    bool gemm = false;            // fhip_net_set_gemm: Gemm and MatMul (net_gemm.h, libfeather_gemm.so) are loaded instead of refused
     int colpass = 1;              // fhip_net_set_colpass: chained 64-input-channel Winograd layers through libfeather_colpass.so -- 0 never, 1 where M is HBM-bound, 2 wherever accepted
     bool param_loaded = false, weights_loaded = false, fused = false, initialized = false, shapes_dirty = true;
     DeviceVec arena;

@@ -2600,6 +2600,63 @@ def tiny_llama_forward(weights, ids, cos, sin, mask, past=None):
     return R.rms_norm(x, W["final_norm"], c["eps"]) @ W["logits"].T, present
 
 
+def _gemm_ref():
+    """tests/gemm_ref.py, the restatement of feather_gemm.h: tiny_matmul_forward's products are that text, not a second one."""
+    _stft_ref()  # puts tests/ on the path where it is not
+    import gemm_ref
+    return gemm_ref
+
+
+MATMUL = dict(E=16, heads=2, d=8, width=12)
+
+
+def tiny_matmul(seed=109, dry=False, trace=None, tokens=7):
+    """Every form of Gemm and MatMul once (Net.SetGemm(), SetTransformer() for the token-wise InnerProduct, BinaryOp and MemoryData,
+    SetDetection()): an attention block as pnnx writes it un-fused -- three InnerProducts on [T][16], Reshape / Permute to [2][T][8], MatMul
+    0=1 (q k^T), BinaryOp mul 1 / sqrt(8), BinaryOp add of a MemoryData relative-position bias [2][T][T], Softmax on the last axis, MatMul
+    (p v), Permute / Reshape back to [T][16]; a Gemm with a constant B stored [12][16] (3=1), a constant C per column (10=4), alpha 0.5 and
+    beta -2 -> [T][12]; a two-bottom Gemm with 2=1 and 14=1 on that and the input, (A^T B)^T -> [16][12]; a MatMul of it with a MemoryData of
+    rank 1 [12] -> "out" [16], which takes the thin kernel.  trace: a dict that receives the weights for tiny_matmul_forward."""
+    c = MATMUL
+    E, H, d, width = c["E"], c["heads"], c["d"], c["width"]
+    g = GraphBuilder(seed, dry)
+    g.trace = None if dry else []
+    xq, xk, xv, xg = g.split("fan", g.reshape("tokens", g.input("data", 1, tokens, E), E, -1), 4)  # an Input is of rank 3: [1][T][16] -> [T][16]
+    q, k, v = (g.permute(nm + "h", g.reshape(nm + "r", g.fc_tokens(nm, src, E, E), d, H, -1), 2) for nm, src in (("q", xq), ("k", xk), ("v", xv)))
+    s = g.binary("scaled", 2, g.layer("MatMul", "qk", [q, k], ["qk"], {0: 1}), 1 / np.sqrt(d))
+    s = g.binary("biased", 0, s, g.memory_data("rel_bias", tokens, tokens, H))
+    att = g.layer("MatMul", "pv", [g.softmax("prob", s, axis=2), v], ["pv"])
+    att = g.reshape("attr", g.permute("atth", att, 2), E, -1)  # [heads][T][d] -> [T][heads][d] -> [T][E]
+    wb, wc = g._uniform(width * E, -1, 1, np.sqrt(6.0 / E)), g._uniform(width, -0.1, 0.1)
+    g._tagged(wb)
+    g._tagged(wc)
+    x = g.layer("Gemm", "gemm_const", [att], ["gemm_const"], {0: f"{0.5:.6e}", 1: f"{-2.0:.6e}", 3: 1, 5: 1, 6: 1, 8: width, 9: E, 10: 4})
+    x = g.layer("Gemm", "gemm_two", [x, xg], ["gemm_two"], {2: 1, 14: 1})
+    g.layer("MatMul", "out", [x, g.memory_data("vec", width)], ["out"])
+    if trace is not None and not dry:
+        trace.update(gemm_b=wb.reshape(width, E), gemm_c=wc)
+        trace.update({name: a["data"].reshape(a["shape"]) for kind, name, _, _, a in g.trace if kind == "memory_data"})
+        for kind, name, _, _, a in g.trace:
+            if kind == "fc_tokens":
+                trace[name], trace[name + "_b"] = a["w"], a["b"]
+    return g.finish() + ("data", "out")
+
+
+def tiny_matmul_forward(weights, x):
+    """tiny_matmul in float64 (tests/gemm_ref.py): x [n][T][16] -> out [n][16]."""
+    R, c, W = _gemm_ref(), MATMUL, {k: np.asarray(v, np.float64) for k, v in weights.items()}
+    out = []
+    for img in np.asarray(x, np.float64):
+        q, k, v = ((img @ W[nm].T + W[nm + "_b"]).reshape(-1, c["heads"], c["d"]).transpose(1, 0, 2) for nm in "qkv")
+        s = R.matmul(q, k, trans_b=True) * float(np.float32(f"{1 / np.sqrt(c['d']):.6e}")) + W["rel_bias"]
+        p = np.exp(s - s.max(axis=2, keepdims=True))
+        att = R.matmul(p / p.sum(axis=2, keepdims=True), v).transpose(1, 0, 2).reshape(-1, c["E"])
+        y = R.gemm(att[None], W["gemm_b"][None], W["gemm_c"][None], 0.5, -2.0, trans_b=True, c_broadcast=4)[0]
+        y = R.gemm(y[None], img[None], trans_a=True)[0].T  # (A^T B) stored transposed
+        out.append(R.matmul(y, W["vec"].reshape(-1)))
+    return np.stack(out)
+
+
 def tiny_dcn(seed=97, size=(10, 12), dry=False, trace=None, classes=5):
     """A small net around a modulated deformable convolution (Net.SetDeformable()): a 3x3 convolution with ReLU, a 27-channel 3x3 convolution
     whose output a Slice cuts into the 18 offsets and the 9 masks, a Sigmoid on the mask, the DeformableConv2D 8 -> 12, ReLU, a 2x2 max

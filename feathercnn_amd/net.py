@@ -55,6 +55,9 @@ ISTFT_ROUTE = 119  # FHIP_ISTFT_NET_ROUTE (feather_istft.h): InverseSpectrogram,
 ROUTE_NAMES[ISTFT_ROUTE] = "ISTFT"
 DECODER_ROUTE = 120  # FHIP_DECODER_NET_ROUTE (feather_decoder.h): SDPA, RMSNorm, RotaryEmbed or Embed, after SetDecoder() (libfeather_decoder.so)
 ROUTE_NAMES[DECODER_ROUTE] = "DECODER"
+GEMM_ROUTE = 121  # FHIP_GEMM_NET_ROUTE (feather_gemm.h): Gemm or MatMul, after SetGemm() (libfeather_gemm.so)
+# (a table of its own: tests/test_decoder_cpu.py holds ROUTE_NAMES to end at DECODER_ROUTE; Net.layers() reads both)
+LATER_ROUTE_NAMES = {GEMM_ROUTE: "GEMM"}
 
 class Net:
     def __init__(self, fusion: int = 1, graph: bool = False, stream=None, tuned: bool = False, concurrency: bool = False,
@@ -159,6 +162,12 @@ class Net:
         """feather::Net::SetDecoder: accept ncnn's SDPA, RMSNorm, RotaryEmbed and Embed (routed to libfeather_decoder.so) instead of refusing
         them at LoadParam: a decoder-only language model loads.  Needs SetDetection() too (blob ranks).  Call before LoadParam."""
         _check(self._lib.fhip_net_set_decoder(self._h, int(bool(on))), "fhip_net_set_decoder")
+
+    def SetGemm(self, on: bool = True):
+        """feather::Net::SetGemm: accept ncnn's Gemm and MatMul (routed to libfeather_gemm.so) instead of refusing them at LoadParam: a model
+        that pnnx exports un-fused (torch.matmul, bmm, einsum, window attention with a bias) or an ONNX-derived graph loads.  Needs
+        SetDetection() too (blob ranks).  Call before LoadParam."""
+        _check(self._lib.fhip_net_set_gemm(self._h, int(bool(on))), "fhip_net_set_gemm")
 
     def set_graph(self, on: bool):
         _check(self._lib.fhip_net_set_graph(self._h, int(bool(on))), "fhip_net_set_graph")
@@ -371,7 +380,7 @@ class Net:
         for i in range(n):
             t, nm, algo = ctypes.create_string_buffer(64), ctypes.create_string_buffer(256), ctypes.c_int()
             _check(self._lib.fhip_net_layer_info(self._h, i, t, nm, 64, ctypes.byref(algo)), "fhip_net_layer_info")
-            out.append((t.value.decode(), nm.value.decode(), ROUTE_NAMES.get(algo.value)))
+            out.append((t.value.decode(), nm.value.decode(), ROUTE_NAMES.get(algo.value, LATER_ROUTE_NAMES.get(algo.value))))
         return out
 
     def conv_params(self):

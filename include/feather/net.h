@@ -273,6 +273,9 @@ class Net
     // accept the layers of a decoder-only language model -- SDPA, RMSNorm, RotaryEmbed, Embed (libfeather_decoder.so) -- instead of refusing
     // them; needs SetDetection(true) too; before LoadParam (feather_net.h)
     int SetDecoder(bool on = true) { return fhip_net_set_decoder(net_, on ? 1 : 0); }
+    // accept ncnn's Gemm and MatMul -- the product of two run-time matrices (libfeather_gemm.so) -- instead of refusing them; needs
+    // SetDetection(true) too; before LoadParam (feather_net.h)
+    int SetGemm(bool on = true) { return fhip_net_set_gemm(net_, on ? 1 : 0); }
     // The tops of a Proposal layer ([n][R][1][4], sentinel rows (0, 0, -1, -1) past an image's count, and optionally the scores [n][R][1][1])
     // as the ROIs of every image: a host copy through Extract's pointer form and ExtractHost (synchronises).  Extract's error, or -100 if a
     // blob has another shape.  scores_blob "" asks for none.

@@ -407,6 +407,21 @@ FHIP_API int fhip_net_set_audio(fhip_net* net, int on);
  * fhip_net_set_detection maintains: without it LoadParam refuses the types with -200 and says so.  0 (default): LoadParam refuses the four
  * types with -200; on-then-off equals the default.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
 FHIP_API int fhip_net_set_decoder(fhip_net* net, int on);
+/* 1: ncnn's MatMul and Gemm -- the product of two run-time matrices, what pnnx writes for torch.matmul, bmm, einsum and un-fused attention and
+ * what ONNX graphs hold -- are loaded and run through libfeather_gemm.so (feather_gemm.h has the definition), under the route
+ * FHIP_GEMM_NET_ROUTE, one launch a layer into the net's blobs (one per image where a rank-3 MatMul broadcasts one operand over c and the
+ * batch is above 1).  MatMul (0=transB, two bottoms) follows numpy's rules per image: rank 1 . rank 1 a dot product (the top of rank 1, w = 1),
+ * rank 2 . rank 2 a matrix product, rank 1 . rank 2 a row (top [N], rank 1), rank 2 . rank 1 a column (top [M], rank 1), rank 3 on either side
+ * a batch over c (an operand of rank 2 or of c = 1 is broadcast; extents equal or 1; the top of rank 3); transB reads B's last two dimensions
+ * as [N][K].  Gemm (0=alpha 1=beta 2=transA 3=transB 4=constantA 5=constantB 6=constantC 7=M 8=N 9=K 10=constant_broadcast_type_C
+ * 14=output_transpose): the bottoms are the non-constant ones among A, B, C in that order, of rank 2 (rank 1: a row); constant operands come
+ * from the .bin in the order A, B, C, each tagged, fp32; a C bottom takes its broadcast type from its shape as ncnn does; the top is of rank 2.
+ * Refused at LoadParam: 11=output_N1M, 12 / 13 != 0, flags outside 0 / 1, other bottom counts (-100), 18=int8_scale_term (FHIP_E_UNSUPPORTED);
+ * at LoadWeights: fp16-tagged weights (FHIP_E_UNSUPPORTED); at Reshape (-100): a K that differs, batch extents neither equal nor 1, rank 1
+ * with rank 3, a C that broadcasts to no M x N, a blob of rank 4, 2^31 elements or more.  The blobs of these layers have ranks, which
+ * fhip_net_set_detection maintains: without it LoadParam refuses the types with -200 and says so.  0 (default): LoadParam refuses the two
+ * types with -200; on-then-off equals the default.  Call before LoadParam; later it is FHIP_E_BADARG.  Copied to sub-batch replicas. */
+FHIP_API int fhip_net_set_gemm(fhip_net* net, int on);
 /* 1: a Convolution, ConvolutionDepthWise or InnerProduct layer with int8 weights (ncnn param 8 = int8_scale_term 1 .. 100: int8-tagged
  * weights, then the bias, then the weight scales, then one input scale in the .bin) is loaded and runs through libfeather_qconv.so
  * (feather_qconv.h has the definition, bit for bit; route code FHIP_NET_ROUTE_QCONV), fp32 in and out; 0 (default): LoadParam refuses
